@@ -15,11 +15,19 @@ HBM when the timed region starts.  Workload for every N: BASELINE.json configs[2
 ONE corpus of vocab 100k x 10M docs x ~1B nnz, k = 1000 (ncv = 2010, include/hyperparams.h:38-40).  It fits one MI355X (~110 GB of
 288 GB), so N = 1 runs all of it on one GPU; at N > 1 it is column-sharded N ways (strong scaling: rank r holds documents
 [r D/N, (r+1) D/N); Gram / centroid sums are all-reduced with RCCL inside libisle_hip.so).  `--workload c2` runs BASELINE
-configs[1] (vocab 50k, 1M docs, ~100M nnz, k = 200; weak scaling at N > 1: 1M documents per rank); at N = 1 the default run also
-reports C2's ms_per_step as a secondary key ("secondary_c2", a short separate run after the main one, --no-secondary skips it).
+configs[1] (vocab 50k, 1M docs, ~100M nnz, k = 200; weak scaling at N > 1: 1M documents per rank).
+
+A plain run does what the headline figure needs: it generates and uploads the input, warms up, times the steps and prints the line.
+`--full` adds everything else the benchmark measures or checks, all of it outside the timed region: the per-family breakdown
+`device_ms_per_step` / `roofline_by_family` (one more, untimed pass), the accuracy gate against the CPU oracle, the CPU baseline, the stages
+either side of the path and, for the default workload at N = 1, the secondary runs ("secondary_c2", "secondary_c3shard", "full_cli_c2";
+--no-secondary skips them).
 
 Inside the timed region only the Gram-apply launches are bracketed by HIP events (the `roofline` object needs their average
-duration over exactly those steps); the per-family breakdown `device_ms_per_step` comes from one more, untimed pass.
+duration over exactly those steps).
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed as DIR/<name>.npy (float32 / float64, a fixed seeded
+sample where an output is large; dump_outputs).  The inputs depend on the arguments only, so two builds can be compared output for output.
 
 One JSON line on stdout (rank 0).  See DESIGN.md §Measurement for the roofline arithmetic.
 """
@@ -57,10 +65,34 @@ MFMA_F32_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: dense f32 matrix-core peak 
 SIGMA_GATE = 1e-4        # north_star: top-k singular values within 1e-4 relative error
 PARTITION_GATE = 0.999   # k-means against the oracle from the same U and seeds (SURVEY 8c asks >= 0.99; near-ties are all that may differ)
 BIG_NNZ = 400_000_000  # above this the CPU legs (accuracy, k-means sample, cpu_baseline) run on bounded samples
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs: all files together
+DUMP_DOCS = 1 << 19        # --dump-outputs: documents of the partitions (a fixed sample when B has more)
+DUMP_WORDS = 2048          # --dump-outputs: rows of U and of the fetched centres (a fixed sample when the vocabulary is larger)
+T_START = time.time()
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_sample(n, m, seed):
+    """A fixed, seeded sample of m of range(n) in ascending order (all of range(n) when n <= m)."""
+    if n <= m:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, m, replace=False))
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: arrays (name -> float32 / float64 array) as dirname/<name>.npy, at most DUMP_BYTES_MAX bytes in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (at most %d)" % (total, DUMP_BYTES_MAX))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise SystemExit("bench.py: --dump-outputs: %s is %s, not float32 / float64" % (name, a.dtype))
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log("bench.py: wrote %d outputs of the last timed step (%d bytes) to %s" % (len(arrays), total, dirname))
 
 
 def csc_columns(B, cols):
@@ -280,8 +312,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                     help="default: c3 = BASELINE.json configs[2] (one 10M-document corpus, k = 1000; sharded over the ranks at N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-family breakdown, the accuracy gate, the CPU baseline, the side stages and the secondary runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short C2 run behind the default N = 1 run")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the short runs behind the default N = 1 run")
     ap.add_argument("--fetch-centers", action="store_true", help="also copy the final V x k centres to the host inside the timed step")
     ap.add_argument("--no-upstream", action="store_true", help="skip the (untimed-region) stages either side of the path")
     ap.add_argument("--blk", type=int, default=0, help="experiment: block size of the eigensolver (0 = the reference's 10)")
@@ -323,8 +358,10 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("gloo", rank=rank, world_size=world)  # host control plane only
 
-    out = run(args, args.workload, rank, world, local_rank, dist, torch, args.steps, args.warmup, full=True)
-    if out is not None and defaulted and world == 1 and not args.no_secondary:
+    out = run(args, args.workload, rank, world, local_rank, dist, torch, args.steps, args.warmup, full=args.full, breakdown=args.full,
+              dump_dir=args.dump_outputs)
+    secondary = args.full and defaulted and world == 1 and not args.no_secondary
+    if out is not None and secondary:
         # BASELINE configs[1] beside the headline, so that rounds stay comparable: a short run, hot path only
         try:
             sec = run(args, "c2", rank, world, local_rank, dist, torch, 3, 1, full=False)
@@ -333,7 +370,7 @@ def main():
                                    "avg_gram_apply_ms": sec["roofline"]["avg_launch_ms"]}
         except Exception as e:  # the headline line must not depend on the secondary run
             out["secondary_c2"] = {"error": repr(e)[:300]}
-    if out is not None and defaulted and world == 1 and not args.no_secondary:
+    if out is not None and secondary:
         # one GPU's share of configs[2] at N = 8 — the unit an 8-GPU step actually runs (1.25 M documents, the full vocabulary and k): its
         # step, its Gram apply and its latency chains (QR, EVD) are what the scaling curve is made of, so they are reported next to the headline
         try:
@@ -344,7 +381,7 @@ def main():
                                         "roofline_frac_by_family": {f: v["frac"] for f, v in sec["roofline_by_family"].items()}}
         except Exception as e:
             out["secondary_c3shard"] = {"error": repr(e)[:300]}
-    if out is not None and defaulted and world == 1 and not args.no_secondary:
+    if out is not None and secondary:
         # SURVEY 8(d)'s second figure: full ISLETrain wall time, tdf text in -> M_hat_catch_sparse out, at BASELINE configs[1]
         try:
             out["full_cli_c2"] = full_cli_leg("c2")
@@ -353,6 +390,7 @@ def main():
     if out is not None:
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(out) + "\n").encode())
+    log("[rank %d] done at %.1f s since start" % (rank, time.time() - T_START))
     failed_gate = None
     if out is not None:
         gate = out.get("accuracy", {}).get("gate")
@@ -423,8 +461,9 @@ def full_cli_leg(workload):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
-def run(args, workload, rank, world, local_rank, dist, torch, steps, warmup, full):
-    """One workload: generate, upload, warm up, time `steps` steps; with full=True also the accuracy / CPU / side-stage legs.
+def run(args, workload, rank, world, local_rank, dist, torch, steps, warmup, full, breakdown=True, dump_dir=None):
+    """One workload: generate, upload, warm up, time `steps` steps; with breakdown=True also one more, untimed pass for the per-family
+    device times; with full=True also the accuracy / CPU / side-stage legs; with dump_dir the outputs of the last timed step go there.
     Returns the result object on rank 0, None elsewhere."""
     from isle_amd import HotPath
     from tools.synth import Corpus, effective_cpus
@@ -457,7 +496,7 @@ def run(args, workload, rank, world, local_rank, dist, torch, steps, warmup, ful
     A_host = corp.A() if upstream else None
     tdf_text = corp.tdf_bytes() if upstream else None
     t_thr0 = time.time()
-    planted_all = corp.planted()
+    planted_all = corp.planted() if full else None  # the accuracy leg's planted-topic agreement
 
     # ISLE_BENCH_REHEARSE=1: all ranks on GPU 0 with the host-staged test transport (RCCL refuses two ranks on one device).
     # For checking this script's N > 1 control flow on a one-GPU box only: the line it prints is marked and is not a measurement.
@@ -492,13 +531,16 @@ def run(args, workload, rank, world, local_rank, dist, torch, steps, warmup, ful
         t_thr_dev = time.perf_counter() - t1
         thr_dev_ms = hp.timing_get()["threshold"][0]
         hp.timing_enable(False)
-        B = hp.get_B()
-        B["D"], B["nnz"] = int(B["D"]), int(B["nnz"])
+        if full:  # the host copy of B serves the checks of the full run only
+            B = hp.get_B()
+            B["D"], B["nnz"] = int(B["D"]), int(B["nnz"])
+        else:
+            B = {"D": hp.D, "nnz": hp.nnz}
         stage_in = {"stage": "A on the device -> B (normalize_docs + compute_thresholds + %s, src/trainer.cpp:430-485)"
                              % ("sampled_threshold_and_copy, sample_rate %.2f" % sample_rate if sample_rate else "threshold_and_copy"),
                     "docs_A": int(D_per), "nnz_A": int(nnz_A), "docs_kept": info["docs_kept"], "nnz_kept": info["nnz_kept"],
                     "upload_A_wall_ms": round(t_h2d * 1e3, 1), "wall_ms": round(t_thr_dev * 1e3, 1), "device_ms": round(thr_dev_ms, 3)}
-        if world == 1:
+        if world == 1 and full:
             t1 = time.time()
             Bc = corp.threshold(k, free_A=True, sample_rate=sample_rate, sample_seed=seed)
             stage_in["cpu_port_ms"] = round((time.time() - t1) * 1e3, 1)
@@ -512,7 +554,7 @@ def run(args, workload, rank, world, local_rank, dist, torch, steps, warmup, ful
     else:
         B = corp.threshold(k, free_A=True, allreduce=allreduce_np if dist is not None else None)
     # dominant planted topic of every column of B (the device numbers B's columns by their GLOBAL document, the port by the rank's own)
-    planted = planted_all[B["original_cols"].astype(np.int64) - (doc_base if device_stage else 0)]
+    planted = planted_all[B["original_cols"].astype(np.int64) - (doc_base if device_stage else 0)] if full else None
     t_thr_cpu = time.time() - t_thr0
     del corp, planted_all
     t_gen = time.time() - t0
@@ -526,11 +568,12 @@ def run(args, workload, rank, world, local_rank, dist, torch, steps, warmup, ful
     allreduce_np(tot)
     nnz_glob = int(tot[0])
     docs_metric = D_A_total if device_stage else D_glob  # docs/sec counts the documents of the INPUT (config 4 keeps a tenth of them in B)
-    log("[rank %d] %s corpus: V=%d docs=%d (global %d) nnz(A)=%d nnz(B)=%d  generated in %.1fs" %
-        (rank, workload, V, D_loc, D_glob, nnz_A, nnz_loc, t_gen))
+    log("[rank %d] %s corpus: V=%d docs=%d (global %d) nnz(A)=%d nnz(B)=%d  generated in %.1fs (%.1f s since start)" %
+        (rank, workload, V, D_loc, D_glob, nnz_A, nnz_loc, t_gen, time.time() - T_START))
 
     if not device_stage:
         hp.upload_csc(V, B["vals"], B["rows"], B["offs"], doc_offset=doc_offset, docs_global=D_glob)
+        log("[rank %d] B on the device at %.1f s since start" % (rank, time.time() - T_START))
 
     phase_wall = {"block_ks": 0.0, "kmeanspp": 0.0, "lloyd_projected": 0.0, "lift": 0.0, "lloyd_sparse": 0.0}
 
@@ -555,7 +598,8 @@ def run(args, workload, rank, world, local_rank, dist, torch, steps, warmup, ful
         if wall:
             for j, name in enumerate(phase_wall):
                 phase_wall[name] += t[j + 1] - t[j]
-        return dict(ks=r, kmpp_rounds=g["rounds"], lp_iters=lp["iters"], ls_iters=ls["iters"], assign=ls["assign"])
+        return dict(ks=r, kmpp_rounds=g["rounds"], lp_iters=lp["iters"], ls_iters=ls["iters"], assign=ls["assign"], kmpp_C_lowd=g["C_lowd"],
+                    lp_C_lowd=lp["C_lowd"], lp_assign=lp["assign"], centers=ls["centers"])
 
     def fence():
         hp.synchronize()
@@ -567,7 +611,7 @@ def run(args, workload, rank, world, local_rank, dist, torch, steps, warmup, ful
     for i in range(warmup):
         tw = time.perf_counter()
         step(-1 - i, wall=False)
-        log("[rank %d] warm-up step %d: %.2f s" % (rank, i, time.perf_counter() - tw))
+        log("[rank %d] warm-up step %d: %.2f s (%.1f s since start)" % (rank, i, time.perf_counter() - tw, time.time() - T_START))
     hp.timing_enable(2)  # events around the Gram-apply launches only (roofline); everything else runs as in production
     hp.timing_reset()
     fence()
@@ -593,12 +637,32 @@ def run(args, workload, rank, world, local_rank, dist, torch, steps, warmup, ful
         step_largest.append(int(sz.max()))
     del step_assigns
     tm_gram = hp.timing_get()
-    # per-family breakdown: one more pass, untimed, with events around every launch
-    hp.timing_enable(1)
-    hp.timing_reset()
-    step(steps - 1, wall=False)  # the last timed step again (same seeds), so that the per-family device times describe a timed step
-    fence()
-    tm = hp.timing_get()
+    if dump_dir is not None:
+        # what the last timed step handed its caller (the V x k centres only where --fetch-centers fetched them; U as isle_hip_get_U
+        # returns it), before anything else runs on the device
+        sizes_all = np.bincount(last["assign"], minlength=k).astype(np.int64)
+        allreduce_np(sizes_all)
+        if rank == 0:
+            docs, words = dump_sample(D_loc, DUMP_DOCS, 1), dump_sample(V, DUMP_WORDS, 2)
+            ks = last["ks"]
+            outs = {"evals": ks["evals"].astype(np.float64),  # eigenvalues of B B^T (sigma^2)
+                    "U_rows": np.ascontiguousarray(hp.get_U(k)[words]), "U_rows_index": words.astype(np.float64),
+                    "kmeanspp_centers_lowd": last["kmpp_C_lowd"], "lloyd_projected_centers_lowd": last["lp_C_lowd"],
+                    "assign_projected": last["lp_assign"][docs].astype(np.float32), "assign": last["assign"][docs].astype(np.float32),
+                    "assign_index": docs.astype(np.float64), "cluster_sizes": sizes_all.astype(np.float64),
+                    "counts": np.array([ks["rc"], ks["nconv"], ks["restarts"], ks["napplies"], last["kmpp_rounds"], last["lp_iters"],
+                                        last["ls_iters"]], np.float64)}  # rc, nconv, restarts, applications, k-means++ rounds, Lloyd iterations
+            if last["centers"] is not None:
+                outs["centers_rows"] = np.ascontiguousarray(last["centers"][words])
+            dump_outputs(dump_dir, outs)
+    tm = None
+    if breakdown:
+        # per-family breakdown: one more pass, untimed, with events around every launch
+        hp.timing_enable(1)
+        hp.timing_reset()
+        step(steps - 1, wall=False)  # the last timed step again (same seeds), so that the per-family device times describe a timed step
+        fence()
+        tm = hp.timing_get()
     hp.timing_enable(0)
     dtt = np.array([dt], np.float64)
     if dist is not None:
@@ -644,7 +708,7 @@ def run(args, workload, rank, world, local_rank, dist, torch, steps, warmup, ful
                             "this size" % (pmc_key, sha) if traffic is not None else "no counter pass committed for workload '%s'" % pmc_key)
     # HBM bytes of a whole step by kernel family, from the counter pass over one config-3 step (tools/r06_steppmc.sh), while it describes this build
     step_traffic = None
-    if workload in ("c3", "c3full") and world == 1:
+    if breakdown and workload in ("c3", "c3full") and world == 1:
         try:
             with open(os.path.join(ROOT, "profiles", "r06_step_traffic_by_family.json")) as f:
                 st = json.load(f)
@@ -660,10 +724,11 @@ def run(args, workload, rank, world, local_rank, dist, torch, steps, warmup, ful
                 "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_note,
                 "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": round(t_apply_ms, 4), "launches": n_apply}
-    device_ms = {f: round(v[0], 3) for f, v in tm.items() if v[1]}  # the one untimed pass with events around every launch
-    by_family = family_rooflines(V, D_loc, nnz_loc, k, b, (2 * k + b) if k > 10 else 2 * k + 10, last["ks"]["restarts"], last["ks"]["napplies"],
-                                 last["kmpp_rounds"], last["lp_iters"], last["ls_iters"], device_ms)
-    scopes_per_step = int(sum(v[1] for v in tm.values()))  # event-bracketed scopes (a scope may hold several launches; rocprof has the launch count)
+    if breakdown:
+        device_ms = {f: round(v[0], 3) for f, v in tm.items() if v[1]}  # the one untimed pass with events around every launch
+        by_family = family_rooflines(V, D_loc, nnz_loc, k, b, (2 * k + b) if k > 10 else 2 * k + 10, last["ks"]["restarts"],
+                                     last["ks"]["napplies"], last["kmpp_rounds"], last["lp_iters"], last["ls_iters"], device_ms)
+        scopes_per_step = int(sum(v[1] for v in tm.values()))  # event-bracketed scopes (a scope may hold several launches; rocprof has the launch count)
 
     sizes = np.bincount(last["assign"], minlength=k).astype(np.int64)
     allreduce_np(sizes)
@@ -716,12 +781,10 @@ def run(args, workload, rank, world, local_rank, dist, torch, steps, warmup, ful
         "data": "synthetic",
         "config": cfg,
         "roofline": roofline,
-        "roofline_by_family": by_family,
-        "step_traffic": step_traffic,
-        "device_ms_per_step": device_ms,
-        "timed_scopes_per_step": scopes_per_step,
         "host_wall_ms_per_step": {n: round(v * 1e3 / steps, 3) for n, v in phase_wall.items()},
     }
+    if breakdown:
+        out.update(roofline_by_family=by_family, step_traffic=step_traffic, device_ms_per_step=device_ms, timed_scopes_per_step=scopes_per_step)
     if stage_in is not None:
         out["other_stages"] = {"note": "stage upstream of the hot path, run on the device OUTSIDE the timed region at the workload's own size", "input": stage_in}
     if not full:

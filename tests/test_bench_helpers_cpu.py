@@ -6,6 +6,7 @@ import os
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -56,3 +57,17 @@ def test_edge_pair_selection_matches_the_cpu_restatement():
         ref, _ = O.post_edge_topics(M, t1, t2, cap, want_edge=False)
         assert np.array_equal(select_edge_pairs(t1, t2, cap), ref)
     assert select_edge_pairs(np.full(5, -1), np.full(5, -1), 10).shape == (0, 3)
+
+
+def test_dumped_outputs_are_a_fixed_sample_within_the_cap(tmp_path):
+    """--dump-outputs: the same seeded sample on every run, float32 / float64 files only, 64 MB at most in all."""
+    a = bench.dump_sample(10_000_000, 1 << 19, 1)
+    assert np.array_equal(a, bench.dump_sample(10_000_000, 1 << 19, 1)) and len(a) == 1 << 19 and np.all(np.diff(a) > 0)
+    assert np.array_equal(bench.dump_sample(100, 2048, 2), np.arange(100))
+    d = str(tmp_path / "out")
+    bench.dump_outputs(d, {"x": np.arange(3, dtype=np.float32), "y": np.ones((2, 2))})
+    assert np.array_equal(np.load(os.path.join(d, "x.npy")), [0, 1, 2]) and np.load(os.path.join(d, "y.npy")).dtype == np.float64
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros((64 << 20) // 8 + 1)})
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "int"), {"x": np.zeros(3, np.int32)})

@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -39,12 +40,44 @@ def _check(stdout, n_gpus, steps, scaling="weak"):
 
 
 def test_single_gpu_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _check(r.stdout, 1, 2)
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and cb["unit"] == "docs/sec"
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """Without --full the line carries the headline and nothing that needs legs of its own; --dump-outputs writes what the last timed step
+    computed (float32 / float64 .npy, 64 MB at most), and a second run with the same arguments starts from the same input."""
+    def run(d):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = r.stdout.splitlines()
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0]), {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    d, a = run(tmp_path / "a")
+    for key in KEYS:
+        assert key in d, key
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "docs/sec" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    for key in ("accuracy", "cpu_baseline", "roofline_by_family", "device_ms_per_step", "other_stages", "secondary_c2"):
+        assert key not in d, key
+    k, V = 10, 2000
+    assert {"evals", "U_rows", "U_rows_index", "kmeanspp_centers_lowd", "lloyd_projected_centers_lowd", "assign", "assign_projected",
+            "assign_index", "cluster_sizes", "counts"} <= set(a)
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert sum(os.path.getsize(os.path.join(tmp_path / "a", f)) for f in os.listdir(tmp_path / "a")) <= 64 << 20
+    assert a["evals"].shape == (k,) and np.all(a["evals"] > 0)
+    assert a["U_rows"].shape == (V, k) and np.array_equal(a["U_rows_index"], np.arange(V))  # the whole of U at this size
+    n = len(a["assign_index"])
+    assert a["assign"].shape == a["assign_projected"].shape == (n,) and a["cluster_sizes"].sum() == n  # every document of B at this size
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 1e3 * n / d["ms_per_step"]) <= 1e-3 * d["value"]  # docs/sec over the documents of B
+    assert a["assign"].min() >= 0 and a["assign"].max() < k and a["kmeanspp_centers_lowd"].shape == (k, k)
+    _, b = run(tmp_path / "b")
+    assert set(b) == set(a) and np.array_equal(b["assign_index"], a["assign_index"])
+    assert np.allclose(b["evals"], a["evals"], rtol=1e-5, atol=0)
 
 
 def test_single_gpu_line_over_a_one_rank_rccl_communicator():
@@ -53,7 +86,7 @@ def test_single_gpu_line_over_a_one_rank_rccl_communicator():
     collective of the step through it on one GPU; the line must equal the communicator-free one."""
     def run(extra):
         env = dict(os.environ, **extra)
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "1", "--warmup", "1"],
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "1", "--warmup", "1", "--full"],
                            capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
         assert r.returncode == 0, r.stderr[-3000:]
         return _check(r.stdout, 1, 1), r.stderr
@@ -75,7 +108,7 @@ def test_two_rank_line_through_the_launcher():
     env = dict(os.environ, ISLE_BENCH_REHEARSE="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "tiny", "--steps", "1",
-                        "--warmup", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+                        "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _check(r.stdout, 2, 1)
     assert "REHEARSAL" in d["config"]["parallelism"]
@@ -85,7 +118,7 @@ def test_plain_gpus_2_rehearsal():
     """The driver's own form, `python bench.py --gpus 2 ...` with no launcher: the script starts its two ranks itself."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["ISLE_BENCH_REHEARSE"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "tiny", "--steps", "1", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "tiny", "--steps", "1", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _check(r.stdout, 2, 1)
@@ -108,7 +141,7 @@ def test_plain_gpus_2_without_two_gpus_fails_loudly():
 def test_config4_flow_line():
     """`--workload c4`'s flow at a size a test can run: A on the device, importance sampling there (checked against the CPU port bit for
     bit inside bench.py — a difference ends the run), the hot path on the kept documents, docs/sec quoted on the documents of A."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c4small", "--steps", "1", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c4small", "--steps", "1", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _check(r.stdout, 1, 1)
@@ -121,7 +154,7 @@ def test_config4_flow_line():
 def test_config5_flow_line():
     """`--workload c5`'s flow: device thresholding (sample = 0), hot path, then catchwords + topic model + edge topics as an other_stages leg
     whose pair selection and edge columns bench.py holds against the CPU restatement."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c5small", "--steps", "1", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c5small", "--steps", "1", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _check(r.stdout, 1, 1)
@@ -135,9 +168,10 @@ def test_config4_flow_on_two_ranks():
     thresholds come from all-reduced statistics, the sampling pivot from the all-gathered keys — the shards keep what the one-rank run keeps."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["ISLE_BENCH_REHEARSE"] = "1"
-    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c4small", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
+    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c4small", "--steps", "1", "--warmup", "1", "--full",
+                          "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
-    two = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c4small", "--steps", "1", "--warmup", "1"],
+    two = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c4small", "--steps", "1", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert one.returncode == 0 and two.returncode == 0, (one.stderr[-1500:], two.stderr[-3000:])
     d1, d2 = _check(one.stdout, 1, 1), _check(two.stdout, 2, 1, scaling="strong")  # one corpus split over the ranks

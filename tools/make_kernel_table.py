@@ -2,7 +2,7 @@
 """DESIGN.md section 4's kernel table from two rocprofv3 --kernel-trace --stats summaries of bench.py runs (config 3 on one GPU, a C3 shard):
 one row per kernel of config 3's top N by time (and of the shard's top 12), ms per step at both sizes, the family, what it does and the resource that bounds it.
 usage: make_kernel_table.py <c3full kernel_stats.csv> <steps> <c3shard kernel_stats.csv> <steps> [N=40]
-(steps = timed + warm-up + the one untimed pass with events: every kernel of a step runs that many times in the profile)"""
+(steps = timed + warm-up + the one untimed pass with events of bench.py --full: every kernel of a step runs that many times in the profile)"""
 import csv
 import sys
 
