@@ -259,6 +259,21 @@ int isle_hip_get_doc_topic_sums(isle_ctx* ctx, int64_t* doc_offsets, uint32_t* t
  * (1 - primary_ratio) * Model[:, pairs[2e+1]]; edge is vocab x n column-major. */
 int isle_hip_edge_topics(isle_ctx* ctx, const int64_t* pairs, int n, float primary_ratio, float* edge);
 
+/* UMass topic coherence, SparseMatrix::topic_coherence with compute_doc_frequency / compute_joint_doc_frequency
+ * (src/sparseMatrix.cpp:841-1016), on the resident count matrix A (no partition or model needed; single rank).
+ * top_words: num_topics x M row-major, M distinct word ids per topic, heaviest first (1 <= M <= 32).  With
+ * D(w) = documents of A containing w and D(w_i, w_j) = documents containing both:
+ *   coherence[t] = sum_{i=1..M-1} sum_{j=0..i-1} [ ln(D(w_i, w_j) + eps) - ln D(w_j) ]
+ * evaluated in double, i ascending then j ascending (the reference's index order, :858-866); M = 1 gives 0; NaN where any
+ * D(w_j) of a denominator (j < M-1) is 0 (the reference asserts there).
+ * doc_freq (nullable): num_topics x M, D(w_i).  co_doc_freq (nullable): num_topics x M(M-1)/2, D(w_i, w_j) at i(i-1)/2 + j
+ * for i = 1..M-1, j < i.  The counts are exact integers and the result is reproducible bit for bit.
+ * Deviations from the reference: D counts over ALL of A's documents (the reference counts over B's columns only); the sum is
+ * in double without the reference's float accumulation and its race on coherences[topic].
+ * ISLE_E_ARG: no count matrix, world > 1, num_topics < 1, M < 1 or M > 32, a word id >= vocab, a word repeated in a topic. */
+int isle_hip_topic_coherence(isle_ctx* ctx, int num_topics, int M, const uint32_t* top_words, double eps, double* coherence,
+                             uint64_t* doc_freq, uint64_t* co_doc_freq);
+
 /* ---- inference ---------------------------------------------------- */
 /* ISLEInfer over a batch of documents: drivers/ISLEInfer.cpp:60-112 (normalize_docs(true, true),
  * infer_doc_in_file per document, heaviest topics) with ISLEInfer::mwu / grad / calculate_llh

@@ -417,6 +417,71 @@ extern "C" int isle_hip_edge_topics(isle_ctx* c, const int64_t* pairs, int n, fl
   return 0;
 }
 
+// UMass coherence (src/sparseMatrix.cpp:841-1016): the distinct words and word pairs are prepared here, their document frequencies are
+// counted on the device in one pass over A per counter tile (coherence.hip), the sums are formed here in double.
+extern "C" int isle_hip_topic_coherence(isle_ctx* c, int num_topics, int M, const uint32_t* top_words, double eps, double* coherence,
+                                        uint64_t* doc_freq, uint64_t* co_doc_freq) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(post_prepare(c, "topic_coherence"));
+  if (num_topics < 1) return isle_fail(c, ISLE_E_ARG, "topic_coherence: num_topics < 1");
+  if (M < 1 || M > 32) return isle_fail(c, ISLE_E_ARG, "topic_coherence: M = %d outside 1 .. 32", M);
+  if (!top_words || !coherence) return isle_fail(c, ISLE_E_ARG, "topic_coherence: null top_words or coherence");
+  const size_t n = (size_t)num_topics, m = (size_t)M, npt = m * (m - 1) / 2;
+  for (size_t t = 0; t < n; ++t) {
+    const uint32_t* w = top_words + t * m;
+    for (size_t i = 0; i < m; ++i) {
+      if (w[i] >= c->a_V) return isle_fail(c, ISLE_E_ARG, "topic_coherence: word %u of topic %zu >= vocab %llu", w[i], t, (unsigned long long)c->a_V);
+      for (size_t j = 0; j < i; ++j)
+        if (w[j] == w[i]) return isle_fail(c, ISLE_E_ARG, "topic_coherence: word %u repeats in topic %zu", w[i], t);
+    }
+  }
+  // U: distinct words ascending, local id = rank; P: distinct (lo, hi) pairs of local ids, sorted, as a CSR keyed by lo
+  std::vector<uint32_t> U(top_words, top_words + n * m);
+  std::sort(U.begin(), U.end());
+  U.erase(std::unique(U.begin(), U.end()), U.end());
+  std::vector<uint32_t> loc(n * m);
+  for (size_t i = 0; i < n * m; ++i) loc[i] = (uint32_t)(std::lower_bound(U.begin(), U.end(), top_words[i]) - U.begin());
+  std::vector<uint64_t> keys;
+  keys.reserve(n * npt);
+  for (size_t t = 0; t < n; ++t)
+    for (size_t i = 1; i < m; ++i)
+      for (size_t j = 0; j < i; ++j) {
+        const uint64_t a = loc[t * m + i], b = loc[t * m + j];
+        keys.push_back(a < b ? (a << 32 | b) : (b << 32 | a));
+      }
+  std::vector<uint64_t> P(keys);
+  std::sort(P.begin(), P.end());
+  P.erase(std::unique(P.begin(), P.end()), P.end());
+  std::vector<uint32_t> part_off(U.size() + 1, 0u), part_hi(P.size());
+  for (size_t p = 0; p < P.size(); ++p) {
+    part_off[(P[p] >> 32) + 1]++;
+    part_hi[p] = (uint32_t)P[p];
+  }
+  for (size_t u = 0; u < U.size(); ++u) part_off[u + 1] += part_off[u];
+
+  std::vector<uint32_t> cnt;
+  ISLECHK(k_coherence_counts(c, U, part_off, part_hi, cnt, nullptr));
+  const uint32_t* du = cnt.data();
+  const uint32_t* dp = cnt.data() + U.size();
+  for (size_t t = 0; t < n; ++t) {
+    double sum = 0.0;
+    bool undefined = false;
+    for (size_t i = 1; i < m; ++i)
+      for (size_t j = 0; j < i; ++j) {
+        const uint64_t key = keys[t * npt + i * (i - 1) / 2 + j];
+        const uint32_t dij = dp[std::lower_bound(P.begin(), P.end(), key) - P.begin()], dj = du[loc[t * m + j]];
+        if (dj == 0) undefined = true;
+        sum += std::log((double)dij + eps) - std::log((double)dj);
+        if (co_doc_freq) co_doc_freq[t * npt + i * (i - 1) / 2 + j] = dij;
+      }
+    coherence[t] = undefined ? std::nan("") : sum;
+    if (doc_freq)
+      for (size_t i = 0; i < m; ++i) doc_freq[t * m + i] = du[loc[t * m + i]];
+  }
+  return 0;
+}
+
 extern "C" int isle_hip_infer(isle_ctx* c, uint64_t V, int k, const float* model_by_word, uint64_t D, uint64_t nnz, const float* counts,
                               const uint32_t* rows, const int64_t* offs, int iters, float Lf, float avg_doc_sz, float* weights,
                               int32_t* top_topic, float* top_weight, float* llh, uint64_t* nconverged) {

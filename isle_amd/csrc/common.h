@@ -537,6 +537,11 @@ int k_post_model_thresholds(isle_ctx* c, uint32_t k, uint32_t rank);
 int k_post_model(isle_ctx* c, uint32_t k);
 int k_post_edge(isle_ctx* c, const int64_t* pairs_dev, int n, float a, float b, float* edge_dev);
 
+// coherence.hip: D(w) for the distinct top words U (ascending) and D(lo, hi) for the distinct pairs of their local ids (CSR keyed by lo),
+// over the count matrix A; counts = |U| + |P| entries on the host
+int k_coherence_counts(isle_ctx* c, const std::vector<uint32_t>& U, const std::vector<uint32_t>& part_off, const std::vector<uint32_t>& part_hi,
+                       std::vector<uint32_t>& counts, int* passes);
+
 // dense.hip
 int k_vtf(isle_ctx* c, const float* Vb, uint64_t n, int m, const float* F, int b, float* coef /*m x b col-major dev*/, uint64_t ld = 0);
 int k_update(isle_ctx* c, float* F, uint64_t n, int b, const float* Vb, int m, const float* coef, uint64_t ld = 0);

@@ -37,6 +37,8 @@ typedef uint32_t count_t;  // include/types.h:29
 #define ISLE_EPS3_C (5.0)          // :12
 #define ISLE_EDGE_TOPIC_MIN_DOCS 1          // :77
 #define ISLE_EDGE_TOPIC_PRIMARY_RATIO 0.7   // :79
+#define ISLE_DEFAULT_COHERENCE_EPS (1e-5)   // :74
+#define ISLE_DEFAULT_COHERENCE_NUM_WORDS 5  // :75
 
 class FPSparseMatrixHip {
   word_id_t vocab_size_;
@@ -261,6 +263,20 @@ class FPSparseMatrixHip {
       for (doc_id_t d = 0; d < num_docs_A; ++d)
         if (t1[d] >= 0 && t2[d] >= 0) top_topic_pairs->push_back(std::make_tuple((int)t1[d], (int)t2[d], d));
     }
+  }
+  // SparseMatrix::topic_coherence (src/sparseMatrix.cpp:841-870) on the count matrix this object was built from: the first M words of
+  // each top_words[t] (heaviest first), coherences[t] = the UMass sum of include/isle_hip.h (isle_hip_topic_coherence), NaN where a
+  // word in a denominator occurs in no document.  The reference's model argument only fed an assert and is dropped; coherences are
+  // double here (the reference accumulates in float, racing on coherences[topic]).
+  void topic_coherence(const doc_id_t num_topics, const word_id_t& M, const std::vector<std::pair<word_id_t, FPTYPE>>* top_words,
+                       std::vector<double>& coherences, const double coherence_eps = ISLE_DEFAULT_COHERENCE_EPS) {
+    std::vector<uint32_t> tw((size_t)num_topics * M);
+    for (doc_id_t t = 0; t < num_topics; ++t) {
+      if (top_words[t].size() < M) throw std::runtime_error("topic_coherence: topic " + std::to_string(t) + " has fewer than M top words");
+      for (word_id_t i = 0; i < M; ++i) tw[(size_t)t * M + i] = (uint32_t)top_words[t][i].first;
+    }
+    coherences.assign(num_topics, 0.0);
+    check(isle_hip_topic_coherence(ctx_, (int)num_topics, (int)M, tw.data(), coherence_eps, coherences.data(), nullptr, nullptr), "topic_coherence");
   }
   // ISLETrainer::construct_edge_topics_v2 (src/trainer.cpp:1116-1167): pair selection on the host, the FPaxpy pair on the
   // device.  Ties in the count ordering are broken by (primary, secondary) ascending (the reference's sort is unstable).

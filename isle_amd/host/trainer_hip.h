@@ -6,13 +6,20 @@
 // What runs where: ingest, thresholding, the hot path of train() (src/trainer.cpp:490-571), catchwords, the topic model and the edge
 // topics all run on the device through FPSparseMatrixHip (fpsparse_hip.h -> include/isle_hip.h); this class is the host-side order of
 // calls, the log lines (diagnosticLog.txt / timerLog.txt with the reference's formats) and the output files.
+// Topic coherence (compute_avg_coherence, off by default as in the reference): output_cluster_summary() scores the first
+// DEFAULT_COHERENCE_NUM_WORDS top words of every topic on the device (FPSparseMatrixHip::topic_coherence) and prints the reference's
+// commented-out "Coherence:" line per topic (:806), the real "Avg coherence:" (mean over topics with a finite value; a line counts the
+// others) and flt_coh.  Deviations: flt_coh of a row is that row's topic's value (the reference indexes it by sorted position), raw_coh
+// stays 0 (output_avg_topic_coherence is not mirrored).  With the flag off every output byte is what it was without it.
 // Not mirrored (dead under the shipped hyper-parameters or outside the path): load_preprocessed_data_from_file,
-// print_log_combinatorial, print_distinct_top_five_sets, compute_input_svd, the coherence / diversity outputs, construct_edge_topics_v1.
+// print_log_combinatorial, print_distinct_top_five_sets (their flags throw), print_doctopic (accepted, unused: the reference's use is
+// commented out), compute_input_svd, output_avg_topic_coherence, the diversity output, construct_edge_topics_v1.
 #pragma once
 #include <sys/stat.h>
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <ctime>
 #include <fstream>
 #include <iomanip>
@@ -137,6 +144,7 @@ class ISLETrainer {
   const std::string input_file, vocab_file, output_path_base;
   const bool flag_construct_edge_topics;
   const int max_edge_topics;
+  const bool flag_compute_avg_coherence, flag_print_doctopic, flag_print_top_two_topics;
   std::string log_dir;
   std::unique_ptr<trainer_detail::Logs> log;
 
@@ -191,11 +199,16 @@ class ISLETrainer {
   ISLETrainer(const word_id_t vocab_size_, const doc_id_t num_docs_, const offset_t max_entries_, const doc_id_t num_topics_, const bool tf_idf_,
               const bool sample_docs_, const FPTYPE sample_rate_, const data_ingest how_data_loaded_, const std::string& input_file_ = std::string(""),
               const std::string& vocab_file_ = std::string(""), const std::string& output_path_base_ = std::string(""),
-              const bool construct_edge_topics_ = false, const int max_edge_topics_ = 100000)
+              const bool construct_edge_topics_ = false, const int max_edge_topics_ = 100000, const bool compute_log_combinatorial_ = false,
+              const bool compute_distinct_top_five_sets_ = false, const bool compute_avg_coherence_ = false, const bool print_doctopic_ = false,
+              const bool print_top_two_topics_ = true)
       : vocab_size(vocab_size_), num_docs(num_docs_), max_entries(max_entries_), num_topics(num_topics_), flag_tf_idf(tf_idf_),
         flag_sample_docs(sample_docs_), sample_rate(sample_rate_), how_data_loaded(how_data_loaded_), input_file(input_file_),
         vocab_file(vocab_file_), output_path_base(output_path_base_), flag_construct_edge_topics(construct_edge_topics_),
-        max_edge_topics(max_edge_topics_) {
+        max_edge_topics(max_edge_topics_), flag_compute_avg_coherence(compute_avg_coherence_), flag_print_doctopic(print_doctopic_),
+        flag_print_top_two_topics(print_top_two_topics_) {
+    if (compute_log_combinatorial_) throw std::runtime_error("compute_log_combinatorial is not mirrored");
+    if (compute_distinct_top_five_sets_) throw std::runtime_error("compute_distinct_top_five_sets is not mirrored");
     // src/trainer.cpp:8-81: log directory, the two log files, then the data according to the ingest mode
     log_dir = trainer_detail::log_dir_name(num_topics, output_path_base, flag_sample_docs, sample_rate, flag_tf_idf);
     struct stat st;
@@ -349,7 +362,7 @@ class ISLETrainer {
     log->next_time_secs("Collecting word freqs in clusters");
     log->next_time_secs("Finding catchwords for clusters");
     Model = new FPTYPE[(size_t)vocab_size * num_topics];
-    B_fl_CSC->construct_topic_model(Model, num_topics, num_docs, flag_construct_edge_topics ? &top_topic_pairs : NULL);
+    B_fl_CSC->construct_topic_model(Model, num_topics, num_docs, flag_construct_edge_topics && flag_print_top_two_topics ? &top_topic_pairs : NULL);  // :648
     log->next_time_secs("Constructing topic vectors");
     is_training_complete = true;
   }
@@ -379,6 +392,19 @@ class ISLETrainer {
       if (tw[ntop - 1].second == (FPTYPE)0.0) std::cout << "\n ==== WARNING: top words in topic " << t << " have zero weight\n\n";
       tw.resize(ntop);
     }
+    std::vector<double> coherences(num_topics, 0.0);
+    double avg_coherence = 0.0;
+    doc_id_t undefined = 0;
+    if (flag_compute_avg_coherence) {
+      B_fl_CSC->topic_coherence(num_topics, std::min<word_id_t>(ISLE_DEFAULT_COHERENCE_NUM_WORDS, ntop), topwords.data(), coherences);
+      double sum = 0.0;
+      for (doc_id_t t = 0; t < num_topics; ++t) {
+        if (std::isfinite(coherences[t])) sum += coherences[t];
+        else ++undefined;
+      }
+      avg_coherence = sum / (double)(num_topics - undefined);
+      log->next_time_secs("Calculating coherence");
+    }
     for (doc_id_t t = 0; t < num_topics; ++t) {
       std::ostringstream o;
       o << "\n---------- Topic: " << t << ", Cluster_size: " << closest_docs[t].size() << " -----------\n";
@@ -388,10 +414,17 @@ class ISLETrainer {
       o << "\n#Top words: " << topwords[t].size() << "\n";  // src/denseMatrix.cpp:110-121
       for (auto& tw : topwords[t]) o << vocab_words[tw.first] << ":" << tw.first << "(" << tw.second << ") ";
       o << "\n\n";
+      if (flag_compute_avg_coherence) o << "\nCoherence: " << std::to_string(coherences[t]) << "\n";  // :806
       log->diag << o.str();
     }
     log->diag << "\n---------------------------\n";
-    log->print("\n Avg coherence: " + std::to_string(0.0f) + "\n\n");
+    if (flag_compute_avg_coherence) {
+      if (undefined)
+        log->print("\n Topics without a coherence (a top word occurs in no document): " + std::to_string(undefined) + "(" + std::to_string(num_topics) + ")\n");
+      log->print("\n Avg coherence: " + std::to_string(avg_coherence) + "\n\n");
+    } else {
+      log->print("\n Avg coherence: " + std::to_string(0.0f) + "\n\n");
+    }
     {  // LogUtils::print_cluster_details, include/logUtils.h:66-99
       std::vector<std::pair<int, doc_id_t>> cluster_sizes;
       for (doc_id_t t = 0; t < num_topics; ++t) cluster_sizes.push_back(std::make_pair((int)closest_docs[t].size(), t));
@@ -402,8 +435,10 @@ class ISLETrainer {
       for (doc_id_t i = 0; i < num_topics; ++i) {
         const doc_id_t t = cluster_sizes[i].second;
         o << std::setw(12) << std::left << "Cluster" << t << std::setw(12) << std::left << "  size:" << cluster_sizes[i].first << std::setw(15)
-          << std::left << "  distsq_sum:" << 0 << std::setw(15) << std::left << "  raw_coh:" << 0 << std::setw(15) << std::left << "  flt_coh:" << 0
-          << "  #catchwords: " << catchwords[t].size() << std::endl;
+          << std::left << "  distsq_sum:" << 0 << std::setw(15) << std::left << "  raw_coh:" << 0 << std::setw(15) << std::left << "  flt_coh:";
+        if (flag_compute_avg_coherence) o << coherences[t];  // topic t's own value (the reference prints coherences[i], i the sorted position)
+        else o << 0;
+        o << "  #catchwords: " << catchwords[t].size() << std::endl;
         if (catchwords[t].size() == 0) catchless++;
       }
       o << "\n#Topics with no catchwords: " << catchless << "(" << num_topics << ")" << std::endl;
@@ -451,6 +486,7 @@ class ISLETrainer {
   int get_num_edge_topics() { return (int)selected_pairs.size(); }                                                        // :998-1001
   void get_edge_model(FPTYPE* const edgeModel) { std::memcpy(edgeModel, EdgeModel.data(), EdgeModel.size() * sizeof(FPTYPE)); }  // :1003-1007
   const std::vector<FPTYPE>& eigenvalues() const { return evalues; }
+  const std::vector<std::vector<std::pair<word_id_t, FPTYPE>>>& top_words() const { return topwords; }  // after output_cluster_summary()
   const std::vector<doc_id_t>* partition() const { return closest_docs; }
 };
 

@@ -60,6 +60,37 @@ def select_edge_pairs(top1, top2, max_edge_topics, min_docs=EDGE_TOPIC_MIN_DOCS)
     return np.stack([key[order] // base, key[order] % base, cnt[order]], axis=1).astype(np.int64)
 
 
+DEFAULT_COHERENCE_EPS = 1e-5        # include/hyperparams.h:74
+DEFAULT_COHERENCE_NUM_WORDS = 5     # include/hyperparams.h:75
+
+
+def top_words(model, n, vocab_size=None):
+    """The n heaviest words of every topic, heaviest first and the lower word id first among equal weights: the trainer's rule
+    (DenseMatrix::find_n_top_words, src/denseMatrix.cpp:92-107, as isle_amd/host/trainer_hip.h applies it).  NaN weights (the topic
+    vector of an empty cluster) sort last.  model: a (V, cols) array, e.g. the V x k topic model of construct_topic_model or the
+    V x n edge model of edge_topics, or the same as a flat column-major buffer (get_basic_model / get_edge_model) with vocab_size
+    given.  -> uint32 (cols, min(n, V)), the rows what HotPath.topic_coherence takes."""
+    M = np.asarray(model)
+    if M.ndim == 1:
+        if vocab_size is None:
+            raise ValueError("a flat model needs vocab_size")
+        M = M.reshape(int(vocab_size), -1, order="F")
+    if M.ndim != 2:
+        raise ValueError("model must be (V, cols) or a flat column-major buffer")
+    V, k = M.shape
+    n = min(int(n), V)
+    out = np.empty((k, n), np.uint32)
+    if n == 0 or k == 0:
+        return out
+    W = np.where(np.isnan(M), -np.inf, M.astype(np.result_type(M.dtype, np.float32), copy=False))
+    kth = np.partition(W, V - n, axis=0)[V - n]          # the n-th largest weight of every column
+    for t in range(k):
+        cand = np.flatnonzero(W[:, t] >= kth[t])          # ascending ids: every word that can be among the n
+        order = np.lexsort((cand, -W[cand, t]))[:n]       # weight descending, then id ascending
+        out[t] = cand[order]
+    return out
+
+
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -257,6 +288,21 @@ class HotPath:
         E = np.empty((self.V, n), np.float32, order="F")
         self._chk(self._lib.isle_hip_edge_topics(self._h, _p(pairs), n, float(primary_ratio), _p(E)))
         return E
+
+    def topic_coherence(self, top_words, eps=DEFAULT_COHERENCE_EPS, fetch_counts=True):
+        """UMass coherence of each topic's top words over the count matrix A (SparseMatrix::topic_coherence,
+        src/sparseMatrix.cpp:841-1016; the formula, the NaN rule and the deviations: include/isle_hip.h).  top_words: (num_topics, M)
+        word ids, heaviest first (see top_words()).  -> dict(coherence float64 (num_topics,), doc_freq uint64 (num_topics, M),
+        co_doc_freq uint64 (num_topics, M(M-1)/2) with (i, j) at i(i-1)/2 + j); the two count arrays are None without fetch_counts."""
+        tw = np.ascontiguousarray(top_words, np.uint32)
+        if tw.ndim != 2:
+            raise ValueError("top_words must be (num_topics, M)")
+        n, M = tw.shape
+        coh = np.empty(n, np.float64)
+        df = np.empty((n, M), np.uint64) if fetch_counts else None
+        co = np.empty((n, max(M * (M - 1) // 2, 0)), np.uint64) if fetch_counts else None
+        self._chk(self._lib.isle_hip_topic_coherence(self._h, n, M, _p(tw), float(eps), _p(coh), _p(df), _p(co)))
+        return dict(coherence=coh, doc_freq=df, co_doc_freq=co)
 
     def frobenius(self):
         out = C.c_float()
