@@ -274,6 +274,35 @@ int isle_hip_edge_topics(isle_ctx* ctx, const int64_t* pairs, int n, float prima
 int isle_hip_topic_coherence(isle_ctx* ctx, int num_topics, int M, const uint32_t* top_words, double eps, double* coherence,
                              uint64_t* doc_freq, uint64_t* co_doc_freq);
 
+/* Corpus diagnostics of the trainer (print_log_combinatorial / print_distinct_top_five_sets, src/trainer.cpp:373-403) on the resident
+ * count matrix A, right after ingest or upload (no partition or B needed; single rank; ISLE_E_ARG without A).
+ *
+ * Log-combinatorial, SparseMatrix::compute_log_combinatorial (src/sparseMatrix.cpp:1018-1043): out[d] for every document of A,
+ *   N_d = sum of (int)count,  log_fact[0] = 0,  log_fact[i+1] = (float)((double)log_fact[i] + log(i+1)),
+ *   out[d] = ((0 - log_fact[(int)c_0]) - log_fact[(int)c_1] - ...) + log_fact[N_d]   in fp32, entries in CSC order (bit-equal).
+ * max_words (nullable): max N_d.  ISLE_E_ARG: out null, some N_d > INT_MAX (the reference indexes the table with an int).
+ * Deviation: the shipped reference cannot run it (normalize_docs(true) frees vals_CSC, src/sparseMatrix.cpp:163-166, before it reads
+ * them); this computes what the function says from the resident counts. */
+int isle_hip_log_combinatorial(isle_ctx* ctx, float* out, uint64_t* max_words);
+
+/* Distinct top-five sets, SparseMatrix::count_distint_top_five_words (src/sparseMatrix.cpp:170-215): for every document with at least
+ * 5 entries, the 5 largest normalised values avg_doc_sz * (count / doc_sum) (the values the catchword stage uses), descending, with
+ * multiplicity; the tuples sorted lexicographically ascending; num_distinct[i] = the reference's loop with min_distinct = m[i] over
+ * them (see isle_hip_top_five_count_rule).  num_quintuples (nullable): the number of tuples ("top five vec size").  quintuples
+ * (nullable, capacity docs(A) x 5): the sorted tuples, row-major.  run_lengths (nullable, capacity docs(A)) / num_runs (nullable): the
+ * lengths of the runs of equal tuples in sorted order, for isle_hip_top_five_count_rule.
+ * ISLE_E_ARG: n_m < 0, m or num_distinct null with n_m > 0, some m[i] < 2 (an assert in the reference).
+ * Deviation: the reference copies a document into a stack buffer of 1 << 15 values (undefined beyond); any length is handled here. */
+int isle_hip_distinct_top_five(isle_ctx* ctx, int n_m, const int32_t* m, uint64_t* num_distinct, uint64_t* num_quintuples, float* quintuples,
+                               uint64_t* run_lengths, uint64_t* num_runs);
+
+/* Host only: the counting loop of src/sparseMatrix.cpp:198-208 over n = sum(run_lengths) sorted tuples given as the lengths of their
+ * runs of equal tuples.  Literally  num = 0; it = prev = 0; while (it != n) { if (q[it] == q[prev]) { ++it; continue; }
+ * if (it - prev >= m) { prev = it; ++num; } ++it; }  (the trailing "if (prev - it >= m)" never fires), evaluated as jumps
+ * p -> p + max(rem(p), m), rem(p) = distance from p to the end of its run, counting each jump that lands before n.
+ * ISLE_E_ARG: out null, run_lengths null with n_runs > 0, a run of length 0, m < 2. */
+int isle_hip_top_five_count_rule(const uint64_t* run_lengths, uint64_t n_runs, int32_t m, uint64_t* out);
+
 /* ---- inference ---------------------------------------------------- */
 /* ISLEInfer over a batch of documents: drivers/ISLEInfer.cpp:60-112 (normalize_docs(true, true),
  * infer_doc_in_file per document, heaviest topics) with ISLEInfer::mwu / grad / calculate_llh

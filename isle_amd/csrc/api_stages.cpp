@@ -307,6 +307,21 @@ static int post_prepare(isle_ctx* c, const char* who) {
   return 0;
 }
 
+// a_nv = avg_doc_sz * (count / doc_sum) over A (src/sparseMatrix.cpp:136-167), the values the catchword stage and the top-five
+// diagnostic read; avg_doc_sz from the thresholding when it ran, else computed here by the same rule (:92-99)
+static int post_normalize_A(isle_ctx* c) {
+  if (!c->a_avg_valid) {  // B came from the host: the corpus statistics were never computed here
+    HIPCHK(c, c->a_scan.reserve(isle_scan_scratch(c->a_D) + 4));
+    ISLECHK(k_th_stats(c, (uint64_t*)c->a_scan.p));
+    uint64_t st[2];
+    HIPCHK(c, hipMemcpyAsync(st, c->a_scan.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->a_avg = (float)(st[0] / std::max<uint64_t>(st[1], 1));
+    c->a_avg_valid = true;
+  }
+  return k_post_normalize(c, c->a_avg);
+}
+
 extern "C" int isle_hip_catchwords(isle_ctx* c, int num_topics, const uint32_t* assign, uint64_t r, double rho, float* thresholds,
                                    int32_t* catch_topic, uint64_t* num_catchwords) {
   if (!c) return ISLE_E_ARG;
@@ -327,16 +342,7 @@ extern "C" int isle_hip_catchwords(isle_ctx* c, int num_topics, const uint32_t* 
   } else if (!c->assign_valid) {
     return isle_fail(c, ISLE_E_ARG, "catchwords: no partition resident (run isle_hip_lloyds_sparse or pass assign)");
   }
-  if (!c->a_avg_valid) {  // B came from the host: the corpus statistics were never computed here
-    HIPCHK(c, c->a_scan.reserve(isle_scan_scratch(c->a_D) + 4));
-    ISLECHK(k_th_stats(c, (uint64_t*)c->a_scan.p));
-    uint64_t st[2];
-    HIPCHK(c, hipMemcpyAsync(st, c->a_scan.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->a_avg = (float)(st[0] / std::max<uint64_t>(st[1], 1));
-    c->a_avg_valid = true;
-  }
-  ISLECHK(k_post_normalize(c, c->a_avg));
+  ISLECHK(post_normalize_A(c));
   ISLECHK(k_post_cluster_of(c, c->assign.p, identity));
   HIPCHK(c, c->counts.reserve(num_topics));
   ISLECHK(k_count_sizes(c, c->assign.p, c->D, num_topics, c->counts.p));
@@ -479,6 +485,55 @@ extern "C" int isle_hip_topic_coherence(isle_ctx* c, int num_topics, int M, cons
     if (doc_freq)
       for (size_t i = 0; i < m; ++i) doc_freq[t * m + i] = du[loc[t * m + i]];
   }
+  return 0;
+}
+
+// Corpus diagnostics of the trainer (src/trainer.cpp:373-403) on the count matrix A, right after ingest or upload (corpus_stats.hip).
+extern "C" int isle_hip_log_combinatorial(isle_ctx* c, float* out, uint64_t* max_words) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(post_prepare(c, "log_combinatorial"));
+  if (!out) return isle_fail(c, ISLE_E_ARG, "log_combinatorial: null out");
+  return k_log_combinatorial(c, out, max_words);
+}
+
+extern "C" int isle_hip_top_five_count_rule(const uint64_t* run_lengths, uint64_t n_runs, int32_t m, uint64_t* out) {
+  if (!out || (n_runs && !run_lengths) || m < 2) return ISLE_E_ARG;
+  uint64_t n = 0;
+  for (uint64_t r = 0; r < n_runs; ++r) {
+    if (run_lengths[r] == 0) return ISLE_E_ARG;
+    n += run_lengths[r];
+  }
+  // The loop of src/sparseMatrix.cpp:198-208 moves its mark from p to p + max(rem(p), m), rem(p) = distance from p to the end of
+  // its run, and counts every move that lands before n.  r: the run holding p, rb: the run's first position.
+  uint64_t num = 0, p = 0, r = 0, rb = 0;
+  while (n_runs) {
+    const uint64_t next = std::max(rb + run_lengths[r], p + (uint64_t)m);
+    if (next >= n) break;
+    ++num;
+    p = next;
+    while (rb + run_lengths[r] <= p) rb += run_lengths[r++];
+  }
+  *out = num;
+  return 0;
+}
+
+extern "C" int isle_hip_distinct_top_five(isle_ctx* c, int n_m, const int32_t* m, uint64_t* num_distinct, uint64_t* num_quintuples, float* quintuples,
+                                          uint64_t* run_lengths, uint64_t* num_runs) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(post_prepare(c, "distinct_top_five"));
+  if (n_m < 0 || (n_m && (!m || !num_distinct))) return isle_fail(c, ISLE_E_ARG, "distinct_top_five: n_m < 0, or null m / num_distinct");
+  for (int i = 0; i < n_m; ++i)
+    if (m[i] < 2) return isle_fail(c, ISLE_E_ARG, "distinct_top_five: m[%d] = %d < 2 (the reference asserts min_distinct >= 2)", i, (int)m[i]);
+  ISLECHK(post_normalize_A(c));
+  uint64_t n = 0;
+  std::vector<uint64_t> runs;
+  ISLECHK(k_top_five_runs(c, &n, runs, quintuples));
+  for (int i = 0; i < n_m; ++i) (void)isle_hip_top_five_count_rule(runs.data(), runs.size(), m[i], &num_distinct[i]);
+  if (num_quintuples) *num_quintuples = n;
+  if (num_runs) *num_runs = runs.size();
+  if (run_lengths && !runs.empty()) std::memcpy(run_lengths, runs.data(), runs.size() * sizeof(uint64_t));
   return 0;
 }
 

@@ -542,6 +542,12 @@ int k_post_edge(isle_ctx* c, const int64_t* pairs_dev, int n, float a, float b, 
 int k_coherence_counts(isle_ctx* c, const std::vector<uint32_t>& U, const std::vector<uint32_t>& part_off, const std::vector<uint32_t>& part_hi,
                        std::vector<uint32_t>& counts, int* passes);
 
+// corpus_stats.hip: the trainer's corpus diagnostics on A.  k_log_combinatorial: out (host, a_D floats), max_words (nullable);
+// k_top_five_runs (needs a_nv): the number of documents with >= 5 entries, the run lengths of their sorted top-five tuples, the
+// tuples (nullable, host, n x 5)
+int k_log_combinatorial(isle_ctx* c, float* out, uint64_t* max_words);
+int k_top_five_runs(isle_ctx* c, uint64_t* n_out, std::vector<uint64_t>& runs, float* tuples);
+
 // dense.hip
 int k_vtf(isle_ctx* c, const float* Vb, uint64_t n, int m, const float* F, int b, float* coef /*m x b col-major dev*/, uint64_t ld = 0);
 int k_update(isle_ctx* c, float* F, uint64_t n, int b, const float* Vb, int m, const float* coef, uint64_t ld = 0);

@@ -48,6 +48,10 @@ class FPSparseMatrixHip {
   bool uploaded_ = false;
   doc_id_t U_cols_ = 0;
   int last_nconv_ = 0;  // Ritz pairs that really passed the residual test in the last compute_block_ks
+  doc_id_t a_docs_ = 0;  // documents of the count matrix A (from_counts / from_tdf)
+  std::vector<uint64_t> top5_runs_;  // count_distint_top_five_words: run lengths of the sorted tuples, from the first call
+  uint64_t top5_n_ = 0;
+  bool top5_ready_ = false;
 
   void check(int rc, const char* what) const {
     if (rc != 0) throw std::runtime_error(std::string(what) + ": " + isle_hip_last_error(ctx_));
@@ -109,6 +113,7 @@ class FPSparseMatrixHip {
     try {
       B->check(isle_hip_upload_counts_u32(B->ctx_, vocab_size, num_docs, (uint64_t)offsets[num_docs], counts, rows, offsets, 0, num_docs),
                "upload_counts");
+      B->a_docs_ = num_docs;
       B->threshold_on_device(num_topics, sample_rate, original_cols, zetas, entries_above_threshold, avg_doc_sz);
     } catch (...) {
       delete B;
@@ -127,6 +132,7 @@ class FPSparseMatrixHip {
     FPSparseMatrixHip* B = new FPSparseMatrixHip(vocab_size, 0, device);
     try {
       B->check(isle_hip_ingest_tdf(B->ctx_, text, nbytes, vocab_size, num_docs, (uint64_t)max_entries, nullptr, entries_in_A), "ingest_tdf");
+      B->a_docs_ = num_docs;
       B->threshold_on_device(num_topics, sample_rate, original_cols, nullptr, entries_above_threshold, avg_doc_sz);
     } catch (...) {
       delete B;
@@ -277,6 +283,30 @@ class FPSparseMatrixHip {
     }
     coherences.assign(num_topics, 0.0);
     check(isle_hip_topic_coherence(ctx_, (int)num_topics, (int)M, tw.data(), coherence_eps, coherences.data(), nullptr, nullptr), "topic_coherence");
+  }
+  // SparseMatrix::compute_log_combinatorial (src/sparseMatrix.cpp:1018-1043) on the count matrix this object was built from: every
+  // document's log(N_d! / prod count!) with the reference's fp32 table and order (isle_hip_log_combinatorial), bit for bit.
+  void compute_log_combinatorial(std::vector<FPTYPE>& docs_log_fact) {
+    if (!docs_log_fact.empty()) throw std::runtime_error("compute_log_combinatorial: docs_log_fact must be empty");  // :1036
+    docs_log_fact.resize(a_docs_);
+    if (a_docs_) check(isle_hip_log_combinatorial(ctx_, docs_log_fact.data(), nullptr), "compute_log_combinatorial");
+  }
+  // SparseMatrix::count_distint_top_five_words (src/sparseMatrix.cpp:170-215; the reference's spelling): the device sorts the documents'
+  // top-five tuples once, the run lengths stay here, and every call evaluates the counting loop for its min_distinct on them
+  // (isle_hip_top_five_count_rule).  Prints "top five vec size: " as the reference does on every call.
+  size_t count_distint_top_five_words(int min_distinct) {
+    if (min_distinct < 2) throw std::runtime_error("count_distint_top_five_words: min_distinct < 2");  // :172
+    if (!top5_ready_) {
+      top5_runs_.assign(std::max<doc_id_t>(a_docs_, 1), 0);
+      uint64_t nr = 0;
+      check(isle_hip_distinct_top_five(ctx_, 0, nullptr, nullptr, &top5_n_, nullptr, top5_runs_.data(), &nr), "count_distint_top_five_words");
+      top5_runs_.resize(nr);
+      top5_ready_ = true;
+    }
+    std::cout << "top five vec size: " << top5_n_ << std::endl;
+    uint64_t num = 0;
+    check(isle_hip_top_five_count_rule(top5_runs_.data(), top5_runs_.size(), min_distinct, &num), "top_five_count_rule");
+    return (size_t)num;
   }
   // ISLETrainer::construct_edge_topics_v2 (src/trainer.cpp:1116-1167): pair selection on the host, the FPaxpy pair on the
   // device.  Ties in the count ordering are broken by (primary, secondary) ascending (the reference's sort is unstable).

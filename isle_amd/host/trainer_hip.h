@@ -11,9 +11,12 @@
 // commented-out "Coherence:" line per topic (:806), the real "Avg coherence:" (mean over topics with a finite value; a line counts the
 // others) and flt_coh.  Deviations: flt_coh of a row is that row's topic's value (the reference indexes it by sorted position), raw_coh
 // stays 0 (output_avg_topic_coherence is not mirrored).  With the flag off every output byte is what it was without it.
+// Corpus diagnostics (compute_log_combinatorial / compute_distinct_top_five_sets, off by default as in the reference): right after the
+// data is in (both ingest modes), print_log_combinatorial() writes LogCombinatorial.txt and print_distinct_top_five_sets() prints the
+// "Distinct top five sets:" line, both computed on the device from A (FPSparseMatrixHip, include/isle_hip.h for the deviations).
 // Not mirrored (dead under the shipped hyper-parameters or outside the path): load_preprocessed_data_from_file,
-// print_log_combinatorial, print_distinct_top_five_sets (their flags throw), print_doctopic (accepted, unused: the reference's use is
-// commented out), compute_input_svd, output_avg_topic_coherence, the diversity output, construct_edge_topics_v1.
+// print_doctopic (accepted, unused: the reference's use is commented out), compute_input_svd, output_avg_topic_coherence, the diversity
+// output, construct_edge_topics_v1.
 #pragma once
 #include <sys/stat.h>
 
@@ -144,6 +147,7 @@ class ISLETrainer {
   const std::string input_file, vocab_file, output_path_base;
   const bool flag_construct_edge_topics;
   const int max_edge_topics;
+  const bool flag_compute_log_combinatorial, flag_compute_distinct_top_five_sets;
   const bool flag_compute_avg_coherence, flag_print_doctopic, flag_print_top_two_topics;
   std::string log_dir;
   std::unique_ptr<trainer_detail::Logs> log;
@@ -183,11 +187,29 @@ class ISLETrainer {
       << std::setw(15) << std::left << "#Edge topics" << max_edge_topics << std::endl;
     log->print(s.str());
   }
+  void print_log_combinatorial() {  // src/trainer.cpp:373-383
+    std::vector<FPTYPE> docsLogFact;
+    B_fl_CSC->compute_log_combinatorial(docsLogFact);
+    std::ofstream out_comb_log(log_dir + "/LogCombinatorial.txt");
+    for (auto iter = docsLogFact.begin(); iter != docsLogFact.end(); ++iter) out_comb_log << *iter << std::endl;
+    out_comb_log.close();
+    log->next_time_secs("Print Log Combinatorial");
+  }
+  void print_distinct_top_five_sets() {  // src/trainer.cpp:389-403
+    std::ostringstream ostr;
+    ostr << "Distinct top five sets: ";
+    for (int m : {2, 5, 10, 20, 50, 100, 200, 500}) ostr << B_fl_CSC->count_distint_top_five_words(m) << " ";
+    ostr << std::endl;
+    log->print(ostr.str());
+    log->next_time_secs("Distinct top-5 words");
+  }
   void after_matrices_built() {  // the log lines of finalize_data / the thresholding block of train() (src/trainer.cpp:236-371, :430-485)
     log->next_time_secs("Sorting entries");
     log->next_time_secs("De-duplicating entries");
     std::cout << "Entries in sparse matrix: " << entries_in_A << std::endl << "Average document size: " << avg_doc_sz << std::endl;
     log->next_time_secs("Populating CSC");
+    if (flag_compute_log_combinatorial) print_log_combinatorial();  // the end of load_data_from_file / finalize_data (:148-149, :210-211)
+    if (flag_compute_distinct_top_five_sets) print_distinct_top_five_sets();
     log->next_time_secs("Computing thresholds");
     log->print("Number of entries above threshold: " + std::to_string(entries_above_threshold) + "\n");
     std::cout << (flag_sample_docs ? "After sampling docs: cols remaining: " : "Columns remaining after thresholding: ") << B_fl_CSC->num_docs() << "\n";
@@ -205,10 +227,9 @@ class ISLETrainer {
       : vocab_size(vocab_size_), num_docs(num_docs_), max_entries(max_entries_), num_topics(num_topics_), flag_tf_idf(tf_idf_),
         flag_sample_docs(sample_docs_), sample_rate(sample_rate_), how_data_loaded(how_data_loaded_), input_file(input_file_),
         vocab_file(vocab_file_), output_path_base(output_path_base_), flag_construct_edge_topics(construct_edge_topics_),
-        max_edge_topics(max_edge_topics_), flag_compute_avg_coherence(compute_avg_coherence_), flag_print_doctopic(print_doctopic_),
-        flag_print_top_two_topics(print_top_two_topics_) {
-    if (compute_log_combinatorial_) throw std::runtime_error("compute_log_combinatorial is not mirrored");
-    if (compute_distinct_top_five_sets_) throw std::runtime_error("compute_distinct_top_five_sets is not mirrored");
+        max_edge_topics(max_edge_topics_), flag_compute_log_combinatorial(compute_log_combinatorial_),
+        flag_compute_distinct_top_five_sets(compute_distinct_top_five_sets_), flag_compute_avg_coherence(compute_avg_coherence_),
+        flag_print_doctopic(print_doctopic_), flag_print_top_two_topics(print_top_two_topics_) {
     // src/trainer.cpp:8-81: log directory, the two log files, then the data according to the ingest mode
     log_dir = trainer_detail::log_dir_name(num_topics, output_path_base, flag_sample_docs, sample_rate, flag_tf_idf);
     struct stat st;

@@ -304,6 +304,29 @@ class HotPath:
         self._chk(self._lib.isle_hip_topic_coherence(self._h, n, M, _p(tw), float(eps), _p(coh), _p(df), _p(co)))
         return dict(coherence=coh, doc_freq=df, co_doc_freq=co)
 
+    # ---- corpus diagnostics of the trainer on A (include/isle_hip.h for the rules and the deviations) ----------------------
+    def log_combinatorial(self):
+        """SparseMatrix::compute_log_combinatorial (src/sparseMatrix.cpp:1018-1043) on the count matrix A: every document's
+        log(N_d! / prod c!) from the reference's fp32 table, bit for bit.  -> float32 (docs,)."""
+        D = getattr(self, "_a_shape", (0, 0, 0))[1]
+        out = np.empty(max(D, 1), np.float32)
+        self._chk(self._lib.isle_hip_log_combinatorial(self._h, _p(out), None))
+        return out[:D]
+
+    def distinct_top_five_sets(self, m=(2, 5, 10, 20, 50, 100, 200, 500), fetch_quintuples=False):
+        """SparseMatrix::count_distint_top_five_words (src/sparseMatrix.cpp:170-215) on the count matrix A for every min_distinct in m
+        (the trainer's eight by default).  -> dict(counts {m: count}, num_quintuples, run_lengths uint64 (runs,), quintuples float32
+        (num_quintuples, 5) sorted lexicographically, or None without fetch_quintuples)."""
+        ms = np.ascontiguousarray(m, np.int32).reshape(-1)
+        D = getattr(self, "_a_shape", (0, 0, 0))[1]
+        cnt = np.empty(max(ms.size, 1), np.uint64)
+        nq, nr = C.c_uint64(), C.c_uint64()
+        runs = np.empty(max(D, 1), np.uint64)
+        q = np.empty((max(D, 1), 5), np.float32) if fetch_quintuples else None
+        self._chk(self._lib.isle_hip_distinct_top_five(self._h, int(ms.size), _p(ms), _p(cnt), C.byref(nq), _p(q), _p(runs), C.byref(nr)))
+        return dict(counts={int(v): int(c) for v, c in zip(ms, cnt)}, num_quintuples=int(nq.value), run_lengths=runs[:nr.value].copy(),
+                    quintuples=None if q is None else q[:nq.value].copy())
+
     def frobenius(self):
         out = C.c_float()
         self._chk(self._lib.isle_hip_frobenius(self._h, C.byref(out)))
