@@ -697,6 +697,8 @@ extern "C" int isle_hip_gram_apply(isle_ctx* c, const float* X, int b, float* Z)
   if (!c || !X || !Z) return ISLE_E_ARG;
   if (c->V == 0) return isle_fail(c, ISLE_E_ARG, "no matrix uploaded");
   ISLECHK(isle_enter(c));
+  // before the copy: b sizes the host read (b < 1 would wrap the size)
+  if (b < 1 || b > 32) return isle_fail(c, ISLE_E_ARG, "gram_apply: b = %d not in [1, 32]", b);
   const size_t n = (size_t)c->V * b;
   HIPCHK(c, c->Xcm.reserve(n));
   HIPCHK(c, c->Zcm.reserve(n));

@@ -176,20 +176,25 @@ __global__ __launch_bounds__(256) void csr_count_k(const uint32_t* __restrict__ 
   const size_t base = (size_t)(d / Cc) * V;
   for (int64_t i = offs[d] + lane; i < offs[d + 1]; i += 64) atomicAdd(&cnt[base + rows[i]], 1u);
 }
+// One wave per chunk walks the chunk's documents in order: a (chunk, word) segment lists its documents ascending, so the gather's sums
+// run in one order whatever the scheduling (Z depends on B alone).  A document holds a word once, so the lanes of one document touch
+// distinct cells, and no other wave touches this chunk's cells.  A build walks Cc (<= 32768 by default) documents per wave.
 __global__ __launch_bounds__(256) void csr_fill_k(const float* __restrict__ vals, const uint32_t* __restrict__ rows,
-                                                   const int64_t* __restrict__ offs, uint32_t D, uint32_t V, uint32_t Cc,
+                                                   const int64_t* __restrict__ offs, uint32_t D, uint32_t V, uint32_t Cc, uint32_t nch,
                                                    const int64_t* __restrict__ seg_off, uint32_t* __restrict__ fill,
                                                    uint32_t* __restrict__ ccol, float* __restrict__ cval) {
   const int lane = threadIdx.x & 63;
-  const uint32_t d = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (d >= D) return;
-  const size_t base = (size_t)(d / Cc) * V;
-  for (int64_t i = offs[d] + lane; i < offs[d + 1]; i += 64) {
-    const size_t cell = base + rows[i];
-    const int64_t pos = seg_off[cell] + atomicAdd(&fill[cell], 1u);
-    ccol[pos] = d;
-    cval[pos] = vals[i];
-  }
+  const uint32_t ch = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (ch >= nch) return;
+  const size_t base = (size_t)ch * V;
+  const uint64_t d0 = (uint64_t)ch * Cc, d1 = d0 + Cc < D ? d0 + Cc : D;
+  for (uint64_t d = d0; d < d1; ++d)
+    for (int64_t i = offs[d] + lane; i < offs[d + 1]; i += 64) {
+      const size_t cell = base + rows[i];
+      const int64_t pos = seg_off[cell] + atomicAdd(&fill[cell], 1u);  // returned before the next document's lanes ask
+      ccol[pos] = (uint32_t)d;
+      cval[pos] = vals[i];
+    }
 }
 
 // The operator build of a solve: decides between the LDS-banded form (gram_lds.hip; every row of B holds one value) and the
@@ -229,8 +234,8 @@ int k_band_build_chunked(isle_ctx* c) {
   HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, cnt, ncell, c->seg_off.p, blk)));
   HIPCHK(c, hipMemsetAsync(cnt, 0, ncell * sizeof(uint32_t), c->stream));
   if (D)
-    hipLaunchKernelGGL(csr_fill_k, dim3(cdiv(D, 4)), dim3(256), 0, c->stream, c->vals.p, c->rows.p, c->offs.p, D, V, Cc, c->seg_off.p,
-                       cnt, c->bcol.p, c->bval.p);
+    hipLaunchKernelGGL(csr_fill_k, dim3(cdiv(nch, 4)), dim3(256), 0, c->stream, c->vals.p, c->rows.p, c->offs.p, D, V, Cc, nch,
+                       c->seg_off.p, cnt, c->bcol.p, c->bval.p);
   HIPCHK(c, hipGetLastError());
   int64_t total = 0;
   HIPCHK(c, hipMemcpyAsync(&total, c->seg_off.p + ncell, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
