@@ -274,6 +274,41 @@ int isle_hip_edge_topics(isle_ctx* ctx, const int64_t* pairs, int n, float prima
 int isle_hip_topic_coherence(isle_ctx* ctx, int num_topics, int M, const uint32_t* top_words, double eps, double* coherence,
                              uint64_t* doc_freq, uint64_t* co_doc_freq);
 
+/* The cluster-average topic model of ISLETrainer::output_avg_topic_coherence (src/trainer.cpp:705-745: construct_topic_model with
+ * no catchwords): every topic is the L1-normalised sum of its cluster's documents.  Valid after isle_hip_catchwords(num_topics); it
+ * reads the partition mapped onto A's documents there (documents dropped by sampling belong to no topic) and the normalised values
+ * nv the catch model reads.  With s_t[w] = sum over the documents d of cluster t of nv[w, d]:
+ *   model[:, t] = s_t / sum_w s_t[w]
+ * s_t is the exact sum of the fp32 values (every value is an integer multiple of the smallest value's ulp: fixed-point integer
+ * sums), divided in double and rounded once to float, so |m - m64| <= 2^-22 |m64| against fp64 sums of the same nv, entries with
+ * no contribution are exactly 0, an empty cluster gives a NaN column (0 / 0, the catch model's rule), and two calls give the same
+ * bits.  The model stays resident in a buffer of its own (the catch model is untouched) until A, the partition or the catchwords
+ * change.  model (nullable): vocab x num_topics column-major.  ISLE_E_ARG: no count matrix, world > 1, no catchword pass with
+ * num_topics.  ISLE_E_NUMERIC: the normalised values span more than the 2^64 range of the accumulator (a ratio above 2^40).
+ * Deviation from the reference: it accumulates in fp32. */
+int isle_hip_avg_topic_model(isle_ctx* ctx, int num_topics, float* model);
+
+/* Models isle_hip_model_top_words and isle_hip_topic_diversity read. */
+#define ISLE_MODEL_CATCH 0 /* the resident topic model of isle_hip_topic_model */
+#define ISLE_MODEL_AVG 1   /* the resident average model of isle_hip_avg_topic_model */
+#define ISLE_MODEL_HOST 2  /* model_host: vocab x ncols column-major, uploaded for the call */
+
+/* The n heaviest words of every column of a model (DenseMatrix::find_n_top_words, src/denseMatrix.cpp:92-107, with the trainer's
+ * order): heaviest first, the lower word id first among equal weights (-0 == +0), NaN (and -inf) last.  Exact: a radix select on
+ * the float bits per column, one read of the model.  ids: ncols x n row-major; weights (nullable): the model entries at those ids.
+ * For CATCH and AVG, vocab and ncols must be the resident model's (V of A, num_topics); model_host is ignored.
+ * ISLE_E_ARG: world > 1, n < 1 or n > min(vocab, 32), an unknown model, a resident model that does not exist (yet), a size mismatch,
+ * ids or (HOST) model_host null. */
+int isle_hip_model_top_words(isle_ctx* ctx, int which, const float* model_host, uint64_t vocab, int ncols, int n, uint32_t* ids, float* weights);
+
+/* Topic diversity (ISLETrainer::output_topic_diversity, src/trainer.cpp:750-774) of a resident model (CATCH or AVG), in double
+ * with a fixed reduction order.  A topic is finite when every entry of its vector is; k' = the number of finite topics.
+ *   abar = (1/k') sum over finite t of m_t      dist[t] = sum_w (m_t[w] - abar[w])^2      avg = mean of dist over finite t
+ * Non-finite topics get dist = NaN; no finite topic gives avg = NaN.  dist: num_topics doubles (nullable); avg (nullable).
+ * Deviations from the reference: its cross term uses topic 1's vector for every topic (:769-771) and it accumulates in fp32.
+ * ISLE_E_ARG: world > 1, an unknown or HOST model, a resident model that does not exist, num_topics not the model's. */
+int isle_hip_topic_diversity(isle_ctx* ctx, int which, int num_topics, double* dist, double* avg);
+
 /* Corpus diagnostics of the trainer (print_log_combinatorial / print_distinct_top_five_sets, src/trainer.cpp:373-403) on the resident
  * count matrix A, right after ingest or upload (no partition or B needed; single rank; ISLE_E_ARG without A).
  *

@@ -599,6 +599,7 @@ static int upload_common(isle_ctx* c, uint64_t V, uint64_t D, uint64_t nnz, cons
   c->assign_valid = false;
   c->p_catch_ready = false;
   c->p_model_ready = false;
+  c->p_avg_ready = false;
   c->b_from_threshold = false;
   c->kmpp_track_k = 0;
   isle_trim_derived(c, D, nnz);

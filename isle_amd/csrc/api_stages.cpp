@@ -45,6 +45,7 @@ extern "C" int isle_hip_upload_counts_u32(isle_ctx* c, uint64_t V, uint64_t D, u
   c->a_avg_valid = false;
   c->p_catch_ready = false;
   c->p_model_ready = false;
+  c->p_avg_ready = false;
   return 0;
 }
 
@@ -79,6 +80,7 @@ extern "C" int isle_hip_ingest_tdf(isle_ctx* c, const char* text, uint64_t nbyte
   c->a_avg_valid = false;
   c->p_catch_ready = false;
   c->p_model_ready = false;
+  c->p_avg_ready = false;
   if (entries_read) *entries_read = nread;
   if (nnz) *nnz = c->a_nnz;
   return 0;
@@ -267,6 +269,7 @@ extern "C" int isle_hip_threshold(isle_ctx* c, uint64_t num_topics, double sampl
   c->assign_valid = false;
   c->p_catch_ready = false;
   c->p_model_ready = false;
+  c->p_avg_ready = false;
   c->b_from_threshold = true;
   if (docs_kept) *docs_kept = Db;
   if (nnz_kept) *nnz_kept = bnnz;
@@ -353,6 +356,7 @@ extern "C" int isle_hip_catchwords(isle_ctx* c, int num_topics, const uint32_t* 
   c->p_k = num_topics;
   c->p_catch_ready = true;
   c->p_model_ready = false;
+  c->p_avg_ready = false;
   if (thresholds) {
     HIPCHK(c, c->p_segvals.reserve((size_t)c->a_V * num_topics));
     ISLECHK(k_post_thr_colmajor(c, (uint32_t)num_topics, c->p_segvals.p));
@@ -487,6 +491,100 @@ extern "C" int isle_hip_topic_coherence(isle_ctx* c, int num_topics, int M, cons
   }
   return 0;
 }
+
+// The cluster-average model (src/trainer.cpp:705-745) and what reads a model: top words (src/denseMatrix.cpp:92-107) and diversity
+// (src/trainer.cpp:750-774); avg_model.hip
+extern "C" int isle_hip_avg_topic_model(isle_ctx* c, int num_topics, float* model) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(post_prepare(c, "avg_topic_model"));
+  if (num_topics < 1 || !c->p_catch_ready || c->p_k != num_topics)
+    return isle_fail(c, ISLE_E_ARG, "avg_topic_model: run isle_hip_catchwords(num_topics = %d) first", num_topics);
+  c->p_avg_ready = false;
+  ISLECHK(k_avg_model(c, (uint32_t)num_topics));
+  c->p_avg_ready = true;
+  if (model) HIPCHK(c, hipMemcpyAsync(model, c->p_avg_model.p, (size_t)c->a_V * num_topics * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// the resident model `which` names, or null with the reason in the context
+static const float* resident_model(isle_ctx* c, int which, const char* who) {
+  if (which == ISLE_MODEL_CATCH) {
+    if (c->p_model_ready) return c->p_model.p;
+    isle_fail(c, ISLE_E_ARG, "%s: no catch model (run isle_hip_topic_model)", who);
+  } else if (which == ISLE_MODEL_AVG) {
+    if (c->p_avg_ready) return c->p_avg_model.p;
+    isle_fail(c, ISLE_E_ARG, "%s: no average model (run isle_hip_avg_topic_model)", who);
+  } else {
+    isle_fail(c, ISLE_E_ARG, "%s: unknown model %d", who, which);
+  }
+  return nullptr;
+}
+
+extern "C" int isle_hip_model_top_words(isle_ctx* c, int which, const float* model_host, uint64_t vocab, int ncols, int n, uint32_t* ids,
+                                        float* weights) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "model_top_words: single-rank only");
+  if (ncols < 0 || vocab == 0 || vocab > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "model_top_words: vocab or ncols out of range");
+  if (n < 1 || n > 32 || (uint64_t)n > vocab) return isle_fail(c, ISLE_E_ARG, "model_top_words: n = %d outside 1 .. min(vocab, 32)", n);
+  if (!ids) return isle_fail(c, ISLE_E_ARG, "model_top_words: null ids");
+  const float* dev = nullptr;
+  DevBuf<float> up;
+  if (which == ISLE_MODEL_HOST) {
+    if (!model_host && ncols) return isle_fail(c, ISLE_E_ARG, "model_top_words: null model_host");
+    if (ncols) {
+      HIPCHK(c, up.reserve(vocab * (size_t)ncols));
+      HIPCHK(c, hipMemcpyAsync(up.p, model_host, vocab * (size_t)ncols * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    }
+    dev = up.p;
+  } else {
+    dev = resident_model(c, which, "model_top_words");
+    if (!dev) return ISLE_E_ARG;
+    if (vocab != c->a_V || ncols != c->p_k)
+      return isle_fail(c, ISLE_E_ARG, "model_top_words: vocab x ncols = %llu x %d, the resident model is %llu x %d", (unsigned long long)vocab, ncols,
+                       (unsigned long long)c->a_V, c->p_k);
+  }
+  if (ncols == 0) return 0;
+  const size_t m = (size_t)ncols * n;
+  DevBuf<uint32_t> id_d;
+  DevBuf<float> w_d;
+  HIPCHK(c, id_d.reserve(m));
+  HIPCHK(c, w_d.reserve(m));
+  ISLECHK(k_model_top_words(c, dev, vocab, (uint32_t)ncols, n, id_d.p, w_d.p));
+  HIPCHK(c, hipMemcpyAsync(ids, id_d.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (weights) HIPCHK(c, hipMemcpyAsync(weights, w_d.p, m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+extern "C" int isle_hip_topic_diversity(isle_ctx* c, int which, int num_topics, double* dist, double* avg) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "topic_diversity: single-rank only");
+  const float* dev = resident_model(c, which, "topic_diversity");
+  if (!dev) return ISLE_E_ARG;
+  if (num_topics != c->p_k) return isle_fail(c, ISLE_E_ARG, "topic_diversity: num_topics = %d, the resident model has %d", num_topics, c->p_k);
+  const uint32_t k = (uint32_t)num_topics;
+  DevBuf<double> dd, ab;
+  DevBuf<int32_t> fin;
+  HIPCHK(c, dd.reserve(k));
+  HIPCHK(c, ab.reserve(c->a_V));
+  HIPCHK(c, fin.reserve(k));
+  uint32_t kp = 0;
+  ISLECHK(k_topic_diversity(c, dev, c->a_V, k, dd.p, ab.p, fin.p, &kp));
+  std::vector<double> h(k);
+  HIPCHK(c, hipMemcpyAsync(h.data(), dd.p, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  double s = 0.0;
+  for (uint32_t t = 0; t < k; ++t)
+    if (std::isfinite(h[t])) s += h[t];
+  if (dist) std::memcpy(dist, h.data(), k * sizeof(double));
+  if (avg) *avg = kp ? s / (double)kp : std::nan("");
+  return 0;
+}
+
 
 // Corpus diagnostics of the trainer (src/trainer.cpp:373-403) on the count matrix A, right after ingest or upload (corpus_stats.hip).
 extern "C" int isle_hip_log_combinatorial(isle_ctx* c, float* out, uint64_t* max_words) {

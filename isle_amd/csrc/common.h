@@ -209,8 +209,10 @@ struct isle_ctx {
   DevBuf<int64_t> p_toff;
   DevBuf<float> p_mthr;            // k
   DevBuf<float> p_model;           // V x k col-major
+  DevBuf<uint64_t> p_avg_acc;      // V x k (lo, hi) pairs: exact fixed-point sums of the average model (avg_model.hip)
+  DevBuf<float> p_avg_model;       // V x k col-major, the cluster-average model
   int p_k = 0;                     // num_topics of the last catchword pass
-  bool p_catch_ready = false, p_model_ready = false, assign_valid = false;
+  bool p_catch_ready = false, p_model_ready = false, p_avg_ready = false, assign_valid = false;
 
   // --- chunked-CSR copy of B for Z = B*Y (built per eigensolve, like the reference's operator ctor)
   bool band_ready = false;
@@ -541,6 +543,13 @@ int k_post_edge(isle_ctx* c, const int64_t* pairs_dev, int n, float a, float b, 
 // over the count matrix A; counts = |U| + |P| entries on the host
 int k_coherence_counts(isle_ctx* c, const std::vector<uint32_t>& U, const std::vector<uint32_t>& part_off, const std::vector<uint32_t>& part_hi,
                        std::vector<uint32_t>& counts, int* passes);
+
+// avg_model.hip: the cluster-average model into c->p_avg_model (needs a_nv and p_cluster_of); the n heaviest words of every column of a
+// device model (ids / weights: ncols x n on the device); topic diversity of a device model (dist, abar: device; kprime: host)
+int k_avg_model(isle_ctx* c, uint32_t k);
+int k_model_top_words(isle_ctx* c, const float* model_dev, uint64_t V, uint32_t ncols, int n, uint32_t* ids_dev, float* weights_dev);
+int k_topic_diversity(isle_ctx* c, const float* model_dev, uint64_t V, uint32_t k, double* dist_dev, double* abar_dev, int32_t* finite_dev,
+                      uint32_t* kprime);
 
 // corpus_stats.hip: the trainer's corpus diagnostics on A.  k_log_combinatorial: out (host, a_D floats), max_words (nullable);
 // k_top_five_runs (needs a_nv): the number of documents with >= 5 entries, the run lengths of their sorted top-five tuples, the

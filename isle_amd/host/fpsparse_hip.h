@@ -284,6 +284,29 @@ class FPSparseMatrixHip {
     coherences.assign(num_topics, 0.0);
     check(isle_hip_topic_coherence(ctx_, (int)num_topics, (int)M, tw.data(), coherence_eps, coherences.data(), nullptr, nullptr), "topic_coherence");
   }
+  // The cluster-average topic model (src/trainer.cpp:712-716: construct_topic_model with no catchwords) on the partition and the
+  // normalised values of the last construct_topic_model: exact sums, bitwise reproducible, NaN for an empty cluster
+  // (isle_hip_avg_topic_model).  It stays on the device; AvgModel (nullable): vocab x num_topics, column-major.
+  void construct_avg_topic_model(FPTYPE* AvgModel, const doc_id_t num_topics) {
+    check(isle_hip_avg_topic_model(ctx_, (int)num_topics, AvgModel), "avg_topic_model");
+  }
+  // The n heaviest words of every topic of a resident model (ISLE_MODEL_CATCH or ISLE_MODEL_AVG), by the trainer's rule (heaviest
+  // first, lower id first among equal weights, NaN last), selected on the device (isle_hip_model_top_words).
+  void model_top_words(const int which, const doc_id_t num_topics, const word_id_t n, std::vector<std::pair<word_id_t, FPTYPE>>* top_words) {
+    std::vector<uint32_t> ids((size_t)num_topics * n);
+    std::vector<float> w((size_t)num_topics * n);
+    check(isle_hip_model_top_words(ctx_, which, nullptr, vocab_size_, (int)num_topics, (int)n, ids.data(), w.data()), "model_top_words");
+    for (doc_id_t t = 0; t < num_topics; ++t) {
+      top_words[t].clear();
+      for (word_id_t i = 0; i < n; ++i) top_words[t].push_back(std::make_pair((word_id_t)ids[(size_t)t * n + i], w[(size_t)t * n + i]));
+    }
+  }
+  // Topic diversity of a resident model in double (isle_hip_topic_diversity): dist[t] = squared L2 distance of topic t to the mean
+  // topic of the finite topics (NaN for the others), avg = their mean.
+  void topic_diversity(const int which, const doc_id_t num_topics, std::vector<double>& dist, double& avg) {
+    dist.assign(num_topics, 0.0);
+    check(isle_hip_topic_diversity(ctx_, which, (int)num_topics, dist.data(), &avg), "topic_diversity");
+  }
   // SparseMatrix::compute_log_combinatorial (src/sparseMatrix.cpp:1018-1043) on the count matrix this object was built from: every
   // document's log(N_d! / prod count!) with the reference's fp32 table and order (isle_hip_log_combinatorial), bit for bit.
   void compute_log_combinatorial(std::vector<FPTYPE>& docs_log_fact) {

@@ -10,13 +10,20 @@
 // DEFAULT_COHERENCE_NUM_WORDS top words of every topic on the device (FPSparseMatrixHip::topic_coherence) and prints the reference's
 // commented-out "Coherence:" line per topic (:806), the real "Avg coherence:" (mean over topics with a finite value; a line counts the
 // others) and flt_coh.  Deviations: flt_coh of a row is that row's topic's value (the reference indexes it by sorted position), raw_coh
-// stays 0 (output_avg_topic_coherence is not mirrored).  With the flag off every output byte is what it was without it.
+// stays 0.  With the flag off every output byte is what it was without it.
 // Corpus diagnostics (compute_log_combinatorial / compute_distinct_top_five_sets, off by default as in the reference): right after the
 // data is in (both ingest modes), print_log_combinatorial() writes LogCombinatorial.txt and print_distinct_top_five_sets() prints the
 // "Distinct top five sets:" line, both computed on the device from A (FPSparseMatrixHip, include/isle_hip.h for the deviations).
+// Model quality (called by a driver after output_cluster_summary(); nothing in this class or the CLI calls them, as in the reference):
+// output_avg_topic_coherence() builds the cluster-average model on the device (no catchwords), selects its 10 top words on the device,
+// scores the first DEFAULT_COHERENCE_NUM_WORDS with topic_coherence, prints "Avg coherence without catchwords:" and writes M_hat_avg
+// and TopWordsPerTopic_avg.txt; output_topic_diversity() prints the catch model's "Average topic diversity:".  Deviations: the
+// reference scores empty top-word lists (every coherence 0, empty TopWordsPerTopic_avg.txt lines), uses topic 1's vector in every
+// diversity cross term and accumulates in fp32; here the coherence is the mean over topics with a finite value (a line counts the
+// others), the diversity is the stated formula in double, and M_hat_avg writes "nan" for the entries of an empty cluster.  raw_coh
+// stays 0 (the reference's summary has that call commented out).
 // Not mirrored (dead under the shipped hyper-parameters or outside the path): load_preprocessed_data_from_file,
-// print_doctopic (accepted, unused: the reference's use is commented out), compute_input_svd, output_avg_topic_coherence, the diversity
-// output, construct_edge_topics_v1.
+// print_doctopic (accepted, unused: the reference's use is commented out), compute_input_svd, construct_edge_topics_v1.
 #pragma once
 #include <sys/stat.h>
 
@@ -102,6 +109,42 @@ inline size_t weight_text(float w, char* out) {
   }
   return len;
 }
+// DenseMatrix::write_to_file (src/denseMatrix.cpp:124-151, mmap branch) with concat_float -> ftoa_mv (include/utils.h:421-466): one
+// topic per line, every entry followed by '\t', "0.0" for zero, otherwise weight_text's digits; "nan" for a NaN entry (an empty
+// cluster; the reference's conversion of NaN to an integer is undefined).
+inline size_t dense_entry_text(float w, char* out) {
+  if (w != w) {
+    std::memcpy(out, "nan", 3);
+    return 3;
+  }
+  if (w == 0.0f) {
+    std::memcpy(out, "0.0", 3);
+    return 3;
+  }
+  return weight_text(w, out);
+}
+void write_dense(const std::string& filename, const float* M, uint64_t vocab_size, uint64_t ncols) {
+  constexpr size_t kFlushAt = (size_t(1) << 24) - 256;
+  FILE* fp = std::fopen(filename.c_str(), "wb");
+  if (!fp) throw std::runtime_error("cannot open " + filename);
+  std::string pending;
+  pending.reserve(size_t(1) << 24);
+  char text[32];
+  for (uint64_t col = 0; col < ncols; ++col) {
+    const float* column = M + col * vocab_size;
+    for (uint64_t row = 0; row < vocab_size; ++row) {
+      pending.append(text, dense_entry_text(column[row], text));
+      pending += '\t';
+      if (pending.size() > kFlushAt) {
+        std::fwrite(pending.data(), 1, pending.size(), fp);
+        pending.clear();
+      }
+    }
+    pending += '\n';
+  }
+  std::fwrite(pending.data(), 1, pending.size(), fp);
+  std::fclose(fp);
+}
 void write_dense_as_sparse(const std::string& filename, const float* M, uint64_t vocab_size, uint64_t ncols) {
   constexpr size_t kFlushAt = (size_t(1) << 24) - 256;
   FILE* fp = std::fopen(filename.c_str(), "wb");
@@ -172,6 +215,8 @@ class ISLETrainer {
   std::vector<FPTYPE> EdgeModel;
   std::vector<std::string> vocab_words;
   std::vector<std::vector<std::pair<word_id_t, FPTYPE>>> topwords;
+  std::vector<std::vector<std::pair<word_id_t, FPTYPE>>> avg_topwords;  // output_avg_topic_coherence()
+  std::vector<FPTYPE> AvgModel;  // vocab_size x num_topics, column-major, output_avg_topic_coherence()
 
   void print_header() {  // src/trainer.cpp:130-143
     std::ostringstream s;
@@ -388,18 +433,21 @@ class ISLETrainer {
     is_training_complete = true;
   }
 
+  void load_vocab() {  // create_vocab_list, src/utils.cpp:6-25 (once)
+    if (!vocab_words.empty()) return;
+    std::ifstream in(vocab_file);
+    std::string word;
+    while (in.good() && !in.eof() && vocab_words.size() < vocab_size) {
+      in >> word;
+      vocab_words.push_back(word);
+    }
+    vocab_words.resize(vocab_size);
+  }
+
   // src/trainer.cpp:776-826
   void output_cluster_summary() {
     if (!is_training_complete) throw std::runtime_error("output_cluster_summary() before train()");
-    {  // create_vocab_list, src/utils.cpp:6-25
-      std::ifstream in(vocab_file);
-      std::string word;
-      while (in.good() && !in.eof() && vocab_words.size() < vocab_size) {
-        in >> word;
-        vocab_words.push_back(word);
-      }
-      vocab_words.resize(vocab_size);
-    }
+    load_vocab();
     const word_id_t ntop = std::min<word_id_t>(10, vocab_size);  // max(DEFAULT_COHERENCE_NUM_WORDS, 10), :781-783
     topwords.assign(num_topics, {});
     for (doc_id_t t = 0; t < num_topics; ++t) {  // DenseMatrix::find_n_top_words, src/denseMatrix.cpp:92-107 (ties: lower word id first)
@@ -500,6 +548,49 @@ class ISLETrainer {
     trainer_detail::write_dense_as_sparse(log_dir + "/EdgeModel_sparse", EdgeModel.data(), vocab_size, selected_pairs.size());
     log->next_time_secs("Output edge model");
   }
+  // src/trainer.cpp:705-745, the cluster-average model (no catchwords) on the device; see the header comment for the deviations
+  void output_avg_topic_coherence(FPTYPE& avg_nl_coherence, std::vector<FPTYPE>& nl_coherences) {
+    if (!is_training_complete) throw std::runtime_error("output_avg_topic_coherence() before train()");
+    load_vocab();
+    AvgModel.assign((size_t)vocab_size * num_topics, 0.0f);
+    B_fl_CSC->construct_avg_topic_model(AvgModel.data(), num_topics);
+    const word_id_t ntop = std::min<word_id_t>(std::max<word_id_t>(ISLE_DEFAULT_COHERENCE_NUM_WORDS, 10), vocab_size);
+    avg_topwords.assign(num_topics, {});
+    B_fl_CSC->model_top_words(ISLE_MODEL_AVG, num_topics, ntop, avg_topwords.data());
+    std::vector<double> coherences;
+    B_fl_CSC->topic_coherence(num_topics, std::min<word_id_t>(ISLE_DEFAULT_COHERENCE_NUM_WORDS, ntop), avg_topwords.data(), coherences);
+    double sum = 0.0;
+    doc_id_t undefined = 0;
+    for (doc_id_t t = 0; t < num_topics; ++t) {
+      if (std::isfinite(coherences[t])) sum += coherences[t];
+      else ++undefined;
+    }
+    const double avg = sum / (double)(num_topics - undefined);
+    nl_coherences.assign(coherences.begin(), coherences.end());
+    avg_nl_coherence = (FPTYPE)avg;
+    if (undefined)
+      log->print("\n Topics without a coherence (a top word occurs in no document): " + std::to_string(undefined) + "(" + std::to_string(num_topics) + ")\n");
+    log->print("\nAvg coherence without catchwords: " + std::to_string(avg) + "\n");
+    log->next_time_secs("computing coherence without catchwords");
+    trainer_detail::write_dense(log_dir + "/M_hat_avg", AvgModel.data(), vocab_size, num_topics);
+    log->next_time_secs("Writing Mhat to file");
+    std::ofstream out_top_words_avg(log_dir + "/TopWordsPerTopic_avg.txt");
+    for (doc_id_t t = 0; t < num_topics; ++t) {
+      for (auto& tw : avg_topwords[t]) out_top_words_avg << vocab_words[tw.first] << "\t";
+      out_top_words_avg << std::endl;
+    }
+    out_top_words_avg.close();
+    log->next_time_secs("Writing top words to file");
+  }
+  // src/trainer.cpp:750-774 on the catch model, in double (the stated formula; see the header comment)
+  void output_topic_diversity() {
+    if (!is_training_complete) throw std::runtime_error("output_topic_diversity() before train()");
+    std::vector<double> dist;
+    double avg = 0.0;
+    B_fl_CSC->topic_diversity(ISLE_MODEL_CATCH, num_topics, dist, avg);
+    log->print("\n Average topic diversity: " + std::to_string((FPTYPE)avg) + "\n\n");
+    log->next_time_secs("Calculating diversity");
+  }
   void finish_log() { log->total("TVSD"); }  // the "Total time for TVSD" line the reference's train() ends with (:652)
 
   // src/trainer.cpp:993-996: vocab_size x num_topics floats, column-major (element (word, topic) at word + topic * vocab_size)
@@ -508,6 +599,9 @@ class ISLETrainer {
   void get_edge_model(FPTYPE* const edgeModel) { std::memcpy(edgeModel, EdgeModel.data(), EdgeModel.size() * sizeof(FPTYPE)); }  // :1003-1007
   const std::vector<FPTYPE>& eigenvalues() const { return evalues; }
   const std::vector<std::vector<std::pair<word_id_t, FPTYPE>>>& top_words() const { return topwords; }  // after output_cluster_summary()
+  const std::vector<std::vector<std::pair<word_id_t, FPTYPE>>>& avg_top_words() const { return avg_topwords; }  // after output_avg_topic_coherence()
+  const std::vector<FPTYPE>& avg_model() const { return AvgModel; }  // after output_avg_topic_coherence()
+  const std::string& log_directory() const { return log_dir; }
   const std::vector<doc_id_t>* partition() const { return closest_docs; }
 };
 

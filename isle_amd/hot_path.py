@@ -261,6 +261,7 @@ class HotPath:
         n = C.c_uint64()
         a = None if assign is None else np.ascontiguousarray(assign, np.uint32)
         self._chk(self._lib.isle_hip_catchwords(self._h, int(num_topics), _p(a), int(r), float(rho), _p(thr), _p(ct), C.byref(n)))
+        self._post_k = int(num_topics)
         return dict(thresholds=thr, catch_topic=ct, num_catchwords=int(n.value))
 
     def construct_topic_model(self, num_topics, rank_threshold, num_docs_A, fetch_sums=True):
@@ -303,6 +304,45 @@ class HotPath:
         co = np.empty((n, max(M * (M - 1) // 2, 0)), np.uint64) if fetch_counts else None
         self._chk(self._lib.isle_hip_topic_coherence(self._h, n, M, _p(tw), float(eps), _p(coh), _p(df), _p(co)))
         return dict(coherence=coh, doc_freq=df, co_doc_freq=co)
+
+    # ---- the cluster-average model and what reads a model (include/isle_hip.h for the rules and the deviations) -----------------
+    _MODELS = {"catch": 0, "avg": 1}   # ISLE_MODEL_CATCH, ISLE_MODEL_AVG; ISLE_MODEL_HOST = 2
+
+    def _a_vocab(self):
+        return getattr(self, "_a_shape", (self.V,))[0]
+
+    def avg_topic_model(self, num_topics, fetch=True):
+        """The cluster-average topic model (ISLETrainer::output_avg_topic_coherence, src/trainer.cpp:705-745): every topic the
+        L1-normalised sum of its cluster's normalised documents, no catchwords; after find_catchwords(num_topics).  Exact sums,
+        bitwise reproducible, NaN columns for empty clusters.  The model stays resident.  -> (V, num_topics) F-order float32, or None."""
+        M = np.empty((self._a_vocab(), int(num_topics)), np.float32, order="F") if fetch else None
+        self._chk(self._lib.isle_hip_avg_topic_model(self._h, int(num_topics), _p(M)))
+        return M
+
+    def model_top_words(self, n=10, model="catch", with_weights=False):
+        """The n heaviest words of every topic, on the device, by the rule of top_words() (bit-equal to it).  model: "catch" (the
+        resident topic model), "avg" (the resident average model) or a (V, cols) array.  -> uint32 (cols, n), and float32 (cols, n)
+        weights with with_weights."""
+        if isinstance(model, str):
+            which, host = self._MODELS[model], None
+            V, cols = self._a_vocab(), getattr(self, "_post_k", 0)
+        else:
+            host = np.asfortranarray(model, np.float32)
+            if host.ndim != 2:
+                raise ValueError("model must be (V, cols)")
+            which, (V, cols) = 2, host.shape
+        ids = np.empty((cols, int(n)), np.uint32)
+        w = np.empty((cols, int(n)), np.float32) if with_weights else None
+        self._chk(self._lib.isle_hip_model_top_words(self._h, which, _p(host), int(V), int(cols), int(n), _p(ids), _p(w)))
+        return (ids, w) if with_weights else ids
+
+    def topic_diversity(self, num_topics, model="catch"):
+        """Topic diversity (ISLETrainer::output_topic_diversity, src/trainer.cpp:750-774) of a resident model, in double:
+        dist[t] = |m_t - mean topic|^2 over the finite topics (NaN for the others) and their mean.  -> dict(dist float64 (k,), avg)."""
+        dist = np.empty(int(num_topics), np.float64)
+        avg = C.c_double()
+        self._chk(self._lib.isle_hip_topic_diversity(self._h, self._MODELS[model], int(num_topics), _p(dist), C.byref(avg)))
+        return dict(dist=dist, avg=float(avg.value))
 
     # ---- corpus diagnostics of the trainer on A (include/isle_hip.h for the rules and the deviations) ----------------------
     def log_combinatorial(self):
