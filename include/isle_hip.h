@@ -309,6 +309,41 @@ int isle_hip_model_top_words(isle_ctx* ctx, int which, const float* model_host, 
  * ISLE_E_ARG: world > 1, an unknown or HOST model, a resident model that does not exist, num_topics not the model's. */
 int isle_hip_topic_diversity(isle_ctx* ctx, int which, int num_topics, double* dist, double* avg);
 
+/* The reference's model files, formatted on the device (isle_amd/csrc/model_text.hip): MMappedOutput (include/utils.h:383-478) under
+ * DenseMatrix::write_to_file_as_sparse / write_to_file (src/denseMatrix.cpp:124-186), as trainer_detail::weight_text, dense_entry_text,
+ * write_dense_as_sparse and write_dense (isle_amd/host/trainer_hip.h) restate them; the bytes equal theirs.  model: vocab x ncols column-major.
+ *   ISLE_TEXT_SPARSE  columns ascending, rows ascending in a column; every entry w > 1e-8f (float compare; NaN, zero, negative and tiny
+ *                     entries are skipped) gives "<col+1>\t<row+1>\t<weight>\n"  (M_hat_catch_sparse, EdgeModel_sparse)
+ *   ISLE_TEXT_DENSE   one column per line, every entry followed by '\t', the line ended by '\n'; zero and -0 give "0.0", NaN gives "nan",
+ *                     anything else <weight>  (M_hat_avg)
+ *   <weight>          (unsigned)w in decimal, at most its six low digits (1234567.875 -> 234567), '.', then six fraction digits:
+ *                     rest = w - (float)(int)w; six times: rest *= 10; d = (int)rest; emit '0' + d; rest -= d — fp32, each operation
+ *                     rounded on its own (never a fused multiply-add), truncating
+ * An entry that would be printed and is negative, infinite or >= 2^31 is outside the writer's domain ((int)w and (unsigned)w are
+ * undefined there): the call fails with ISLE_E_ARG naming the first such entry (column-major) before any byte is delivered.
+ * One pass counts (bytes per tile, entries, the domain check), a 64-bit exclusive scan places every tile, one pass writes the text in
+ * chunks of at most 16 MiB (whole columns; a longer column is split), each handed to `sink` in order on the calling thread while the
+ * device formats the next; the concatenation of the pieces is the file.  A non-zero return of the sink ends the call with ISLE_E_ARG, no
+ * further piece is delivered and the context stays usable.  sink == NULL: the size query (the counting pass alone).  nbytes / nentries
+ * (nullable): the size of the text and the number of entries it holds (DENSE: every entry, vocab x ncols).  ncols == 0 (n == 0):
+ * no bytes, no sink call, 0.  Single rank.
+ * isle_hip_model_text: which / model_host / vocab / ncols and their ISLE_E_ARG conditions as isle_hip_model_top_words; ISLE_E_ARG also for
+ * an unknown format.
+ * isle_hip_edge_topics_text: the text of the edge model isle_hip_edge_topics(pairs, n, primary_ratio) would return (its ISLE_E_ARG
+ * conditions), column e numbered e + 1; the entries are formed from the resident topic model as they are read (the same two fp32
+ * operations), the vocab x n floats exist neither on the device nor on the host.
+ * isle_hip_entry_text (host only, no context): one entry's text under `format` into out16 (NUL-terminated); returns its length,
+ * 0 = skipped (SPARSE), -1 = outside the writer's domain or an unknown format.  The library's one copy of the digit rule: the kernels
+ * compile the same function. */
+#define ISLE_TEXT_SPARSE 0
+#define ISLE_TEXT_DENSE 1
+typedef int (*isle_text_sink_fn)(const char* bytes, uint64_t n, void* user);
+int isle_hip_model_text(isle_ctx* ctx, int which, const float* model_host, uint64_t vocab, int ncols, int format, isle_text_sink_fn sink,
+                        void* user, uint64_t* nbytes, uint64_t* nentries);
+int isle_hip_edge_topics_text(isle_ctx* ctx, const int64_t* pairs, int n, float primary_ratio, int format, isle_text_sink_fn sink, void* user,
+                              uint64_t* nbytes, uint64_t* nentries);
+int isle_hip_entry_text(float w, int format, char* out16);
+
 /* Corpus diagnostics of the trainer (print_log_combinatorial / print_distinct_top_five_sets, src/trainer.cpp:373-403) on the resident
  * count matrix A, right after ingest or upload (no partition or B needed; single rank; ISLE_E_ARG without A).
  *

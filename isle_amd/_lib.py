@@ -32,6 +32,9 @@ SYMBOLS = {
     "isle_hip_avg_topic_model": (_I, [_P, _I, _P]),
     "isle_hip_model_top_words": (_I, [_P, _I, _P, _U64, _I, _I, _P, _P]),
     "isle_hip_topic_diversity": (_I, [_P, _I, _I, _P, _P]),
+    "isle_hip_model_text": (_I, [_P, _I, _P, _U64, _I, _I, _P, _P, _P, _P]),
+    "isle_hip_edge_topics_text": (_I, [_P, _P, _I, _F, _I, _P, _P, _P, _P]),
+    "isle_hip_entry_text": (_I, [_F, _I, _P]),
     "isle_hip_log_combinatorial": (_I, [_P, _P, _P]),
     "isle_hip_distinct_top_five": (_I, [_P, _I, _P, _P, _P, _P, _P, _P]),
     "isle_hip_top_five_count_rule": (_I, [_P, _U64, C.c_int32, _P]),

@@ -559,6 +559,59 @@ extern "C" int isle_hip_model_top_words(isle_ctx* c, int which, const float* mod
   return 0;
 }
 
+// The reference's model files formatted on the device (model_text.hip): MMappedOutput, include/utils.h:383-478, under
+// DenseMatrix::write_to_file_as_sparse / write_to_file, src/denseMatrix.cpp:124-186
+extern "C" int isle_hip_model_text(isle_ctx* c, int which, const float* model_host, uint64_t vocab, int ncols, int format, isle_text_sink_fn sink,
+                                   void* user, uint64_t* nbytes, uint64_t* nentries) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  if (nbytes) *nbytes = 0;
+  if (nentries) *nentries = 0;
+  if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "model_text: single-rank only");
+  if (format != ISLE_TEXT_SPARSE && format != ISLE_TEXT_DENSE) return isle_fail(c, ISLE_E_ARG, "model_text: unknown format %d", format);
+  if (ncols < 0 || vocab == 0 || vocab > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "model_text: vocab or ncols out of range");
+  const float* dev = nullptr;
+  DevBuf<float> up;
+  if (which == ISLE_MODEL_HOST) {
+    if (!model_host && ncols) return isle_fail(c, ISLE_E_ARG, "model_text: null model_host");
+    if (ncols) {
+      HIPCHK(c, up.reserve(vocab * (size_t)ncols));
+      HIPCHK(c, hipMemcpyAsync(up.p, model_host, vocab * (size_t)ncols * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    }
+    dev = up.p;
+  } else {
+    dev = resident_model(c, which, "model_text");
+    if (!dev) return ISLE_E_ARG;
+    if (vocab != c->a_V || ncols != c->p_k)
+      return isle_fail(c, ISLE_E_ARG, "model_text: vocab x ncols = %llu x %d, the resident model is %llu x %d", (unsigned long long)vocab, ncols,
+                       (unsigned long long)c->a_V, c->p_k);
+  }
+  const int rc = k_model_text(c, dev, vocab, (uint64_t)ncols, nullptr, 0.f, 0.f, format, sink, user, nbytes, nentries);
+  (void)hipStreamSynchronize(c->stream);  // `up` is freed on return
+  return rc;
+}
+
+extern "C" int isle_hip_edge_topics_text(isle_ctx* c, const int64_t* pairs, int n, float primary_ratio, int format, isle_text_sink_fn sink, void* user,
+                                         uint64_t* nbytes, uint64_t* nentries) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  if (nbytes) *nbytes = 0;
+  if (nentries) *nentries = 0;
+  if (!c->p_model_ready) return isle_fail(c, ISLE_E_ARG, "edge_topics_text: run isle_hip_topic_model first");
+  if (format != ISLE_TEXT_SPARSE && format != ISLE_TEXT_DENSE) return isle_fail(c, ISLE_E_ARG, "edge_topics_text: unknown format %d", format);
+  if (n < 0 || (n && !pairs)) return isle_fail(c, ISLE_E_ARG, "edge_topics_text: bad arguments");
+  if (n == 0) return 0;
+  for (int e = 0; e < 2 * n; ++e)
+    if (pairs[e] < 0 || pairs[e] >= c->p_k) return isle_fail(c, ISLE_E_ARG, "edge_topics_text: topic id %lld out of range", (long long)pairs[e]);
+  DevBuf<int64_t> pd;
+  HIPCHK(c, pd.reserve(2 * (size_t)n));
+  HIPCHK(c, hipMemcpy(pd.p, pairs, 2 * (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+  const int rc = k_model_text(c, c->p_model.p, c->a_V, (uint64_t)n, pd.p, primary_ratio, (float)(1.0 - (double)primary_ratio), format, sink, user,
+                              nbytes, nentries);
+  (void)hipStreamSynchronize(c->stream);  // `pd` is freed on return
+  return rc;
+}
+
 extern "C" int isle_hip_topic_diversity(isle_ctx* c, int which, int num_topics, double* dist, double* avg) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));

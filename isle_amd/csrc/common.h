@@ -79,6 +79,27 @@ struct DevBuf {
   ~DevBuf() { release(); }  // every buffer of a context dies with it
 };
 
+// Pinned host buffer with explicit capacity (grows, never shrinks): the landing place of the model text (model_text.hip).
+struct PinBuf {
+  char* p = nullptr;
+  size_t cap = 0;
+  hipError_t reserve(size_t n) {
+    if (n <= cap) return hipSuccess;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+    hipError_t e = hipHostMalloc((void**)&p, n, hipHostMallocDefault);
+    if (e == hipSuccess) cap = n;
+    return e;
+  }
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+};
+
 // One side of the LDS-banded Gram apply (gram_lds.hip): a sliced-ELL stream of band-local u16 source ids.
 // ------------------------------------------------------------------------------------------
 // Environment switches.  Every switch the library honours is in this table; they are read into the context when it is created and
@@ -211,6 +232,10 @@ struct isle_ctx {
   DevBuf<float> p_model;           // V x k col-major
   DevBuf<uint64_t> p_avg_acc;      // V x k (lo, hi) pairs: exact fixed-point sums of the average model (avg_model.hip)
   DevBuf<float> p_avg_model;       // V x k col-major, the cluster-average model
+  DevBuf<uint32_t> mt_sizes;       // model text (model_text.hip): bytes per tile
+  DevBuf<uint64_t> mt_offs, mt_blk, mt_stat;  // their exclusive scan (+ its scratch); entries emitted, first entry outside the domain
+  DevBuf<unsigned char> mt_text[2];  // one chunk of text each (<= ISLE_TEXT_CHUNK_BYTES), formatted while the other one is copied and consumed
+  PinBuf mt_pin[2];
   int p_k = 0;                     // num_topics of the last catchword pass
   bool p_catch_ready = false, p_model_ready = false, p_avg_ready = false, assign_valid = false;
 
@@ -538,6 +563,13 @@ int k_post_doc_topic_sums(isle_ctx* c, uint32_t k, uint64_t* n_out);
 int k_post_model_thresholds(isle_ctx* c, uint32_t k, uint32_t rank);
 int k_post_model(isle_ctx* c, uint32_t k);
 int k_post_edge(isle_ctx* c, const int64_t* pairs_dev, int n, float a, float b, float* edge_dev);
+
+// model_text.hip: the reference's text of a V x ncols column-major device model (ISLE_TEXT_SPARSE / ISLE_TEXT_DENSE) handed to `sink` in
+// pieces of at most ISLE_TEXT_CHUNK_BYTES; pairs_dev != null: column e is a * model[:, pairs[2e]] + b * model[:, pairs[2e + 1]] (post_edge_k's
+// arithmetic) formed while it is read.  sink == null: the counting pass only.
+constexpr uint64_t ISLE_TEXT_CHUNK_BYTES = 16ull << 20;
+int k_model_text(isle_ctx* c, const float* model_dev, uint64_t V, uint64_t ncols, const int64_t* pairs_dev, float a, float b, int format,
+                 isle_text_sink_fn sink, void* user, uint64_t* nbytes, uint64_t* nentries);
 
 // coherence.hip: D(w) for the distinct top words U (ascending) and D(lo, hi) for the distinct pairs of their local ids (CSR keyed by lo),
 // over the count matrix A; counts = |U| + |P| entries on the host

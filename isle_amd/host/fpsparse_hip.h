@@ -8,6 +8,7 @@
 #pragma once
 #include <cassert>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <iostream>
 #include <stdexcept>
@@ -52,6 +53,9 @@ class FPSparseMatrixHip {
   std::vector<uint64_t> top5_runs_;  // count_distint_top_five_words: run lengths of the sorted tuples, from the first call
   uint64_t top5_n_ = 0;
   bool top5_ready_ = false;
+  doc_id_t post_topics_ = 0;  // num_topics of the last find_catchwords: the columns of the resident models
+
+  static int text_to_file(const char* bytes, uint64_t n, void* fp) { return std::fwrite(bytes, 1, (size_t)n, (FILE*)fp) == (size_t)n ? 0 : 1; }
 
   void check(int rc, const char* what) const {
     if (rc != 0) throw std::runtime_error(std::string(what) + ": " + isle_hip_last_error(ctx_));
@@ -247,6 +251,7 @@ class FPSparseMatrixHip {
     std::vector<int32_t> catch_topic(vocab_size_);
     uint64_t n = 0;
     check(isle_hip_catchwords(ctx_, (int)num_topics, nullptr, r, ISLE_RHO_C, catchword_thresholds, catch_topic.data(), &n), "find_catchwords");
+    post_topics_ = num_topics;
     for (doc_id_t t = 0; t < num_topics; ++t) catchwords[t].clear();
     for (word_id_t w = 0; w < vocab_size_; ++w)
       if (catch_topic[w] >= 0) catchwords[catch_topic[w]].push_back(w);
@@ -306,6 +311,33 @@ class FPSparseMatrixHip {
   void topic_diversity(const int which, const doc_id_t num_topics, std::vector<double>& dist, double& avg) {
     dist.assign(num_topics, 0.0);
     check(isle_hip_topic_diversity(ctx_, which, (int)num_topics, dist.data(), &avg), "topic_diversity");
+  }
+  // DenseMatrix::write_to_file_as_sparse (format = ISLE_TEXT_SPARSE) / write_to_file (ISLE_TEXT_DENSE), src/denseMatrix.cpp:124-186, of a
+  // resident model (ISLE_MODEL_CATCH / ISLE_MODEL_AVG), or with ISLE_MODEL_HOST of model_host (vocab x ncols column-major): the text is
+  // formatted on the device (isle_hip_model_text) and its pieces go straight to the file.  Returns the bytes written.
+  uint64_t write_model_text(const int which, const int format, const std::string& filename, const FPTYPE* model_host = nullptr,
+                            const word_id_t vocab = 0, const doc_id_t ncols = 0) {
+    FILE* fp = std::fopen(filename.c_str(), "wb");
+    if (!fp) throw std::runtime_error("cannot open " + filename);
+    uint64_t nbytes = 0;
+    const bool host = which == ISLE_MODEL_HOST;
+    const int rc = isle_hip_model_text(ctx_, which, model_host, host ? vocab : vocab_size_, (int)(host ? ncols : post_topics_), format, text_to_file,
+                                       fp, &nbytes, nullptr);
+    std::fclose(fp);
+    check(rc, "write_model_text");
+    return nbytes;
+  }
+  // ISLETrainer::write_edgemodel_to_file (src/trainer.cpp:687-693) for the edge topics of `pairs` (primary, secondary per edge topic):
+  // the FPaxpy pair of construct_edge_topics and the sparse text in one pass on the device (isle_hip_edge_topics_text).
+  uint64_t write_edge_model_text(const std::vector<int64_t>& pairs, const FPTYPE primary_ratio, const std::string& filename) {
+    FILE* fp = std::fopen(filename.c_str(), "wb");
+    if (!fp) throw std::runtime_error("cannot open " + filename);
+    uint64_t nbytes = 0;
+    const int rc = isle_hip_edge_topics_text(ctx_, pairs.data(), (int)(pairs.size() / 2), primary_ratio, ISLE_TEXT_SPARSE, text_to_file, fp, &nbytes,
+                                             nullptr);
+    std::fclose(fp);
+    check(rc, "write_edge_model_text");
+    return nbytes;
   }
   // SparseMatrix::compute_log_combinatorial (src/sparseMatrix.cpp:1018-1043) on the count matrix this object was built from: every
   // document's log(N_d! / prod count!) with the reference's fp32 table and order (isle_hip_log_combinatorial), bit for bit.

@@ -22,6 +22,9 @@
 // diversity cross term and accumulates in fp32; here the coherence is the mean over topics with a finite value (a line counts the
 // others), the diversity is the stated formula in double, and M_hat_avg writes "nan" for the entries of an empty cluster.  raw_coh
 // stays 0 (the reference's summary has that call commented out).
+// Model files: M_hat_catch_sparse, EdgeModel_sparse and M_hat_avg are formatted on the device from the resident models
+// (FPSparseMatrixHip::write_model_text / write_edge_model_text -> isle_hip_model_text / isle_hip_edge_topics_text) and streamed to the file;
+// trainer_detail's host writers below define those bytes and are what the tests compare the device text against.
 // Not mirrored (dead under the shipped hyper-parameters or outside the path): load_preprocessed_data_from_file,
 // print_doctopic (accepted, unused: the reference's use is commented out), compute_input_svd, construct_edge_topics_v1.
 #pragma once
@@ -526,7 +529,7 @@ class ISLETrainer {
   }
   void output_model(bool output_sparse = false) {  // src/trainer.cpp:831-838 (the CLI asks for the sparse form)
     (void)output_sparse;
-    trainer_detail::write_dense_as_sparse(log_dir + "/M_hat_catch_sparse", Model, vocab_size, num_topics);
+    B_fl_CSC->write_model_text(ISLE_MODEL_CATCH, ISLE_TEXT_SPARSE, log_dir + "/M_hat_catch_sparse");
   }
   // src/trainer.cpp:656-662
   void write_model_to_file() {
@@ -545,7 +548,12 @@ class ISLETrainer {
   }
   // src/trainer.cpp:687-693
   void write_edgemodel_to_file() {
-    trainer_detail::write_dense_as_sparse(log_dir + "/EdgeModel_sparse", EdgeModel.data(), vocab_size, selected_pairs.size());
+    std::vector<int64_t> pq(2 * selected_pairs.size());
+    for (size_t e = 0; e < selected_pairs.size(); ++e) {
+      pq[2 * e] = std::get<0>(selected_pairs[e]);
+      pq[2 * e + 1] = std::get<1>(selected_pairs[e]);
+    }
+    B_fl_CSC->write_edge_model_text(pq, (FPTYPE)ISLE_EDGE_TOPIC_PRIMARY_RATIO, log_dir + "/EdgeModel_sparse");
     log->next_time_secs("Output edge model");
   }
   // src/trainer.cpp:705-745, the cluster-average model (no catchwords) on the device; see the header comment for the deviations
@@ -572,7 +580,7 @@ class ISLETrainer {
       log->print("\n Topics without a coherence (a top word occurs in no document): " + std::to_string(undefined) + "(" + std::to_string(num_topics) + ")\n");
     log->print("\nAvg coherence without catchwords: " + std::to_string(avg) + "\n");
     log->next_time_secs("computing coherence without catchwords");
-    trainer_detail::write_dense(log_dir + "/M_hat_avg", AvgModel.data(), vocab_size, num_topics);
+    B_fl_CSC->write_model_text(ISLE_MODEL_AVG, ISLE_TEXT_DENSE, log_dir + "/M_hat_avg");
     log->next_time_secs("Writing Mhat to file");
     std::ofstream out_top_words_avg(log_dir + "/TopWordsPerTopic_avg.txt");
     for (doc_id_t t = 0; t < num_topics; ++t) {

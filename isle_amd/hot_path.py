@@ -91,6 +91,19 @@ def top_words(model, n, vocab_size=None):
     return out
 
 
+TEXT_FORMATS = {"sparse": 0, "dense": 1}   # ISLE_TEXT_SPARSE, ISLE_TEXT_DENSE
+_TEXT_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p)   # isle_text_sink_fn
+
+
+def entry_text(w, format="dense"):
+    """One model entry as the reference's writers print it (isle_hip_entry_text, the library's host copy of the digit rule its kernels
+    compile): "sparse" -> the weight text, or "" for an entry the sparse writer skips (not w > 1e-8f); "dense" -> "0.0", "nan" or the
+    weight text.  -1 for a printed entry outside the writer's domain (negative, infinite, >= 2^31).  No GPU needed."""
+    buf = C.create_string_buffer(16)
+    n = load_library().isle_hip_entry_text(C.c_float(float(np.float32(w))), TEXT_FORMATS[format], buf)
+    return -1 if n < 0 else buf.raw[:n].decode("ascii")
+
+
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -343,6 +356,73 @@ class HotPath:
         avg = C.c_double()
         self._chk(self._lib.isle_hip_topic_diversity(self._h, self._MODELS[model], int(num_topics), _p(dist), C.byref(avg)))
         return dict(dist=dist, avg=float(avg.value))
+
+    # ---- model files: the reference's text formatted on the device (include/isle_hip.h for the layouts and the domain) ------------
+    def _text_call(self, call, consume):
+        """Runs call(sink) with a sink that hands every piece to consume(memoryview); consume is None: the size query.  An exception
+        in consume stops the delivery and is raised here.  -> (nbytes, nentries)."""
+        err = []
+
+        def tramp(ptr, n, user):
+            try:
+                consume(memoryview((C.c_char * n).from_address(ptr)))
+                return 0
+            except BaseException as e:  # never let an exception cross the C boundary
+                err.append(e)
+                return 1
+
+        sink = _TEXT_SINK(tramp) if consume is not None else None
+        nb, ne = C.c_uint64(), C.c_uint64()
+        rc = call(C.cast(sink, C.c_void_p) if sink is not None else None, C.byref(nb), C.byref(ne))
+        if err:
+            raise err[0]
+        self._chk(rc)
+        return int(nb.value), int(ne.value)
+
+    def _model_text_call(self, which, format, consume):
+        if isinstance(which, str):
+            code, host = self._MODELS[which], None
+            V, cols = self._a_vocab(), getattr(self, "_post_k", 0)
+        else:
+            host = np.asfortranarray(which, np.float32)
+            if host.ndim != 2:
+                raise ValueError("model must be (V, cols)")
+            code, (V, cols) = 2, host.shape
+        fmt = TEXT_FORMATS[format] if isinstance(format, str) else int(format)
+        return self._text_call(lambda sink, nb, ne: self._lib.isle_hip_model_text(self._h, code, _p(host), int(V), int(cols), fmt, sink, None,
+                                                                                  nb, ne), consume)
+
+    def model_text(self, which="catch", format="sparse"):
+        """The text of a model file: "catch" (the resident topic model; sparse = M_hat_catch_sparse), "avg" (the resident average
+        model; dense = M_hat_avg) or a (V, cols) array.  -> bytes."""
+        parts = []
+        self._model_text_call(which, format, lambda mv: parts.append(bytes(mv)))
+        return b"".join(parts)
+
+    def write_model(self, path, which="catch", format="sparse"):
+        """model_text streamed into a file piece by piece; the whole text is never held.  -> (nbytes, nentries)."""
+        with open(path, "wb") as f:
+            return self._model_text_call(which, format, f.write)
+
+    def model_text_size(self, which="catch", format="sparse"):
+        """The counting pass alone.  -> (nbytes, nentries)."""
+        return self._model_text_call(which, format, None)
+
+    def edge_topics_text(self, pairs, primary_ratio=0.7, format="sparse", path=None):
+        """The text of the edge model edge_topics(pairs, primary_ratio) returns (EdgeModel_sparse), formed and formatted on the device
+        without the V x n floats.  -> bytes, or (nbytes, nentries) after streaming into `path`."""
+        pairs = np.ascontiguousarray(pairs, np.int64).reshape(-1, 2)
+        fmt = TEXT_FORMATS[format] if isinstance(format, str) else int(format)
+
+        def call(sink, nb, ne):
+            return self._lib.isle_hip_edge_topics_text(self._h, _p(pairs), pairs.shape[0], float(primary_ratio), fmt, sink, None, nb, ne)
+
+        if path is not None:
+            with open(path, "wb") as f:
+                return self._text_call(call, f.write)
+        parts = []
+        self._text_call(call, lambda mv: parts.append(bytes(mv)))
+        return b"".join(parts)
 
     # ---- corpus diagnostics of the trainer on A (include/isle_hip.h for the rules and the deviations) ----------------------
     def log_combinatorial(self):
