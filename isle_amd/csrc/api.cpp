@@ -282,7 +282,7 @@ static void wd_loop(isle_ctx* c) {
 static int wd_start(isle_ctx* c) {
   if (const char* e = c->knob(KN_COMM_TIMEOUT)) c->wd_timeout_s = atof(e);
   if (!(c->wd_timeout_s > 0.0) || c->wd_thread.joinable()) return 0;
-  c->wd_done = reinterpret_cast<volatile uint32_t*>(c->pin + isle_ctx::PIN_SMALL + (192u << 10) + 256);  // page-locked
+  c->wd_done = &c->pin_small()->wd_done;  // page-locked
   *c->wd_done = 0;
   c->wd_issued.store(0);
   c->wd_stop.store(false);
@@ -340,16 +340,10 @@ int isle_allgather(isle_ctx* c, const void* send, void* recv, size_t count_per_r
 int agree_i32(isle_ctx* c, int v, const char* what) {
   if (!c->multi()) return 0;
   HIPCHK(c, c->flags.reserve(16));
-  int* h = reinterpret_cast<int*>(c->pin + isle_ctx::PIN_SMALL + (192u << 10) + 128);  // page-locked
+  int* h = c->pin_small()->agree;  // page-locked
   h[0] = v;
   h[1] = -v;
-  HIPCHK(c, hipMemcpyAsync(c->flags.p + 8, h, 2 * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  {
-    TimeScope ts(c, ISLE_T_COMM);
-    ISLECHK(isle_allreduce(c, c->flags.p + 8, 2, ISLE_DT_I32, true));
-  }
-  HIPCHK(c, hipMemcpyAsync(h, c->flags.p + 8, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  ISLECHK(allreduce_host<int>(c, h, 2, c->flags.p + 8, true));
   if (h[0] != -h[1]) return isle_fail(c, ISLE_E_COMM, "ranks disagree on %s (min %d, max %d): replicated state diverged", what, -h[1], h[0]);
   return 0;
 }
@@ -416,7 +410,6 @@ extern "C" void isle_hip_destroy(isle_ctx* c) {
   wd_end(c);
   if (c->comm && !c->comm_dead.load()) ncclCommDestroy(c->comm);  // (an aborted communicator is already gone)
   if (c->pin) (void)hipHostFree(c->pin);
-  if (c->pin_stage) (void)hipHostFree(c->pin_stage);
   for (auto& e : c->ev_used) {
     (void)hipEventDestroy(e.a);
     (void)hipEventDestroy(e.b);
@@ -576,6 +569,32 @@ void isle_trim_derived(isle_ctx* c, uint64_t D, uint64_t nnz) {
   if (c->gl_fb_tmp.cap > 2 * z) c->gl_fb_tmp.release();
 }
 
+// What a new count matrix A voids, and what a new B voids: the one statement of each, for every call that replaces a matrix (upload,
+// ingest, thresholding).  b_from_threshold is the caller's to set.
+static void void_downstream(isle_ctx* c) {  // catchwords and models are read off both matrices
+  c->p_catch_ready = false;
+  c->p_model_ready = false;
+  c->p_avg_ready = false;
+}
+void isle_void_derived_from_A(isle_ctx* c) {
+  c->a_avg_valid = false;
+  void_downstream(c);
+}
+void isle_void_derived_from_B(isle_ctx* c) {
+  c->band_ready = false;
+  c->gl_mode = -1;
+  c->P_ready = false;
+  c->Pt_ready = false;
+  c->Pt2_ready = false;
+  c->lift_valid = false;
+  c->members_valid = false;
+  c->U_k = 0;
+  c->centers_ready = false;
+  c->assign_valid = false;
+  c->kmpp_track_k = 0;
+  void_downstream(c);
+}
+
 static int upload_common(isle_ctx* c, uint64_t V, uint64_t D, uint64_t nnz, const float* vals, const uint32_t* rows32,
                          const int64_t* offs, uint64_t doc_offset, uint64_t docs_global) {
   if (!c) return ISLE_E_ARG;
@@ -587,21 +606,8 @@ static int upload_common(isle_ctx* c, uint64_t V, uint64_t D, uint64_t nnz, cons
   for (uint64_t d = 0; d < D; ++d)
     if (offs[d + 1] < offs[d] || (uint64_t)offs[d + 1] > nnz) return isle_fail(c, ISLE_E_ARG, "offsets not monotone at column %llu", (unsigned long long)d);
   // everything derived from the previous matrix is void from here on, whether or not the new one is accepted
-  c->band_ready = false;
-  c->gl_mode = -1;
-  c->P_ready = false;
-  c->Pt_ready = false;
-  c->Pt2_ready = false;
-  c->lift_valid = false;
-  c->members_valid = false;
-  c->U_k = 0;
-  c->centers_ready = false;
-  c->assign_valid = false;
-  c->p_catch_ready = false;
-  c->p_model_ready = false;
-  c->p_avg_ready = false;
+  isle_void_derived_from_B(c);
   c->b_from_threshold = false;
-  c->kmpp_track_k = 0;
   isle_trim_derived(c, D, nnz);
   c->V = V;
   c->D = D;
@@ -654,10 +660,7 @@ extern "C" int isle_hip_frobenius(isle_ctx* c, float* out) {
   ISLECHK(k_frobenius(c, &s));
   if (c->multi()) {
     HIPCHK(c, c->gram.reserve(1024));
-    HIPCHK(c, hipMemcpyAsync(c->gram.p, &s, sizeof(double), hipMemcpyHostToDevice, c->stream));
-    ISLECHK(allreduce_sum<double>(c, c->gram.p, 1));
-    HIPCHK(c, hipMemcpyAsync(&s, c->gram.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ISLECHK(allreduce_host<double>(c, &s, 1, c->gram.p));
   }
   *out = (float)s;
   return 0;

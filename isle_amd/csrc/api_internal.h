@@ -2,6 +2,7 @@
 // api_ks.cpp: the block Krylov-Schur solver; api_kmeans.cpp: k-means++ and the two Lloyd loops; api_stages.cpp: the stages either side of the
 // path).  Nothing here is part of the boundary: include/isle_hip.h is.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <vector>
 
@@ -27,6 +28,38 @@ inline int allreduce_sum(isle_ctx* c, T* buf, size_t count) {
   return isle_allreduce(c, buf, count, DtOf<T>::v);
 }
 
+// Host values through the ranks and back: host -> device scratch -> collective -> host, behind a synchronisation of the stream (so `host`
+// may be pageable or stack memory).  All-reduce: n values in place, sum or max.  All-gather: n values per rank, `dev` holds (world + 1) n
+// (the ranks' blocks, then this rank's own as the send buffer), `all_host` world x n.
+template <class T>
+inline int allreduce_host(isle_ctx* c, T* host, size_t n, T* dev, bool max_op = false, bool timed = true) {
+  if (!c->multi()) return 0;
+  HIPCHK(c, hipMemcpyAsync(dev, host, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+  {
+    TimeScope ts(c, timed ? ISLE_T_COMM : -1);
+    ISLECHK(isle_allreduce(c, dev, n, DtOf<T>::v, max_op));
+  }
+  HIPCHK(c, hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+template <class T>
+inline int allgather_host(isle_ctx* c, const T* mine_host, size_t n, T* dev, T* all_host) {
+  if (!c->multi()) return std::copy(mine_host, mine_host + n, all_host), 0;  // one rank: its own block
+  T* send = dev + (size_t)c->world * n;
+  HIPCHK(c, hipMemcpyAsync(send, mine_host, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+  {
+    TimeScope ts(c, ISLE_T_COMM);
+    ISLECHK(isle_allgather(c, send, dev, n, DtOf<T>::v));
+  }
+  HIPCHK(c, hipMemcpyAsync(all_host, dev, (size_t)c->world * n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// what a new count matrix A / a new B voids in the context (api.cpp)
+void isle_void_derived_from_A(isle_ctx* c);
+void isle_void_derived_from_B(isle_ctx* c);
 int agree_i32(isle_ctx* c, int v, const char* what);  // all ranks hold the same control value, or all return ISLE_E_COMM (api.cpp)
 int drain_events(isle_ctx* c);
 inline int round4(int k) { return (k + 3) & ~3; }
@@ -38,9 +71,6 @@ int gram_apply_dev(isle_ctx* c, const float* Xcm, int b, float* Zcm);
 // U (V x k col-major on the device) becomes the context's basis: row-major copy, validity flags (api_ks.cpp)
 int install_U(isle_ctx* c, const float* Ucm_dev, int k);
 
-// ------------------------------------------------------------------------------------------
-// host RNG (rand() stand-in)
-// ------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------
 // host RNG (rand() stand-in)
 // ------------------------------------------------------------------------------------------

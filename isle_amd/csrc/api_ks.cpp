@@ -309,8 +309,8 @@ struct Ks {
     // Everything that crosses the bus here lives in the context's page-locked staging area — [subH n x n | vH n x keep | locked
     // rows of H nconv x n | top nconv x keep], 36 MB at k = 1000: copies from freshly allocated pageable vectors blocked the host
     // (registration with the driver) and made their release slow, with the GPU idle in between.
-    HIPCHK(c, c->pin_stage_reserve((n * n + n * keep + nconv * n + nconv * keep) * sizeof(float)));
-    float* subH = reinterpret_cast<float*>(c->pin_stage);
+    HIPCHK(c, c->pin_stage.reserve((n * n + n * keep + nconv * n + nconv * keep) * sizeof(float)));
+    float* subH = reinterpret_cast<float*>(c->pin_stage.p);
     float* vH = subH + n * n;
     float* blkH = vH + n * keep;
     float* top = blkH + nconv * n;

@@ -42,10 +42,7 @@ extern "C" int isle_hip_upload_counts_u32(isle_ctx* c, uint64_t V, uint64_t D, u
   }
   HIPCHK(c, hipMemcpy(c->a_offs.p, offs, (D + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
   c->a_ready = true;
-  c->a_avg_valid = false;
-  c->p_catch_ready = false;
-  c->p_model_ready = false;
-  c->p_avg_ready = false;
+  isle_void_derived_from_A(c);
   return 0;
 }
 
@@ -77,10 +74,7 @@ extern "C" int isle_hip_ingest_tdf(isle_ctx* c, const char* text, uint64_t nbyte
   c->a_doc_offset = 0;
   c->a_D_global = D;
   c->a_ready = true;
-  c->a_avg_valid = false;
-  c->p_catch_ready = false;
-  c->p_model_ready = false;
-  c->p_avg_ready = false;
+  isle_void_derived_from_A(c);
   if (entries_read) *entries_read = nread;
   if (nnz) *nnz = c->a_nnz;
   return 0;
@@ -147,12 +141,7 @@ extern "C" int isle_hip_threshold(isle_ctx* c, uint64_t num_topics, double sampl
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (entries_above) {
     uint64_t g = (uint64_t)above_local;
-    if (c->multi()) {
-      HIPCHK(c, hipMemcpyAsync(st_dev, &g, sizeof(g), hipMemcpyHostToDevice, c->stream));
-      ISLECHK(allreduce_sum<uint64_t>(c, st_dev, 1));
-      HIPCHK(c, hipMemcpyAsync(&g, st_dev, sizeof(g), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    ISLECHK(allreduce_host<uint64_t>(c, &g, 1, st_dev));
     *entries_above = g;
   }
 
@@ -176,10 +165,7 @@ extern "C" int isle_hip_threshold(isle_ctx* c, uint64_t num_topics, double sampl
     uint64_t Dg = D;
     if (c->multi()) {  // all keys of the corpus on every rank: shards padded with -1 to the largest one
       uint64_t dmax = D;
-      HIPCHK(c, hipMemcpyAsync(st_dev, &dmax, sizeof(dmax), hipMemcpyHostToDevice, c->stream));
-      ISLECHK(isle_allreduce(c, st_dev, 1, ISLE_DT_U64, true));
-      HIPCHK(c, hipMemcpyAsync(&dmax, st_dev, sizeof(dmax), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
+      ISLECHK(allreduce_host<uint64_t>(c, &dmax, 1, st_dev, true, false /*not counted among the collectives' time, as before*/));
       if (dmax == 0) dmax = 1;
       DevBuf<float> keys_all;
       HIPCHK(c, keys_all.reserve((size_t)c->world * dmax));
@@ -228,14 +214,8 @@ extern "C" int isle_hip_threshold(isle_ctx* c, uint64_t num_topics, double sampl
   if (c->multi()) {
     DevBuf<uint64_t> all;
     HIPCHK(c, all.reserve((size_t)c->world + 1));
-    HIPCHK(c, hipMemcpyAsync(all.p + c->world, &Db, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    {
-      TimeScope ts(c, ISLE_T_COMM);
-      ISLECHK(isle_allgather(c, all.p + c->world, all.p, 1, ISLE_DT_U64));
-    }
     std::vector<uint64_t> h(c->world);
-    HIPCHK(c, hipMemcpyAsync(h.data(), all.p, c->world * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ISLECHK(allgather_host<uint64_t>(c, &Db, 1, all.p, h.data()));
     all.release();
     b_glob = 0;
     for (int r = 0; r < c->world; ++r) {
@@ -257,19 +237,7 @@ extern "C" int isle_hip_threshold(isle_ctx* c, uint64_t num_topics, double sampl
   if (D == 0) HIPCHK(c, hipMemsetAsync(c->offs.p, 0, sizeof(int64_t), c->stream));
   ISLECHK(k_th_emit(c, c->a_doc_offset));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->band_ready = false;
-  c->gl_mode = -1;
-  c->P_ready = false;
-  c->Pt_ready = false;
-  c->Pt2_ready = false;
-  c->lift_valid = false;
-  c->members_valid = false;
-  c->U_k = 0;
-  c->centers_ready = false;
-  c->assign_valid = false;
-  c->p_catch_ready = false;
-  c->p_model_ready = false;
-  c->p_avg_ready = false;
+  isle_void_derived_from_B(c);
   c->b_from_threshold = true;
   if (docs_kept) *docs_kept = Db;
   if (nnz_kept) *nnz_kept = bnnz;
@@ -399,14 +367,19 @@ extern "C" int isle_hip_get_doc_topic_sums(isle_ctx* c, int64_t* doc_offsets, ui
   return 0;
 }
 
+static int check_topic_pairs(isle_ctx* c, const int64_t* pairs, int n, const char* who) {
+  for (int e = 0; e < 2 * n; ++e)
+    if (pairs[e] < 0 || pairs[e] >= c->p_k) return isle_fail(c, ISLE_E_ARG, "%s: topic id %lld out of range", who, (long long)pairs[e]);
+  return 0;
+}
+
 extern "C" int isle_hip_edge_topics(isle_ctx* c, const int64_t* pairs, int n, float primary_ratio, float* edge) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
   if (!c->p_model_ready) return isle_fail(c, ISLE_E_ARG, "edge_topics: run isle_hip_topic_model first");
   if (n < 0 || (n && (!pairs || !edge))) return isle_fail(c, ISLE_E_ARG, "edge_topics: bad arguments");
   if (n == 0) return 0;
-  for (int e = 0; e < 2 * n; ++e)
-    if (pairs[e] < 0 || pairs[e] >= c->p_k) return isle_fail(c, ISLE_E_ARG, "edge_topics: topic id %lld out of range", (long long)pairs[e]);
+  ISLECHK(check_topic_pairs(c, pairs, n, "edge_topics"));
   DevBuf<int64_t> pd;
   DevBuf<float> ed;
   HIPCHK(c, pd.reserve(2 * (size_t)n));
@@ -522,6 +495,25 @@ static const float* resident_model(isle_ctx* c, int which, const char* who) {
   return nullptr;
 }
 
+// the model a call reads: the caller's (uploaded into `up`, which the caller keeps alive until its stream work is done) or a resident one
+static int model_source(isle_ctx* c, int which, const float* model_host, uint64_t vocab, int ncols, const char* who, DevBuf<float>* up, const float** dev) {
+  if (which == ISLE_MODEL_HOST) {
+    if (!model_host && ncols) return isle_fail(c, ISLE_E_ARG, "%s: null model_host", who);
+    if (ncols) {
+      HIPCHK(c, up->reserve(vocab * (size_t)ncols));
+      HIPCHK(c, hipMemcpyAsync(up->p, model_host, vocab * (size_t)ncols * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    }
+    *dev = up->p;
+    return 0;
+  }
+  *dev = resident_model(c, which, who);
+  if (!*dev) return ISLE_E_ARG;
+  if (vocab != c->a_V || ncols != c->p_k)
+    return isle_fail(c, ISLE_E_ARG, "%s: vocab x ncols = %llu x %d, the resident model is %llu x %d", who, (unsigned long long)vocab, ncols,
+                     (unsigned long long)c->a_V, c->p_k);
+  return 0;
+}
+
 extern "C" int isle_hip_model_top_words(isle_ctx* c, int which, const float* model_host, uint64_t vocab, int ncols, int n, uint32_t* ids,
                                         float* weights) {
   if (!c) return ISLE_E_ARG;
@@ -532,20 +524,7 @@ extern "C" int isle_hip_model_top_words(isle_ctx* c, int which, const float* mod
   if (!ids) return isle_fail(c, ISLE_E_ARG, "model_top_words: null ids");
   const float* dev = nullptr;
   DevBuf<float> up;
-  if (which == ISLE_MODEL_HOST) {
-    if (!model_host && ncols) return isle_fail(c, ISLE_E_ARG, "model_top_words: null model_host");
-    if (ncols) {
-      HIPCHK(c, up.reserve(vocab * (size_t)ncols));
-      HIPCHK(c, hipMemcpyAsync(up.p, model_host, vocab * (size_t)ncols * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    }
-    dev = up.p;
-  } else {
-    dev = resident_model(c, which, "model_top_words");
-    if (!dev) return ISLE_E_ARG;
-    if (vocab != c->a_V || ncols != c->p_k)
-      return isle_fail(c, ISLE_E_ARG, "model_top_words: vocab x ncols = %llu x %d, the resident model is %llu x %d", (unsigned long long)vocab, ncols,
-                       (unsigned long long)c->a_V, c->p_k);
-  }
+  ISLECHK(model_source(c, which, model_host, vocab, ncols, "model_top_words", &up, &dev));
   if (ncols == 0) return 0;
   const size_t m = (size_t)ncols * n;
   DevBuf<uint32_t> id_d;
@@ -572,20 +551,7 @@ extern "C" int isle_hip_model_text(isle_ctx* c, int which, const float* model_ho
   if (ncols < 0 || vocab == 0 || vocab > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "model_text: vocab or ncols out of range");
   const float* dev = nullptr;
   DevBuf<float> up;
-  if (which == ISLE_MODEL_HOST) {
-    if (!model_host && ncols) return isle_fail(c, ISLE_E_ARG, "model_text: null model_host");
-    if (ncols) {
-      HIPCHK(c, up.reserve(vocab * (size_t)ncols));
-      HIPCHK(c, hipMemcpyAsync(up.p, model_host, vocab * (size_t)ncols * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    }
-    dev = up.p;
-  } else {
-    dev = resident_model(c, which, "model_text");
-    if (!dev) return ISLE_E_ARG;
-    if (vocab != c->a_V || ncols != c->p_k)
-      return isle_fail(c, ISLE_E_ARG, "model_text: vocab x ncols = %llu x %d, the resident model is %llu x %d", (unsigned long long)vocab, ncols,
-                       (unsigned long long)c->a_V, c->p_k);
-  }
+  ISLECHK(model_source(c, which, model_host, vocab, ncols, "model_text", &up, &dev));
   const int rc = k_model_text(c, dev, vocab, (uint64_t)ncols, nullptr, 0.f, 0.f, format, sink, user, nbytes, nentries);
   (void)hipStreamSynchronize(c->stream);  // `up` is freed on return
   return rc;
@@ -601,8 +567,7 @@ extern "C" int isle_hip_edge_topics_text(isle_ctx* c, const int64_t* pairs, int 
   if (format != ISLE_TEXT_SPARSE && format != ISLE_TEXT_DENSE) return isle_fail(c, ISLE_E_ARG, "edge_topics_text: unknown format %d", format);
   if (n < 0 || (n && !pairs)) return isle_fail(c, ISLE_E_ARG, "edge_topics_text: bad arguments");
   if (n == 0) return 0;
-  for (int e = 0; e < 2 * n; ++e)
-    if (pairs[e] < 0 || pairs[e] >= c->p_k) return isle_fail(c, ISLE_E_ARG, "edge_topics_text: topic id %lld out of range", (long long)pairs[e]);
+  ISLECHK(check_topic_pairs(c, pairs, n, "edge_topics_text"));
   DevBuf<int64_t> pd;
   HIPCHK(c, pd.reserve(2 * (size_t)n));
   HIPCHK(c, hipMemcpy(pd.p, pairs, 2 * (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));

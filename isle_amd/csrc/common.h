@@ -79,7 +79,8 @@ struct DevBuf {
   ~DevBuf() { release(); }  // every buffer of a context dies with it
 };
 
-// Pinned host buffer with explicit capacity (grows, never shrinks): the landing place of the model text (model_text.hip).
+// Pinned host buffer with explicit capacity (grows, never shrinks): the landing place of the model text (model_text.hip), the staging
+// of the centre matrices (isle_ctx::pin_stage).
 struct PinBuf {
   char* p = nullptr;
   size_t cap = 0;
@@ -100,7 +101,6 @@ struct PinBuf {
   }
 };
 
-// One side of the LDS-banded Gram apply (gram_lds.hip): a sliced-ELL stream of band-local u16 source ids.
 // ------------------------------------------------------------------------------------------
 // Environment switches.  Every switch the library honours is in this table; they are read into the context when it is created and
 // again at the entry of every C-ABI call (isle_enter, api.cpp) — never inside a loop or a launch path — and the code asks the context
@@ -121,6 +121,7 @@ struct IsleKnobInfo {
 };
 extern const IsleKnobInfo isle_knob_table[KN_COUNT];
 
+// One side of the LDS-banded Gram apply (gram_lds.hip): a sliced-ELL stream of band-local u16 source ids.
 struct GlDesc {  // one workgroup: 16 waves wave0 + i*wstride (i < nw), source bands [b0, b1), output slab
   uint32_t wave0, wstride, nw, b0, b1, slab, pos_base, pad;
 };
@@ -134,6 +135,23 @@ struct GlSide {
   DevBuf<uint2> ids;          // super-rounds x 64 lanes: four u16 band-local source ids per lane (+ prefetch slack)
   DevBuf<GlDesc> desc;
   int64_t total_sr = 0;
+};
+
+// The small page-locked region (isle_ctx::pin + PIN_SMALL): one member per user, so that no two of them share a word by accident.  The
+// single words sit on cache lines of their own; the watchdog's is read by a second thread for the life of the communicator.
+struct IslePinSmall {
+  double kmpp_stage[(128u << 10) / 8];  // k-means++ rounds: [my 2 | tot 2 * world | local maxdraw] doubles, drawn maxdraw u64, 42 words of the search
+  int cluster_sizes[(64u << 10) / 4];   // fetch_sizes (larger k: pageable memory)
+  alignas(64) uint32_t stop_flag;       // StopRule: the partitions differ
+  alignas(64) uint32_t active_count;    // Lloyd in span(U): documents up for re-examination
+  alignas(64) int agree[2];             // agree_i32: (v, -v)
+  alignas(64) uint32_t changed_count;   // k_proj_accumulate_delta: documents that changed centre
+  alignas(64) uint32_t redo_count;      // dense.hip: rows the two-term pass of an assignment product left open
+  alignas(64) volatile uint32_t wd_done;  // the watchdog's word (isle_ctx::wd_done)
+  alignas(64) union {
+    float movements[(32u << 10) / 4];     // fetch_delta (larger k: a blocking copy)
+    float centre_norms[(32u << 10) / 4];  // Lloyd on B, regrouping (k <= 2048); each view is copied out right behind its own synchronisation
+  };
 };
 
 struct isle_ctx {
@@ -156,18 +174,9 @@ struct isle_ctx {
   char* pin = nullptr;
   // growable page-locked staging for the k x k centre matrices that cross the boundary at the ends of the k-means calls (4 MB at
   // k = 1000): hipMemcpyAsync from freshly allocated pageable memory was seen to block for 26 ms there (api.cpp, lloyds_projected)
-  char* pin_stage = nullptr;
-  size_t pin_stage_cap = 0;
-  hipError_t pin_stage_reserve(size_t bytes) {
-    if (bytes <= pin_stage_cap) return hipSuccess;
-    if (pin_stage) (void)hipHostFree(pin_stage);
-    pin_stage = nullptr;
-    pin_stage_cap = 0;
-    hipError_t e = hipHostMalloc((void**)&pin_stage, bytes, hipHostMallocDefault);
-    if (e == hipSuccess) pin_stage_cap = bytes;
-    return e;
-  }
+  PinBuf pin_stage;
   static constexpr size_t PIN_MAIL = 0, PIN_MAIL_SLOT = 1u << 20, PIN_SMALL = 2u << 20, PIN_BYTES = (2u << 20) + (256u << 10);
+  IslePinSmall* pin_small() const { return reinterpret_cast<IslePinSmall*>(pin + PIN_SMALL); }
 
   // --- communicator (null for single GPU)
   ncclComm_t comm = nullptr;
@@ -403,6 +412,8 @@ struct isle_ctx {
   uint64_t t_n[ISLE_T_COUNT] = {0};
 };
 
+static_assert(sizeof(IslePinSmall) <= isle_ctx::PIN_BYTES - isle_ctx::PIN_SMALL, "the small page-locked region holds every slot");
+
 int isle_fail(isle_ctx* c, int code, const char* fmt, ...);
 // A new matrix of D documents and nnz entries replaces the context's: the largest derived buffers (projection and its copies, product scratch,
 // build scratch) are released where they are sized for a far larger matrix — everything derived from the old one is void anyway (api.cpp)
@@ -436,6 +447,14 @@ void isle_host_mark(const char* what);
     if (rc__ != 0) return rc__;  \
   } while (0)
 
+// One device word on the host: through its page-locked slot (IslePinSmall), behind a synchronisation of the stream.
+inline int isle_fetch_u32(isle_ctx* c, const uint32_t* dev, uint32_t* slot, uint32_t* out) {
+  HIPCHK(c, hipMemcpyAsync(slot, dev, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *out = *slot;
+  return 0;
+}
+
 // RAII timing scope: records an event pair on the stream when timing is enabled.
 struct TimeScope {
   isle_ctx* c;
@@ -450,6 +469,10 @@ static inline uint64_t isle_scan_scratch(uint64_t n) { return (n + 4095) / 4096 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ---------------- kernel launchers (each defined in one .hip file) -------------------------
+// api.cpp: collectives on c->stream: RCCL, or the host-staged rehearsal transport; no-ops without a communicator
+enum { ISLE_DT_F32 = 0, ISLE_DT_F64 = 1, ISLE_DT_I32 = 2, ISLE_DT_U32 = 3, ISLE_DT_U64 = 4 };
+int isle_allreduce(isle_ctx* c, void* buf, size_t count, int dtype, bool max_op = false);  // in place
+int isle_allgather(isle_ctx* c, const void* send, void* recv, size_t count_per_rank, int dtype);  // recv: world * count_per_rank
 // spmm.hip
 int k_pack_rm(isle_ctx* c, const float* Xcm, uint64_t V, int b, int BP, float* Xrm);
 int k_unpack_cm(isle_ctx* c, const float* Zrm, uint64_t V, int b, int BP, float* Zcm);
@@ -457,26 +480,11 @@ int k_gram_pass1(isle_ctx* c, int BP);   // Yrm = B^T Xrm
 int k_gram_pass2(isle_ctx* c, int BP);   // Zrm = B Yrm
 int k_band_build(isle_ctx* c);
 int k_band_build_chunked(isle_ctx* c);   // chunk-major cells for the gather path (spmm.hip)
-// gram_lds.hip
-// collectives on c->stream (api.cpp): RCCL, or the host-staged rehearsal transport; no-ops without a communicator
-enum { ISLE_DT_F32 = 0, ISLE_DT_F64 = 1, ISLE_DT_I32 = 2, ISLE_DT_U32 = 3, ISLE_DT_U64 = 4 };
-int isle_allreduce(isle_ctx* c, void* buf, size_t count, int dtype, bool max_op = false);  // in place
-int isle_allgather(isle_ctx* c, const void* send, void* recv, size_t count_per_rank, int dtype);  // recv: world * count_per_rank
 int k_dots_assign(isle_ctx* c, int k, int ldk, const float* cn, const float* dn, uint32_t* assign, float* ub, float* lb, int G);
 int k_dots_assign_cm(isle_ctx* c, const float* dotsT, int k, int G, const float* cn, const float* dn, const float* cn_max_dev, uint32_t* assign, float* ub,
                      float* lb);  // the same from column-major dot products, Yinyang bounds
-int k_gl_detect(isle_ctx* c);            // sets c->gl_mode for the current B (no-op once decided)
-int k_centers_counts(isle_ctx* c, const uint32_t* assign, int k, int ldk, float* Crm, bool fresh);  // fresh: needs c->members grouped by `assign`
-int k_gl_build(isle_ctx* c);
-int k_gl_wide(isle_ctx* c, const float* Mrm, int k, int ld, float* Out, float* norms = nullptr /*also the rows' squared norms (selects the grouped form)*/,
-              void* A2pos = nullptr /*grouped form only: also the split copy of Out by POSITION (k_gemm_split_a_bytes(D, k) bytes)*/, bool* a2_done = nullptr);
-int k_gl_thin(isle_ctx* c, const float* Wcm, int nc, int ld, float* Out, bool by_position = false);  // Out (D x ld) = B^T W, W V x nc col-major, nc <= 32  // Out (D x ld) = B^T M, LDS-banded form only
-int k_gl_apply_cm(isle_ctx* c, const float* Xcm, int b, int BP, float* Zcm);  // Zcm (V x b col-major) = B (B^T Xcm), b columns in a panel of BP in {4, 8, 12}
-// ingest.hip
-int k_sort_pairs_u64(isle_ctx* c, uint64_t* key_a, uint32_t* val_a, uint64_t* key_b, uint32_t* val_b, uint64_t n, int key_bits, bool* in_a);
 int k_frobenius(isle_ctx* c, double* out_host);
 int k_spmm_wide_project(isle_ctx* c, const float* Mrm, int k, int ldk, float* P, float* norms, void* A2pos = nullptr, bool* a2_done = nullptr);
-int k_ensure_pt(isle_ctx* c);  // the coordinate-major f32 copy of the projection, made from P when a route asks for it (dense.hip)
 int k_spmm_wide_assign(isle_ctx* c, const float* Mrm, int k, int ldk, const float* cn, const float* dn, uint32_t* assign,
                        const uint32_t* perm /*nullable: slot -> doc*/, const uint32_t* nslots = nullptr /*device slot count*/,
                        float* ub = nullptr, float* lb = nullptr, int G = 0 /*> 0: lb holds G Yinyang group bounds per document*/);
@@ -528,13 +536,22 @@ struct HamTop {  // largest and second largest centre movement of an iteration (
 int k_ham_delta(isle_ctx* c, float* delta_dev /*in: squared movements, out: rounded-up movements*/, int k, HamTop* top_dev);
 int k_hamerly_filter(isle_ctx* c, const uint32_t* order, const uint32_t* assign, float* ub, float* lb, const float* delta_dev, const HamTop* top_dev,
                      uint32_t* active, uint32_t* nactive, int fam = ISLE_T_SPARSE_ASSIGN);
-int k_member_lists(isle_ctx* c, const uint32_t* assign, uint64_t D, int k, const int* counts_dev, int* max_out, std::vector<int>* counts_host = nullptr);
-int k_member_lists_dev(isle_ctx* c, const uint32_t* assign, uint64_t D, int k, const int* counts_dev);  // no host round trip
-int k_yy_delta(isle_ctx* c, float* delta_dev, int k, int G, int group, float* gmax_dev, const uint32_t* id_of_slot = nullptr);
-int k_max_f32(isle_ctx* c, const float* v, int n, float* out_dev);
 int k_csc_validate(isle_ctx* c, unsigned long long* err_host2);  // the uploaded CSC arrays on the device: [0] first bad column + 1 (0 = fine), [1] what (spmm.hip)
 int k_doc_norms(isle_ctx* c, float* dn);
 int k_centers_from_rows(isle_ctx* c, const uint32_t* assign, int k, int ldk, float* Crm, bool first_of_run = true);
+int k_pt_filter(isle_ctx* c, const uint32_t* order, const uint32_t* assign, float* ub, float* tlb, int T, int TL, const float* delta_dev,
+                const float* tmove_dev, uint32_t* need, uint32_t* active, uint32_t* nactive, const YyMovers& mv, const float* mdots, const float* cn, const float* pn);
+int k_pt_tighten(isle_ctx* c, const float* P, const float* pn, int ldk, const float* C, const float* cn, const uint32_t* assign, const uint32_t* cand,
+                 const uint32_t* ncand, float* ub, const float* tlb, int T, int TL, uint32_t* need, uint32_t* active, uint32_t* nactive);
+// gram_lds.hip
+int k_gl_detect(isle_ctx* c);            // sets c->gl_mode for the current B (no-op once decided)
+int k_centers_counts(isle_ctx* c, const uint32_t* assign, int k, int ldk, float* Crm, bool fresh);  // fresh: needs c->members grouped by `assign`
+int k_gl_build(isle_ctx* c);
+int k_gl_wide(isle_ctx* c, const float* Mrm, int k, int ld, float* Out, float* norms = nullptr /*also the rows' squared norms (selects the grouped form)*/,
+              void* A2pos = nullptr /*grouped form only: also the split copy of Out by POSITION (k_gemm_split_a_bytes(D, k) bytes)*/, bool* a2_done = nullptr);
+int k_gl_thin(isle_ctx* c, const float* Wcm, int nc, int ld, float* Out, bool by_position = false);  // Out (D x ld) = B^T W, W V x nc col-major, nc <= 32  // Out (D x ld) = B^T M, LDS-banded form only
+int k_gl_apply_cm(isle_ctx* c, const float* Xcm, int b, int BP, float* Zcm);  // Zcm (V x b col-major) = B (B^T Xcm), b columns in a panel of BP in {4, 8, 12}
+int k_gl_panel_width(const isle_ctx* c);  // columns per pass of the k-wide / thin products through the pass-1 stream (gram_lds.hip)
 
 // threshold.hip
 int k_th_stats(isle_ctx* c, uint64_t* tokens_nz_dev);
@@ -546,6 +563,7 @@ int k_th_scans(isle_ctx* c);
 int k_th_emit(isle_ctx* c, uint64_t doc_base);
 
 // ingest.hip
+int k_sort_pairs_u64(isle_ctx* c, uint64_t* key_a, uint32_t* val_a, uint64_t* key_b, uint32_t* val_b, uint64_t n, int key_bits, bool* in_a);
 int k_ingest_tdf(isle_ctx* c, const unsigned char* text_dev, uint64_t n, uint64_t V, uint64_t D, uint64_t* entries_read, uint64_t* err_out);
 
 // infer.hip
@@ -590,6 +608,7 @@ int k_log_combinatorial(isle_ctx* c, float* out, uint64_t* max_words);
 int k_top_five_runs(isle_ctx* c, uint64_t* n_out, std::vector<uint64_t>& runs, float* tuples);
 
 // dense.hip
+int k_ensure_pt(isle_ctx* c);  // the coordinate-major f32 copy of the projection, made from P when a route asks for it (dense.hip)
 int k_vtf(isle_ctx* c, const float* Vb, uint64_t n, int m, const float* F, int b, float* coef /*m x b col-major dev*/, uint64_t ld = 0);
 int k_update(isle_ctx* c, float* F, uint64_t n, int b, const float* Vb, int m, const float* coef, uint64_t ld = 0);
 int k_panel_qr(isle_ctx* c, float* F, uint64_t n, int w, float* Qdst, float* R_host /*w*w*/, int* rank_out);
@@ -608,20 +627,25 @@ int k_gemm_assign_tiles(isle_ctx* c, const float* A, const float* Arm, int lda_r
 // A2 = the two bf16 terms of a coordinate-major M x K operand in the layout gemm_bf16x2_dma_k stages by LDS-DMA (gemm_bf16x3.h); bytes it needs
 int k_gemm_split_a(isle_ctx* c, const float* A, uint64_t M, int K, void* A2);
 size_t k_gemm_split_a_bytes(uint64_t M, int K);
-int k_compact_rows(isle_ctx* c, const float* P, const float* pn, int ldk, const uint32_t* active, uint32_t n, float* Pa, float* pna);
 int k_transpose(isle_ctx* c, const float* in, uint64_t rows, uint64_t cols, uint64_t ld_in, float* out, uint64_t ld_out);  // out[c*ld_out + r]... see impl
 int k_jacobi_eig(isle_ctx* c, const float* S_host, int n, float* evals_host, float* vecs_dev /*n x n col-major*/);
-int k_tridiag_eig(isle_ctx* c, const float* S_host, int n, float* evals_host, float* vecs_dev, int nvec);  // evd_tridiag.hip; 1 = use another solver; evals_host[nvec..n) = 0
 int k_eig_small(isle_ctx* c, const float* S_host, int n, float* evals_host, float* vecs_dev /*n x nvec col-major*/, int nvec);
 int k_colnorms_rm(isle_ctx* c, const float* Mrm, uint64_t rows, int k, int ldk, float* out, const float* Sub = nullptr);
 int k_scale_centers(isle_ctx* c, float* Crm, uint64_t rows, int k, int ldk, const int* counts);
 
+// evd_tridiag.hip
+int k_tridiag_eig(isle_ctx* c, const float* S_host, int n, float* evals_host, float* vecs_dev, int nvec);  // evd_tridiag.hip; 1 = use another solver; evals_host[nvec..n) = 0
+
 // kmeans.hip
+int k_member_lists(isle_ctx* c, const uint32_t* assign, uint64_t D, int k, const int* counts_dev, int* max_out, std::vector<int>* counts_host = nullptr);
+int k_member_lists_dev(isle_ctx* c, const uint32_t* assign, uint64_t D, int k, const int* counts_dev);  // no host round trip
+int k_yy_delta(isle_ctx* c, float* delta_dev, int k, int G, int group, float* gmax_dev, const uint32_t* id_of_slot = nullptr);
+int k_max_f32(isle_ctx* c, const float* v, int n, float* out_dev);
+int k_compact_rows(isle_ctx* c, const float* P, const float* pn, int ldk, const uint32_t* active, uint32_t n, float* Pa, float* pna);
 // s_old = seeds before the nc new ones; track: also keep the nearest seed and the tile minima where the route allows (c->kmpp_track)
 int k_kmpp_update(isle_ctx* c, const float* P, const float* pn, uint64_t D, int k, int ldk, const float* newC, int nc, float* min_dist, int s_old = -1,
                   bool track = false);
 int k_kmpp_to_tiles(isle_ctx* c, uint64_t D, int k, const float* pn, const float* cn, const float* best, uint32_t* assign, float* ub, int TL);
-int k_gl_panel_width(const isle_ctx* c);  // columns per pass of the k-wide / thin products through the pass-1 stream (gram_lds.hip)
 int k_scan_f2d(isle_ctx* c, const float* in, uint64_t n, double* cum /*n+1*/);
 int k_search(isle_ctx* c, const double* cum, uint64_t n, const double* dice_dev, int nd, uint64_t* out_dev);
 int k_search_args(isle_ctx* c, const double* cum, uint64_t n, const double* dice_host, int nd /*<= 16*/, uint64_t* out_dev);
@@ -636,10 +660,6 @@ int k_proj_assign_active(isle_ctx* c, const float* P, const float* pn, int k, in
 bool k_proj_full_by_gemm(isle_ctx* c, uint64_t D, int k);  // the full tile-bound pass goes through the library GEMM (kmeans.hip)
 int k_proj_assign_tiles(isle_ctx* c, const float* P, const float* pn, uint64_t D, int k, int ldk, const float* C, const float* cn, uint32_t* assign,
                         float* ub, float* tlb, int TL, const uint32_t* active, uint32_t n, const uint32_t* need, float* Pa, float* pna);
-int k_pt_filter(isle_ctx* c, const uint32_t* order, const uint32_t* assign, float* ub, float* tlb, int T, int TL, const float* delta_dev,
-                const float* tmove_dev, uint32_t* need, uint32_t* active, uint32_t* nactive, const YyMovers& mv, const float* mdots, const float* cn, const float* pn);
-int k_pt_tighten(isle_ctx* c, const float* P, const float* pn, int ldk, const float* C, const float* cn, const uint32_t* assign, const uint32_t* cand,
-                 const uint32_t* ncand, float* ub, const float* tlb, int T, int TL, uint32_t* need, uint32_t* active, uint32_t* nactive);
 int k_rownorms_diff(isle_ctx* c, const float* A, const float* B, int rows, int k, int ldk, float* out);
 int k_rownorms(isle_ctx* c, const float* M, int rows, int k, int ldk, float* out);
 int k_proj_accumulate(isle_ctx* c, const float* P, uint64_t D, int k, int ldk, const uint32_t* assign, float* Csum, int* counts);

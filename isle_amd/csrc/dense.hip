@@ -1011,10 +1011,8 @@ static int gemm_assign_two_pass(isle_ctx* c, const float* A, const float* Arm, i
     combine(part, (uint32_t)M, map0, eta2, c->ga_redo.p, nredo);
   }
   HIPCHK(c, hipGetLastError());
-  uint32_t* n_pin = reinterpret_cast<uint32_t*>(c->pin + isle_ctx::PIN_SMALL + (192u << 10) + 192);  // page-locked
-  HIPCHK(c, hipMemcpyAsync(n_pin, nredo, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint32_t n = *n_pin;
+  uint32_t n = 0;
+  ISLECHK(isle_fetch_u32(c, nredo, &c->pin_small()->redo_count, &n));
   c->ga_last_redo = n;
   if (c->knob_on(KN_DEBUG_HAMERLY)) fprintf(stderr, "[assignment product] the two-term pass left %u of %llu rows open\n", n, (unsigned long long)M);
   if (n == 0) return 0;

@@ -1520,10 +1520,9 @@ int k_proj_accumulate_delta(isle_ctx* c, const float* P, uint64_t D, int k, int 
   hipLaunchKernelGGL(proj_changed_k, dim3(cdiv(D, 256)), dim3(256), 0, c->stream, assign, counted, (uint32_t)D, dbits, c->gl_key_a.p, c->gl_val_a.p, cap,
                      c->proj_nch.p);
   HIPCHK(c, hipGetLastError());
-  uint32_t* n_pin = reinterpret_cast<uint32_t*>(c->pin + isle_ctx::PIN_SMALL + (192u << 10) + 128);  // page-locked
-  HIPCHK(c, hipMemcpyAsync(n_pin, c->proj_nch.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t n = 2 * (uint64_t)*n_pin;
+  uint32_t nch = 0;
+  ISLECHK(isle_fetch_u32(c, c->proj_nch.p, &c->pin_small()->changed_count, &nch));
+  const uint64_t n = 2 * (uint64_t)nch;
   if (n > cap) return 0;  // `counted` already holds the new assignment: the fresh sums the caller computes agree with it
   *done = true;
   if (n == 0) return 0;

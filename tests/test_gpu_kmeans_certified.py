@@ -272,13 +272,13 @@ def test_both_loops_iteration_by_iteration(hp, k, monkeypatch, capfd):
     assert hp.operator_form() == 1
 
 
-# Forms of Lloyd in span(U).  Tile bounds exist at k > 224 only (api_kmeans.cpp: tiles = k > 224 && ...), and ISLE_PROJ_BOUNDS,
+# Forms of Lloyd in span(U).  Tile bounds exist at k > 224 only (api_kmeans.cpp, proj_plan: tiles = hamerly && k > 224 && ...), and ISLE_PROJ_BOUNDS,
 # ISLE_PROJ_FULL and ISLE_PROJ_ACTIVE are read on that path alone (k_proj_full_by_gemm, k_proj_assign_tiles): at k = 9 and 65 they would
 # rerun the default form, so they run at k = 257 and 1000.
 PROJ_TILE_FORMS = [{"ISLE_PROJ_BOUNDS": "hamerly"}, {"ISLE_PROJ_FULL": "gemm"}, {"ISLE_PROJ_FULL": "fused"}, {"ISLE_PROJ_ACTIVE": "tiles"}]
 PROJ_FORMS = PROJ_TILE_FORMS + [{"ISLE_PROJ_SUMS": "fresh"}, {"ISLE_NO_HAMERLY": "1"}]
 # Forms of Lloyd on B.  Regrouping and the fused filter-and-tighten launch belong to the by-group Yinyang form, which the loop takes at
-# k >= 256 (api_kmeans.cpp: yy_mode = G >= 32 ? 2 : 0; regroup = yy_mode == 2 && ...): they run at k = 257 and 1000.
+# k >= 256 (api_kmeans.cpp, sparse_plan: yy_mode = ... G >= 32 ? 2 : 0; regroup = yinyang && yy_mode == 2 && ...): they run at k = 257 and 1000.
 SPARSE_GROUP_FORMS = [{"ISLE_YY_FUSED": "0"}, {"ISLE_YY_REGROUP": "0"}]
 SPARSE_FORMS = [{"ISLE_KMEANS_BOUNDS": "hamerly"}, {"ISLE_KMEANS_BOUNDS": "none"}, {"ISLE_YY_MODE": "doc"}, {"ISLE_YY_MODE": "docg"},
                 {"ISLE_YY_MODE": "group"}, {"ISLE_YY_MOVERS": "0"}, {"ISLE_CENTERS_FRESH": "1"}, {"ISLE_FIRST_ASSIGN": "sparse"},
