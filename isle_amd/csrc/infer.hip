@@ -615,8 +615,7 @@ int k_infer(isle_ctx* c, uint64_t V, int k, const float* model_by_word, uint64_t
         if (nf <= 1) INF((inf_docs16_k<1>));
         else if (nf <= 2) INF((inf_docs16_k<2>));
         else INF((inf_docs16_k<4>));
-      } else if (nit <= 1) INF((inf_docs_k<1>));
-      else if (nit <= 2) INF((inf_docs_k<2>));
+      } else if (nit <= 2) INF((inf_docs_k<2>));  // nq > 64 here: two or four float4 per lane
       else INF((inf_docs_k<4>));
 #undef INF
       HIPCHK(c, hipGetLastError());
