@@ -391,6 +391,37 @@ int isle_hip_infer(isle_ctx* ctx, uint64_t vocab_size, int num_topics, const flo
                    const int64_t* offsets, int iters, float Lf_guess, float avg_doc_sz, float* weights,
                    int32_t* top_topic, float* top_weight, float* llh, uint64_t* nconverged);
 
+/* The same inference on what is resident: documents [doc_begin, doc_end) of the count matrix A (isle_hip_upload_counts_u32 or
+ * isle_hip_ingest_tdf; the counts as they are, normalised per document by the kernel) under the catch model, the average model or a
+ * caller's model, with the weights returned as sparse entries.  No B, partition or catchwords are needed with ISLE_MODEL_HOST.
+ *   which / model_host / vocab / ncols: as isle_hip_model_top_words (ISLE_MODEL_HOST: vocab x ncols COLUMN-major, uploaded once for the
+ *     call), with its ISLE_E_ARG conditions; vocab must be A's; ncols outside [1, 1024] is refused as by isle_hip_infer.  The model is
+ *     transposed on the device into the row-major, zero-padded layout the iteration kernels read; the iterations are the launches of
+ *     isle_hip_infer on the resident buffers, so for the same fp32 model and documents every output equals isle_hip_infer's bit for bit.
+ *   iters / Lf_guess: as isle_hip_infer.  avg_doc_sz is the corpus value the context holds (the thresholding's, or computed here by the
+ *     same rule, SparseMatrix::populate_CSC src/sparseMatrix.cpp:87-98: floor(sum of counts / number of non-empty documents) over ALL of
+ *     A, not over the range): llh.first is scaled by the corpus average, whatever the range.
+ *   top_topic / top_weight (range x 5), llh (range x 2), nconverged: as isle_hip_infer, over the range only (the first document of the
+ *     range is row 0); each nullable.
+ *   Entries: for every converged document (llh.first != 0) every topic with weight > min_weight, compared in float, topics ascending;
+ *     min_weight < 0 selects 1.0f / (float)ncols, the rule of the top topics.  Documents that did not converge (empty ones, documents
+ *     whose words are all absent from the model) have no entries.  nentries (nullable): their number.  They stay resident until the next
+ *     call or until A changes; isle_hip_get_infer_entries copies them out: doc_offsets (doc_end - doc_begin) + 1 entries (64-bit: the
+ *     count can reach docs x ncols), topic / weight nentries entries, (document, topic) ascending; each nullable.
+ *   chunk_docs: documents per pass; the device holds the dense weights of one pass only (chunk_docs x ncols floats), never docs x ncols.
+ *     0 = as many as keep them within 1 GiB (at most 2^22).  No result depends on it, bit for bit.
+ * ISLE_E_ARG: world > 1, no count matrix, doc_begin > doc_end, doc_end > docs(A), iters < 1, Lf_guess <= 0, the model conditions above.
+ * doc_begin == doc_end is valid: no entries, nconverged = 0.  Every argument is checked before any work: after a refusal the context is
+ * usable and the entries of the previous call are intact; a call that fails later (ISLE_E_HIP) leaves none (isle_hip_get_infer_entries
+ * then returns ISLE_E_ARG, as it does before the first call and after a new A).  Device time is booked under ISLE_T_INFER. */
+int isle_hip_infer_resident(isle_ctx* ctx, int which, const float* model_host, uint64_t vocab, int ncols, uint64_t doc_begin,
+                            uint64_t doc_end, int iters, float Lf_guess, float min_weight, uint64_t chunk_docs, int32_t* top_topic,
+                            float* top_weight, float* llh, uint64_t* nconverged, uint64_t* nentries);
+int isle_hip_get_infer_entries(isle_ctx* ctx, int64_t* doc_offsets, uint32_t* topic, float* weight);
+/* The avg_doc_sz of the resident count matrix as the context holds it (see above; computed on first use).  ISLE_E_ARG: no count matrix,
+ * world > 1, out null. */
+int isle_hip_avg_doc_sz(isle_ctx* ctx, float* out);
+
 /* ---- measurement ----------------------------------------------------------------------- */
 /* Per-kernel-family device time accumulated with HIP events on the context's stream since the
  * last reset (only while enabled; enabling adds event records around each launch).

@@ -578,6 +578,7 @@ static void void_downstream(isle_ctx* c) {  // catchwords and models are read of
 }
 void isle_void_derived_from_A(isle_ctx* c) {
   c->a_avg_valid = false;
+  c->inf_valid = false;  // the entries of isle_hip_infer_resident are about A's documents
   void_downstream(c);
 }
 void isle_void_derived_from_B(isle_ctx* c) {

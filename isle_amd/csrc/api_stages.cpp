@@ -280,7 +280,7 @@ static int post_prepare(isle_ctx* c, const char* who) {
 
 // a_nv = avg_doc_sz * (count / doc_sum) over A (src/sparseMatrix.cpp:136-167), the values the catchword stage and the top-five
 // diagnostic read; avg_doc_sz from the thresholding when it ran, else computed here by the same rule (:92-99)
-static int post_normalize_A(isle_ctx* c) {
+static int ensure_avg_doc_sz(isle_ctx* c) {
   if (!c->a_avg_valid) {  // B came from the host: the corpus statistics were never computed here
     HIPCHK(c, c->a_scan.reserve(isle_scan_scratch(c->a_D) + 4));
     ISLECHK(k_th_stats(c, (uint64_t*)c->a_scan.p));
@@ -290,6 +290,10 @@ static int post_normalize_A(isle_ctx* c) {
     c->a_avg = (float)(st[0] / std::max<uint64_t>(st[1], 1));
     c->a_avg_valid = true;
   }
+  return 0;
+}
+static int post_normalize_A(isle_ctx* c) {
+  ISLECHK(ensure_avg_doc_sz(c));
   return k_post_normalize(c, c->a_avg);
 }
 
@@ -663,3 +667,50 @@ extern "C" int isle_hip_infer(isle_ctx* c, uint64_t V, int k, const float* model
   return k_infer(c, V, k, model_by_word, D, nnz, counts, rows, offs, iters, Lf, avg_doc_sz, weights, top_topic, top_weight, llh, nconverged);
 }
 
+
+// Document-topic inference on the resident count matrix under a resident or uploaded model (infer_resident.hip).  Every argument is
+// checked before any work: a refused call leaves the entries of the previous call as they were.
+extern "C" int isle_hip_infer_resident(isle_ctx* c, int which, const float* model_host, uint64_t vocab, int ncols, uint64_t doc_begin,
+                                       uint64_t doc_end, int iters, float Lf, float min_weight, uint64_t chunk_docs, int32_t* top_topic,
+                                       float* top_weight, float* llh, uint64_t* nconverged, uint64_t* nentries) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(post_prepare(c, "infer_resident"));
+  if (doc_begin > doc_end || doc_end > c->a_D)
+    return isle_fail(c, ISLE_E_ARG, "infer_resident: documents [%llu, %llu) of %llu", (unsigned long long)doc_begin, (unsigned long long)doc_end,
+                     (unsigned long long)c->a_D);
+  if (iters < 1 || !(Lf > 0.f)) return isle_fail(c, ISLE_E_ARG, "infer_resident: iters = %d, Lf = %g", iters, (double)Lf);
+  if (ncols < 1 || ncols > 1024) return isle_fail(c, ISLE_E_ARG, "infer: num_topics = %d not in [1, 1024]", ncols);
+  if (vocab != c->a_V)
+    return isle_fail(c, ISLE_E_ARG, "infer_resident: the model has %llu words, the count matrix %llu", (unsigned long long)vocab, (unsigned long long)c->a_V);
+  const float* dev = nullptr;
+  DevBuf<float> up;
+  ISLECHK(model_source(c, which, model_host, vocab, ncols, "infer_resident", &up, &dev));
+  int rc = ensure_avg_doc_sz(c);
+  if (rc == 0)
+    rc = k_infer_resident(c, dev, ncols, doc_begin, doc_end, iters, Lf, c->a_avg, min_weight, chunk_docs, top_topic, top_weight, llh, nconverged,
+                          nentries);
+  (void)hipStreamSynchronize(c->stream);  // `up` is freed on return
+  return rc;
+}
+
+extern "C" int isle_hip_get_infer_entries(isle_ctx* c, int64_t* doc_offsets, uint32_t* topic, float* weight) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  if (!c->inf_valid) return isle_fail(c, ISLE_E_ARG, "get_infer_entries: no entries (run isle_hip_infer_resident; a new count matrix voids them)");
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (doc_offsets) HIPCHK(c, hipMemcpy(doc_offsets, c->inf_off.p, (c->inf_docs + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (topic && c->inf_n) HIPCHK(c, hipMemcpy(topic, c->inf_topic.p, c->inf_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (weight && c->inf_n) HIPCHK(c, hipMemcpy(weight, c->inf_weight.p, c->inf_n * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+extern "C" int isle_hip_avg_doc_sz(isle_ctx* c, float* out) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(post_prepare(c, "avg_doc_sz"));
+  if (!out) return isle_fail(c, ISLE_E_ARG, "avg_doc_sz: null out");
+  ISLECHK(ensure_avg_doc_sz(c));
+  *out = c->a_avg;
+  return 0;
+}

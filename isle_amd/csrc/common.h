@@ -245,6 +245,12 @@ struct isle_ctx {
   DevBuf<uint64_t> mt_offs, mt_blk, mt_stat;  // their exclusive scan (+ its scratch); entries emitted, first entry outside the domain
   DevBuf<unsigned char> mt_text[2];  // one chunk of text each (<= ISLE_TEXT_CHUNK_BYTES), formatted while the other one is copied and consumed
   PinBuf mt_pin[2];
+  // document-topic weights of the last isle_hip_infer_resident (infer_resident.hip), CSR over its document range; void when A changes
+  DevBuf<int64_t> inf_off;         // docs + 1
+  DevBuf<uint32_t> inf_topic;
+  DevBuf<float> inf_weight;
+  uint64_t inf_docs = 0, inf_n = 0;
+  bool inf_valid = false;
   int p_k = 0;                     // num_topics of the last catchword pass
   bool p_catch_ready = false, p_model_ready = false, p_avg_ready = false, assign_valid = false;
 
@@ -570,6 +576,18 @@ int k_ingest_tdf(isle_ctx* c, const unsigned char* text_dev, uint64_t n, uint64_
 int k_infer(isle_ctx* c, uint64_t V, int k, const float* model_by_word, uint64_t D, uint64_t nnz, const float* counts, const uint32_t* rows,
             const int64_t* offs, int iters, float Lfguess, float avg_doc_sz, float* weights, int32_t* top_topic, float* top_weight, float* llh,
             uint64_t* nconverged);
+// its steps on device pointers: the rows of a packed model (V x round4(k) row-major, zero padding) that take part; D documents given by
+// offs[0 .. D] (positions in counts / rows / fw / fa) prepared and iterated, outputs indexed from 0, *nconverged added to
+int k_infer_rowok(isle_ctx* c, const float* M, uint64_t V, int k, unsigned char* ok);
+int k_infer_docs(isle_ctx* c, const float* M, int k, uint64_t D, const float* counts, const uint32_t* rows, const int64_t* offs,
+                 const unsigned char* ok, uint32_t* fw, float* fa, uint32_t* nkeep, int iters, float Lfguess, float avg_doc_sz, float* weights,
+                 int32_t* top_topic, float* top_weight, float* llh, unsigned int* nconverged);
+
+// infer_resident.hip: documents [doc_begin, doc_end) of the resident A under a V x k column-major device model, in chunks of chunk_docs
+// (0 = ISLE_INFER_CHUNK_BYTES of dense weights); the entries above min_weight into c->inf_off / inf_topic / inf_weight
+int k_infer_resident(isle_ctx* c, const float* model_cm_dev, int k, uint64_t doc_begin, uint64_t doc_end, int iters, float Lfguess,
+                     float avg_doc_sz, float min_weight, uint64_t chunk_docs, int32_t* top_topic, float* top_weight, float* llh,
+                     uint64_t* nconverged, uint64_t* nentries);
 
 // post.hip
 int k_post_normalize(isle_ctx* c, float avg);

@@ -549,14 +549,68 @@ __global__ __launch_bounds__(INF_T) void inf_docs16_k(const float4* __restrict__
 
 }  // namespace
 
+// The steps of an inference call on device pointers, shared by k_infer (host pointers in and out) and k_infer_resident
+// (infer_resident.hip: the resident count matrix in chunks).  Each books its launches under ISLE_T_INFER; inside a caller's scope they
+// are part of that scope.
+//
+// ok[w] = the model row w (V x ld row-major, ld = round4(k), padding zero) takes part (:376)
+int k_infer_rowok(isle_ctx* c, const float* M, uint64_t V, int k, unsigned char* ok) {
+  TimeScope ts(c, ISLE_T_INFER);
+  const int ld = (k + 3) & ~3;
+  hipLaunchKernelGGL(inf_rowok_k, dim3(cdiv((long)V, 256)), dim3(256), 0, c->stream, M, V, k, ld, ok);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+// D documents given by offs[0 .. D] (absolute positions in counts / rows / fw / fa): the kept words and their normalised counts into
+// fw / fa, then the multiplicative-weights iterations.  Outputs are indexed by the document's position in offs; nconverged is added to.
+int k_infer_docs(isle_ctx* c, const float* M, int k, uint64_t D, const float* counts, const uint32_t* rows, const int64_t* offs,
+                 const unsigned char* ok, uint32_t* fw, float* fa, uint32_t* nkeep, int iters, float Lfguess, float avg_doc_sz,
+                 float* weights /*nullable*/, int32_t* top_topic, float* top_weight, float* llh, unsigned int* nconverged) {
+  if (!D) return 0;
+  TimeScope ts(c, ISLE_T_INFER);
+  const int ld = (k + 3) & ~3, nq = ld / 4;
+  const int nit = (nq + 63) / 64;
+  hipLaunchKernelGGL(inf_prep_k, dim3(cdiv((long)D, 4)), dim3(256), 0, c->stream, counts, rows, offs, D, ok, fw, fa, nkeep);
+  HIPCHK(c, hipGetLastError());
+  // LDS: cap_rows model rows + 4 partial gradients + the weights + cap_rows values of a
+  const bool lanes16 = nq <= 64;  // k <= 256: sixteen lanes per row
+  const size_t fixed = (lanes16 ? 17 : 5) * (size_t)ld * sizeof(float);
+  uint32_t cap_rows = (uint32_t)((INF_LDS - fixed) / ((size_t)ld * sizeof(float) + sizeof(float)));
+  // Measured at C2 size (50k x 200 model, ~108 kept words per document): staging a document's slice in LDS (one workgroup per
+  // CU at 160 KB) runs 3.1 M docs/s, re-reading the rows from L2 / Infinity Cache in every iteration with ~10 workgroups per
+  // CU 5.3 M docs/s (6.9 TB/s of row gathers) — occupancy beats locality, so no rows are staged unless
+  // ISLE_INFER_CAP_ROWS asks for it.
+  {
+    const char* e = c->knob(KN_INFER_CAP_ROWS);
+    cap_rows = std::min<uint32_t>(cap_rows, e ? (uint32_t)atoi(e) : 0u);
+  }
+  const size_t lds = (size_t)cap_rows * ld * sizeof(float) + fixed + (size_t)cap_rows * sizeof(float);
+#define INF(KERNEL)                                                                                                                  \
+  do {                                                                                                                               \
+    ISLECHK(isle_max_lds(c, (const void*)KERNEL, (int)INF_LDS));                                                                      \
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)D), dim3(INF_T), lds, c->stream, (const float4*)M, k, nq, offs, fw, fa, nkeep, D, iters, \
+                       Lfguess, avg_doc_sz, cap_rows, weights, top_topic, top_weight, llh, nconverged);                              \
+  } while (0)
+  if (lanes16) {
+    const int nf = (nq + 15) / 16;
+    if (nf <= 1) INF((inf_docs16_k<1>));
+    else if (nf <= 2) INF((inf_docs16_k<2>));
+    else INF((inf_docs16_k<4>));
+  } else if (nit <= 2) INF((inf_docs_k<2>));  // nq > 64 here: two or four float4 per lane
+  else INF((inf_docs_k<4>));
+#undef INF
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
 // Host pointers in and out; the model and the documents are uploaded for the call (inference is independent of the
 // context's training matrices).  Returns the number of converged documents in *nconverged.
 int k_infer(isle_ctx* c, uint64_t V, int k, const float* model_by_word, uint64_t D, uint64_t nnz, const float* counts, const uint32_t* rows,
             const int64_t* offs, int iters, float Lfguess, float avg_doc_sz, float* weights, int32_t* top_topic, float* top_weight, float* llh,
             uint64_t* nconverged) {
   if (k < 1 || k > 1024) return isle_fail(c, ISLE_E_ARG, "infer: num_topics = %d not in [1, 1024]", k);
-  const int ld = (k + 3) & ~3, nq = ld / 4;
-  const int nit = (nq + 63) / 64;
+  const int ld = (k + 3) & ~3;
   DevBuf<float> dM, dcounts, dfa, dW, dtw, dllh;
   DevBuf<uint32_t> drows, dfw, dnk;
   DevBuf<int64_t> doffs;
@@ -587,39 +641,9 @@ int k_infer(isle_ctx* c, uint64_t V, int k, const float* model_by_word, uint64_t
   HIPCHK(c, hipMemsetAsync(dnc.p, 0, sizeof(unsigned int), c->stream));
   {
     TimeScope ts(c, ISLE_T_INFER);
-    hipLaunchKernelGGL(inf_rowok_k, dim3(cdiv((long)V, 256)), dim3(256), 0, c->stream, dM.p, V, k, ld, dok.p);
-    if (D) hipLaunchKernelGGL(inf_prep_k, dim3(cdiv((long)D, 4)), dim3(256), 0, c->stream, dcounts.p, drows.p, doffs.p, D, dok.p, dfw.p, dfa.p, dnk.p);
-    HIPCHK(c, hipGetLastError());
-    // LDS: cap_rows model rows + 4 partial gradients + the weights + cap_rows values of a
-    const bool lanes16 = nq <= 64;  // k <= 256: sixteen lanes per row
-    const size_t fixed = (lanes16 ? 17 : 5) * (size_t)ld * sizeof(float);
-    uint32_t cap_rows = (uint32_t)((INF_LDS - fixed) / ((size_t)ld * sizeof(float) + sizeof(float)));
-    // Measured at C2 size (50k x 200 model, ~108 kept words per document): staging a document's slice in LDS (one workgroup per
-    // CU at 160 KB) runs 3.1 M docs/s, re-reading the rows from L2 / Infinity Cache in every iteration with ~10 workgroups per
-    // CU 5.3 M docs/s (6.9 TB/s of row gathers) — occupancy beats locality, so no rows are staged unless
-    // ISLE_INFER_CAP_ROWS asks for it.
-    {
-      const char* e = c->knob(KN_INFER_CAP_ROWS);
-      cap_rows = std::min<uint32_t>(cap_rows, e ? (uint32_t)atoi(e) : 0u);
-    }
-    const size_t lds = (size_t)cap_rows * ld * sizeof(float) + fixed + (size_t)cap_rows * sizeof(float);
-    if (D) {
-#define INF(KERNEL)                                                                                                                     \
-  do {                                                                                                                                  \
-    ISLECHK(isle_max_lds(c, (const void*)KERNEL, (int)INF_LDS));                                                                         \
-    hipLaunchKernelGGL(KERNEL, dim3((unsigned)D), dim3(INF_T), lds, c->stream, (const float4*)dM.p, k, nq, doffs.p, dfw.p, dfa.p, dnk.p, \
-                       D, iters, Lfguess, avg_doc_sz, cap_rows, weights ? dW.p : nullptr, dtt.p, dtw.p, dllh.p, dnc.p);                 \
-  } while (0)
-      if (lanes16) {
-        const int nf = (nq + 15) / 16;
-        if (nf <= 1) INF((inf_docs16_k<1>));
-        else if (nf <= 2) INF((inf_docs16_k<2>));
-        else INF((inf_docs16_k<4>));
-      } else if (nit <= 2) INF((inf_docs_k<2>));  // nq > 64 here: two or four float4 per lane
-      else INF((inf_docs_k<4>));
-#undef INF
-      HIPCHK(c, hipGetLastError());
-    }
+    ISLECHK(k_infer_rowok(c, dM.p, V, k, dok.p));
+    ISLECHK(k_infer_docs(c, dM.p, k, D, dcounts.p, drows.p, doffs.p, dok.p, dfw.p, dfa.p, dnk.p, iters, Lfguess, avg_doc_sz,
+                         weights ? dW.p : nullptr, dtt.p, dtw.p, dllh.p, dnc.p));
   }
   unsigned int nc = 0;
   HIPCHK(c, hipMemcpyAsync(&nc, dnc.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));

@@ -40,6 +40,8 @@ typedef uint32_t count_t;  // include/types.h:29
 #define ISLE_EDGE_TOPIC_PRIMARY_RATIO 0.7   // :79
 #define ISLE_DEFAULT_COHERENCE_EPS (1e-5)   // :74
 #define ISLE_DEFAULT_COHERENCE_NUM_WORDS 5  // :75
+#define ISLE_INFER_ITERS_DEFAULT 15  // :81
+#define ISLE_INFER_LF_DEFAULT 10.0f  // :82 (INFER_LF_DEAFULT there)
 
 class FPSparseMatrixHip {
   word_id_t vocab_size_;
@@ -312,6 +314,25 @@ class FPSparseMatrixHip {
     dist.assign(num_topics, 0.0);
     check(isle_hip_topic_diversity(ctx_, which, (int)num_topics, dist.data(), &avg), "topic_diversity");
   }
+  // Topic weights of documents [doc_begin, doc_end) of the count matrix this object was built from, under a resident model
+  // (ISLE_MODEL_CATCH / ISLE_MODEL_AVG) or, with ISLE_MODEL_HOST, under model_host (vocab x ncols column-major): ISLEInfer's iterations
+  // (src/infer.cpp:361-492) on the device-resident data (isle_hip_infer_resident).  For every converged document the topics with
+  // weight > min_weight (negative: 1 / topics), ascending: doc_offsets (range + 1), topic, weight.  Returns the converged documents.
+  uint64_t infer_documents(const int which, const doc_id_t doc_begin, const doc_id_t doc_end, const int iters, const FPTYPE Lf,
+                           std::vector<int64_t>& doc_offsets, std::vector<uint32_t>& topic, std::vector<FPTYPE>& weight,
+                           const FPTYPE min_weight = -1.0f, const FPTYPE* model_host = nullptr, const doc_id_t ncols = 0,
+                           const uint64_t chunk_docs = 0) {
+    uint64_t nconv = 0, n = 0;
+    const bool host = which == ISLE_MODEL_HOST;
+    check(isle_hip_infer_resident(ctx_, which, model_host, vocab_size_, (int)(host ? ncols : post_topics_), doc_begin, doc_end, iters, Lf,
+                                  min_weight, chunk_docs, nullptr, nullptr, nullptr, &nconv, &n), "infer_documents");
+    doc_offsets.assign((size_t)(doc_end - doc_begin) + 1, 0);
+    topic.assign(n, 0);
+    weight.assign(n, 0.0f);
+    check(isle_hip_get_infer_entries(ctx_, doc_offsets.data(), topic.data(), weight.data()), "get_infer_entries");
+    return nconv;
+  }
+  doc_id_t count_docs() const { return a_docs_; }  // documents of the count matrix A (B may hold fewer after sampling)
   // DenseMatrix::write_to_file_as_sparse (format = ISLE_TEXT_SPARSE) / write_to_file (ISLE_TEXT_DENSE), src/denseMatrix.cpp:124-186, of a
   // resident model (ISLE_MODEL_CATCH / ISLE_MODEL_AVG), or with ISLE_MODEL_HOST of model_host (vocab x ncols column-major): the text is
   // formatted on the device (isle_hip_model_text) and its pieces go straight to the file.  Returns the bytes written.

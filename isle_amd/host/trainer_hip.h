@@ -599,6 +599,44 @@ class ISLETrainer {
     log->print("\n Average topic diversity: " + std::to_string((FPTYPE)avg) + "\n\n");
     log->next_time_secs("Calculating diversity");
   }
+  // The reference accepts print_doctopic and never uses it; this is what it asks for.  The topic weights of every document of A
+  // under the resident model (ISLEInfer's iterations on the device, FPSparseMatrixHip::infer_documents) into DocTopicWeights.tsv:
+  // "<doc>\t<topic>\t<weight>\n", 1-based, documents and topics ascending, topics with weight > 1 / num_topics of the converged
+  // documents, <weight> as weight_text prints it.  Deviation from running ISLEInfer on M_hat_catch_sparse: the model is the fp32
+  // model, not the file's six truncated digits.
+  void output_doc_topic_weights(const int which = ISLE_MODEL_CATCH, const int iters = ISLE_INFER_ITERS_DEFAULT, const FPTYPE Lf = ISLE_INFER_LF_DEFAULT) {
+    if (!is_training_complete) throw std::runtime_error("output_doc_topic_weights() before train()");
+    std::vector<int64_t> offs;
+    std::vector<uint32_t> topic;
+    std::vector<FPTYPE> weight;
+    const doc_id_t docs = B_fl_CSC->count_docs();
+    const uint64_t nconv = B_fl_CSC->infer_documents(which, 0, docs, iters, Lf, offs, topic, weight);
+    log->print("Number of docs for which inference converged: " + std::to_string(nconv) + " (of " + std::to_string(docs) + ")\n");
+    log->next_time_secs("Inferring document topic weights");
+    constexpr size_t kFlushAt = (size_t(1) << 24) - 256;
+    const std::string filename = log_dir + "/DocTopicWeights.tsv";
+    FILE* fp = std::fopen(filename.c_str(), "wb");
+    if (!fp) throw std::runtime_error("cannot open " + filename);
+    std::string pending;
+    pending.reserve(size_t(1) << 24);
+    char text[32];
+    for (doc_id_t d = 0; d < docs; ++d)
+      for (int64_t i = offs[d]; i < offs[d + 1]; ++i) {
+        pending += std::to_string(d + 1);
+        pending += '\t';
+        pending += std::to_string(topic[i] + 1);
+        pending += '\t';
+        pending.append(text, trainer_detail::weight_text(weight[i], text));
+        pending += '\n';
+        if (pending.size() > kFlushAt) {
+          std::fwrite(pending.data(), 1, pending.size(), fp);
+          pending.clear();
+        }
+      }
+    std::fwrite(pending.data(), 1, pending.size(), fp);
+    std::fclose(fp);
+    log->next_time_secs("Writing document topic weights to file");
+  }
   void finish_log() { log->total("TVSD"); }  // the "Total time for TVSD" line the reference's train() ends with (:652)
 
   // src/trainer.cpp:993-996: vocab_size x num_topics floats, column-major (element (word, topic) at word + topic * vocab_size)

@@ -571,6 +571,50 @@ class HotPath:
                                            float(avg_doc_sz), _p(W) if want_weights else None, _p(tt), _p(tw), _p(llh), C.byref(nc)))
         return dict(weights=W, top_topic=tt, top_weight=tw, llh=llh, nconverged=int(nc.value), avg_doc_sz=avg_doc_sz)
 
+    def infer_resident(self, model="catch", docs=None, iters=15, Lf=10.0, min_weight=None, chunk_docs=0, fetch_entries=True):
+        """Topic weights of documents of the resident count matrix A under a resident model ("catch", "avg") or a (V, cols) array, the
+        iterations of infer() on the device-resident data: the same bits for the same fp32 model and documents.  docs: None (all of
+        A) or (begin, end); row 0 of the outputs is document `begin`.  avg_doc_sz is the corpus value of the context, over all of A.
+        The weights come back sparse: for every converged document the topics with weight > min_weight (None: 1 / cols), ascending,
+        as CSR (offs int64 (n + 1,), topic uint32, weight float32); the dense (n, cols) matrix never exists.  chunk_docs: documents
+        per pass on the device (0: a 1 GiB budget of dense weights); no result depends on it.
+        -> dict(top_topic, top_weight, llh, nconverged, nentries, avg_doc_sz[, offs, topic, weight])."""
+        if isinstance(model, str):
+            which, host = self._MODELS[model], None
+            V, cols = self._a_vocab(), getattr(self, "_post_k", 0)
+        else:
+            host = np.asfortranarray(model, np.float32)
+            if host.ndim != 2:
+                raise ValueError("model must be (V, cols)")
+            which, (V, cols) = 2, host.shape
+        b, e = (0, getattr(self, "_a_shape", (0, 0, 0))[1]) if docs is None else (int(docs[0]), int(docs[1]))
+        n = max(e - b, 0)
+        tt = np.empty((n, 5), np.int32)
+        tw = np.empty((n, 5), np.float32)
+        llh = np.empty((n, 2), np.float32)
+        nc, ne = C.c_uint64(), C.c_uint64()
+        self._chk(self._lib.isle_hip_infer_resident(self._h, which, _p(host), int(V), int(cols), b, e, int(iters), float(Lf),
+                                                    -1.0 if min_weight is None else float(min_weight), int(chunk_docs), _p(tt), _p(tw),
+                                                    _p(llh), C.byref(nc), C.byref(ne)))
+        out = dict(top_topic=tt, top_weight=tw, llh=llh, nconverged=int(nc.value), nentries=int(ne.value), avg_doc_sz=self.avg_doc_sz())
+        if fetch_entries:
+            out.update(zip(("offs", "topic", "weight"), self.infer_entries(n, out["nentries"])))
+        return out
+
+    def avg_doc_sz(self):
+        """avg_doc_sz of the resident count matrix (populate_CSC, src/sparseMatrix.cpp:87-98: floor(tokens / non-empty documents))."""
+        v = C.c_float()
+        self._chk(self._lib.isle_hip_avg_doc_sz(self._h, C.byref(v)))
+        return float(v.value)
+
+    def infer_entries(self, num_docs, nentries):
+        """The entries of the last infer_resident (num_docs, nentries as it returned them) -> (offs, topic, weight)."""
+        off = np.empty(num_docs + 1, np.int64)
+        tp = np.empty(nentries, np.uint32)
+        wt = np.empty(nentries, np.float32)
+        self._chk(self._lib.isle_hip_get_infer_entries(self._h, _p(off), _p(tp), _p(wt)))
+        return off, tp, wt
+
     def timing_enable(self, on=True):
         """0 / False: off; 1 / True: events around every launch; 2: around the Gram-apply launches only."""
         self._chk(self._lib.isle_hip_timing_enable(self._h, int(on)))
