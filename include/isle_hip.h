@@ -292,16 +292,17 @@ int isle_hip_avg_topic_model(isle_ctx* ctx, int num_topics, float* model);
 #define ISLE_MODEL_CATCH 0 /* the resident topic model of isle_hip_topic_model */
 #define ISLE_MODEL_AVG 1   /* the resident average model of isle_hip_avg_topic_model */
 #define ISLE_MODEL_HOST 2  /* model_host: vocab x ncols column-major, uploaded for the call */
+#define ISLE_MODEL_LOADED 3 /* the resident model of isle_hip_load_model_text; vocab and ncols must be its own */
 
 /* The n heaviest words of every column of a model (DenseMatrix::find_n_top_words, src/denseMatrix.cpp:92-107, with the trainer's
  * order): heaviest first, the lower word id first among equal weights (-0 == +0), NaN (and -inf) last.  Exact: a radix select on
  * the float bits per column, one read of the model.  ids: ncols x n row-major; weights (nullable): the model entries at those ids.
- * For CATCH and AVG, vocab and ncols must be the resident model's (V of A, num_topics); model_host is ignored.
+ * For CATCH and AVG, vocab and ncols must be the resident model's (V of A, num_topics), for LOADED the loaded model's; model_host is ignored.
  * ISLE_E_ARG: world > 1, n < 1 or n > min(vocab, 32), an unknown model, a resident model that does not exist (yet), a size mismatch,
  * ids or (HOST) model_host null. */
 int isle_hip_model_top_words(isle_ctx* ctx, int which, const float* model_host, uint64_t vocab, int ncols, int n, uint32_t* ids, float* weights);
 
-/* Topic diversity (ISLETrainer::output_topic_diversity, src/trainer.cpp:750-774) of a resident model (CATCH or AVG), in double
+/* Topic diversity (ISLETrainer::output_topic_diversity, src/trainer.cpp:750-774) of a resident model (CATCH, AVG or LOADED), in double
  * with a fixed reduction order.  A topic is finite when every entry of its vector is; k' = the number of finite topics.
  *   abar = (1/k') sum over finite t of m_t      dist[t] = sum_w (m_t[w] - abar[w])^2      avg = mean of dist over finite t
  * Non-finite topics get dist = NaN; no finite topic gives avg = NaN.  dist: num_topics doubles (nullable); avg (nullable).
@@ -343,6 +344,46 @@ int isle_hip_model_text(isle_ctx* ctx, int which, const float* model_host, uint6
 int isle_hip_edge_topics_text(isle_ctx* ctx, const int64_t* pairs, int n, float primary_ratio, int format, isle_text_sink_fn sink, void* user,
                               uint64_t* nbytes, uint64_t* nentries);
 int isle_hip_entry_text(float w, int format, char* out16);
+
+/* The same files read back on the device (isle_amd/csrc/model_load.hip), the inverse of isle_hip_model_text: read_sparse_model
+ * (src/infer.cpp:125-208) and read_model (:8-76) as isle_amd/host/model_read.h restates them.  The text goes up in one copy and is parsed
+ * into a resident model of its own, vocab x ncols column-major, ISLE_MODEL_LOADED: isle_hip_model_top_words, isle_hip_topic_diversity,
+ * isle_hip_model_text and isle_hip_infer_resident take it wherever they take CATCH or AVG (vocab and ncols must be the loaded model's,
+ * for isle_hip_infer_resident vocab must also be A's; ISLE_E_ARG when nothing is loaded).  It does not depend on A, B, the partition or
+ * the catchwords and lives until the next successful load or isle_hip_destroy.  The text is parsed into scratch and swapped in on
+ * success: a failed call leaves the previous model intact and the context usable.
+ *   <weight>          <digits>[.<digits>], at least one digit (".5" and "5." are weights).  vb (before the point) and va (after it) are
+ *                     accumulated in fp32 digit by digit, v = v * 10; v = v + d, each operation rounded on its own (never a fused
+ *                     multiply-add); the value is (float)((double)vb + (double)va * P[n]), n = the digits after the point, P[n] = the
+ *                     host's std::pow(0.1, n), computed once on the host (the device calls no pow).  A second '.', any other
+ *                     character or a token longer than 64 bytes is an error.  Deviation: the reference has no length limit.
+ *   ISLE_TEXT_SPARSE  lines end in '\n' (the last one may go without), '\r' is ignored everywhere, fields are separated by runs of
+ *                     blanks or tabs, blanks may lead and trail, blank lines are skipped.  A line is "<topic> <word> <weight>", the ids
+ *                     decimal with at most 18 digits; id - base (base 0 or 1) must lie in [0, ncols) and [0, vocab).  Cells no line
+ *                     names are +0; of several lines naming one cell the LAST in the file wins, whatever the launch geometry.  nentries:
+ *                     the lines parsed, repeated cells included.  An empty text is the zero model, 0 entries.  At most 2^34 - 16 bytes
+ *                     (the order of the lines is kept in 32 bits), ISLE_E_ARG beyond.
+ *   ISLE_TEXT_DENSE   one line per column, tokens separated by runs of blanks or tabs (the writer's trailing tab is fine), '\r' ignored,
+ *                     blank lines skipped: token j of the t-th non-blank line is model[j, t].  "nan" is the quiet NaN 0x7fc00000, as
+ *                     the library's dense writer prints it (SPARSE refuses it).  Every non-blank line must hold exactly vocab tokens,
+ *                     there must be exactly ncols non-blank lines (an empty text is an error).  nentries: vocab x ncols.
+ * Deviations from the reference readers: they assert, or only print "Bad format" and go on; here every violation is an error.  Two
+ * limits beside the token's keep every walk of the parser short on a corrupt text, both refused as "bad character": a SPARSE line of
+ * more than 4096 bytes (its '\n' excluded), more than 64 consecutive '\r' in a DENSE text.  The line named is the rule; where one line
+ * holds several violations the kind named is one of them.
+ * ISLE_E_ARG: world > 1, an unknown format, base > 1, vocab 0 or above 0xfffffff0, ncols < 1, text null with nbytes > 0, and the parse
+ * errors: the FIRST offending line of the file (whatever the launch order) is named, 1-based, with its kind, as
+ * "load_model_text: line <n>: <kind>" in isle_hip_last_error; the kinds are "bad character", "too many fields", "too few fields",
+ * "id zero or out of range", "token too long", "wrong token count", "wrong line count" (named at the last line).  Where the host
+ * parser of model_read.h throws, this call fails.  Device time is booked under ISLE_T_INGEST.  Single rank.
+ * isle_hip_get_loaded_model: the loaded model (vocab x ncols column-major) and its size, each nullable; ISLE_E_ARG when nothing is loaded.
+ * isle_hip_parse_weight (host only, no context): the n bytes of one <weight> token under `format` into *out; 0, or -1 for a token
+ * outside the grammar ("nan" under SPARSE, the empty token, '\r' included) or an unknown format.  The library's one copy of the weight
+ * rule: the kernels compile the same function. */
+int isle_hip_load_model_text(isle_ctx* ctx, const char* text, uint64_t nbytes, uint64_t vocab, int ncols, int format, unsigned base,
+                             uint64_t* nentries);
+int isle_hip_get_loaded_model(isle_ctx* ctx, float* model_colmajor, uint64_t* vocab, int* ncols);
+int isle_hip_parse_weight(const char* token, uint64_t n, int format, float* out);
 
 /* Corpus diagnostics of the trainer (print_log_combinatorial / print_distinct_top_five_sets, src/trainer.cpp:373-403) on the resident
  * count matrix A, right after ingest or upload (no partition or B needed; single rank; ISLE_E_ARG without A).

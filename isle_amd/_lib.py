@@ -35,6 +35,9 @@ SYMBOLS = {
     "isle_hip_model_text": (_I, [_P, _I, _P, _U64, _I, _I, _P, _P, _P, _P]),
     "isle_hip_edge_topics_text": (_I, [_P, _P, _I, _F, _I, _P, _P, _P, _P]),
     "isle_hip_entry_text": (_I, [_F, _I, _P]),
+    "isle_hip_load_model_text": (_I, [_P, _P, _U64, _U64, _I, _I, C.c_uint, _P]),
+    "isle_hip_get_loaded_model": (_I, [_P, _P, _P, _P]),
+    "isle_hip_parse_weight": (_I, [_P, _U64, _I, _P]),
     "isle_hip_log_combinatorial": (_I, [_P, _P, _P]),
     "isle_hip_distinct_top_five": (_I, [_P, _I, _P, _P, _P, _P, _P, _P]),
     "isle_hip_top_five_count_rule": (_I, [_P, _U64, C.c_int32, _P]),

@@ -485,14 +485,21 @@ extern "C" int isle_hip_avg_topic_model(isle_ctx* c, int num_topics, float* mode
   return 0;
 }
 
-// the resident model `which` names, or null with the reason in the context
-static const float* resident_model(isle_ctx* c, int which, const char* who) {
+// the resident model `which` names and its size, or null with the reason in the context
+static const float* resident_model(isle_ctx* c, int which, const char* who, uint64_t* V, int* cols) {
+  *V = c->a_V;
+  *cols = c->p_k;
   if (which == ISLE_MODEL_CATCH) {
     if (c->p_model_ready) return c->p_model.p;
     isle_fail(c, ISLE_E_ARG, "%s: no catch model (run isle_hip_topic_model)", who);
   } else if (which == ISLE_MODEL_AVG) {
     if (c->p_avg_ready) return c->p_avg_model.p;
     isle_fail(c, ISLE_E_ARG, "%s: no average model (run isle_hip_avg_topic_model)", who);
+  } else if (which == ISLE_MODEL_LOADED) {
+    *V = c->ml_V;
+    *cols = c->ml_cols;
+    if (c->ml_ready) return c->ml_model.p;
+    isle_fail(c, ISLE_E_ARG, "%s: no loaded model (run isle_hip_load_model_text)", who);
   } else {
     isle_fail(c, ISLE_E_ARG, "%s: unknown model %d", who, which);
   }
@@ -510,11 +517,13 @@ static int model_source(isle_ctx* c, int which, const float* model_host, uint64_
     *dev = up->p;
     return 0;
   }
-  *dev = resident_model(c, which, who);
+  uint64_t rV = 0;
+  int rcols = 0;
+  *dev = resident_model(c, which, who, &rV, &rcols);
   if (!*dev) return ISLE_E_ARG;
-  if (vocab != c->a_V || ncols != c->p_k)
+  if (vocab != rV || ncols != rcols)
     return isle_fail(c, ISLE_E_ARG, "%s: vocab x ncols = %llu x %d, the resident model is %llu x %d", who, (unsigned long long)vocab, ncols,
-                     (unsigned long long)c->a_V, c->p_k);
+                     (unsigned long long)rV, rcols);
   return 0;
 }
 
@@ -561,6 +570,56 @@ extern "C" int isle_hip_model_text(isle_ctx* c, int which, const float* model_ho
   return rc;
 }
 
+// A model file read on the device (model_load.hip) into a resident model of its own: parsed into scratch, swapped in on success
+extern "C" int isle_hip_load_model_text(isle_ctx* c, const char* text, uint64_t nbytes, uint64_t vocab, int ncols, int format, unsigned base,
+                                        uint64_t* nentries) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  if (nentries) *nentries = 0;
+  if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "load_model_text: single-rank only");
+  if (format != ISLE_TEXT_SPARSE && format != ISLE_TEXT_DENSE) return isle_fail(c, ISLE_E_ARG, "load_model_text: unknown format %d", format);
+  if (base > 1) return isle_fail(c, ISLE_E_ARG, "load_model_text: base = %u (0 or 1)", base);
+  if (vocab == 0 || vocab > 0xfffffff0ull || ncols < 1) return isle_fail(c, ISLE_E_ARG, "load_model_text: vocab or ncols out of range");
+  if (nbytes && !text) return isle_fail(c, ISLE_E_ARG, "load_model_text: null text");
+  if (format == ISLE_TEXT_SPARSE && nbytes > 0x3fffffff0ull)
+    return isle_fail(c, ISLE_E_ARG, "load_model_text: a sparse text of %llu bytes (the line order is kept in 32 bits: at most 2^34 - 16)", (unsigned long long)nbytes);
+  DevBuf<unsigned char> td;
+  DevBuf<float> next;
+  HIPCHK(c, td.reserve(nbytes + 16));
+  HIPCHK(c, next.reserve(vocab * (size_t)ncols));
+  if (nbytes) HIPCHK(c, hipMemcpy(td.p, text, nbytes, hipMemcpyHostToDevice));
+  uint64_t n = 0, key = ~0ull;
+  const int rc = k_load_model_text(c, td.p, nbytes, vocab, (uint32_t)ncols, format, base, next.p, &n, &key);
+  (void)hipStreamSynchronize(c->stream);  // `td` and `next` are freed on return
+  ISLECHK(rc);
+  if (key != ~0ull) {
+    static const char* what[] = {"", "bad character", "too many fields", "too few fields", "id zero or out of range", "token too long",
+                                 "wrong token count", "wrong line count"};
+    const uint64_t pos = key >> 3, upto = std::min<uint64_t>(pos, nbytes ? nbytes - 1 : 0);  // the line an error at the end of the text belongs to
+    uint64_t line = 1;
+    for (uint64_t i = 0; i < upto; ++i) line += text[i] == '\n';
+    return isle_fail(c, ISLE_E_ARG, "load_model_text: line %llu: %s", (unsigned long long)line, what[key & 7]);
+  }
+  std::swap(c->ml_model.p, next.p);  // the previous model leaves with `next`
+  std::swap(c->ml_model.cap, next.cap);
+  c->ml_V = vocab;
+  c->ml_cols = ncols;
+  c->ml_ready = true;
+  if (nentries) *nentries = n;
+  return 0;
+}
+
+extern "C" int isle_hip_get_loaded_model(isle_ctx* c, float* model, uint64_t* vocab, int* ncols) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  if (!c->ml_ready) return isle_fail(c, ISLE_E_ARG, "get_loaded_model: no loaded model (run isle_hip_load_model_text)");
+  if (vocab) *vocab = c->ml_V;
+  if (ncols) *ncols = c->ml_cols;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (model) HIPCHK(c, hipMemcpy(model, c->ml_model.p, c->ml_V * (size_t)c->ml_cols * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 extern "C" int isle_hip_edge_topics_text(isle_ctx* c, const int64_t* pairs, int n, float primary_ratio, int format, isle_text_sink_fn sink, void* user,
                                          uint64_t* nbytes, uint64_t* nentries) {
   if (!c) return ISLE_E_ARG;
@@ -585,17 +644,19 @@ extern "C" int isle_hip_topic_diversity(isle_ctx* c, int which, int num_topics, 
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
   if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "topic_diversity: single-rank only");
-  const float* dev = resident_model(c, which, "topic_diversity");
+  uint64_t V = 0;
+  int cols = 0;
+  const float* dev = resident_model(c, which, "topic_diversity", &V, &cols);
   if (!dev) return ISLE_E_ARG;
-  if (num_topics != c->p_k) return isle_fail(c, ISLE_E_ARG, "topic_diversity: num_topics = %d, the resident model has %d", num_topics, c->p_k);
+  if (num_topics != cols) return isle_fail(c, ISLE_E_ARG, "topic_diversity: num_topics = %d, the resident model has %d", num_topics, cols);
   const uint32_t k = (uint32_t)num_topics;
   DevBuf<double> dd, ab;
   DevBuf<int32_t> fin;
   HIPCHK(c, dd.reserve(k));
-  HIPCHK(c, ab.reserve(c->a_V));
+  HIPCHK(c, ab.reserve(V));
   HIPCHK(c, fin.reserve(k));
   uint32_t kp = 0;
-  ISLECHK(k_topic_diversity(c, dev, c->a_V, k, dd.p, ab.p, fin.p, &kp));
+  ISLECHK(k_topic_diversity(c, dev, V, k, dd.p, ab.p, fin.p, &kp));
   std::vector<double> h(k);
   HIPCHK(c, hipMemcpyAsync(h.data(), dd.p, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));

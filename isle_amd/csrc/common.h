@@ -252,6 +252,11 @@ struct isle_ctx {
   uint64_t inf_docs = 0, inf_n = 0;
   bool inf_valid = false;
   int p_k = 0;                     // num_topics of the last catchword pass
+  // the model of the last successful isle_hip_load_model_text (model_load.hip): independent of A, B, the partition and the catchwords
+  DevBuf<float> ml_model;          // ml_V x ml_cols col-major
+  uint64_t ml_V = 0;
+  int ml_cols = 0;
+  bool ml_ready = false;
   bool p_catch_ready = false, p_model_ready = false, p_avg_ready = false, assign_valid = false;
 
   // --- chunked-CSR copy of B for Z = B*Y (built per eigensolve, like the reference's operator ctor)
@@ -606,6 +611,12 @@ int k_post_edge(isle_ctx* c, const int64_t* pairs_dev, int n, float a, float b, 
 constexpr uint64_t ISLE_TEXT_CHUNK_BYTES = 16ull << 20;
 int k_model_text(isle_ctx* c, const float* model_dev, uint64_t V, uint64_t ncols, const int64_t* pairs_dev, float a, float b, int format,
                  isle_text_sink_fn sink, void* user, uint64_t* nbytes, uint64_t* nentries);
+
+// model_load.hip: the text of a model file (n bytes on the device, ISLE_TEXT_SPARSE / ISLE_TEXT_DENSE) parsed into model_dev (V x ncols
+// column-major).  *err_key: ~0 = none, else (byte position << 3) | kind of the first offending byte (isle_hip_load_model_text names them);
+// *nentries: lines parsed (SPARSE), tokens (DENSE)
+int k_load_model_text(isle_ctx* c, const unsigned char* text_dev, uint64_t n, uint64_t V, uint32_t ncols, int format, unsigned base, float* model_dev,
+                      uint64_t* nentries, uint64_t* err_key);
 
 // coherence.hip: D(w) for the distinct top words U (ascending) and D(lo, hi) for the distinct pairs of their local ids (CSR keyed by lo),
 // over the count matrix A; counts = |U| + |P| entries on the host

@@ -8,7 +8,10 @@
 // (M_hat_catch_sparse as written by ISLETrain: "<topic>\t<word>\t<weight>", 1-based, src/infer.cpp:125-190; tdf documents),
 // same outputs: per block of 1,000,000 documents a file top_topics_iters_<iters>_Lf_<Lf>_doc_<first>_to_<last> with
 // "<doc>\t<topic>\t<weight>" for the (at most five) topics heavier than 1 / num_topics (:100-112), and the summary lines on
-// stdout (:159-176).  The arithmetic runs in isle_hip_infer (isle_amd/csrc/infer.hip); there is no CPU fallback.
+// stdout (:159-176).  Everything heavy runs on the device and stays there: the model file is parsed by isle_hip_load_model_text
+// (isle_amd/csrc/model_load.hip; model_read.h states its rule for the host), the documents go up once as a count matrix and
+// isle_hip_infer_resident(ISLE_MODEL_LOADED) runs over the whole range; include/isle_hip.h documents that path as bit-equal to
+// isle_hip_infer.  There is no CPU fallback.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -20,77 +23,10 @@
 #include <vector>
 
 #include "../../include/isle_hip.h"
+#include "model_read.h"
 #include "prestage.h"
 
 namespace {
-
-// read_sparse_model, src/infer.cpp:125-190 (mmap branch): three blank-separated fields per line, the weight as
-// <digits>[.<digits>] assembled in FPTYPE as before + after * 0.1^n
-void read_sparse_model(const std::string& path, uint64_t num_topics, uint64_t vocab_size, unsigned base, std::vector<float>& model_by_word,
-                       uint64_t* entries) {
-  FILE* f = std::fopen(path.c_str(), "rb");
-  if (!f) throw std::runtime_error("cannot open model file " + path);
-  std::fseek(f, 0, SEEK_END);
-  const long sz = std::ftell(f);
-  std::fseek(f, 0, SEEK_SET);
-  std::vector<char> buf((size_t)sz);
-  if (sz && std::fread(buf.data(), 1, (size_t)sz, f) != (size_t)sz) {
-    std::fclose(f);
-    throw std::runtime_error("short read on " + path);
-  }
-  std::fclose(f);
-  model_by_word.assign(vocab_size * num_topics, 0.f);
-  uint64_t topic = 0, word = 0, n = 0;
-  bool was_ws = false, before_dec = true, any = false;
-  float vb = 0.f, va = 0.f;
-  int pos = 0, state = 1;
-  auto flush = [&]() {
-    if (!any) return;
-    if (state != 3) throw std::runtime_error("Bad line in sparse model file");
-    if (topic < base || word < base || topic - base >= num_topics || word - base >= vocab_size)
-      throw std::runtime_error("sparse model entry out of range");
-    model_by_word[num_topics * (word - base) + (topic - base)] = (float)((double)vb + (double)va * std::pow(0.1, pos));
-    ++n;
-  };
-  for (long i = 0; i < sz; ++i) {
-    const char ch = buf[(size_t)i];
-    switch (ch) {
-      case '\r': break;
-      case '\n':
-        flush();
-        state = 1;
-        word = topic = 0;
-        pos = 0;
-        va = vb = 0.f;
-        before_dec = true;
-        was_ws = false;
-        any = false;
-        break;
-      case ' ':
-      case '\t': was_ws = true; break;
-      case '.':
-        if (state != 3 || !before_dec) throw std::runtime_error("Bad format in sparse model file");
-        before_dec = false;
-        break;
-      default:
-        if (ch < '0' || ch > '9') throw std::runtime_error("Bad format in sparse model file");
-        if (was_ws && any) ++state;
-        was_ws = false;
-        any = true;
-        if (state == 1) topic = topic * 10 + (uint64_t)(ch - '0');
-        else if (state == 2) word = word * 10 + (uint64_t)(ch - '0');
-        else if (state == 3) {
-          if (before_dec) vb = vb * 10 + (float)(ch - '0');
-          else {
-            va = va * 10 + (float)(ch - '0');
-            ++pos;
-          }
-        } else throw std::runtime_error("Bad line in sparse model file");
-    }
-  }
-  flush();  // no trailing newline
-  *entries = n;
-}
 
 // The weight as the reference's writer prints it (MMappedOutput::concat_float, include/utils.h:421-478): "0.0" for zero, a sign, the integer
 // part, a point, and six fraction digits taken one at a time by multiplying the single-precision remainder by ten (truncating).
@@ -164,10 +100,20 @@ int main(int argc, char** argv) {
     const int iters = args.iterations;
     const float Lfguess = args.lipschitz;
 
+    isle_ctx* ctx = isle_hip_create(0);
+    if (!ctx) throw std::runtime_error("no HIP device (there is no CPU fallback)");
+    auto check = [&](int rc) {
+      if (rc == 0) return;
+      const std::string msg = isle_hip_last_error(ctx);
+      isle_hip_destroy(ctx);
+      throw std::runtime_error(msg);
+    };
+
     std::cout << "Loading sparse model file: " << sparse_model_file << std::endl;
-    std::vector<float> model_by_word;
-    uint64_t model_entries = 0;
-    read_sparse_model(sparse_model_file, num_topics, vocab_size, 1, model_by_word, &model_entries);
+    {
+      const std::vector<char> text = ISLE::model_read::read_file(sparse_model_file);
+      check(isle_hip_load_model_text(ctx, text.data(), text.size(), vocab_size, (int)num_topics, ISLE_TEXT_SPARSE, 1, nullptr));
+    }
 
     std::cout << "Loading data from inference file: " << infer_file << std::endl;
     std::vector<ISLE::prestage::DocWordEntry> entries;
@@ -178,23 +124,18 @@ int main(int argc, char** argv) {
       e.doc -= (doc_begin - 1);
     }
     ISLE::prestage::Csc A;
-    float avg_doc_sz = 0.f;
+    float avg_doc_sz = 0.f;  // the context computes the same value from the resident counts (populate_CSC's rule)
     uint64_t nz_docs = 0;
     ISLE::prestage::build_A(entries, vocab_size, num_docs, A, &avg_doc_sz, &nz_docs);  // sort, de-duplicate, populate_CSC (:50-59)
     std::vector<uint32_t> rows32(A.rows.begin(), A.rows.end());
+    check(isle_hip_upload_counts_u32(ctx, vocab_size, num_docs, A.vals.size(), A.vals.data(), rows32.data(), A.offs.data(), 0, num_docs));
 
-    isle_ctx* ctx = isle_hip_create(0);
-    if (!ctx) throw std::runtime_error("no HIP device (there is no CPU fallback)");
     std::vector<int32_t> top_topic(num_docs * 5);
     std::vector<float> top_weight(num_docs * 5), llh(num_docs * 2);
     uint64_t nconverged = 0;
     std::cout << "Creating inference engine" << std::endl;
-    if (isle_hip_infer(ctx, vocab_size, (int)num_topics, model_by_word.data(), num_docs, A.vals.size(), A.vals.data(), rows32.data(),
-                       A.offs.data(), iters, Lfguess, avg_doc_sz, nullptr, top_topic.data(), top_weight.data(), llh.data(), &nconverged)) {
-      const std::string msg = isle_hip_last_error(ctx);
-      isle_hip_destroy(ctx);
-      throw std::runtime_error(msg);
-    }
+    check(isle_hip_infer_resident(ctx, ISLE_MODEL_LOADED, nullptr, vocab_size, (int)num_topics, 0, num_docs, iters, Lfguess, -1.0f, 0, top_topic.data(),
+                                  top_weight.data(), llh.data(), &nconverged, nullptr));
     isle_hip_destroy(ctx);
 
     const uint64_t block = 1000000;  // :66

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/isle_hip.h"
+#include "model_read.h"
 
 namespace ISLE {
 
@@ -56,6 +57,10 @@ class FPSparseMatrixHip {
   uint64_t top5_n_ = 0;
   bool top5_ready_ = false;
   doc_id_t post_topics_ = 0;  // num_topics of the last find_catchwords: the columns of the resident models
+  word_id_t loaded_vocab_ = 0;  // the model of the last load_model_file (ISLE_MODEL_LOADED)
+  doc_id_t loaded_cols_ = 0;
+  word_id_t model_vocab(int which) const { return which == ISLE_MODEL_LOADED ? loaded_vocab_ : vocab_size_; }
+  doc_id_t model_cols(int which) const { return which == ISLE_MODEL_LOADED ? loaded_cols_ : post_topics_; }
 
   static int text_to_file(const char* bytes, uint64_t n, void* fp) { return std::fwrite(bytes, 1, (size_t)n, (FILE*)fp) == (size_t)n ? 0 : 1; }
 
@@ -297,12 +302,12 @@ class FPSparseMatrixHip {
   void construct_avg_topic_model(FPTYPE* AvgModel, const doc_id_t num_topics) {
     check(isle_hip_avg_topic_model(ctx_, (int)num_topics, AvgModel), "avg_topic_model");
   }
-  // The n heaviest words of every topic of a resident model (ISLE_MODEL_CATCH or ISLE_MODEL_AVG), by the trainer's rule (heaviest
+  // The n heaviest words of every topic of a resident model (ISLE_MODEL_CATCH, ISLE_MODEL_AVG or ISLE_MODEL_LOADED), by the trainer's rule (heaviest
   // first, lower id first among equal weights, NaN last), selected on the device (isle_hip_model_top_words).
   void model_top_words(const int which, const doc_id_t num_topics, const word_id_t n, std::vector<std::pair<word_id_t, FPTYPE>>* top_words) {
     std::vector<uint32_t> ids((size_t)num_topics * n);
     std::vector<float> w((size_t)num_topics * n);
-    check(isle_hip_model_top_words(ctx_, which, nullptr, vocab_size_, (int)num_topics, (int)n, ids.data(), w.data()), "model_top_words");
+    check(isle_hip_model_top_words(ctx_, which, nullptr, model_vocab(which), (int)num_topics, (int)n, ids.data(), w.data()), "model_top_words");
     for (doc_id_t t = 0; t < num_topics; ++t) {
       top_words[t].clear();
       for (word_id_t i = 0; i < n; ++i) top_words[t].push_back(std::make_pair((word_id_t)ids[(size_t)t * n + i], w[(size_t)t * n + i]));
@@ -324,7 +329,7 @@ class FPSparseMatrixHip {
                            const uint64_t chunk_docs = 0) {
     uint64_t nconv = 0, n = 0;
     const bool host = which == ISLE_MODEL_HOST;
-    check(isle_hip_infer_resident(ctx_, which, model_host, vocab_size_, (int)(host ? ncols : post_topics_), doc_begin, doc_end, iters, Lf,
+    check(isle_hip_infer_resident(ctx_, which, model_host, vocab_size_, (int)(host ? ncols : model_cols(which)), doc_begin, doc_end, iters, Lf,
                                   min_weight, chunk_docs, nullptr, nullptr, nullptr, &nconv, &n), "infer_documents");
     doc_offsets.assign((size_t)(doc_end - doc_begin) + 1, 0);
     topic.assign(n, 0);
@@ -342,11 +347,27 @@ class FPSparseMatrixHip {
     if (!fp) throw std::runtime_error("cannot open " + filename);
     uint64_t nbytes = 0;
     const bool host = which == ISLE_MODEL_HOST;
-    const int rc = isle_hip_model_text(ctx_, which, model_host, host ? vocab : vocab_size_, (int)(host ? ncols : post_topics_), format, text_to_file,
+    const int rc = isle_hip_model_text(ctx_, which, model_host, host ? vocab : model_vocab(which), (int)(host ? ncols : model_cols(which)), format, text_to_file,
                                        fp, &nbytes, nullptr);
     std::fclose(fp);
     check(rc, "write_model_text");
     return nbytes;
+  }
+  // The inverse: a model file (ISLE_TEXT_SPARSE: "<topic> <word> <weight>" lines, ids minus `base`; ISLE_TEXT_DENSE: one line per column)
+  // read into the resident model ISLE_MODEL_LOADED, parsed on the device (isle_hip_load_model_text; model_read.h states the rule).  It
+  // does not depend on the matrices of this object; model_top_words, topic_diversity, infer_documents and write_model_text take it as
+  // `which`.  Returns the entries read (SPARSE: lines, DENSE: vocab x ncols).  A refused file leaves the previous model in place.
+  uint64_t load_model_file(const std::string& filename, const word_id_t vocab, const doc_id_t ncols, const int format, const unsigned base = 1) {
+    const std::vector<char> text = model_read::read_file(filename);
+    uint64_t n = 0;
+    check(isle_hip_load_model_text(ctx_, text.data(), text.size(), vocab, (int)ncols, format, base, &n), "load_model_file");
+    loaded_vocab_ = vocab;
+    loaded_cols_ = ncols;
+    return n;
+  }
+  void get_loaded_model(std::vector<FPTYPE>& model) {  // vocab x ncols, column-major
+    model.assign((size_t)loaded_vocab_ * loaded_cols_, 0.0f);
+    check(isle_hip_get_loaded_model(ctx_, model.data(), nullptr, nullptr), "get_loaded_model");
   }
   // ISLETrainer::write_edgemodel_to_file (src/trainer.cpp:687-693) for the edge topics of `pairs` (primary, secondary per edge topic):
   // the FPaxpy pair of construct_edge_topics and the sparse text in one pass on the device (isle_hip_edge_topics_text).

@@ -104,6 +104,16 @@ def entry_text(w, format="dense"):
     return -1 if n < 0 else buf.raw[:n].decode("ascii")
 
 
+def parse_weight(token, format="sparse"):
+    """One weight token of a model file as the library's readers take it (isle_hip_parse_weight, the host copy of the rule the loader's
+    kernels compile): <digits>[.<digits>] -> np.float32; "nan" under "dense" -> the quiet NaN.  None for a token outside the grammar.
+    No GPU needed."""
+    raw = token if isinstance(token, bytes) else str(token).encode("ascii")
+    out = C.c_float()
+    rc = load_library().isle_hip_parse_weight(raw, len(raw), TEXT_FORMATS[format], C.byref(out))
+    return None if rc else np.float32(out.value)
+
+
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -319,10 +329,42 @@ class HotPath:
         return dict(coherence=coh, doc_freq=df, co_doc_freq=co)
 
     # ---- the cluster-average model and what reads a model (include/isle_hip.h for the rules and the deviations) -----------------
-    _MODELS = {"catch": 0, "avg": 1}   # ISLE_MODEL_CATCH, ISLE_MODEL_AVG; ISLE_MODEL_HOST = 2
+    _MODELS = {"catch": 0, "avg": 1, "loaded": 3}   # ISLE_MODEL_CATCH, ISLE_MODEL_AVG, ISLE_MODEL_LOADED; ISLE_MODEL_HOST = 2
 
     def _a_vocab(self):
         return getattr(self, "_a_shape", (self.V,))[0]
+
+    def _resident_shape(self, model):
+        """(V, cols) of the resident model a name stands for: the loaded model's own, else V of A and the topics of the last pass."""
+        if model == "loaded":
+            V, cols = C.c_uint64(), C.c_int()
+            self._chk(self._lib.isle_hip_get_loaded_model(self._h, None, C.byref(V), C.byref(cols)))   # refused when nothing is loaded
+            return int(V.value), int(cols.value)
+        return self._a_vocab(), getattr(self, "_post_k", 0)
+
+    # ---- model files read back on the device (include/isle_hip.h for the rule, the deviations and the errors) ----------------------
+    def load_model_text(self, text, vocab, cols, format="sparse", base=1):
+        """The text of a model file (bytes; "sparse": "<topic> <word> <weight>" lines with ids minus base, "dense": one line per
+        column) parsed on the device into the resident model "loaded", which model_top_words, topic_diversity, model_text /
+        write_model / model_text_size and infer_resident take as model="loaded".  It is independent of A and of the other resident
+        models and lives until the next successful load.  A refused text (IsleHipError naming the first offending line and the kind
+        of error) leaves the previous model in place.  -> entries read (sparse: lines, dense: vocab x cols)."""
+        buf = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else text
+        fmt = TEXT_FORMATS[format] if isinstance(format, str) else int(format)
+        n = C.c_uint64()
+        self._chk(self._lib.isle_hip_load_model_text(self._h, _p(buf) if buf.size else None, int(buf.size), int(vocab), int(cols), fmt, int(base),
+                                                     C.byref(n)))
+        return int(n.value)
+
+    def load_model(self, path, vocab, cols, format="sparse", base=1):
+        """load_model_text of a file."""
+        return self.load_model_text(np.fromfile(path, dtype=np.uint8), vocab, cols, format, base)
+
+    def loaded_model(self):
+        """The resident loaded model -> (V, cols) F-order float32."""
+        M = np.empty(self._resident_shape("loaded"), np.float32, order="F")
+        self._chk(self._lib.isle_hip_get_loaded_model(self._h, _p(M), None, None))
+        return M
 
     def avg_topic_model(self, num_topics, fetch=True):
         """The cluster-average topic model (ISLETrainer::output_avg_topic_coherence, src/trainer.cpp:705-745): every topic the
@@ -334,11 +376,11 @@ class HotPath:
 
     def model_top_words(self, n=10, model="catch", with_weights=False):
         """The n heaviest words of every topic, on the device, by the rule of top_words() (bit-equal to it).  model: "catch" (the
-        resident topic model), "avg" (the resident average model) or a (V, cols) array.  -> uint32 (cols, n), and float32 (cols, n)
+        resident topic model), "avg" (the resident average model), "loaded" (the model of load_model_text) or a (V, cols) array.  -> uint32 (cols, n), and float32 (cols, n)
         weights with with_weights."""
         if isinstance(model, str):
             which, host = self._MODELS[model], None
-            V, cols = self._a_vocab(), getattr(self, "_post_k", 0)
+            V, cols = self._resident_shape(model)
         else:
             host = np.asfortranarray(model, np.float32)
             if host.ndim != 2:
@@ -382,7 +424,7 @@ class HotPath:
     def _model_text_call(self, which, format, consume):
         if isinstance(which, str):
             code, host = self._MODELS[which], None
-            V, cols = self._a_vocab(), getattr(self, "_post_k", 0)
+            V, cols = self._resident_shape(which)
         else:
             host = np.asfortranarray(which, np.float32)
             if host.ndim != 2:
@@ -581,7 +623,7 @@ class HotPath:
         -> dict(top_topic, top_weight, llh, nconverged, nentries, avg_doc_sz[, offs, topic, weight])."""
         if isinstance(model, str):
             which, host = self._MODELS[model], None
-            V, cols = self._a_vocab(), getattr(self, "_post_k", 0)
+            V, cols = self._resident_shape(model)
         else:
             host = np.asfortranarray(model, np.float32)
             if host.ndim != 2:
