@@ -96,7 +96,11 @@ int isle_hip_upload_counts_u32(isle_ctx* ctx, uint64_t vocab_size, uint64_t num_
  * as if it had been passed to isle_hip_upload_counts_u32 (single rank: doc_offset 0).  max_entries:
  * the reference asserts the file holds exactly that many lines; 0 = do not check.  Of several
  * lines with the same (doc, word) the first in the file survives (the reference keeps an unspecified
- * one).  entries_read / nnz (nullable): lines parsed / entries after de-duplication. */
+ * one).  entries_read / nnz (nullable): lines parsed / entries after de-duplication.
+ * ISLE_E_ARG, with the kind and the 1-based number of the first bad line of the file: a character other than
+ * a digit, blank, tab, '\r' or '\n'; more or fewer than three fields; a doc / word id that is 0 or exceeds
+ * num_docs / vocab_size; a count of 0; a count that exceeds 4294967295 (counts are held in 32 bits before
+ * they become floats).  Fields are read exactly, whatever their length: none wraps into range. */
 int isle_hip_ingest_tdf(isle_ctx* ctx, const char* text, uint64_t nbytes, uint64_t vocab_size, uint64_t num_docs,
                         uint64_t max_entries, uint64_t* entries_read, uint64_t* nnz);
 /* Copies the context's count matrix to the host (any pointer may be NULL); nnz via the call above

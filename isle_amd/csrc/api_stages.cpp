@@ -66,8 +66,8 @@ extern "C" int isle_hip_ingest_tdf(isle_ctx* c, const char* text, uint64_t nbyte
   ISLECHK(rc);
   if (err[0]) {
     static const char* what[] = {"", "bad character", "more than three fields", "fewer than three fields", "doc/word id is 0 or exceeds <num_docs>/<vocab_size>",
-                                 "count is 0"};
-    return isle_fail(c, ISLE_E_ARG, "ingest_tdf: %s on line %llu", what[err[0] < 6 ? err[0] : 0], (unsigned long long)(err[1] + 1));
+                                 "count is 0", "count exceeds 4294967295"};
+    return isle_fail(c, ISLE_E_ARG, "ingest_tdf: %s on line %llu", what[err[0] < 7 ? err[0] : 0], (unsigned long long)(err[1] + 1));
   }
   if (max_entries && nread != max_entries)  // include/utils.h:227
     return isle_fail(c, ISLE_E_ARG, "ingest_tdf: file has %llu entries, <max_entries> says %llu", (unsigned long long)nread, (unsigned long long)max_entries);

@@ -10,8 +10,10 @@
 //
 // Deviations from the reference parser, shared with the host parser of isle_amd/host/prestage.h: trailing blanks do not
 // leak into the next line (the reference keeps its was_whitespace flag across '\n'), blank lines are skipped, a bad
-// character or a line with more than three fields is an error instead of a debug assert.  The reference's
-// std::sort + std::unique keeps an unspecified one of several equal (doc, word) lines; here it is the first in the file.
+// character or a line with more than three fields is an error instead of a debug assert, and so are a line with fewer than three
+// fields, an id outside 1..D / 1..V, a count of 0 and a count above 4294967295.  A field saturates at 2^32 while it is read (no id or
+// count needs more), so no digit string, however long, wraps into range.  Of several bad lines the first in the file is reported.  The
+// reference's std::sort + std::unique keeps an unspecified one of several equal (doc, word) lines; here it is the first in the file.
 #include <utility>
 
 #include "common.h"
@@ -65,10 +67,13 @@ __global__ __launch_bounds__(IT) void ing_nl_fill_k(const unsigned char* __restr
   }
 }
 
-// err[0]: 0 ok, 1 bad character, 2 too many fields, 3 fewer than three fields, 4 doc/word id 0 or out of range; err[1] = line
+// kinds: 1 bad character, 2 too many fields, 3 fewer than three fields, 4 doc/word id 0 or out of range, 5 count 0, 6 count above
+// 2^32 - 1.  *err starts as all ones and ends as the smallest (line << 3) | kind over the bad lines: the first bad line, whichever
+// thread gets there first.
 __global__ __launch_bounds__(IT) void ing_parse_k(const unsigned char* __restrict__ text, uint64_t n, const uint64_t* __restrict__ line_start, uint64_t nlines,
                                                    uint64_t V, uint64_t D, int wbits, uint64_t* __restrict__ key, uint32_t* __restrict__ cnt,
                                                    uint32_t* __restrict__ valid, unsigned long long* __restrict__ err) {
+  constexpr unsigned long long FIELD_MAX = 0xffffffffull;
   const uint64_t l = (uint64_t)blockIdx.x * IT + threadIdx.x;
   if (l >= nlines) return;
   const uint64_t s = line_start[l];
@@ -96,12 +101,14 @@ __global__ __launch_bounds__(IT) void ing_parse_k(const unsigned char* __restric
       break;
     }
     f[state] = f[state] * 10ull + (unsigned long long)(ch - '0');
+    if (f[state] > FIELD_MAX) f[state] = FIELD_MAX + 1ull;  // saturated: above every id and every count, and 10 * 2^32 + 9 still fits
   }
   uint32_t ok = 0;
   if (!bad && any) {
     if (state != 2) bad = 3;
     else if (f[0] == 0 || f[1] == 0 || f[0] > D || f[1] > V) bad = 4;
     else if (f[2] == 0) bad = 5;  // a document made of zero counts would normalise to 0 / 0 (src/sparseMatrix.cpp:136-167)
+    else if (f[2] > FIELD_MAX) bad = 6;
     else {
       ok = 1;
       key[l] = ((f[0] - 1) << wbits) | (f[1] - 1);
@@ -109,7 +116,7 @@ __global__ __launch_bounds__(IT) void ing_parse_k(const unsigned char* __restric
     }
   }
   valid[l] = ok;
-  if (bad && atomicCAS(&err[0], 0ull, (unsigned long long)bad) == 0ull) err[1] = l;
+  if (bad) atomicMin(err, ((unsigned long long)l << 3) | (unsigned long long)bad);
 }
 
 __global__ __launch_bounds__(IT) void ing_pack_k(const uint64_t* __restrict__ key, const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ valid,
@@ -292,8 +299,8 @@ int k_ingest_tdf(isle_ctx* c, const unsigned char* text_dev, uint64_t n, uint64_
   ING(cnt0.reserve(nlines ? nlines : 1));
   ING(valid.reserve(nlines ? nlines : 1));
   ING(at.reserve(nlines + 1));
-  ING(errd.reserve(2));
-  ING(hipMemsetAsync(errd.p, 0, 2 * sizeof(uint64_t), c->stream));
+  ING(errd.reserve(1));
+  ING(hipMemsetAsync(errd.p, 0xff, sizeof(uint64_t), c->stream));
   if (nlines)
     hipLaunchKernelGGL(ing_parse_k, dim3(cdiv((long)nlines, IT)), dim3(IT), 0, c->stream, text_dev, n, line_start.p, nlines, V, D, wbits, key0.p, cnt0.p,
                        valid.p, (unsigned long long*)errd.p);
@@ -301,10 +308,13 @@ int k_ingest_tdf(isle_ctx* c, const unsigned char* text_dev, uint64_t n, uint64_
   ING((isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, valid.p, nlines, at.p, scratch.p)));
   int64_t nent = 0;
   ING(hipMemcpyAsync(&nent, at.p + nlines, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  ING(hipMemcpyAsync(err_out, errd.p, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  uint64_t first_bad = ~0ull;
+  ING(hipMemcpyAsync(&first_bad, errd.p, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
   ING(hipStreamSynchronize(c->stream));
   *entries_read = (uint64_t)nent;
-  if (err_out[0]) {
+  if (first_bad != ~0ull) {
+    err_out[0] = first_bad & 7ull;  // kind
+    err_out[1] = first_bad >> 3;    // 0-based line
     cleanup();
     return 0;  // the caller formats the message
   }

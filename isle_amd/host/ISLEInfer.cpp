@@ -117,7 +117,7 @@ int main(int argc, char** argv) {
 
     std::cout << "Loading data from inference file: " << infer_file << std::endl;
     std::vector<ISLE::prestage::DocWordEntry> entries;
-    ISLE::prestage::read_tdf(infer_file, max_entries, entries);
+    ISLE::prestage::read_tdf(infer_file, max_entries, entries, vocab_size, doc_end);  // ids up to doc_end pass; build_A holds them to the range
     const uint64_t num_docs = doc_end - doc_begin;  // drivers/ISLEInfer.cpp:49 (the last id of the range is not a document of its own)
     for (auto& e : entries) {  // :58: entries[i].doc -= (doc_begin - 1), ids already 0-based here
       if (e.doc + 1 < doc_begin) throw std::runtime_error("document id below <min_doc_id_in_infer_file>");

@@ -25,8 +25,19 @@ struct DocWordEntry {
   uint32_t count;
 };
 
-// tdf text: one "<doc> <word> <count>" per line, 1-based ids, any mix of blanks/tabs, optional '\r', last newline optional.
-inline void read_tdf(const std::string& path, uint64_t max_entries, std::vector<DocWordEntry>& entries) {
+// The kinds of a rejected line, shared with the device parser (isle_amd/csrc/ingest.hip, message table in api_stages.cpp).
+inline const char* tdf_error_wording(int kind) {
+  static const char* what[] = {"", "bad character", "more than three fields", "fewer than three fields", "doc/word id is 0 or exceeds <num_docs>/<vocab_size>",
+                               "count is 0", "count exceeds 4294967295"};
+  return what[kind >= 1 && kind <= 6 ? kind : 0];
+}
+
+// tdf text: one "<doc> <word> <count>" per line, 1-based ids, any mix of blanks/tabs, optional '\r', last newline optional, lines
+// without a digit skipped.  Same rules, same kinds and the same line (the first bad one, 1-based) as the device parser: doc ids in
+// 1..max_doc, word ids in 1..vocab_size (both at most 0xfffffff0, as in the library), counts in 1..4294967295.  A field saturates at 2^32
+// while it is read, so no digit string, however long, wraps into range.
+inline void read_tdf(const std::string& path, uint64_t max_entries, std::vector<DocWordEntry>& entries, uint64_t vocab_size, uint64_t max_doc) {
+  if (vocab_size == 0 || vocab_size > 0xfffffff0ull || max_doc == 0 || max_doc > 0xfffffff0ull) throw std::runtime_error("tdf file: vocab/doc count out of range");
   FILE* f = std::fopen(path.c_str(), "rb");
   if (!f) throw std::runtime_error("cannot open tdf file " + path);
   std::fseek(f, 0, SEEK_END);
@@ -40,38 +51,40 @@ inline void read_tdf(const std::string& path, uint64_t max_entries, std::vector<
   std::fclose(f);
   entries.clear();
   entries.reserve(max_entries);
-  uint64_t doc = 0, word = 0, count = 0;
-  int state = 1;
+  uint64_t fld[3] = {0, 0, 0}, line = 1;
+  int state = 0;
   bool was_ws = false, any = false;
+  auto fail = [&](int kind) { throw std::runtime_error(std::string("tdf file: ") + tdf_error_wording(kind) + " on line " + std::to_string(line)); };
+  auto end_of_line = [&]() {
+    if (any) {
+      if (state != 2) fail(3);
+      if (fld[0] == 0 || fld[1] == 0 || fld[0] > max_doc || fld[1] > vocab_size) fail(4);
+      if (fld[2] == 0) fail(5);  // a document made of zero counts would normalise to 0 / 0 (src/sparseMatrix.cpp:136-167)
+      if (fld[2] > 0xffffffffull) fail(6);
+      entries.push_back({fld[0] - 1, fld[1] - 1, (uint32_t)fld[2]});
+    }
+    fld[0] = fld[1] = fld[2] = 0;
+    state = 0;
+    was_ws = any = false;
+    ++line;
+  };
   for (long i = 0; i < sz; ++i) {
     const char ch = buf[(size_t)i];
     switch (ch) {
       case '\r': break;
-      case '\n':
-        if (any && state == 3 && count == 0) throw std::runtime_error("tdf file: count is 0 (entry " + std::to_string(entries.size() + 1) + ")");
-        if (any) entries.push_back({doc - 1, word - 1, (uint32_t)count});
-        doc = word = count = 0;
-        state = 1;
-        was_ws = false;
-        any = false;
-        break;
+      case '\n': end_of_line(); break;
       case ' ':
       case '\t': was_ws = true; break;
       default:
-        if (ch < '0' || ch > '9') throw std::runtime_error("Bad format in tdf file");
-        if (was_ws && any) {
-          state++;
-          was_ws = false;
-        }
+        if (ch < '0' || ch > '9') fail(1);
+        if (was_ws && any && ++state > 2) fail(2);
         was_ws = false;
         any = true;
-        if (state == 1) doc = doc * 10 + (uint64_t)(ch - '0');
-        else if (state == 2) word = word * 10 + (uint64_t)(ch - '0');
-        else if (state == 3) count = count * 10 + (uint64_t)(ch - '0');
-        else throw std::runtime_error("Bad line in tdf file");
+        fld[state] = fld[state] * 10 + (uint64_t)(ch - '0');
+        if (fld[state] > 0xffffffffull) fld[state] = 0x100000000ull;
     }
   }
-  if (any && state == 3) entries.push_back({doc - 1, word - 1, (uint32_t)count});  // no trailing newline
+  end_of_line();  // a last line without a newline is a line like any other
   if (entries.size() != max_entries)  // include/utils.h:227 assert(nRead == max_entries)
     throw std::runtime_error("tdf file has " + std::to_string(entries.size()) + " entries, <max_entries> says " + std::to_string(max_entries));
 }
@@ -83,10 +96,11 @@ struct Csc {
   std::vector<int64_t> offs;
 };
 
-// sort by (doc, word), drop duplicates, build CSC of raw counts; returns avg_doc_sz and nz_docs like populate_CSC
+// sort by (doc, word), drop duplicates (the first in file order survives, as on the device: the sort is stable and std::unique keeps
+// the first of a run), build CSC of raw counts; returns avg_doc_sz and nz_docs like populate_CSC
 inline void build_A(std::vector<DocWordEntry>& entries, uint64_t V, uint64_t D, Csc& A, float* avg_doc_sz, uint64_t* nz_docs) {
-  std::sort(entries.begin(), entries.end(),
-            [](const DocWordEntry& l, const DocWordEntry& r) { return (l.doc < r.doc) || (l.doc == r.doc && l.word < r.word); });
+  std::stable_sort(entries.begin(), entries.end(),
+                          [](const DocWordEntry& l, const DocWordEntry& r) { return (l.doc < r.doc) || (l.doc == r.doc && l.word < r.word); });
   entries.erase(std::unique(entries.begin(), entries.end(),
                             [](const DocWordEntry& l, const DocWordEntry& r) { return l.doc == r.doc && l.word == r.word; }),
                 entries.end());

@@ -1,28 +1,23 @@
 """GPU parity for tdf ingest on the device: text -> count matrix A in HBM.
 
-Checker: an independent NumPy statement of the reference's rules (include/utils.h:158-228 parser, src/trainer.cpp:236-247
-sort + de-duplication, src/sparseMatrix.cpp:58-87 CSC build).  Integer / index work: bit-exact.
+Checker: the plain rule of tests/ingest_rule.py, an independent statement of the reference's rules (include/utils.h:158-228 parser,
+src/trainer.cpp:236-247 sort + de-duplication, src/sparseMatrix.cpp:58-87 CSC build).  Integer / index work: bit-exact.
+test_gpu_ingest_certified.py holds the kernels to the same rule at their tile, digit and range edges.
 """
 import numpy as np
 import pytest
 
 from tools.synth import Corpus
+from ingest_rule import ingest_rule
 from test_cli_cpu import write_tdf
 
 pytestmark = pytest.mark.gpu
 
 
 def numpy_ingest(text, V, D):
-    trip = np.array([[int(x) for x in ln.split()] for ln in text.decode().replace("\r", "").split("\n") if ln.strip()], np.int64).reshape(-1, 3)
-    doc, word, cnt = trip[:, 0] - 1, trip[:, 1] - 1, trip[:, 2]
-    order = np.lexsort((np.arange(len(doc)), word, doc))       # stable: first occurrence in the file wins
-    doc, word, cnt = doc[order], word[order], cnt[order]
-    first = np.ones(len(doc), bool)
-    first[1:] = (doc[1:] != doc[:-1]) | (word[1:] != word[:-1])
-    doc, word, cnt = doc[first], word[first], cnt[first]
-    offs = np.zeros(D + 1, np.int64)
-    np.add.at(offs, doc + 1, 1)
-    return cnt.astype(np.float32), word.astype(np.uint32), np.cumsum(offs), len(trip)
+    tag, counts, rows, offs, entries_read = ingest_rule(text, V, D)   # byte-level state machine: accepts exactly what the parsers accept
+    assert tag == "ok"
+    return counts, rows, offs, entries_read
 
 
 @pytest.mark.parametrize("style,shuffle", [("plain", None), ("messy", 7)])
@@ -71,6 +66,8 @@ def test_ingest_errors(hp):
         hp.ingest_tdf(b"1 1 1\n2 2 2\n", 5, 5, max_entries=3)
     with pytest.raises(Exception, match="count is 0 on line 2"):  # a document of zero counts would normalise to 0 / 0
         hp.ingest_tdf(b"1 1 1\n2 2 0\n", 5, 5)
+    with pytest.raises(Exception, match="count exceeds 4294967295 on line 3"):  # 2^32 would be stored as 0 after the 32-bit cast
+        hp.ingest_tdf(b"1 1 1\n\n2 2 4294967296\n", 5, 5)
 
 
 def test_ingest_then_threshold_equals_upload(hp, tmp_path):
