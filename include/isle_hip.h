@@ -458,11 +458,41 @@ int isle_hip_infer(isle_ctx* ctx, uint64_t vocab_size, int num_topics, const flo
  * ISLE_E_ARG: world > 1, no count matrix, doc_begin > doc_end, doc_end > docs(A), iters < 1, Lf_guess <= 0, the model conditions above.
  * doc_begin == doc_end is valid: no entries, nconverged = 0.  Every argument is checked before any work: after a refusal the context is
  * usable and the entries of the previous call are intact; a call that fails later (ISLE_E_HIP) leaves none (isle_hip_get_infer_entries
- * then returns ISLE_E_ARG, as it does before the first call and after a new A).  Device time is booked under ISLE_T_INFER. */
+ * then returns ISLE_E_ARG, as it does before the first call and after a new A).  top_topic / top_weight of the call stay resident with the
+ * entries, for isle_hip_infer_text.  Device time is booked under ISLE_T_INFER. */
 int isle_hip_infer_resident(isle_ctx* ctx, int which, const float* model_host, uint64_t vocab, int ncols, uint64_t doc_begin,
                             uint64_t doc_end, int iters, float Lf_guess, float min_weight, uint64_t chunk_docs, int32_t* top_topic,
                             float* top_weight, float* llh, uint64_t* nconverged, uint64_t* nentries);
 int isle_hip_get_infer_entries(isle_ctx* ctx, int64_t* doc_offsets, uint32_t* topic, float* weight);
+/* The per-document topic files, formatted on the device (isle_amd/csrc/infer_text.hip) from the result of the last
+ * isle_hip_infer_resident where it lies: row 0 is that call's doc_begin, the call formats rows [row_begin, row_end).  A line is
+ *   "<row + number_base>\t<topic + 1>\t<weight>\n"
+ * with the two integers in plain decimal (MMappedOutput::concat_int, include/utils.h:383-418) and <weight> exactly the <weight> of
+ * ISLE_TEXT_SPARSE above (the same function).  trainer_detail::doc_line_text / write_doc_topic_lines (isle_amd/host/trainer_hip.h) restate
+ * the bytes on the host.
+ *   ISLE_DOCTEXT_ENTRIES  every resident entry of the rows, rows ascending, topics ascending within a row; rows without entries give
+ *                         nothing  (ISLETrainer::output_doc_topic_weights, DocTopicWeights.tsv with number_base = 1)
+ *   ISLE_DOCTEXT_TOP      for each row the slots i = 0..4 of top_topic / top_weight in order while top_topic[5 row + i] >= 0
+ *                         (ISLEInfer's top_topics_* files, drivers/ISLEInfer.cpp:100-112, with number_base = <min_doc_id_in_infer_file>)
+ * Domain: concat_int asserts num < 0x7fffffff, and the weight's (int)w / (unsigned)w are undefined outside [0, 2^31).  A printed
+ * number (row + number_base or topic + 1) >= 0x7fffffff, or a printed weight that is negative, NaN, infinite or >= 2^31, fails the call
+ * with ISLE_E_ARG naming the first such line, before any byte is delivered.
+ * Delivery is isle_hip_model_text's: a counting pass (bytes per tile of 1024 lines, the line count, the domain check), a 64-bit
+ * exclusive scan, a writing pass in pieces of at most 16 MiB, each non-empty and ending at a line end, handed to `sink` in order on the
+ * calling thread while the device formats the next.  sink == NULL: the size query.  A non-zero return of the sink ends the call with
+ * ISLE_E_ARG and the context stays usable.  nbytes / nlines (nullable): the size of the text and its lines.  No lines: no sink call, 0.
+ * ISLE_E_ARG also for: an unknown `what`, row_begin > row_end, row_end beyond the rows of the last isle_hip_infer_resident, no valid
+ * resident result (before the first call, after a new count matrix, after a call that failed), world > 1.
+ * The call changes nothing resident: a second call gives the same bytes and isle_hip_get_infer_entries returns what it returned before.
+ * Device time is booked under ISLE_T_INFER.
+ * isle_hip_doc_line_text (host only, no context): one line for the printed numbers doc_number, topic_number (the + base and + 1 already
+ * applied) and w into out40 (NUL-terminated); returns its length, -1 outside the writers' domain (a number >= 0x7fffffff, a weight as
+ * above) or for a null out40.  It compiles the functions the kernels compile. */
+#define ISLE_DOCTEXT_ENTRIES 0 /* the resident entries of the last isle_hip_infer_resident (DocTopicWeights.tsv) */
+#define ISLE_DOCTEXT_TOP 1     /* its heaviest topics, at most five per document (ISLEInfer's top_topics_* files) */
+int isle_hip_infer_text(isle_ctx* ctx, int what, uint64_t row_begin, uint64_t row_end, uint64_t number_base, isle_text_sink_fn sink,
+                        void* user, uint64_t* nbytes, uint64_t* nlines);
+int isle_hip_doc_line_text(uint64_t doc_number, uint64_t topic_number, float w, char* out40);
 /* The avg_doc_sz of the resident count matrix as the context holds it (see above; computed on first use).  ISLE_E_ARG: no count matrix,
  * world > 1, out null. */
 int isle_hip_avg_doc_sz(isle_ctx* ctx, float* out);

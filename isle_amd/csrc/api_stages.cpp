@@ -766,6 +766,22 @@ extern "C" int isle_hip_get_infer_entries(isle_ctx* c, int64_t* doc_offsets, uin
   return 0;
 }
 
+// The per-document topic files formatted on the device (infer_text.hip) from the resident result of the last isle_hip_infer_resident
+extern "C" int isle_hip_infer_text(isle_ctx* c, int what, uint64_t row_begin, uint64_t row_end, uint64_t number_base, isle_text_sink_fn sink,
+                                   void* user, uint64_t* nbytes, uint64_t* nlines) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  if (nbytes) *nbytes = 0;
+  if (nlines) *nlines = 0;
+  if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "infer_text: single-rank only");
+  if (what != ISLE_DOCTEXT_ENTRIES && what != ISLE_DOCTEXT_TOP) return isle_fail(c, ISLE_E_ARG, "infer_text: unknown kind %d", what);
+  if (!c->inf_valid) return isle_fail(c, ISLE_E_ARG, "infer_text: no resident result (run isle_hip_infer_resident; a new count matrix voids it)");
+  if (row_begin > row_end || row_end > c->inf_docs)
+    return isle_fail(c, ISLE_E_ARG, "infer_text: rows [%llu, %llu) of %llu", (unsigned long long)row_begin, (unsigned long long)row_end,
+                     (unsigned long long)c->inf_docs);
+  return k_infer_text(c, what, row_begin, row_end, number_base, sink, user, nbytes, nlines);
+}
+
 extern "C" int isle_hip_avg_doc_sz(isle_ctx* c, float* out) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));

@@ -6,6 +6,7 @@
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -241,7 +242,7 @@ struct isle_ctx {
   DevBuf<float> p_model;           // V x k col-major
   DevBuf<uint64_t> p_avg_acc;      // V x k (lo, hi) pairs: exact fixed-point sums of the average model (avg_model.hip)
   DevBuf<float> p_avg_model;       // V x k col-major, the cluster-average model
-  DevBuf<uint32_t> mt_sizes;       // model text (model_text.hip): bytes per tile
+  DevBuf<uint32_t> mt_sizes;       // the text formatters (model_text.hip, infer_text.hip): bytes per tile
   DevBuf<uint64_t> mt_offs, mt_blk, mt_stat;  // their exclusive scan (+ its scratch); entries emitted, first entry outside the domain
   DevBuf<unsigned char> mt_text[2];  // one chunk of text each (<= ISLE_TEXT_CHUNK_BYTES), formatted while the other one is copied and consumed
   PinBuf mt_pin[2];
@@ -249,6 +250,8 @@ struct isle_ctx {
   DevBuf<int64_t> inf_off;         // docs + 1
   DevBuf<uint32_t> inf_topic;
   DevBuf<float> inf_weight;
+  DevBuf<int32_t> inf_top_topic;   // docs x 5, < 0 = no further topic: what isle_hip_infer_text(ISLE_DOCTEXT_TOP) prints
+  DevBuf<float> inf_top_weight;
   uint64_t inf_docs = 0, inf_n = 0;
   bool inf_valid = false;
   int p_k = 0;                     // num_topics of the last catchword pass
@@ -611,6 +614,17 @@ int k_post_edge(isle_ctx* c, const int64_t* pairs_dev, int n, float a, float b, 
 constexpr uint64_t ISLE_TEXT_CHUNK_BYTES = 16ull << 20;
 int k_model_text(isle_ctx* c, const float* model_dev, uint64_t V, uint64_t ncols, const int64_t* pairs_dev, float a, float b, int format,
                  isle_text_sink_fn sink, void* user, uint64_t* nbytes, uint64_t* nentries);
+// ... and the delivery both text formatters share: a text of `total` > 0 bytes whose ntiles tiles lie at offs_dev (ntiles + 1 offsets on
+// the device) goes to `sink` in chunks of at most ISLE_TEXT_CHUNK_BYTES cut between tiles (at multiples of `group` tiles where possible);
+// write(t0, n, out) launches the formatting of tiles [t0, t0 + n) into out on the context's stream
+int k_text_pump(isle_ctx* c, const char* who, const uint64_t* offs_dev, uint64_t ntiles, uint64_t total, uint64_t group, isle_text_sink_fn sink,
+                void* user, const std::function<int(uint64_t, uint64_t, unsigned char*)>& write);
+
+// infer_text.hip: the lines "<row + base>\t<topic + 1>\t<weight>\n" of rows [row_begin, row_end) of the resident inference result
+// (ISLE_DOCTEXT_ENTRIES: c->inf_off / inf_topic / inf_weight; ISLE_DOCTEXT_TOP: c->inf_top_topic / inf_top_weight), delivered as k_model_text
+// delivers.  The caller has checked the range and c->inf_valid.
+int k_infer_text(isle_ctx* c, int what, uint64_t row_begin, uint64_t row_end, uint64_t base, isle_text_sink_fn sink, void* user, uint64_t* nbytes,
+                 uint64_t* nlines);
 
 // model_load.hip: the text of a model file (n bytes on the device, ISLE_TEXT_SPARSE / ISLE_TEXT_DENSE) parsed into model_dev (V x ncols
 // column-major).  *err_key: ~0 = none, else (byte position << 3) | kind of the first offending byte (isle_hip_load_model_text names them);

@@ -8,6 +8,8 @@
 //   inf_count_k    per document of a chunk, the number of topics above the threshold (one wave per document, ballot + popcount)
 //   inf_write_k    the same ballots again, every entry placed at its document's offset + the popcount of the lanes before it
 // with the 64-bit scan of scan.h between the two.  No atomics: the entries are in (document, topic) order and reproducible bit for bit.
+// The five heaviest topics of every document stay resident beside the entries (c->inf_top_topic / inf_top_weight, under the same
+// validity flag): infer_text.hip prints both from where they are.
 // The documents go in chunks so that the device never holds more than ISLE_INFER_CHUNK_BYTES of dense weights; a document is computed
 // by one workgroup from its own words alone, so the chunk size does not enter any result.
 #include <algorithm>
@@ -157,11 +159,10 @@ int k_infer_resident(isle_ctx* c, const float* model_cm_dev, int k, uint64_t doc
   const uint64_t nch = (R + chunk - 1) / chunk;
   c->inf_valid = false;
 
-  DevBuf<float> dM, dfa, dW, dtw, dllh;
+  DevBuf<float> dM, dfa, dW, dllh;
   DevBuf<uint32_t> dfw, dnk, dcnt;
   DevBuf<int64_t> dbo, dco, dblk;
   DevBuf<unsigned char> dok;
-  DevBuf<int32_t> dtt;
   DevBuf<unsigned int> dnc;
   HIPCHK(c, dM.reserve((size_t)V * ld));
   HIPCHK(c, dok.reserve(V));
@@ -195,14 +196,14 @@ int k_infer_resident(isle_ctx* c, const float* model_cm_dev, int k, uint64_t doc
     HIPCHK(c, dco.reserve(chunk + 1));
     HIPCHK(c, dblk.reserve(isle_scan::scan_scratch_elems(chunk)));
     HIPCHK(c, dW.reserve(chunk * (size_t)k));
-    HIPCHK(c, dtt.reserve(5 * R));
-    HIPCHK(c, dtw.reserve(5 * R));
+    HIPCHK(c, c->inf_top_topic.reserve(5 * R));
+    HIPCHK(c, c->inf_top_weight.reserve(5 * R));
     HIPCHK(c, dllh.reserve(2 * R));
     for (uint64_t i = 0; i < nch; ++i) {
       const uint64_t r0 = i * chunk, n = std::min(chunk, R - r0);
       const int64_t* offs = c->a_offs.p + doc_begin + r0;
       ISLECHK(k_infer_docs(c, dM.p, k, n, c->a_cnt.p, c->a_rows.p, offs, dok.p, shifted(dfw.p, bo[i]), shifted(dfa.p, bo[i]), dnk.p, iters, Lfguess,
-                           avg_doc_sz, dW.p, dtt.p + 5 * r0, dtw.p + 5 * r0, dllh.p + 2 * r0, dnc.p));
+                           avg_doc_sz, dW.p, c->inf_top_topic.p + 5 * r0, c->inf_top_weight.p + 5 * r0, dllh.p + 2 * r0, dnc.p));
       int64_t total = 0;
       {
         TimeScope ts(c, ISLE_T_INFER);
@@ -227,8 +228,8 @@ int k_infer_resident(isle_ctx* c, const float* model_cm_dev, int k, uint64_t doc
   unsigned int nc = 0;
   HIPCHK(c, hipMemcpyAsync(&nc, dnc.p, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
   if (R) {
-    if (top_topic) HIPCHK(c, hipMemcpyAsync(top_topic, dtt.p, 5 * R * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (top_weight) HIPCHK(c, hipMemcpyAsync(top_weight, dtw.p, 5 * R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (top_topic) HIPCHK(c, hipMemcpyAsync(top_topic, c->inf_top_topic.p, 5 * R * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (top_weight) HIPCHK(c, hipMemcpyAsync(top_weight, c->inf_top_weight.p, 5 * R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (llh) HIPCHK(c, hipMemcpyAsync(llh, dllh.p, 2 * R * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -19,38 +19,21 @@
 // post_edge_k (post.hip) does, y = a * m_p rounded, then fmaf(b, m_q, y), while they read the two topic columns, so a V x n edge
 // model costs two reads of two columns per pass and no scratch.
 //
-// Floating-point contraction: hipcc contracts a * b - c into an fma by default, which would take the fraction digits from an unrounded
-// product, and this toolchain's __fmul_rn / __fsub_rn are plain operators that contract all the same (seen in the ISA).  Contraction is
-// therefore switched off for this whole file, host and device, by the "#pragma clang fp contract(off)" below the includes; mt_weight is
+// Floating-point contraction is switched off for this whole file, host and device (text_format.h gives the reason); mt_weight there is
 // the one copy of the digit rule for both sides.  The only fused operation left is the explicit fmaf of the edge entries.
+//
+// k_text_pump below is the delivery both text formatters share (infer_text.hip is the other one).
 #include <algorithm>
 #include <cstring>
+#include <functional>
 
 #include "common.h"
 #include "scan.h"
+#include "text_format.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-constexpr int MT = isle_scan::SCAN_T;  // 256: block_exclusive's width
-constexpr int MT_ITEMS = 4;            // consecutive rows per thread
-constexpr int MT_TILE = MT * MT_ITEMS;
-constexpr int MT_MAX_ENTRY = 36;       // "<col+1 <= 2^31>\t<row+1 < 2^32>\t<6>.<6>\n" = 10 + 1 + 10 + 1 + 13 + 1
-constexpr int MT_LDS_LINES = (MT_TILE * MT_MAX_ENTRY + 15 /*alignment shift*/ + 1 /*dense '\n'*/ + 15) / 16;
-
-__host__ __device__ inline int mt_ndigits(uint32_t v) {
-  return 1 + (v >= 10u) + (v >= 100u) + (v >= 1000u) + (v >= 10000u) + (v >= 100000u) + (v >= 1000000u) + (v >= 10000000u) + (v >= 100000000u) +
-         (v >= 1000000000u);
-}
-__host__ __device__ inline char* mt_put_uint(char* out, uint32_t v, int nd) {  // the nd low digits of v
-  char* q = out + nd;
-  for (int i = 0; i < nd; ++i) {
-    *--q = (char)('0' + v % 10u);
-    v /= 10u;
-  }
-  return out + nd;
-}
 
 // what the writer does with an entry: 0 skipped (SPARSE), 1 "0.0", 2 "nan", 3 <weight>, -1 printed but outside the writer's domain
 __host__ __device__ inline int mt_class(float w, int format) {
@@ -60,27 +43,11 @@ __host__ __device__ inline int mt_class(float w, int format) {
     if (w != w) return 2;
     if (w == 0.0f) return 1;
   }
-  if (!(w >= 0.0f) || !(w < 2147483648.0f)) return -1;
+  if (!mt_weight_in_domain(w)) return -1;
   return 3;
 }
-__host__ __device__ inline int mt_whole_digits(float w) { return std::min(6, mt_ndigits((uint32_t)w)); }  // class 3 only
 __host__ __device__ inline int mt_entry_len(int cls, float w) { return cls == 3 ? mt_whole_digits(w) + 7 : cls ? 3 : 0; }
 
-// trainer_detail::weight_text for a class-3 entry: at most the six low digits of (unsigned)w, '.', six fraction digits peeled off the
-// fp32 remainder by separately rounded multiply and subtract (no contraction in this file).  Returns the end.
-__host__ __device__ inline char* mt_weight(float w, char* out) {
-  const uint32_t whole = (uint32_t)w;
-  out = mt_put_uint(out, whole % 1000000u, std::min(6, mt_ndigits(whole)));
-  *out++ = '.';
-  float rest = w - (float)(int)w;
-  for (int place = 0; place < 6; ++place) {
-    rest = rest * 10.0f;
-    const int digit = (int)rest;
-    *out++ = (char)('0' + digit);
-    rest = rest - (float)digit;
-  }
-  return out;
-}
 __host__ __device__ inline char* mt_entry(int cls, float w, char* out) {
   if (cls == 3) return mt_weight(w, out);
   out[0] = cls == 1 ? '0' : 'n';
@@ -107,18 +74,6 @@ __device__ inline float mt_load(const MtSrc& s, const MtCol& c, uint64_t row) {
   if (!c.q) return c.p[row];
   const float y = s.a * c.p[row];
   return fmaf(s.b, c.q[row], y);  // post_edge_k's two FPaxpy steps
-}
-
-__device__ inline uint32_t mt_block_sum(uint32_t v, uint32_t* sh /*MT / 64*/) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();  // sh may still be read from the previous use
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint32_t s = 0;
-#pragma unroll
-  for (int i = 0; i < MT / ISLE_WAVE; ++i) s += sh[i];
-  return s;
 }
 
 // stat[0] += entries emitted; stat[1] = min over offending entries of col * V + row
@@ -205,21 +160,7 @@ __global__ __launch_bounds__(MT) void mt_write_k(MtSrc src, int format, uint64_t
       }
     }
     if (threadIdx.x == 0 && total < nbytes) text[shift + total] = '\n';  // DENSE: the column ends in this tile
-    __syncthreads();
-    const uint32_t end = shift + nbytes;
-    const uint32_t first = shift ? 1u : 0u, last = end >> 4;  // whole lines [first, last)
-    uint4* const gl = reinterpret_cast<uint4*>(out + (dst0 - shift));
-    for (uint32_t j = first + threadIdx.x; j < last; j += MT) gl[j] = lines[j];
-    const uint32_t head_end = shift ? min(16u, end) : 0u;  // [shift, head_end): the line shared with the tile before
-    const uint32_t tail = max(last << 4, head_end);        // [tail, end): the line shared with the tile after
-    if (threadIdx.x < 16) {
-      const uint32_t j = shift + threadIdx.x;
-      if (j < head_end) out[dst0 - shift + j] = (unsigned char)text[j];
-    } else if (threadIdx.x < 32) {
-      const uint32_t j = tail + (threadIdx.x - 16);
-      if (j < end) out[dst0 - shift + j] = (unsigned char)text[j];
-    }
-    __syncthreads();  // the next tile overwrites the lines
+    mt_store_tile(lines, shift, nbytes, out, dst0);
   }
 }
 
@@ -241,6 +182,67 @@ struct MtPipe {
 }  // namespace
 
 #define LAUNCH_CHECK(c) HIPCHK(c, hipGetLastError())
+
+// The delivery of a text whose tiles are placed by offs_dev (ntiles + 1 exclusive 64-bit offsets on the device, offs[ntiles] = total > 0):
+// chunks of at most ISLE_TEXT_CHUNK_BYTES, cut between tiles, at a multiple of `group` tiles where one lies inside the chunk (whole
+// columns; group = 1: any tile); write(t0, n, out) launches on the context's stream what formats tiles [t0, t0 + n) into out (16-byte
+// aligned, position offs[tile] - offs[t0]).  Two device and two pinned buffers: chunk i + 1 is formatted while chunk i is copied on the
+// copy stream and consumed by the sink on the calling thread.
+int k_text_pump(isle_ctx* c, const char* who, const uint64_t* offs_dev, uint64_t ntiles, uint64_t total, uint64_t group, isle_text_sink_fn sink,
+                void* user, const std::function<int(uint64_t, uint64_t, unsigned char*)>& write) {
+  std::vector<uint64_t> cut{0};
+  std::vector<uint64_t> ho;
+  if (total <= ISLE_TEXT_CHUNK_BYTES) {
+    ho = {0, total};
+    cut.push_back(ntiles);
+  } else {
+    ho.resize(ntiles + 1);
+    HIPCHK(c, hipMemcpy(ho.data(), offs_dev, (ntiles + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (uint64_t t0 = 0; t0 < ntiles;) {
+      uint64_t t1 = (uint64_t)(std::upper_bound(ho.begin() + t0 + 1, ho.end(), ho[t0] + ISLE_TEXT_CHUNK_BYTES) - ho.begin()) - 1;  // > t0: a tile is < 37 KB
+      if (t1 < ntiles && (t1 / group) * group > t0) t1 = (t1 / group) * group;
+      cut.push_back(t1);
+      t0 = t1;
+    }
+  }
+  auto off_at = [&](uint64_t t) { return ho.size() == 2 ? (t ? total : 0) : ho[t]; };
+  std::vector<std::pair<uint64_t, uint64_t>> chunks;  // (first tile, tiles), the empty ones dropped
+  for (size_t i = 0; i + 1 < cut.size(); ++i)
+    if (off_at(cut[i + 1]) > off_at(cut[i])) chunks.push_back({cut[i], cut[i + 1] - cut[i]});
+
+  const size_t buf = (size_t)std::min<uint64_t>(total, ISLE_TEXT_CHUNK_BYTES) + 16;
+  const int nbuf = chunks.size() > 1 ? 2 : 1;
+  for (int i = 0; i < nbuf; ++i) {
+    HIPCHK(c, c->mt_text[i].reserve(buf));
+    HIPCHK(c, c->mt_pin[i].reserve(buf));
+  }
+  if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+  MtPipe pipe(c);
+  for (int i = 0; i < nbuf; ++i) {
+    HIPCHK(c, hipEventCreateWithFlags(&pipe.formatted[i], hipEventDisableTiming));
+    HIPCHK(c, hipEventCreateWithFlags(&pipe.landed[i], hipEventDisableTiming));
+  }
+  auto issue = [&](size_t i) -> int {
+    const int s = (int)(i & 1);
+    const uint64_t t0 = chunks[i].first, n = chunks[i].second, len = off_at(t0 + n) - off_at(t0);
+    ISLECHK(write(t0, n, c->mt_text[s].p));
+    HIPCHK(c, hipEventRecord(pipe.formatted[s], c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->copy_stream, pipe.formatted[s], 0));
+    HIPCHK(c, hipMemcpyAsync(c->mt_pin[s].p, c->mt_text[s].p, len, hipMemcpyDeviceToHost, c->copy_stream));
+    HIPCHK(c, hipEventRecord(pipe.landed[s], c->copy_stream));
+    return 0;
+  };
+  ISLECHK(issue(0));
+  for (size_t i = 0; i < chunks.size(); ++i) {
+    // chunk i + 1 goes into the buffers chunk i - 1 used: its copy was waited for and its sink has returned
+    if (i + 1 < chunks.size()) ISLECHK(issue(i + 1));
+    HIPCHK(c, hipEventSynchronize(pipe.landed[i & 1]));
+    const uint64_t len = off_at(chunks[i].first + chunks[i].second) - off_at(chunks[i].first);
+    if (sink(c->mt_pin[i & 1].p, len, user) != 0)
+      return isle_fail(c, ISLE_E_ARG, "%s: the sink refused piece %zu (%llu bytes)", who, i, (unsigned long long)len);
+  }
+  return 0;
+}
 
 int k_model_text(isle_ctx* c, const float* model_dev, uint64_t V, uint64_t ncols, const int64_t* pairs_dev, float a, float b, int format,
                  isle_text_sink_fn sink, void* user, uint64_t* nbytes, uint64_t* nentries) {
@@ -276,63 +278,12 @@ int k_model_text(isle_ctx* c, const float* model_dev, uint64_t V, uint64_t ncols
   if (nentries) *nentries = h[0];
   if (!sink || total == 0) return 0;
 
-  // chunks of tiles: whole columns up to the bound; a column longer than the bound ends its chunk at a tile
-  std::vector<uint64_t> cut{0};
-  std::vector<uint64_t> ho;
-  if (total <= ISLE_TEXT_CHUNK_BYTES) {
-    ho = {0, total};
-    cut.push_back(ntiles);
-  } else {
-    ho.resize(ntiles + 1);
-    HIPCHK(c, hipMemcpy(ho.data(), c->mt_offs.p, (ntiles + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    for (uint64_t t0 = 0; t0 < ntiles;) {
-      uint64_t t1 = (uint64_t)(std::upper_bound(ho.begin() + t0 + 1, ho.end(), ho[t0] + ISLE_TEXT_CHUNK_BYTES) - ho.begin()) - 1;  // > t0: a tile is < 37 KB
-      if (t1 < ntiles && (t1 / tpc) * tpc > t0) t1 = (t1 / tpc) * tpc;
-      cut.push_back(t1);
-      t0 = t1;
-    }
-  }
-  auto off_at = [&](uint64_t t) { return ho.size() == 2 ? (t ? total : 0) : ho[t]; };
-  std::vector<std::pair<uint64_t, uint64_t>> chunks;  // (first tile, tiles), the empty ones dropped
-  for (size_t i = 0; i + 1 < cut.size(); ++i)
-    if (off_at(cut[i + 1]) > off_at(cut[i])) chunks.push_back({cut[i], cut[i + 1] - cut[i]});
-
-  const size_t buf = (size_t)std::min<uint64_t>(total, ISLE_TEXT_CHUNK_BYTES) + 16;
-  const int nbuf = chunks.size() > 1 ? 2 : 1;
-  for (int i = 0; i < nbuf; ++i) {
-    HIPCHK(c, c->mt_text[i].reserve(buf));
-    HIPCHK(c, c->mt_pin[i].reserve(buf));
-  }
-  if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-  MtPipe pipe(c);
-  for (int i = 0; i < nbuf; ++i) {
-    HIPCHK(c, hipEventCreateWithFlags(&pipe.formatted[i], hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&pipe.landed[i], hipEventDisableTiming));
-  }
-  auto issue = [&](size_t i) -> int {
-    const int s = (int)(i & 1);
-    const uint64_t t0 = chunks[i].first, n = chunks[i].second, len = off_at(t0 + n) - off_at(t0);
-    {
-      TimeScope ts(c, ISLE_T_POST);
-      hipLaunchKernelGGL(mt_write_k, dim3((unsigned)std::min<uint64_t>(n, cap)), dim3(MT), 0, c->stream, src, format, tpc, t0, n, c->mt_offs.p, c->mt_text[s].p);
-      LAUNCH_CHECK(c);
-    }
-    HIPCHK(c, hipEventRecord(pipe.formatted[s], c->stream));
-    HIPCHK(c, hipStreamWaitEvent(c->copy_stream, pipe.formatted[s], 0));
-    HIPCHK(c, hipMemcpyAsync(c->mt_pin[s].p, c->mt_text[s].p, len, hipMemcpyDeviceToHost, c->copy_stream));
-    HIPCHK(c, hipEventRecord(pipe.landed[s], c->copy_stream));
+  return k_text_pump(c, "model_text", c->mt_offs.p, ntiles, total, tpc, sink, user, [&](uint64_t t0, uint64_t n, unsigned char* out) -> int {
+    TimeScope ts(c, ISLE_T_POST);
+    hipLaunchKernelGGL(mt_write_k, dim3((unsigned)std::min<uint64_t>(n, cap)), dim3(MT), 0, c->stream, src, format, tpc, t0, n, c->mt_offs.p, out);
+    LAUNCH_CHECK(c);
     return 0;
-  };
-  ISLECHK(issue(0));
-  for (size_t i = 0; i < chunks.size(); ++i) {
-    // chunk i + 1 goes into the buffers chunk i - 1 used: its copy was waited for and its sink has returned
-    if (i + 1 < chunks.size()) ISLECHK(issue(i + 1));
-    HIPCHK(c, hipEventSynchronize(pipe.landed[i & 1]));
-    const uint64_t len = off_at(chunks[i].first + chunks[i].second) - off_at(chunks[i].first);
-    if (sink(c->mt_pin[i & 1].p, len, user) != 0)
-      return isle_fail(c, ISLE_E_ARG, "model_text: the sink refused piece %zu (%llu bytes)", i, (unsigned long long)len);
-  }
-  return 0;
+  });
 }
 
 extern "C" int isle_hip_entry_text(float w, int format, char* out16) {

@@ -11,7 +11,9 @@
 // stdout (:159-176).  Everything heavy runs on the device and stays there: the model file is parsed by isle_hip_load_model_text
 // (isle_amd/csrc/model_load.hip; model_read.h states its rule for the host), the documents go up once as a count matrix and
 // isle_hip_infer_resident(ISLE_MODEL_LOADED) runs over the whole range; include/isle_hip.h documents that path as bit-equal to
-// isle_hip_infer.  There is no CPU fallback.
+// isle_hip_infer.  The output files are formatted on the device as well (isle_hip_infer_text, isle_amd/csrc/infer_text.hip), one call
+// per file with the file as the sink; trainer_detail::write_doc_topic_lines (trainer_hip.h) states their bytes for the host.  There is
+// no CPU fallback.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -28,27 +30,7 @@
 
 namespace {
 
-// The weight as the reference's writer prints it (MMappedOutput::concat_float, include/utils.h:421-478): "0.0" for zero, a sign, the integer
-// part, a point, and six fraction digits taken one at a time by multiplying the single-precision remainder by ten (truncating).
-void append_weight(std::string& out, float w) {
-  if (w == 0.0f) {
-    out += "0.0";
-    return;
-  }
-  if (w < 0.f) {
-    out += '-';
-    w = -w;
-  }
-  out += std::to_string((unsigned int)w);
-  out += '.';
-  float rest = w - (float)((int)w);
-  for (int place = 0; place < 6; ++place) {
-    rest *= 10;
-    const int digit = (int)rest;
-    out += (char)('0' + digit);
-    rest -= digit;
-  }
-}
+int text_to_file(const char* bytes, uint64_t n, void* fp) { return std::fwrite(bytes, 1, (size_t)n, (FILE*)fp) == (size_t)n ? 0 : 1; }
 
 // the eleven positional arguments (drivers/ISLEInfer.cpp:11-33: this order is the interface)
 struct InferArgs {
@@ -130,38 +112,28 @@ int main(int argc, char** argv) {
     std::vector<uint32_t> rows32(A.rows.begin(), A.rows.end());
     check(isle_hip_upload_counts_u32(ctx, vocab_size, num_docs, A.vals.size(), A.vals.data(), rows32.data(), A.offs.data(), 0, num_docs));
 
-    std::vector<int32_t> top_topic(num_docs * 5);
-    std::vector<float> top_weight(num_docs * 5), llh(num_docs * 2);
+    std::vector<float> llh(num_docs * 2);
     uint64_t nconverged = 0;
     std::cout << "Creating inference engine" << std::endl;
-    check(isle_hip_infer_resident(ctx, ISLE_MODEL_LOADED, nullptr, vocab_size, (int)num_topics, 0, num_docs, iters, Lfguess, -1.0f, 0, top_topic.data(),
-                                  top_weight.data(), llh.data(), &nconverged, nullptr));
-    isle_hip_destroy(ctx);
+    check(isle_hip_infer_resident(ctx, ISLE_MODEL_LOADED, nullptr, vocab_size, (int)num_topics, 0, num_docs, iters, Lfguess, -1.0f, 0, nullptr, nullptr,
+                                  llh.data(), &nconverged, nullptr));
 
+    // the heaviest topics stay on the device and every file is formatted there (isle_hip_infer_text), the file as the sink
     const uint64_t block = 1000000;  // :66
     for (uint64_t b0 = 0; b0 < num_docs; b0 += block) {
       const uint64_t b1 = std::min(num_docs, b0 + block);
       const std::string name = output_dir + "/top_topics_iters_" + std::to_string(iters) + "_Lf_" + std::to_string(Lfguess) + "_doc_" +
                                std::to_string(doc_begin + b0) + "_to_" + std::to_string(doc_begin + b1);
       FILE* f = std::fopen(name.c_str(), "wb");
-      if (!f) throw std::runtime_error("cannot open " + name);
-      std::string buf;
-      for (uint64_t d = b0; d < b1; ++d)
-        for (int i = 0; i < 5 && top_topic[d * 5 + i] >= 0; ++i) {
-          buf += std::to_string(d + doc_begin);
-          buf += '\t';
-          buf += std::to_string(1 + top_topic[d * 5 + i]);
-          buf += '\t';
-          append_weight(buf, top_weight[d * 5 + i]);
-          buf += '\n';
-          if (buf.size() > (1u << 24)) {
-            std::fwrite(buf.data(), 1, buf.size(), f);
-            buf.clear();
-          }
-        }
-      std::fwrite(buf.data(), 1, buf.size(), f);
+      if (!f) {
+        isle_hip_destroy(ctx);
+        throw std::runtime_error("cannot open " + name);
+      }
+      const int rc = isle_hip_infer_text(ctx, ISLE_DOCTEXT_TOP, b0, b1, doc_begin, text_to_file, f, nullptr, nullptr);
       std::fclose(f);
+      check(rc);
     }
+    isle_hip_destroy(ctx);
     std::cout << "Number of docs for which inference converged: " << nconverged << " (of " << num_docs << ")" << std::endl;
     float sum_first = 0.f, sum_second = 0.f;  // :165-171 (fp32 sums in document order)
     for (uint64_t d = 0; d < num_docs; ++d) {

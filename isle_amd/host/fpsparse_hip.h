@@ -327,15 +327,42 @@ class FPSparseMatrixHip {
                            std::vector<int64_t>& doc_offsets, std::vector<uint32_t>& topic, std::vector<FPTYPE>& weight,
                            const FPTYPE min_weight = -1.0f, const FPTYPE* model_host = nullptr, const doc_id_t ncols = 0,
                            const uint64_t chunk_docs = 0) {
-    uint64_t nconv = 0, n = 0;
-    const bool host = which == ISLE_MODEL_HOST;
-    check(isle_hip_infer_resident(ctx_, which, model_host, vocab_size_, (int)(host ? ncols : model_cols(which)), doc_begin, doc_end, iters, Lf,
-                                  min_weight, chunk_docs, nullptr, nullptr, nullptr, &nconv, &n), "infer_documents");
+    uint64_t n = 0;
+    const uint64_t nconv = infer_documents_resident(which, doc_begin, doc_end, iters, Lf, min_weight, model_host, ncols, chunk_docs, &n);
     doc_offsets.assign((size_t)(doc_end - doc_begin) + 1, 0);
     topic.assign(n, 0);
     weight.assign(n, 0.0f);
     check(isle_hip_get_infer_entries(ctx_, doc_offsets.data(), topic.data(), weight.data()), "get_infer_entries");
     return nconv;
+  }
+  // The same inference with the entries (and the five heaviest topics of every document) left on the device, where write_infer_text
+  // formats them.  Returns the converged documents; nentries (nullable): the entries.
+  uint64_t infer_documents_resident(const int which, const doc_id_t doc_begin, const doc_id_t doc_end, const int iters, const FPTYPE Lf,
+                                    const FPTYPE min_weight = -1.0f, const FPTYPE* model_host = nullptr, const doc_id_t ncols = 0,
+                                    const uint64_t chunk_docs = 0, uint64_t* nentries = nullptr) {
+    uint64_t nconv = 0;
+    const bool host = which == ISLE_MODEL_HOST;
+    check(isle_hip_infer_resident(ctx_, which, model_host, vocab_size_, (int)(host ? ncols : model_cols(which)), doc_begin, doc_end, iters, Lf,
+                                  min_weight, chunk_docs, nullptr, nullptr, nullptr, &nconv, nentries), "infer_documents");
+    return nconv;
+  }
+  // The lines "<row + number_base>\t<topic + 1>\t<weight>\n" of rows [row_begin, row_end) of the last inference (row 0 = its doc_begin),
+  // formatted on the device (isle_hip_infer_text) and streamed to the file: what = ISLE_DOCTEXT_ENTRIES (every entry; DocTopicWeights.tsv)
+  // or ISLE_DOCTEXT_TOP (the at most five heaviest topics; ISLEInfer's top_topics_* files).  Returns the bytes written; nlines nullable.
+  uint64_t write_infer_text(const std::string& filename, const int what, const doc_id_t row_begin, const doc_id_t row_end,
+                            const uint64_t number_base, uint64_t* nlines = nullptr) {
+    FILE* fp = std::fopen(filename.c_str(), "wb");
+    if (!fp) throw std::runtime_error("cannot open " + filename);
+    uint64_t nbytes = 0;
+    const int rc = isle_hip_infer_text(ctx_, what, row_begin, row_end, number_base, text_to_file, fp, &nbytes, nlines);
+    std::fclose(fp);
+    check(rc, "write_infer_text");
+    return nbytes;
+  }
+  uint64_t infer_text_size(const int what, const doc_id_t row_begin, const doc_id_t row_end, const uint64_t number_base, uint64_t* nlines = nullptr) {
+    uint64_t nbytes = 0;
+    check(isle_hip_infer_text(ctx_, what, row_begin, row_end, number_base, nullptr, nullptr, &nbytes, nlines), "infer_text_size");
+    return nbytes;
   }
   doc_id_t count_docs() const { return a_docs_; }  // documents of the count matrix A (B may hold fewer after sampling)
   // DenseMatrix::write_to_file_as_sparse (format = ISLE_TEXT_SPARSE) / write_to_file (ISLE_TEXT_DENSE), src/denseMatrix.cpp:124-186, of a

@@ -24,7 +24,8 @@
 // stays 0 (the reference's summary has that call commented out).
 // Model files: M_hat_catch_sparse, EdgeModel_sparse and M_hat_avg are formatted on the device from the resident models
 // (FPSparseMatrixHip::write_model_text / write_edge_model_text -> isle_hip_model_text / isle_hip_edge_topics_text) and streamed to the file;
-// trainer_detail's host writers below define those bytes and are what the tests compare the device text against.
+// trainer_detail's host writers below define those bytes and are what the tests compare the device text against.  DocTopicWeights.tsv
+// is formatted on the device in the same way (write_infer_text -> isle_hip_infer_text; trainer_detail::write_doc_topic_lines).
 // Not mirrored (dead under the shipped hyper-parameters or outside the path): load_preprocessed_data_from_file,
 // print_doctopic (accepted, unused: the reference's use is commented out), compute_input_svd, construct_edge_topics_v1.
 #pragma once
@@ -174,6 +175,45 @@ void write_dense_as_sparse(const std::string& filename, const float* M, uint64_t
   }
   std::fwrite(pending.data(), 1, pending.size(), fp);
   std::fclose(fp);
+}
+// One line of the per-document topic files (ISLEInfer's top_topics_*, drivers/ISLEInfer.cpp:100-112; DocTopicWeights.tsv):
+// "<doc>\t<topic>\t<weight>\n" with MMappedOutput::concat_int's plain decimals (include/utils.h:383-418) and weight_text's digits.
+// doc_number and topic_number are the numbers as printed.  Returns the length (at most 36).
+inline size_t doc_line_text(uint64_t doc_number, uint64_t topic_number, float w, char* out) {
+  size_t len = 0;
+  for (const uint64_t v : {doc_number, topic_number}) {
+    const std::string digits = std::to_string(v);
+    std::memcpy(out + len, digits.data(), digits.size());
+    len += digits.size();
+    out[len++] = '\t';
+  }
+  len += weight_text(w, out + len);
+  out[len++] = '\n';
+  return len;
+}
+// The two host loops the device formatter (isle_hip_infer_text) replaces, kept as the statement of its bytes: every entry of a CSR of
+// document rows (offs: rows + 1; ISLE_DOCTEXT_ENTRIES), or with offs == nullptr the slots i = 0..4 of every row while topic[5 row + i] >= 0
+// (ISLE_DOCTEXT_TOP).  Row r prints as r + number_base, a topic as topic + 1.
+template <class TopicT>
+void write_doc_topic_lines(FILE* fp, const int64_t* offs, const TopicT* topic, const float* weight, uint64_t rows, uint64_t number_base) {
+  constexpr size_t kFlushAt = (size_t(1) << 24) - 256;
+  std::string pending;
+  pending.reserve(size_t(1) << 24);
+  char text[40];
+  auto put = [&](uint64_t row, int64_t at) {
+    pending.append(text, doc_line_text(row + number_base, (uint64_t)topic[at] + 1, weight[at], text));
+    if (pending.size() > kFlushAt) {
+      std::fwrite(pending.data(), 1, pending.size(), fp);
+      pending.clear();
+    }
+  };
+  for (uint64_t row = 0; row < rows; ++row) {
+    if (offs)
+      for (int64_t i = offs[row]; i < offs[row + 1]; ++i) put(row, i);
+    else
+      for (int i = 0; i < 5 && topic[row * 5 + i] >= 0; ++i) put(row, (int64_t)(row * 5 + i));
+  }
+  std::fwrite(pending.data(), 1, pending.size(), fp);
 }
 }  // namespace trainer_detail
 
@@ -602,39 +642,16 @@ class ISLETrainer {
   // The reference accepts print_doctopic and never uses it; this is what it asks for.  The topic weights of every document of A
   // under the resident model (ISLEInfer's iterations on the device, FPSparseMatrixHip::infer_documents) into DocTopicWeights.tsv:
   // "<doc>\t<topic>\t<weight>\n", 1-based, documents and topics ascending, topics with weight > 1 / num_topics of the converged
-  // documents, <weight> as weight_text prints it.  Deviation from running ISLEInfer on M_hat_catch_sparse: the model is the fp32
+  // documents, <weight> as weight_text prints it; the entries stay on the device and the file is formatted there
+  // (FPSparseMatrixHip::write_infer_text -> isle_hip_infer_text; trainer_detail::write_doc_topic_lines states the bytes).  Deviation from running ISLEInfer on M_hat_catch_sparse: the model is the fp32
   // model, not the file's six truncated digits.
   void output_doc_topic_weights(const int which = ISLE_MODEL_CATCH, const int iters = ISLE_INFER_ITERS_DEFAULT, const FPTYPE Lf = ISLE_INFER_LF_DEFAULT) {
     if (!is_training_complete) throw std::runtime_error("output_doc_topic_weights() before train()");
-    std::vector<int64_t> offs;
-    std::vector<uint32_t> topic;
-    std::vector<FPTYPE> weight;
     const doc_id_t docs = B_fl_CSC->count_docs();
-    const uint64_t nconv = B_fl_CSC->infer_documents(which, 0, docs, iters, Lf, offs, topic, weight);
+    const uint64_t nconv = B_fl_CSC->infer_documents_resident(which, 0, docs, iters, Lf);
     log->print("Number of docs for which inference converged: " + std::to_string(nconv) + " (of " + std::to_string(docs) + ")\n");
     log->next_time_secs("Inferring document topic weights");
-    constexpr size_t kFlushAt = (size_t(1) << 24) - 256;
-    const std::string filename = log_dir + "/DocTopicWeights.tsv";
-    FILE* fp = std::fopen(filename.c_str(), "wb");
-    if (!fp) throw std::runtime_error("cannot open " + filename);
-    std::string pending;
-    pending.reserve(size_t(1) << 24);
-    char text[32];
-    for (doc_id_t d = 0; d < docs; ++d)
-      for (int64_t i = offs[d]; i < offs[d + 1]; ++i) {
-        pending += std::to_string(d + 1);
-        pending += '\t';
-        pending += std::to_string(topic[i] + 1);
-        pending += '\t';
-        pending.append(text, trainer_detail::weight_text(weight[i], text));
-        pending += '\n';
-        if (pending.size() > kFlushAt) {
-          std::fwrite(pending.data(), 1, pending.size(), fp);
-          pending.clear();
-        }
-      }
-    std::fwrite(pending.data(), 1, pending.size(), fp);
-    std::fclose(fp);
+    B_fl_CSC->write_infer_text(log_dir + "/DocTopicWeights.tsv", ISLE_DOCTEXT_ENTRIES, 0, docs, 1);
     log->next_time_secs("Writing document topic weights to file");
   }
   void finish_log() { log->total("TVSD"); }  // the "Total time for TVSD" line the reference's train() ends with (:652)

@@ -104,6 +104,18 @@ def entry_text(w, format="dense"):
     return -1 if n < 0 else buf.raw[:n].decode("ascii")
 
 
+DOC_TEXT_KINDS = {"entries": 0, "top": 1}   # ISLE_DOCTEXT_ENTRIES, ISLE_DOCTEXT_TOP
+
+
+def doc_line_text(doc_number, topic_number, w):
+    """One line "<doc>\\t<topic>\\t<weight>\\n" of the per-document topic files for the numbers as printed (isle_hip_doc_line_text, the
+    host copy of what the kernels of infer_text.hip compile) -> bytes, or -1 outside the writers' domain (a number >= 0x7fffffff, a
+    weight that is negative, NaN, infinite or >= 2^31).  No GPU needed."""
+    buf = C.create_string_buffer(40)
+    n = load_library().isle_hip_doc_line_text(int(doc_number), int(topic_number), C.c_float(float(np.float32(w))), buf)
+    return -1 if n < 0 else buf.raw[:n]
+
+
 def parse_weight(token, format="sparse"):
     """One weight token of a model file as the library's readers take it (isle_hip_parse_weight, the host copy of the rule the loader's
     kernels compile): <digits>[.<digits>] -> np.float32; "nan" under "dense" -> the quiet NaN.  None for a token outside the grammar.
@@ -638,10 +650,34 @@ class HotPath:
         self._chk(self._lib.isle_hip_infer_resident(self._h, which, _p(host), int(V), int(cols), b, e, int(iters), float(Lf),
                                                     -1.0 if min_weight is None else float(min_weight), int(chunk_docs), _p(tt), _p(tw),
                                                     _p(llh), C.byref(nc), C.byref(ne)))
+        self._inf_rows = n
         out = dict(top_topic=tt, top_weight=tw, llh=llh, nconverged=int(nc.value), nentries=int(ne.value), avg_doc_sz=self.avg_doc_sz())
         if fetch_entries:
             out.update(zip(("offs", "topic", "weight"), self.infer_entries(n, out["nentries"])))
         return out
+
+    # ---- the per-document topic files formatted on the device (include/isle_hip.h, isle_hip_infer_text) --------------------------
+    def _infer_text_call(self, what, rows, base, consume):
+        kind = DOC_TEXT_KINDS[what] if isinstance(what, str) else int(what)
+        b, e = (0, getattr(self, "_inf_rows", 0)) if rows is None else (int(rows[0]), int(rows[1]))
+        return self._text_call(lambda sink, nb, nl: self._lib.isle_hip_infer_text(self._h, kind, b, e, int(base), sink, None, nb, nl), consume)
+
+    def infer_text(self, what="entries", rows=None, base=1):
+        """The lines "<row + base>\\t<topic + 1>\\t<weight>\\n" of rows (None: all; or (begin, end), row 0 = the first document) of the
+        last infer_resident, formatted on the device from the resident result: "entries" (every entry, DocTopicWeights.tsv) or "top"
+        (the at most five heaviest topics of a document, ISLEInfer's top_topics_* files).  -> bytes."""
+        parts = []
+        self._infer_text_call(what, rows, base, lambda mv: parts.append(bytes(mv)))
+        return b"".join(parts)
+
+    def write_infer_text(self, path, what="entries", rows=None, base=1):
+        """infer_text streamed into a file piece by piece; the whole text is never held.  -> (nbytes, nlines)."""
+        with open(path, "wb") as f:
+            return self._infer_text_call(what, rows, base, f.write)
+
+    def infer_text_size(self, what="entries", rows=None, base=1):
+        """The counting pass alone.  -> (nbytes, nlines)."""
+        return self._infer_text_call(what, rows, base, None)
 
     def avg_doc_sz(self):
         """avg_doc_sz of the resident count matrix (populate_CSC, src/sparseMatrix.cpp:87-98: floor(tokens / non-empty documents))."""
