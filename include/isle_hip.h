@@ -103,6 +103,32 @@ int isle_hip_upload_counts_u32(isle_ctx* ctx, uint64_t vocab_size, uint64_t num_
  * they become floats).  Fields are read exactly, whatever their length: none wraps into range. */
 int isle_hip_ingest_tdf(isle_ctx* ctx, const char* text, uint64_t nbytes, uint64_t vocab_size, uint64_t num_docs,
                         uint64_t max_entries, uint64_t* entries_read, uint64_t* nnz);
+/* The count matrix from (doc, word, count) triples in any order, fed in batches: what ISLETrainer::feed_data / finalize_data
+ * (src/trainer.cpp:214-371) do, with the sort, the de-duplication and the offsets on the device (the tail of isle_hip_ingest_tdf).
+ * feed_begin opens a feed for a vocab_size x num_docs matrix (both 1 .. 0xfffffff0), discarding an open one; the context's
+ * current count matrix stays as it is until feed_finalize.  reserve_entries: capacity hint (0 allowed); the entry store doubles
+ * when a batch does not fit.
+ * feed_entries: n entries, docs[i] the 0-based local column, words[i] the 0-based word id, counts[i] the count; the arrays are
+ * the caller's again when the call returns; n == 0 is a no-op; batches of any size (large ones are cut inside).  An entry with
+ * count 0 is skipped and takes no part in duplicate resolution.  A batch is taken whole or not at all: with docs[i] >= num_docs
+ * or words[i] >= vocab_size anywhere in it (entries with count 0 included) the call returns ISLE_E_ARG, the message names
+ * "document" or "word" and the 0-based ordinal of the first such entry, counted over every entry offered since feed_begin
+ * (skipped ones included, rejected batches not), and the feed stays open holding what it held before the call.
+ * feed_finalize: entries sorted by (doc, word); of several with the same (doc, word) the one offered first stays (call order,
+ * then index); offsets with the empty documents.  The result is this context's count matrix exactly as if it had been passed to
+ * isle_hip_upload_counts_u32 with the same doc_offset / docs_global (0 / 0 on a single rank), and the feed is released.
+ * entries_fed / nnz (nullable): entries kept before / after de-duplication.  A feed without entries gives num_docs empty columns.
+ * Allowed with several ranks: each feeds its own shard under local column numbers, no collective is involved.
+ * ISLE_E_ARG: feed_entries / feed_finalize without an open feed, a null array with n > 0.  After an allocation or device
+ * failure the feed is discarded. */
+int isle_hip_feed_begin(isle_ctx* ctx, uint64_t vocab_size, uint64_t num_docs, uint64_t reserve_entries);
+int isle_hip_feed_entries(isle_ctx* ctx, uint64_t n, const uint32_t* docs, const uint32_t* words, const uint32_t* counts);
+/* isle_hip_feed_entries with the size of the pieces a batch is cut into given (0, or anything above the library's own 2^26 entries:
+ * that size).  The result does not depend on it; it exists so that the cutting, the ordinals across pieces and the whole-batch
+ * refusal can be tested on small batches. */
+int isle_hip_feed_entries_pieces(isle_ctx* ctx, uint64_t n, const uint32_t* docs, const uint32_t* words, const uint32_t* counts,
+                                 uint64_t piece_entries);
+int isle_hip_feed_finalize(isle_ctx* ctx, uint64_t doc_offset, uint64_t docs_global, uint64_t* entries_fed, uint64_t* nnz);
 /* Copies the context's count matrix to the host (any pointer may be NULL); nnz via the call above
  * or offsets[num_docs]. */
 int isle_hip_get_A(isle_ctx* ctx, float* counts, uint32_t* rows, int64_t* offsets);

@@ -80,6 +80,75 @@ extern "C" int isle_hip_ingest_tdf(isle_ctx* c, const char* text, uint64_t nbyte
   return 0;
 }
 
+// ---- (doc, word, count) triples in batches -> A (ingest.hip: feed_key_k, then the tail tdf ingest runs)
+extern "C" int isle_hip_feed_begin(isle_ctx* c, uint64_t V, uint64_t D, uint64_t reserve_entries) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  c->feed.release();  // an open feed is discarded
+  if (V == 0 || V > 0xfffffff0ull || D == 0 || D > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "feed_begin: vocab/doc count out of range");
+  if (reserve_entries) {
+    hipError_t e = c->feed.key.reserve(reserve_entries);
+    if (e == hipSuccess) e = c->feed.cnt.reserve(reserve_entries);
+    if (e != hipSuccess) c->feed.release();
+    HIPCHK(c, e);
+  }
+  c->feed.V = V;
+  c->feed.D = D;
+  c->feed.open = true;
+  return 0;
+}
+
+extern "C" int isle_hip_feed_entries(isle_ctx* c, uint64_t n, const uint32_t* docs, const uint32_t* words, const uint32_t* counts) {
+  return isle_hip_feed_entries_pieces(c, n, docs, words, counts, 0);
+}
+
+extern "C" int isle_hip_feed_entries_pieces(isle_ctx* c, uint64_t n, const uint32_t* docs, const uint32_t* words, const uint32_t* counts,
+                                            uint64_t piece_entries) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  IsleFeed& f = c->feed;
+  if (!f.open) return isle_fail(c, ISLE_E_ARG, "feed_entries: no open feed (isle_hip_feed_begin)");
+  if (n == 0) return 0;
+  if (!docs || !words || !counts) return isle_fail(c, ISLE_E_ARG, "feed_entries: null array");
+  const uint64_t piece = (piece_entries && piece_entries < ISLE_FEED_CHUNK) ? piece_entries : ISLE_FEED_CHUNK;
+  const uint64_t n0 = f.n, offered0 = f.offered;  // a batch is taken whole or not at all
+  for (uint64_t at = 0; at < n; at += piece) {
+    uint64_t bad = ~0ull;
+    const int rc = k_feed_chunk(c, docs + at, words + at, counts + at, std::min<uint64_t>(piece, n - at), &bad);
+    if (rc) {  // allocation or device failure: the feed is discarded, once no copy from the caller's arrays is queued any more
+      (void)hipStreamSynchronize(c->stream);
+      f.release();
+      return rc;
+    }
+    if (bad != ~0ull) {
+      f.n = n0;
+      f.offered = offered0;
+      return isle_fail(c, ISLE_E_ARG, "feed_entries: %s id out of range at entry %llu (0-based, counted from feed_begin)",
+                       (bad & 7ull) == 1 ? "document" : "word", (unsigned long long)(bad >> 3));
+    }
+  }
+  return 0;
+}
+
+extern "C" int isle_hip_feed_finalize(isle_ctx* c, uint64_t doc_offset, uint64_t docs_global, uint64_t* entries_fed, uint64_t* nnz) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  if (!c->feed.open) return isle_fail(c, ISLE_E_ARG, "feed_finalize: no open feed (isle_hip_feed_begin)");
+  c->a_ready = false;  // a_cnt / a_rows / a_offs are rewritten from here
+  const uint64_t fed = c->feed.n, D = c->feed.D;
+  const int rc = k_feed_finalize(c);
+  (void)hipStreamSynchronize(c->stream);
+  c->feed.release();
+  ISLECHK(rc);
+  c->a_doc_offset = doc_offset;
+  c->a_D_global = docs_global ? docs_global : D;
+  c->a_ready = true;
+  isle_void_derived_from_A(c);
+  if (entries_fed) *entries_fed = fed;
+  if (nnz) *nnz = c->a_nnz;
+  return 0;
+}
+
 extern "C" int isle_hip_get_A(isle_ctx* c, float* counts, uint32_t* rows, int64_t* offs) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));

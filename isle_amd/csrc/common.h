@@ -155,6 +155,22 @@ struct IslePinSmall {
   };
 };
 
+// An open feed of (doc, word, count) triples (isle_hip_feed_begin ... isle_hip_feed_finalize; ingest.hip): the entries kept so far as
+// sort keys (doc << wbits) | word and counts, in the order they were offered, and the staging of one chunk of a batch.
+constexpr uint64_t ISLE_FEED_CHUNK = 1ull << 26;  // entries per upload + launch: larger batches are cut into these
+struct IsleFeed {
+  bool open = false;
+  uint64_t V = 0, D = 0;
+  uint64_t n = 0;        // entries held (zero counts are not)
+  uint64_t offered = 0;  // entries offered since feed_begin, skipped ones included: the ordinal an error names
+  DevBuf<uint64_t> key;  // the entry store: grows by doubling, contents kept
+  DevBuf<uint32_t> cnt;
+  DevBuf<uint32_t> in_docs, in_words, in_cnt, t_cnt, t_valid;  // one chunk: as uploaded; keyed, before compaction
+  DevBuf<uint64_t> t_key, t_err;
+  DevBuf<int64_t> t_at, t_scratch;
+  void release();
+};
+
 struct isle_ctx {
   // environment switches as read at the last C-ABI entry (isle_refresh_knobs)
   std::string knob_val[KN_COUNT];
@@ -207,6 +223,7 @@ struct isle_ctx {
   // --- A (word-document counts, this rank's column shard) and the thresholding workspaces (threshold.hip)
   uint64_t a_V = 0, a_D = 0, a_nnz = 0, a_doc_offset = 0, a_D_global = 0;
   bool a_ready = false;
+  IsleFeed feed;
   DevBuf<float> a_cnt;
   DevBuf<uint32_t> a_rows;
   DevBuf<int64_t> a_offs;
@@ -579,6 +596,8 @@ int k_th_emit(isle_ctx* c, uint64_t doc_base);
 // ingest.hip
 int k_sort_pairs_u64(isle_ctx* c, uint64_t* key_a, uint32_t* val_a, uint64_t* key_b, uint32_t* val_b, uint64_t n, int key_bits, bool* in_a);
 int k_ingest_tdf(isle_ctx* c, const unsigned char* text_dev, uint64_t n, uint64_t V, uint64_t D, uint64_t* entries_read, uint64_t* err_out);
+int k_feed_chunk(isle_ctx* c, const uint32_t* docs, const uint32_t* words, const uint32_t* counts, uint64_t n, uint64_t* bad);
+int k_feed_finalize(isle_ctx* c);
 
 // infer.hip
 int k_infer(isle_ctx* c, uint64_t V, int k, const float* model_by_word, uint64_t D, uint64_t nnz, const float* counts, const uint32_t* rows,

@@ -14,6 +14,7 @@
 // fields, an id outside 1..D / 1..V, a count of 0 and a count above 4294967295.  A field saturates at 2^32 while it is read (no id or
 // count needs more), so no digit string, however long, wraps into range.  Of several bad lines the first in the file is reported.  The
 // reference's std::sort + std::unique keeps an unspecified one of several equal (doc, word) lines; here it is the first in the file.
+#include <algorithm>
 #include <utility>
 
 #include "common.h"
@@ -251,24 +252,78 @@ int k_sort_pairs_u64(isle_ctx* c, uint64_t* key_a, uint32_t* val_a, uint64_t* ke
   return 0;
 }
 
+// The part both front ends share: ne (key, count) pairs in offered order in (key_a, cnt_a), keys (doc << wbits) | word; (key_b, cnt_b) is
+// the other half of the sort's ping-pong, ne elements each.  Stable sort by (doc, word), the first of equal pairs kept, offsets with the
+// empty documents: the result becomes the context's a_cnt / a_rows / a_offs, a_V, a_D, a_nnz.
+static int ing_sort_dedup_install(isle_ctx* c, uint64_t V, uint64_t D, int wbits, int dbits, uint64_t* key_a, uint32_t* cnt_a, uint64_t* key_b,
+                                  uint32_t* cnt_b, uint64_t ne) {
+  DevBuf<uint32_t> flag, docs, hist;
+  DevBuf<int64_t> at, hist_off, scratch;
+  // ---- sort by (doc, word)
+  uint64_t *ka = key_a, *kb = key_b;
+  uint32_t *va = cnt_a, *vb = cnt_b;
+  HIPCHK(c, scratch.reserve(isle_scan_scratch(ne + 16) + 8));
+  if (ne > 1) {
+    const uint32_t nblocks = (uint32_t)((ne + RS_TILE - 1) / RS_TILE);
+    HIPCHK(c, hist.reserve((size_t)256 * nblocks));
+    HIPCHK(c, hist_off.reserve((size_t)256 * nblocks + 1));
+    HIPCHK(c, scratch.reserve(isle_scan_scratch((uint64_t)256 * nblocks) + 8));
+    for (int shift = 0; shift < wbits + dbits; shift += 8) {
+      hipLaunchKernelGGL(rs_hist_k, dim3(nblocks), dim3(IT), 0, c->stream, ka, ne, shift, nblocks, hist.p);
+      LAUNCH_CHECK(c);
+      HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, hist.p, (uint64_t)256 * nblocks, hist_off.p, scratch.p)));
+      hipLaunchKernelGGL(rs_scatter_k, dim3(nblocks), dim3(IT), 0, c->stream, ka, va, ne, shift, nblocks, hist_off.p, kb, vb);
+      LAUNCH_CHECK(c);
+      std::swap(ka, kb);
+      std::swap(va, vb);
+    }
+  }
+  // ---- drop repeated pairs, build the CSC
+  HIPCHK(c, flag.reserve(ne ? ne : 1));
+  HIPCHK(c, at.reserve(ne + 1));
+  if (ne) hipLaunchKernelGGL(ing_flag_k, dim3(cdiv((long)ne, IT)), dim3(IT), 0, c->stream, ka, ne, flag.p);
+  LAUNCH_CHECK(c);
+  HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, flag.p, ne, at.p, scratch.p)));
+  int64_t m = 0;
+  HIPCHK(c, hipMemcpyAsync(&m, at.p + ne, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, c->a_cnt.reserve(m ? m : 1));
+  HIPCHK(c, c->a_rows.reserve(m ? m : 1));
+  HIPCHK(c, c->a_offs.reserve(D + 1));
+  HIPCHK(c, docs.reserve(m ? m : 1));
+  if (ne) hipLaunchKernelGGL(ing_compact_k, dim3(cdiv((long)ne, IT)), dim3(IT), 0, c->stream, ka, va, flag.p, at.p, ne, wbits, c->a_rows.p, c->a_cnt.p, docs.p);
+  LAUNCH_CHECK(c);
+  hipLaunchKernelGGL(ing_offsets_k, dim3(cdiv((long)m + 1, IT)), dim3(IT), 0, c->stream, docs.p, (uint64_t)m, D, c->a_offs.p);
+  LAUNCH_CHECK(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->a_V = V;
+  c->a_D = D;
+  c->a_nnz = (uint64_t)m;
+  return 0;  // (the local buffers are released by their destructors, on the error returns too)
+}
+
+static void ing_key_bits(uint64_t V, uint64_t D, int* wbits, int* dbits) {
+  *wbits = 1;
+  while ((1ull << *wbits) < V) ++*wbits;
+  *dbits = 1;
+  while ((1ull << *dbits) < D) ++*dbits;
+}
+
 // text_dev: n bytes on the device.  On success the context's count matrix is set (a_cnt / a_rows / a_offs, a_nnz).
 int k_ingest_tdf(isle_ctx* c, const unsigned char* text_dev, uint64_t n, uint64_t V, uint64_t D, uint64_t* entries_read, uint64_t* err_out /*2*/) {
   TimeScope ts(c, ISLE_T_INGEST);
   err_out[0] = err_out[1] = 0;
-  int wbits = 1;
-  while ((1ull << wbits) < V) ++wbits;
-  int dbits = 1;
-  while ((1ull << dbits) < D) ++dbits;
+  int wbits, dbits;
+  ing_key_bits(V, D, &wbits, &dbits);
   // ---- line starts
   const uint64_t ntiles = (n + TILE_BYTES - 1) / TILE_BYTES;
-  DevBuf<uint32_t> tile_cnt, valid, cnt0, cnt1, flag, docs;
-  DevBuf<int64_t> tile_off, at, hist_off, scratch;
+  DevBuf<uint32_t> tile_cnt, valid, cnt0, cnt1;
+  DevBuf<int64_t> tile_off, at, scratch;
   DevBuf<uint64_t> line_start, key0, key1, errd;
-  DevBuf<uint32_t> hist;
   auto cleanup = [&]() {
-    tile_cnt.release(); valid.release(); cnt0.release(); cnt1.release(); flag.release(); docs.release();
-    tile_off.release(); at.release(); hist_off.release(); scratch.release();
-    line_start.release(); key0.release(); key1.release(); errd.release(); hist.release();
+    tile_cnt.release(); valid.release(); cnt0.release(); cnt1.release();
+    tile_off.release(); at.release(); scratch.release();
+    line_start.release(); key0.release(); key1.release(); errd.release();
   };
 #define ING(call)            \
   do {                       \
@@ -323,45 +378,118 @@ int k_ingest_tdf(isle_ctx* c, const unsigned char* text_dev, uint64_t n, uint64_
   ING(cnt1.reserve(ne ? ne : 1));
   if (nlines) hipLaunchKernelGGL(ing_pack_k, dim3(cdiv((long)nlines, IT)), dim3(IT), 0, c->stream, key0.p, cnt0.p, valid.p, at.p, nlines, key1.p, cnt1.p);
   ING(hipGetLastError());
-  // ---- sort by (doc, word): keys in key1/cnt1, ping-pong with key0/cnt0
-  uint64_t *ka = key1.p, *kb = key0.p;
-  uint32_t *va = cnt1.p, *vb = cnt0.p;
-  if (ne > 1) {
-    const uint32_t nblocks = (uint32_t)((ne + RS_TILE - 1) / RS_TILE);
-    ING(hist.reserve((size_t)256 * nblocks));
-    ING(hist_off.reserve((size_t)256 * nblocks + 1));
-    ING(scratch.reserve(isle_scan_scratch((uint64_t)256 * nblocks) + 8));
-    for (int shift = 0; shift < wbits + dbits; shift += 8) {
-      hipLaunchKernelGGL(rs_hist_k, dim3(nblocks), dim3(IT), 0, c->stream, ka, ne, shift, nblocks, hist.p);
-      ING(hipGetLastError());
-      ING((isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, hist.p, (uint64_t)256 * nblocks, hist_off.p, scratch.p)));
-      hipLaunchKernelGGL(rs_scatter_k, dim3(nblocks), dim3(IT), 0, c->stream, ka, va, ne, shift, nblocks, hist_off.p, kb, vb);
-      ING(hipGetLastError());
-      std::swap(ka, kb);
-      std::swap(va, vb);
-    }
-  }
-  // ---- drop repeated pairs, build the CSC
-  ING(flag.reserve(ne ? ne : 1));
-  ING(at.reserve(ne + 1));
-  if (ne) hipLaunchKernelGGL(ing_flag_k, dim3(cdiv((long)ne, IT)), dim3(IT), 0, c->stream, ka, ne, flag.p);
-  ING(hipGetLastError());
-  ING((isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, flag.p, ne, at.p, scratch.p)));
-  int64_t m = 0;
-  ING(hipMemcpyAsync(&m, at.p + ne, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  ING(hipStreamSynchronize(c->stream));
-  ING(c->a_cnt.reserve(m ? m : 1));
-  ING(c->a_rows.reserve(m ? m : 1));
-  ING(c->a_offs.reserve(D + 1));
-  ING(docs.reserve(m ? m : 1));
-  if (ne) hipLaunchKernelGGL(ing_compact_k, dim3(cdiv((long)ne, IT)), dim3(IT), 0, c->stream, ka, va, flag.p, at.p, ne, wbits, c->a_rows.p, c->a_cnt.p, docs.p);
-  hipLaunchKernelGGL(ing_offsets_k, dim3(cdiv((long)m + 1, IT)), dim3(IT), 0, c->stream, docs.p, (uint64_t)m, D, c->a_offs.p);
-  ING(hipGetLastError());
-  ING(hipStreamSynchronize(c->stream));
-  c->a_V = V;
-  c->a_D = D;
-  c->a_nnz = (uint64_t)m;
+  // ---- sort by (doc, word), drop repeated pairs, build the CSC: keys in key1/cnt1, ping-pong with key0/cnt0
+  const int rc = ing_sort_dedup_install(c, V, D, wbits, dbits, key1.p, cnt1.p, key0.p, cnt0.p, ne);
   cleanup();
 #undef ING
+  return rc;
+}
+
+// ---------------- binary (doc, word, count) triples in batches (isle_hip_feed_*) --------------------------------------------------------
+namespace {
+
+// kinds: 1 document out of range, 2 word out of range.  *err as in ing_parse_k: the smallest (ordinal << 3) | kind, the ordinal counted
+// over every entry offered since the feed was opened.  An entry with count 0 is in range or an error like any other, and is then skipped.
+__global__ __launch_bounds__(IT) void feed_key_k(const uint32_t* __restrict__ docs, const uint32_t* __restrict__ words, const uint32_t* __restrict__ counts,
+                                                  uint64_t n, uint64_t ordinal0, uint64_t V, uint64_t D, int wbits, uint64_t* __restrict__ key,
+                                                  uint32_t* __restrict__ cnt, uint32_t* __restrict__ valid, unsigned long long* __restrict__ err) {
+  const uint64_t i = (uint64_t)blockIdx.x * IT + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t d = docs[i], w = words[i], x = counts[i];
+  const int bad = d >= D ? 1 : (w >= V ? 2 : 0);
+  key[i] = ((uint64_t)d << wbits) | (uint64_t)w;
+  cnt[i] = x;
+  valid[i] = (!bad && x != 0u) ? 1u : 0u;
+  if (bad) atomicMin(err, ((unsigned long long)(ordinal0 + i) << 3) | (unsigned long long)bad);
+}
+
+// a buffer of at least `want` elements whose first `keep` elements are those it held
+template <class T>
+hipError_t grow_keeping(hipStream_t st, DevBuf<T>& b, size_t keep, size_t want) {
+  if (want <= b.cap) return hipSuccess;
+  T* q = nullptr;
+  hipError_t e = hipMalloc((void**)&q, want * sizeof(T));
+  if (e != hipSuccess) return e;
+  if (keep) e = hipMemcpyAsync(q, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    (void)hipFree(q);
+    return e;
+  }
+  if (b.p) (void)hipFree(b.p);
+  b.p = q;
+  b.cap = want;
+  return hipSuccess;
+}
+
+}  // namespace
+
+void IsleFeed::release() {
+  open = false;
+  n = offered = 0;
+  key.release(); cnt.release(); in_docs.release(); in_words.release(); in_cnt.release(); t_key.release(); t_cnt.release(); t_valid.release();
+  t_at.release(); t_scratch.release(); t_err.release();
+}
+
+// n <= ISLE_FEED_CHUNK entries from host memory behind what the feed holds.  *bad: ~0, or (ordinal << 3) | kind of the first entry out of
+// range, in which case nothing was appended.
+int k_feed_chunk(isle_ctx* c, const uint32_t* docs, const uint32_t* words, const uint32_t* counts, uint64_t n, uint64_t* bad) {
+  IsleFeed& f = c->feed;
+  *bad = ~0ull;
+  if (n == 0) return 0;
+  int wbits, dbits;
+  ing_key_bits(f.V, f.D, &wbits, &dbits);
+  HIPCHK(c, f.in_docs.reserve(n));
+  HIPCHK(c, f.in_words.reserve(n));
+  HIPCHK(c, f.in_cnt.reserve(n));
+  HIPCHK(c, f.t_key.reserve(n));
+  HIPCHK(c, f.t_cnt.reserve(n));
+  HIPCHK(c, f.t_valid.reserve(n));
+  HIPCHK(c, f.t_at.reserve(n + 1));
+  HIPCHK(c, f.t_scratch.reserve(isle_scan_scratch(n) + 8));
+  HIPCHK(c, f.t_err.reserve(1));
+  HIPCHK(c, hipMemcpyAsync(f.in_docs.p, docs, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(f.in_words.p, words, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(f.in_cnt.p, counts, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  int64_t nvalid = 0;
+  {
+    TimeScope ts(c, ISLE_T_INGEST);
+    HIPCHK(c, hipMemsetAsync(f.t_err.p, 0xff, sizeof(uint64_t), c->stream));
+    hipLaunchKernelGGL(feed_key_k, dim3(cdiv((long)n, IT)), dim3(IT), 0, c->stream, f.in_docs.p, f.in_words.p, f.in_cnt.p, n, f.offered, f.V, f.D, wbits,
+                       f.t_key.p, f.t_cnt.p, f.t_valid.p, (unsigned long long*)f.t_err.p);
+    LAUNCH_CHECK(c);
+    HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, f.t_valid.p, n, f.t_at.p, f.t_scratch.p)));
+  }
+  HIPCHK(c, hipMemcpyAsync(&nvalid, f.t_at.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(bad, f.t_err.p, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // (the host arrays are the caller's again from here)
+  if (*bad != ~0ull) return 0;
+  const uint64_t need = f.n + (uint64_t)nvalid;
+  if (need > f.key.cap) {
+    const size_t want = (size_t)std::max<uint64_t>(need, 2 * (uint64_t)f.key.cap);
+    HIPCHK(c, grow_keeping(c->stream, f.key, f.n, want));
+    HIPCHK(c, grow_keeping(c->stream, f.cnt, f.n, want));
+  }
+  if (nvalid) {
+    TimeScope ts(c, ISLE_T_INGEST);
+    hipLaunchKernelGGL(ing_pack_k, dim3(cdiv((long)n, IT)), dim3(IT), 0, c->stream, f.t_key.p, f.t_cnt.p, f.t_valid.p, f.t_at.p, n, f.key.p + f.n, f.cnt.p + f.n);
+    LAUNCH_CHECK(c);
+  }
+  f.n = need;
+  f.offered += n;
   return 0;
+}
+
+// the entries held -> the context's count matrix (a_cnt / a_rows / a_offs, a_V, a_D, a_nnz)
+int k_feed_finalize(isle_ctx* c) {
+  IsleFeed& f = c->feed;
+  TimeScope ts(c, ISLE_T_INGEST);
+  int wbits, dbits;
+  ing_key_bits(f.V, f.D, &wbits, &dbits);
+  f.in_docs.release(); f.in_words.release(); f.in_cnt.release(); f.t_valid.release(); f.t_at.release(); f.t_scratch.release();
+  HIPCHK(c, f.key.reserve(1));  // (a feed without entries: the kernels below still take pointers)
+  HIPCHK(c, f.cnt.reserve(1));
+  HIPCHK(c, f.t_key.reserve(f.n ? f.n : 1));
+  HIPCHK(c, f.t_cnt.reserve(f.n ? f.n : 1));
+  return ing_sort_dedup_install(c, f.V, f.D, wbits, dbits, f.key.p, f.cnt.p, f.t_key.p, f.t_cnt.p, f.n);
 }

@@ -133,6 +133,37 @@ class FPSparseMatrixHip {
     return B;
   }
 
+  // The same from (doc, word, count) triples in any order, fed in batches (ISLETrainer::feed_data / finalize_data, src/trainer.cpp:214-371):
+  // begin_feed makes the object and opens the feed (isle_hip_feed_begin), feed appends a batch (0-based columns and word ids; zero counts are
+  // skipped, an id out of range throws and leaves the feed as it was), from_feed sorts, keeps the first fed of equal (doc, word) pairs, builds
+  // A and thresholds it, with from_counts' outputs; on failure it deletes the object like from_counts.
+  static FPSparseMatrixHip* begin_feed(word_id_t vocab_size, doc_id_t num_docs, uint64_t reserve_entries, int device = 0) {
+    FPSparseMatrixHip* B = new FPSparseMatrixHip(vocab_size, 0, device);
+    try {
+      B->check(isle_hip_feed_begin(B->ctx_, vocab_size, num_docs, reserve_entries), "feed_begin");
+      B->a_docs_ = num_docs;
+    } catch (...) {
+      delete B;
+      throw;
+    }
+    return B;
+  }
+  void feed(uint64_t n, const uint32_t* docs, const uint32_t* words, const uint32_t* counts) {
+    check(isle_hip_feed_entries(ctx_, n, docs, words, counts), "feed_entries");
+  }
+  static FPSparseMatrixHip* from_feed(FPSparseMatrixHip* B, doc_id_t num_topics, double sample_rate, std::vector<doc_id_t>& original_cols,
+                                      std::vector<FPTYPE>* zetas = nullptr, uint64_t* entries_above_threshold = nullptr, float* avg_doc_sz = nullptr,
+                                      uint64_t* entries_fed = nullptr, uint64_t* entries_in_A = nullptr) {
+    try {
+      B->check(isle_hip_feed_finalize(B->ctx_, 0, 0, entries_fed, entries_in_A), "feed_finalize");
+      B->threshold_on_device(num_topics, sample_rate, original_cols, zetas, entries_above_threshold, avg_doc_sz);
+    } catch (...) {
+      delete B;
+      throw;
+    }
+    return B;
+  }
+
   // The same with the ingest on the device as well: `text` holds the bytes of the tdf file
   // (DocWordEntriesReader::fill_doc_word_entries include/utils.h:158-228, the sort / de-duplication of
   // ISLETrainer::finalize_data src/trainer.cpp:236-247 and SparseMatrix::populate_CSC src/sparseMatrix.cpp:58-87).

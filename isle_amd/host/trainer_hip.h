@@ -215,6 +215,31 @@ void write_doc_topic_lines(FILE* fp, const int64_t* offs, const TopicT* topic, c
   }
   std::fwrite(pending.data(), 1, pending.size(), fp);
 }
+// The rule of ITERATIVE_DATA_LOAD on the host (src/trainer.cpp:232-371): the fed entries (zero counts already left out) sorted stably by
+// (doc, word), the first fed of equal pairs kept, the CSC of A with its empty documents.  The trainer's data goes through the device feed
+// (FPSparseMatrixHip::feed / from_feed -> isle_hip_feed_*), which is held to this statement by isle_amd/host/feed_main.cpp.
+inline void csc_from_fed(doc_id_t num_docs, const std::vector<uint32_t>& fed_doc, const std::vector<uint32_t>& fed_word,
+                         const std::vector<uint32_t>& fed_count, std::vector<float>& counts, std::vector<uint32_t>& rows, std::vector<offset_t>& offsets) {
+  const size_t n = fed_doc.size();
+  std::vector<size_t> order(n);
+  std::iota(order.begin(), order.end(), (size_t)0);
+  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+    return fed_doc[a] < fed_doc[b] || (fed_doc[a] == fed_doc[b] && fed_word[a] < fed_word[b]);
+  });
+  counts.clear();
+  rows.clear();
+  offsets.assign((size_t)num_docs + 1, 0);
+  counts.reserve(n);
+  rows.reserve(n);
+  for (size_t i = 0; i < n; ++i) {
+    const size_t e = order[i];
+    if (i && fed_doc[e] == fed_doc[order[i - 1]] && fed_word[e] == fed_word[order[i - 1]]) continue;  // duplicate (doc, word): the first stays
+    counts.push_back((float)fed_count[e]);
+    rows.push_back(fed_word[e]);
+    offsets[fed_doc[e] + 1]++;
+  }
+  for (doc_id_t d = 0; d < num_docs; ++d) offsets[d + 1] += offsets[d];
+}
 }  // namespace trainer_detail
 
 class ISLETrainer {
@@ -239,10 +264,36 @@ class ISLETrainer {
   std::unique_ptr<trainer_detail::Logs> log;
 
   bool is_data_loaded = false, is_training_complete = false;
-  // ITERATIVE_DATA_LOAD: the (doc, word, count) triples fed so far (src/trainer.cpp:200-230 keeps DocWordEntry records)
-  std::vector<uint64_t> fed_doc;
-  std::vector<uint32_t> fed_word;
-  std::vector<float> fed_count;
+  // ITERATIVE_DATA_LOAD: the (doc, word, count) triples not yet on the device (src/trainer.cpp:200-230 keeps every DocWordEntry on the
+  // host); at most kFeedStage of them, whatever the corpus: a full buffer goes to the device feed (flush_fed)
+  enum : size_t { kFeedStage = size_t(4) << 20 };  // entries
+  std::vector<uint32_t> fed_doc, fed_word, fed_count;
+  bool feed_failed = false;  // the device feed was lost with batches in it: no later call may start a fresh one from the remainder
+  void flush_fed() {
+    if (feed_failed) throw std::runtime_error("the device feed failed earlier: the data fed so far is lost, build a new trainer");
+    if (!B_fl_CSC) {
+      B_fl_CSC = FPSparseMatrixHip::begin_feed(vocab_size, num_docs, (uint64_t)std::max<offset_t>(max_entries, 0));
+      const size_t stage = std::min<size_t>(kFeedStage, max_entries > 0 ? (size_t)max_entries : kFeedStage);
+      fed_doc.reserve(stage);
+      fed_word.reserve(stage);
+      fed_count.reserve(stage);
+    }
+    if (fed_doc.empty()) return;
+    try {
+      B_fl_CSC->feed(fed_doc.size(), fed_doc.data(), fed_word.data(), fed_count.data());
+    } catch (...) {  // (ids were checked as they came in: this is the device failing)
+      delete B_fl_CSC;
+      B_fl_CSC = nullptr;
+      feed_failed = true;
+      std::vector<uint32_t>().swap(fed_doc);
+      std::vector<uint32_t>().swap(fed_word);
+      std::vector<uint32_t>().swap(fed_count);
+      throw;
+    }
+    fed_doc.clear();
+    fed_word.clear();
+    fed_count.clear();
+  }
 
   FPSparseMatrixHip* B_fl_CSC = nullptr;  // owns the device context: A (counts), B and everything derived from them live there
   std::vector<doc_id_t> original_cols;
@@ -365,44 +416,33 @@ class ISLETrainer {
   inline void feed_data(const doc_id_t doc, const word_id_t* const words, const count_t* const counts, const offset_t num_words) {
     if (how_data_loaded != ITERATIVE_DATA_LOAD) throw std::runtime_error("feed_data needs ITERATIVE_DATA_LOAD");
     if (is_data_loaded) throw std::runtime_error("feed_data after finalize_data");
+    if (!B_fl_CSC || feed_failed) flush_fed();  // the first call opens the device feed, with room for max_entries; after a lost feed: throws
     for (offset_t i = 0; i < num_words; ++i) {
       if (doc >= num_docs || words[i] < 1 || words[i] > vocab_size) throw std::runtime_error("feed_data: id out of range (documents 0-based, words 1-based)");
       if (counts[i] == 0) continue;
-      fed_doc.push_back(doc);
+      fed_doc.push_back((uint32_t)doc);
       fed_word.push_back((uint32_t)(words[i] - 1));
-      fed_count.push_back((float)counts[i]);
+      fed_count.push_back((uint32_t)counts[i]);
+      if (fed_doc.size() >= kFeedStage) flush_fed();
     }
   }
-  // src/trainer.cpp:232-371: sort by (doc, word), keep the first of equal pairs, CSC of A — then A goes to the device, where B is built
+  // src/trainer.cpp:232-371: sort by (doc, word), keep the first of equal pairs, CSC of A — on the device, from the batches fed so far
+  // (trainer_detail::csc_from_fed states the rule); then B is built there
   void finalize_data() {
     if (how_data_loaded != ITERATIVE_DATA_LOAD) throw std::runtime_error("finalize_data needs ITERATIVE_DATA_LOAD");
+    if (is_data_loaded) throw std::runtime_error("finalize_data called twice");
     print_header();
     log->next_time_secs("Reading file Entries");
-    const size_t n = fed_doc.size();
-    std::vector<size_t> order(n);
-    std::iota(order.begin(), order.end(), (size_t)0);
-    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
-      return fed_doc[a] < fed_doc[b] || (fed_doc[a] == fed_doc[b] && fed_word[a] < fed_word[b]);
-    });
-    std::vector<float> counts;
-    std::vector<uint32_t> rows;
-    std::vector<offset_t> offsets((size_t)num_docs + 1, 0);
-    counts.reserve(n);
-    rows.reserve(n);
-    for (size_t i = 0; i < n; ++i) {
-      const size_t e = order[i];
-      if (i && fed_doc[e] == fed_doc[order[i - 1]] && fed_word[e] == fed_word[order[i - 1]]) continue;  // duplicate (doc, word): the first stays
-      counts.push_back(fed_count[e]);
-      rows.push_back(fed_word[e]);
-      offsets[fed_doc[e] + 1]++;
-    }
-    for (doc_id_t d = 0; d < num_docs; ++d) offsets[d + 1] += offsets[d];
-    entries_in_A = counts.size();
-    std::vector<uint64_t>().swap(fed_doc);
+    flush_fed();
+    std::vector<uint32_t>().swap(fed_doc);
     std::vector<uint32_t>().swap(fed_word);
-    std::vector<float>().swap(fed_count);
-    B_fl_CSC = FPSparseMatrixHip::from_counts(vocab_size, num_docs, counts.data(), rows.data(), offsets.data(), num_topics,
-                                              flag_sample_docs ? (double)sample_rate : 0.0, original_cols, nullptr, &entries_above_threshold, &avg_doc_sz);
+    std::vector<uint32_t>().swap(fed_count);
+    FPSparseMatrixHip* fed = B_fl_CSC;
+    B_fl_CSC = nullptr;  // from_feed deletes it when it throws
+    feed_failed = true;  // ... and the fed data is gone with it
+    B_fl_CSC = FPSparseMatrixHip::from_feed(fed, num_topics, flag_sample_docs ? (double)sample_rate : 0.0, original_cols, nullptr,
+                                            &entries_above_threshold, &avg_doc_sz, nullptr, &entries_in_A);
+    feed_failed = false;
     after_matrices_built();
   }
 

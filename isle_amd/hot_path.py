@@ -130,6 +130,24 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _as_u32(a, name):
+    """A flat contiguous uint32 array holding exactly the values of `a`, or ValueError: nothing is wrapped or truncated."""
+    a = np.asarray(a)
+    if a.ndim != 1:
+        a = a.reshape(-1)
+    if a.dtype == np.uint32:
+        return np.ascontiguousarray(a)
+    if a.size == 0:
+        return np.empty(0, np.uint32)
+    if a.dtype.kind not in "iubf":
+        raise ValueError("%s: not an array of numbers" % name)
+    if a.dtype.kind == "f" and not np.all(a == np.floor(a)):   # (NaN and infinities fail here or below)
+        raise ValueError("%s holds a value that is not a whole number" % name)
+    if a.min() < 0 or a.max() > 0xFFFFFFFF:
+        raise ValueError("%s holds a value outside 0 .. 4294967295" % name)
+    return np.ascontiguousarray(a.astype(np.uint32))
+
+
 class HotPath:
     def __init__(self, device=0):
         self._lib = load_library()
@@ -254,6 +272,45 @@ class HotPath:
         self._a_shape = (int(vocab_size), int(num_docs), int(nz.value))
         return dict(entries_read=int(nr.value), nnz=int(nz.value))
 
+    # ---- (doc, word, count) triples in batches -> A (isle_hip_feed_*) -----------------------
+    def feed_begin(self, vocab_size, num_docs, reserve_entries=0):
+        """Opens a feed for a vocab_size x num_docs count matrix (an open one is discarded; the current A stays until feed_finalize)."""
+        self._chk(self._lib.isle_hip_feed_begin(self._h, int(vocab_size), int(num_docs), int(reserve_entries)))
+        self._feed_shape = (int(vocab_size), int(num_docs))
+
+    def feed(self, docs, words, counts, _piece_entries=0):
+        """One batch of entries in any order: 0-based local columns, 0-based word ids, counts (anything np.asarray accepts).  Zero counts
+        are skipped; a value that is negative, not whole or above 2^32 - 1 raises ValueError (nothing is wrapped).  _piece_entries (tests): the
+        size of the pieces the library cuts the batch into, 0 = its own (isle_hip_feed_entries_pieces)."""
+        arrs = [_as_u32(a, name) for a, name in ((docs, "docs"), (words, "words"), (counts, "counts"))]
+        if not (arrs[0].shape == arrs[1].shape == arrs[2].shape):
+            raise ValueError("docs, words and counts differ in length")
+        n = int(arrs[0].size)
+        self._chk(self._lib.isle_hip_feed_entries_pieces(self._h, n, *(_p(a) if n else None for a in arrs), int(_piece_entries)))
+
+    def feed_finalize(self, doc_offset=0, docs_global=0):
+        """Sorts by (doc, word), keeps the first fed of equal pairs, builds the offsets: the result is the context's count matrix as after
+        upload_counts with the same doc_offset / docs_global.  -> (entries_fed, nnz)."""
+        fed, nz = C.c_uint64(), C.c_uint64()
+        self._chk(self._lib.isle_hip_feed_finalize(self._h, int(doc_offset), int(docs_global), C.byref(fed), C.byref(nz)))
+        self._a_shape = self._feed_shape + (int(nz.value),)
+        return int(fed.value), int(nz.value)
+
+    def upload_coo(self, V, D, docs, words, counts, batch=None):
+        """feed_begin + feed + feed_finalize for triples held in arrays, fed in slices of `batch` entries (None: one call).
+        -> (entries_fed, nnz)."""
+        docs, words, counts = (_as_u32(a, name) for a, name in ((docs, "docs"), (words, "words"), (counts, "counts")))
+        if not (docs.shape == words.shape == counts.shape):
+            raise ValueError("docs, words and counts differ in length")
+        n = int(docs.size)
+        step = n if batch is None else int(batch)
+        if batch is not None and step < 1:
+            raise ValueError("batch must be positive")
+        self.feed_begin(V, D, reserve_entries=n)
+        for at in range(0, n, max(step, 1)):
+            self.feed(docs[at:at + step], words[at:at + step], counts[at:at + step])
+        return self.feed_finalize()
+
     def get_A(self):
         V, D, nnz = self._a_shape
         cnt, rows, offs = np.empty(nnz, np.float32), np.empty(nnz, np.uint32), np.empty(D + 1, np.int64)
@@ -273,6 +330,12 @@ class HotPath:
         self.doc_offset, self.D_global = int(off.value), int(glob.value)
         return dict(docs_kept=int(dk.value), nnz_kept=int(nk.value), entries_above_threshold=int(ab.value),
                     avg_doc_sz=float(avg.value))
+
+    def shape(self):
+        """(V, D, nnz, doc_offset, docs_global) of the context's B (isle_hip_shape)."""
+        v = [C.c_uint64() for _ in range(5)]
+        self._chk(self._lib.isle_hip_shape(self._h, *(C.byref(x) for x in v)))
+        return tuple(int(x.value) for x in v)
 
     def get_B(self, with_threshold_outputs=True):
         """Host copy of the context's B: dict(V, D, nnz, vals, rows, offs[, original_cols, zetas])."""
