@@ -289,6 +289,21 @@ int isle_hip_get_doc_topic_sums(isle_ctx* ctx, int64_t* doc_offsets, uint32_t* t
  * (1 - primary_ratio) * Model[:, pairs[2e+1]]; edge is vocab x n column-major. */
 int isle_hip_edge_topics(isle_ctx* ctx, const int64_t* pairs, int n, float primary_ratio, float* edge);
 
+/* construct_edge_topics_v2's selection (src/trainer.cpp:1120-1145), on the device: documents with top1 >= 0 and top2 >= 0 are counted per
+ * ordered pair (top1, top2); pairs with >= max(min_docs, 1) documents are candidates; they are ordered by count descending, ties by
+ * (primary, secondary) ascending (the reference's sort is unstable there); the first max_edge_topics are kept.
+ * top1 / top2 NULL: the resident pairs of the last isle_hip_topic_model (n_docs, num_topics must be its own); else n_docs host entries
+ * each, uploaded for the call.  pairs: room for cap triples (primary, secondary, documents); selected > cap is ISLE_E_ARG with
+ * *n_selected set.  n_selected / n_candidates / threshold are nullable; *threshold = the count of the first candidate cut off.
+ * The pairs are counted in a table of num_topics^2 32-bit counters (integer atomics: the result does not depend on arrival order).
+ * ISLE_E_ARG: world > 1, num_topics < 1 or > 8192 (the table's limit), max_edge_topics < 0, exactly one of top1 / top2 null, n_docs
+ * >= 2^32, a resident call before isle_hip_topic_model or with another size, a topic id >= num_topics or < -1 (the message names the
+ * first such document; such an id is never used as an index). */
+#define ISLE_EDGE_TABLE_MAX_TOPICS 8192 /* 256 MB of counters */
+int isle_hip_select_edge_pairs(isle_ctx* ctx, const int32_t* top1, const int32_t* top2, uint64_t n_docs, int num_topics,
+                               int64_t max_edge_topics, uint64_t min_docs, int64_t* pairs, uint64_t cap, uint64_t* n_selected,
+                               uint64_t* n_candidates, uint64_t* threshold /* 0: nothing cut */);
+
 /* UMass topic coherence, SparseMatrix::topic_coherence with compute_doc_frequency / compute_joint_doc_frequency
  * (src/sparseMatrix.cpp:841-1016), on the resident count matrix A (no partition or model needed; single rank).
  * top_words: num_topics x M row-major, M distinct word ids per topic, heaviest first (1 <= M <= 32).  With
@@ -331,6 +346,14 @@ int isle_hip_avg_topic_model(isle_ctx* ctx, int num_topics, float* model);
  * ISLE_E_ARG: world > 1, n < 1 or n > min(vocab, 32), an unknown model, a resident model that does not exist (yet), a size mismatch,
  * ids or (HOST) model_host null. */
 int isle_hip_model_top_words(isle_ctx* ctx, int which, const float* model_host, uint64_t vocab, int ncols, int n, uint32_t* ids, float* weights);
+
+/* The n heaviest words of the edge topics primary_ratio * M[:, pairs[2e]] + (1 - primary_ratio) * M[:, pairs[2e + 1]], e < n_edge, of
+ * model `which` (CATCH, AVG, LOADED, HOST as in isle_hip_model_top_words, with its conditions on model_host / vocab / ncols): order
+ * and NaN rule of isle_hip_model_top_words, entries formed as isle_hip_edge_topics forms them (bit-equal), from the model's two columns
+ * while they are read: no vocab x n_edge matrix is stored.  ids: n_edge x n row-major; weights (nullable): the entries at those ids.
+ * ISLE_E_ARG also for: n_edge < 0, pairs or ids null with n_edge > 0, a pair id outside 0 .. ncols - 1. */
+int isle_hip_edge_top_words(isle_ctx* ctx, int which, const float* model_host, uint64_t vocab, int ncols, const int64_t* pairs, int n_edge,
+                            float primary_ratio, int n, uint32_t* ids, float* weights);
 
 /* Topic diversity (ISLETrainer::output_topic_diversity, src/trainer.cpp:750-774) of a resident model (CATCH, AVG or LOADED), in double
  * with a fixed reduction order.  A topic is finite when every entry of its vector is; k' = the number of finite topics.

@@ -32,6 +32,8 @@ SYMBOLS = {
     "isle_hip_topic_model": (_I, [_P, _I, _U64, _P, _P, _P, _P, _P]),
     "isle_hip_get_doc_topic_sums": (_I, [_P, _P, _P, _P]),
     "isle_hip_edge_topics": (_I, [_P, _P, _I, _F, _P]),
+    "isle_hip_select_edge_pairs": (_I, [_P, _P, _P, _U64, _I, C.c_int64, _U64, _P, _U64, _P, _P, _P]),
+    "isle_hip_edge_top_words": (_I, [_P, _I, _P, _U64, _I, _P, _I, _F, _I, _P, _P]),
     "isle_hip_topic_coherence": (_I, [_P, _I, _I, _P, C.c_double, _P, _P, _P]),
     "isle_hip_avg_topic_model": (_I, [_P, _I, _P]),
     "isle_hip_model_top_words": (_I, [_P, _I, _P, _U64, _I, _I, _P, _P]),

@@ -473,6 +473,59 @@ extern "C" int isle_hip_edge_topics(isle_ctx* c, const int64_t* pairs, int n, fl
   return 0;
 }
 
+// construct_edge_topics_v2's pair selection (src/trainer.cpp:1120-1145) on the device (edge_select.hip), over the resident top-two topics
+// of the last topic model or over the caller's arrays
+extern "C" int isle_hip_select_edge_pairs(isle_ctx* c, const int32_t* top1, const int32_t* top2, uint64_t n_docs, int num_topics,
+                                          int64_t max_edge_topics, uint64_t min_docs, int64_t* pairs, uint64_t cap, uint64_t* n_selected,
+                                          uint64_t* n_candidates, uint64_t* threshold) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  if (n_selected) *n_selected = 0;
+  if (n_candidates) *n_candidates = 0;
+  if (threshold) *threshold = 0;
+  if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: single-rank only");
+  if (num_topics < 1) return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: num_topics < 1");
+  if (num_topics > ISLE_EDGE_TABLE_MAX_TOPICS)
+    return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: num_topics = %d, the pairs are counted in a table of num_topics^2 counters and %d is its limit",
+                     num_topics, ISLE_EDGE_TABLE_MAX_TOPICS);
+  if (max_edge_topics < 0) return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: max_edge_topics < 0");
+  if ((top1 == nullptr) != (top2 == nullptr)) return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: one of top1 / top2 is null (both, or neither for the resident pairs)");
+  if (n_docs > 0xffffffffull) return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: %llu documents (the counters hold 32 bits)", (unsigned long long)n_docs);
+  if (cap && !pairs) return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: null pairs");
+  const bool resident = top1 == nullptr;
+  const int32_t *t1 = nullptr, *t2 = nullptr;
+  DevBuf<int32_t> u1, u2;
+  if (resident) {
+    if (!c->p_model_ready) return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: no resident top topics (run isle_hip_topic_model, or pass top1 / top2)");
+    if (n_docs != c->a_D || num_topics != c->p_k)
+      return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: n_docs x num_topics = %llu x %d, the resident topic model has %llu x %d", (unsigned long long)n_docs,
+                       num_topics, (unsigned long long)c->a_D, c->p_k);
+    t1 = c->p_top1.p;
+    t2 = c->p_top2.p;
+  } else {
+    HIPCHK(c, u1.reserve(n_docs ? n_docs : 1));
+    HIPCHK(c, u2.reserve(n_docs ? n_docs : 1));
+    if (n_docs) {
+      HIPCHK(c, hipMemcpyAsync(u1.p, top1, n_docs * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(u2.p, top2, n_docs * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    t1 = u1.p;
+    t2 = u2.p;
+  }
+  uint64_t nsel = 0, ncand = 0, thr = 0, bad = ~0ull;
+  const int rc = k_edge_select(c, t1, t2, n_docs, (uint32_t)num_topics, (uint64_t)max_edge_topics, min_docs, pairs, cap, &nsel, &ncand, &thr, &bad);
+  (void)hipStreamSynchronize(c->stream);  // `u1` and `u2` are freed on return
+  ISLECHK(rc);
+  if (bad != ~0ull)
+    return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: document %llu: a topic id outside -1 .. %d", (unsigned long long)bad, num_topics - 1);
+  if (n_selected) *n_selected = nsel;
+  if (n_candidates) *n_candidates = ncand;
+  if (nsel > cap)
+    return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: %llu pairs selected, room for %llu", (unsigned long long)nsel, (unsigned long long)cap);
+  if (threshold) *threshold = thr;
+  return 0;
+}
+
 // UMass coherence (src/sparseMatrix.cpp:841-1016): the distinct words and word pairs are prepared here, their document frequencies are
 // counted on the device in one pass over A per counter tile (coherence.hip), the sums are formed here in double.
 extern "C" int isle_hip_topic_coherence(isle_ctx* c, int num_topics, int M, const uint32_t* top_words, double eps, double* coherence,
@@ -617,6 +670,45 @@ extern "C" int isle_hip_model_top_words(isle_ctx* c, int which, const float* mod
   HIPCHK(c, hipMemcpyAsync(ids, id_d.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   if (weights) HIPCHK(c, hipMemcpyAsync(weights, w_d.p, m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ... of the edge topics a * M[:, p] + b * M[:, s] of a model, formed from its two columns while they are read (tw_select_k's edge source)
+extern "C" int isle_hip_edge_top_words(isle_ctx* c, int which, const float* model_host, uint64_t vocab, int ncols, const int64_t* pairs, int n_edge,
+                                       float primary_ratio, int n, uint32_t* ids, float* weights) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "edge_top_words: single-rank only");
+  if (ncols < 0 || vocab == 0 || vocab > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "edge_top_words: vocab or ncols out of range");
+  if (n < 1 || n > 32 || (uint64_t)n > vocab) return isle_fail(c, ISLE_E_ARG, "edge_top_words: n = %d outside 1 .. min(vocab, 32)", n);
+  if (n_edge < 0 || (n_edge && (!pairs || !ids))) return isle_fail(c, ISLE_E_ARG, "edge_top_words: bad arguments");
+  for (int e = 0; e < 2 * n_edge; ++e)
+    if (pairs[e] < 0 || pairs[e] >= ncols)
+      return isle_fail(c, ISLE_E_ARG, "edge_top_words: edge topic %d: topic id %lld outside 0 .. %d", e / 2, (long long)pairs[e], ncols - 1);
+  const float* dev = nullptr;
+  DevBuf<float> up;
+  ISLECHK(model_source(c, which, model_host, vocab, ncols, "edge_top_words", &up, &dev));
+  if (n_edge == 0) {
+    (void)hipStreamSynchronize(c->stream);  // `up` is freed on return
+    return 0;
+  }
+  const size_t m = (size_t)n_edge * n;
+  DevBuf<int64_t> pd;
+  DevBuf<uint32_t> id_d;
+  DevBuf<float> w_d;
+  int rc = 0;
+  hipError_t he = pd.reserve(2 * (size_t)n_edge);
+  if (he == hipSuccess) he = id_d.reserve(m);
+  if (he == hipSuccess) he = w_d.reserve(m);
+  if (he == hipSuccess) he = hipMemcpyAsync(pd.p, pairs, 2 * (size_t)n_edge * sizeof(int64_t), hipMemcpyHostToDevice, c->stream);
+  if (he == hipSuccess)
+    rc = k_edge_top_words(c, dev, vocab, pd.p, (uint32_t)n_edge, primary_ratio, (float)(1.0 - (double)primary_ratio), n, id_d.p, w_d.p);
+  if (he == hipSuccess && rc == 0) he = hipMemcpyAsync(ids, id_d.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+  if (he == hipSuccess && rc == 0 && weights) he = hipMemcpyAsync(weights, w_d.p, m * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+  const hipError_t hs = hipStreamSynchronize(c->stream);  // the local buffers are freed on return
+  ISLECHK(rc);
+  HIPCHK(c, he);
+  HIPCHK(c, hs);
   return 0;
 }
 

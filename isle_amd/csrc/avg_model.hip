@@ -9,7 +9,8 @@
 //   am_finalize_k   s = hi * 2^32 + lo in double, the column's L1 norm by a fixed-shape reduction, model = (float)(s / norm);
 //                   an empty cluster gives 0 / 0 = NaN
 //   tw_select_k     n heaviest words of a column: 4-pass radix select of the n-th largest key on the float bits, then the keys
-//                   above it and the first ties in id order, ranked (weight descending, id ascending, NaN last)
+//                   above it and the first ties in id order, ranked (weight descending, id ascending, NaN last).  The column is a
+//                   stored one (TwPlain) or an edge topic formed from the model's two columns as it is read (TwEdge)
 //   dv_*_k          diversity in double: finite columns, the mean topic over them (topics ascending), squared distances
 #include <cmath>
 #include <cstring>
@@ -91,15 +92,35 @@ __device__ inline uint32_t tw_key(float x) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// Where tw_select_k reads column blockIdx.x from.  TwPlain: a stored column of a V x ncols model.  TwEdge: the edge topic
+// a * model[:, p] + b * model[:, q] formed as it is read, entry for entry as post_edge_k and model_text.hip form it (the product rounded,
+// then one fused multiply-add), so that no V x n_edge matrix is stored.
+struct TwPlain {
+  const float* col;
+  __device__ TwPlain(const float* model, const int64_t*, float, float, uint64_t V) : col(model + (size_t)blockIdx.x * V) {}
+  __device__ inline float operator[](uint64_t w) const { return col[w]; }
+};
+struct TwEdge {
+  const float *mp, *mq;
+  float a, b;
+  __device__ TwEdge(const float* model, const int64_t* pairs, float a_, float b_, uint64_t V)
+      : mp(model + (size_t)pairs[2 * blockIdx.x] * V), mq(model + (size_t)pairs[2 * blockIdx.x + 1] * V), a(a_), b(b_) {}
+  __device__ inline float operator[](uint64_t w) const {
+    const float y = a * mp[w];  // FPaxpy into a zeroed column (src/trainer.cpp:1154-1156)
+    return fmaf(b, mq[w], y);   // second FPaxpy (:1157-1159)
+  }
+};
+
 // One workgroup per column; n <= 32 <= AT.
-__global__ __launch_bounds__(AT) void tw_select_k(const float* __restrict__ model, uint64_t V, int n, uint32_t* __restrict__ ids,
-                                                   float* __restrict__ weights) {
+template <class Src>
+__global__ __launch_bounds__(AT) void tw_select_k(const float* __restrict__ model, const int64_t* __restrict__ pairs, float ea, float eb, uint64_t V,
+                                                   int n, uint32_t* __restrict__ ids, float* __restrict__ weights) {
   __shared__ uint32_t hist[256];
   __shared__ uint32_t sh_digit, sh_remaining, n_gt;
   __shared__ uint32_t sel_id[32];
   __shared__ uint32_t tie_id[AW][32];
   __shared__ uint32_t tie_n[AW];
-  const float* col = model + (size_t)blockIdx.x * V;
+  const Src col(model, pairs, ea, eb, V);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   uint32_t prefix = 0, mask = 0, remaining = (uint32_t)n;
   for (int shift = 24; shift >= 0; shift -= 8) {
@@ -262,7 +283,17 @@ int k_avg_model(isle_ctx* c, uint32_t k) {
 int k_model_top_words(isle_ctx* c, const float* model_dev, uint64_t V, uint32_t ncols, int n, uint32_t* ids_dev, float* weights_dev) {
   TimeScope ts(c, ISLE_T_POST);
   if (ncols == 0) return 0;
-  hipLaunchKernelGGL(tw_select_k, dim3(ncols), dim3(AT), 0, c->stream, model_dev, V, n, ids_dev, weights_dev);
+  hipLaunchKernelGGL(tw_select_k<TwPlain>, dim3(ncols), dim3(AT), 0, c->stream, model_dev, (const int64_t*)nullptr, 0.f, 0.f, V, n, ids_dev,
+                     weights_dev);
+  LAUNCH_CHECK(c);
+  return 0;
+}
+
+int k_edge_top_words(isle_ctx* c, const float* model_dev, uint64_t V, const int64_t* pairs_dev, uint32_t n_edge, float a, float b, int n,
+                     uint32_t* ids_dev, float* weights_dev) {
+  TimeScope ts(c, ISLE_T_POST);
+  if (n_edge == 0) return 0;
+  hipLaunchKernelGGL(tw_select_k<TwEdge>, dim3(n_edge), dim3(AT), 0, c->stream, model_dev, pairs_dev, a, b, V, n, ids_dev, weights_dev);
   LAUNCH_CHECK(c);
   return 0;
 }

@@ -662,6 +662,16 @@ int k_avg_model(isle_ctx* c, uint32_t k);
 int k_model_top_words(isle_ctx* c, const float* model_dev, uint64_t V, uint32_t ncols, int n, uint32_t* ids_dev, float* weights_dev);
 int k_topic_diversity(isle_ctx* c, const float* model_dev, uint64_t V, uint32_t k, double* dist_dev, double* abar_dev, int32_t* finite_dev,
                       uint32_t* kprime);
+// ... and the n heaviest words of the edge topics a * model[:, pairs[2e]] + b * model[:, pairs[2e + 1]] (post_edge_k's arithmetic), formed
+// while they are read: no V x n_edge buffer
+int k_edge_top_words(isle_ctx* c, const float* model_dev, uint64_t V, const int64_t* pairs_dev, uint32_t n_edge, float a, float b, int n,
+                     uint32_t* ids_dev, float* weights_dev);
+
+// edge_select.hip: the pair selection of construct_edge_topics_v2 over D device-resident (top1, top2), k <= ISLE_EDGE_TABLE_MAX_TOPICS.
+// pairs_host: min(*n_selected, cap) triples (primary, secondary, documents); *threshold: the count of the first candidate cut off, 0 when
+// nothing is cut; *bad_doc: ~0, or the first document whose id is >= k or < -1 (nothing else is defined then)
+int k_edge_select(isle_ctx* c, const int32_t* top1_dev, const int32_t* top2_dev, uint64_t D, uint32_t k, uint64_t max_edge_topics, uint64_t min_docs,
+                  int64_t* pairs_host, uint64_t cap, uint64_t* n_selected, uint64_t* n_candidates, uint64_t* threshold, uint64_t* bad_doc);
 
 // corpus_stats.hip: the trainer's corpus diagnostics on A.  k_log_combinatorial: out (host, a_D floats), max_words (nullable);
 // k_top_five_runs (needs a_nv): the number of documents with >= 5 entries, the run lengths of their sorted top-five tuples, the

@@ -44,6 +44,39 @@ typedef uint32_t count_t;  // include/types.h:29
 #define ISLE_INFER_ITERS_DEFAULT 15  // :81
 #define ISLE_INFER_LF_DEFAULT 10.0f  // :82 (INFER_LF_DEAFULT there)
 
+namespace fpsparse_detail {
+
+// The pair selection of ISLETrainer::construct_edge_topics_v2 (src/trainer.cpp:1120-1145) on the host: THE RULE that
+// isle_hip_select_edge_pairs (isle_amd/csrc/edge_select.hip) and hot_path.select_edge_pairs restate, and the path taken for more than
+// ISLE_EDGE_TABLE_MAX_TOPICS topics.  Documents with top1 >= 0 and top2 >= 0 are counted per ordered pair; pairs with >= min_docs
+// documents are candidates; candidates are ordered by count descending, ties by (primary, secondary) ascending (the reference's sort
+// is unstable there); the first max_edge_topics are kept.  *threshold: the count of the first candidate cut off, 0 when nothing is cut.
+inline void select_edge_pairs_host(const int32_t* top1, const int32_t* top2, const uint64_t n_docs, const int64_t max_edge_topics, const uint64_t min_docs,
+                                   std::vector<std::tuple<int, int, uint64_t>>& selected_pairs, uint64_t* candidates, uint64_t* threshold) {
+  std::vector<std::pair<int, int>> pairs;
+  for (uint64_t d = 0; d < n_docs; ++d)
+    if (top1[d] >= 0 && top2[d] >= 0) pairs.push_back(std::make_pair((int)top1[d], (int)top2[d]));
+  std::sort(pairs.begin(), pairs.end());  // (primary, secondary) ascending
+  selected_pairs.clear();
+  for (size_t i = 0; i < pairs.size();) {
+    size_t j = i;
+    while (j < pairs.size() && pairs[j] == pairs[i]) ++j;
+    if ((uint64_t)(j - i) >= min_docs) selected_pairs.push_back(std::make_tuple(pairs[i].first, pairs[i].second, (uint64_t)(j - i)));
+    i = j;
+  }
+  if (candidates) *candidates = selected_pairs.size();
+  std::stable_sort(selected_pairs.begin(), selected_pairs.end(),
+                   [](const std::tuple<int, int, uint64_t>& l, const std::tuple<int, int, uint64_t>& r) { return std::get<2>(l) > std::get<2>(r); });
+  if (threshold) *threshold = 0;
+  const size_t keep = (size_t)std::max<int64_t>(max_edge_topics, 0);
+  if (selected_pairs.size() > keep) {
+    if (threshold) *threshold = std::get<2>(selected_pairs[keep]);
+    selected_pairs.resize(keep);
+  }
+}
+
+}  // namespace fpsparse_detail
+
 class FPSparseMatrixHip {
   word_id_t vocab_size_;
   doc_id_t num_docs_;
@@ -463,39 +496,61 @@ class FPSparseMatrixHip {
     check(isle_hip_top_five_count_rule(top5_runs_.data(), top5_runs_.size(), min_distinct, &num), "top_five_count_rule");
     return (size_t)num;
   }
-  // ISLETrainer::construct_edge_topics_v2 (src/trainer.cpp:1116-1167): pair selection on the host, the FPaxpy pair on the
-  // device.  Ties in the count ordering are broken by (primary, secondary) ascending (the reference's sort is unstable).
-  void construct_edge_topics(std::vector<std::tuple<int, int, doc_id_t>>& top_topic_pairs, const int max_edge_topics,
-                             std::vector<std::tuple<int, int, uint64_t>>& selected_pairs, std::vector<FPTYPE>& EdgeModel /*vocab x #edge*/) {
-    auto lt = [](const std::tuple<int, int, doc_id_t>& l, const std::tuple<int, int, doc_id_t>& r) {
-      return std::get<0>(l) < std::get<0>(r) || (std::get<0>(l) == std::get<0>(r) && std::get<1>(l) < std::get<1>(r));
-    };
-    std::sort(top_topic_pairs.begin(), top_topic_pairs.end(), lt);
-    selected_pairs.clear();
-    for (size_t i = 0; i < top_topic_pairs.size();) {
-      size_t j = i;
-      while (j < top_topic_pairs.size() && !lt(top_topic_pairs[i], top_topic_pairs[j])) ++j;
-      if ((int64_t)(j - i) >= ISLE_EDGE_TOPIC_MIN_DOCS)
-        selected_pairs.push_back(std::make_tuple(std::get<0>(top_topic_pairs[i]), std::get<1>(top_topic_pairs[i]), (uint64_t)(j - i)));
-      i = j;
+  // ISLETrainer::construct_edge_topics_v2's selection (src/trainer.cpp:1116-1148), on the device over the resident top-two topics of the
+  // last construct_topic_model (isle_hip_select_edge_pairs; nothing is fetched).  host_pairs non-null: the host rule on those pairs
+  // instead (fpsparse_detail::select_edge_pairs_host) — the path for more than ISLE_EDGE_TABLE_MAX_TOPICS topics.  Ties in the count
+  // ordering are broken by (primary, secondary) ascending (the reference's sort is unstable).  The edge model itself is not formed
+  // here: edge_model(), write_edge_model_text() and edge_top_words() form its entries from the resident model when they are asked.
+  void construct_edge_topics(const std::vector<std::tuple<int, int, doc_id_t>>* host_pairs, const int max_edge_topics,
+                             std::vector<std::tuple<int, int, uint64_t>>& selected_pairs) {
+    uint64_t candidates = 0, threshold = 0;
+    if (host_pairs) {
+      std::vector<int32_t> t1(host_pairs->size()), t2(host_pairs->size());
+      for (size_t i = 0; i < host_pairs->size(); ++i) {
+        t1[i] = (int32_t)std::get<0>((*host_pairs)[i]);
+        t2[i] = (int32_t)std::get<1>((*host_pairs)[i]);
+      }
+      fpsparse_detail::select_edge_pairs_host(t1.data(), t2.data(), t1.size(), max_edge_topics, ISLE_EDGE_TOPIC_MIN_DOCS, selected_pairs, &candidates,
+                                              &threshold);
+    } else {
+      const uint64_t k = post_topics_;
+      const uint64_t cap = std::min<uint64_t>(std::min<uint64_t>((uint64_t)std::max(max_edge_topics, 0), k * k), a_docs_);
+      std::vector<int64_t> triples(3 * cap + 1);
+      uint64_t n = 0;
+      check(isle_hip_select_edge_pairs(ctx_, nullptr, nullptr, a_docs_, (int)k, max_edge_topics, ISLE_EDGE_TOPIC_MIN_DOCS, triples.data(), cap, &n, &candidates,
+                                       &threshold),
+            "construct_edge_topics");
+      selected_pairs.clear();
+      for (uint64_t e = 0; e < n; ++e) selected_pairs.push_back(std::make_tuple((int)triples[3 * e], (int)triples[3 * e + 1], (uint64_t)triples[3 * e + 2]));
     }
-    std::cout << "#Candidates for edge topics: " << selected_pairs.size() << std::endl;
-    std::stable_sort(selected_pairs.begin(), selected_pairs.end(),
-                     [](const std::tuple<int, int, uint64_t>& l, const std::tuple<int, int, uint64_t>& r) { return std::get<2>(l) > std::get<2>(r); });
-    if ((int64_t)selected_pairs.size() > (int64_t)max_edge_topics) {
-      std::cout << "Edge topic threshold: " << std::get<2>(selected_pairs[max_edge_topics]) << std::endl;
-      selected_pairs.resize(max_edge_topics);
-    }
+    std::cout << "#Candidates for edge topics: " << candidates << std::endl;
+    if (candidates > selected_pairs.size()) std::cout << "Edge topic threshold: " << threshold << std::endl;
     std::cout << "#Edge topics: " << selected_pairs.size() << std::endl;
+    std::cout << "Completed edge topic construction" << std::endl;
+  }
+  static std::vector<int64_t> pair_ids(const std::vector<std::tuple<int, int, uint64_t>>& selected_pairs) {  // (primary, secondary) per edge topic
     std::vector<int64_t> pq(2 * selected_pairs.size());
     for (size_t e = 0; e < selected_pairs.size(); ++e) {
       pq[2 * e] = std::get<0>(selected_pairs[e]);
       pq[2 * e + 1] = std::get<1>(selected_pairs[e]);
     }
+    return pq;
+  }
+  // The FPaxpy pair of construct_edge_topics_v2 (:1150-1160) on the device (isle_hip_edge_topics): EdgeModel = vocab x #edge, column-major.
+  void edge_model(const std::vector<std::tuple<int, int, uint64_t>>& selected_pairs, std::vector<FPTYPE>& EdgeModel) {
+    const std::vector<int64_t> pq = pair_ids(selected_pairs);
     EdgeModel.assign((size_t)vocab_size_ * selected_pairs.size(), 0.f);
-    check(isle_hip_edge_topics(ctx_, pq.data(), (int)selected_pairs.size(), (float)ISLE_EDGE_TOPIC_PRIMARY_RATIO, EdgeModel.data()),
-          "construct_edge_topics");
-    std::cout << "Completed edge topic construction" << std::endl;
+    check(isle_hip_edge_topics(ctx_, pq.data(), (int)selected_pairs.size(), (float)ISLE_EDGE_TOPIC_PRIMARY_RATIO, EdgeModel.data()), "edge_model");
+  }
+  // The n heaviest words of every edge topic (DenseMatrix::find_n_top_words on EdgeModel, :1221), selected on the device from the two
+  // columns of the resident catch model without storing the edge model (isle_hip_edge_top_words): entries bit-equal to edge_model()'s.
+  void edge_top_words(const std::vector<std::tuple<int, int, uint64_t>>& selected_pairs, const word_id_t n, std::vector<uint32_t>& ids, std::vector<FPTYPE>& weights) {
+    const std::vector<int64_t> pq = pair_ids(selected_pairs);
+    ids.assign(selected_pairs.size() * n, 0);
+    weights.assign(selected_pairs.size() * n, 0.f);
+    check(isle_hip_edge_top_words(ctx_, ISLE_MODEL_CATCH, nullptr, vocab_size_, (int)post_topics_, pq.data(), (int)selected_pairs.size(),
+                                  (float)ISLE_EDGE_TOPIC_PRIMARY_RATIO, (int)n, ids.data(), weights.data()),
+          "edge_top_words");
   }
 };
 

@@ -26,6 +26,13 @@
 // (FPSparseMatrixHip::write_model_text / write_edge_model_text -> isle_hip_model_text / isle_hip_edge_topics_text) and streamed to the file;
 // trainer_detail's host writers below define those bytes and are what the tests compare the device text against.  DocTopicWeights.tsv
 // is formatted on the device in the same way (write_infer_text -> isle_hip_infer_text; trainer_detail::write_doc_topic_lines).
+// Edge topics: train_edge_topics() selects the pairs on the device from the resident top-two topics (FPSparseMatrixHip::construct_edge_topics
+// -> isle_hip_select_edge_pairs; the host rule fpsparse_detail::select_edge_pairs_host beyond ISLE_EDGE_TABLE_MAX_TOPICS topics) and writes
+// the reference's two report files, EdgeTopicComposition.txt and EdgeTopicTopWords.txt (print_edge_topic_composition /
+// print_edge_topic_top_words, src/trainer.cpp:1169-1245; trainer_detail::edge_composition_text / edge_top_words_text state their bytes),
+// the edge topics' words selected on the device from the catch model's columns (isle_hip_edge_top_words).  No vocab x #edge matrix is
+// kept on the host: get_edge_model() fetches it on first use.  Deviation: with fewer than 20 (10) words in the vocabulary the blocks
+// print min(., vocab_size) entries; the reference reads out of range there.
 // Not mirrored (dead under the shipped hyper-parameters or outside the path): load_preprocessed_data_from_file,
 // print_doctopic (accepted, unused: the reference's use is commented out), compute_input_svd, construct_edge_topics_v1.
 #pragma once
@@ -240,6 +247,38 @@ inline void csc_from_fed(doc_id_t num_docs, const std::vector<uint32_t>& fed_doc
   }
   for (doc_id_t d = 0; d < num_docs; ++d) offsets[d + 1] += offsets[d];
 }
+// EdgeTopicComposition.txt (print_edge_topic_composition, src/trainer.cpp:1169-1194): "<primary>\t<secondary>\t<documents>\n" per edge
+// topic, topic ids 0-based as the reference prints them.
+inline std::string edge_composition_text(const std::vector<std::tuple<int, int, uint64_t>>& pairs) {
+  std::ostringstream o;
+  for (const auto& p : pairs) o << std::get<0>(p) << '\t' << std::get<1>(p) << '\t' << std::get<2>(p) << '\n';
+  return o.str();
+}
+// EdgeTopicTopWords.txt (print_edge_topic_top_words, src/trainer.cpp:1196-1245).  edge_ids / edge_w: n_edge_words top words per edge
+// topic (row-major); topic_ids / topic_w: n_topic_words top words per BASIC topic (row-major, every topic); entries
+// "word(id,weight)\t" with 0-based word ids and operator<< of the float.
+inline std::string edge_top_words_text(const std::vector<std::tuple<int, int, uint64_t>>& pairs, const std::vector<std::string>& vocab_words,
+                                       const uint32_t* edge_ids, const float* edge_w, const size_t n_edge_words, const uint32_t* topic_ids,
+                                       const float* topic_w, const size_t n_topic_words) {
+  std::ostringstream o;
+  auto entries = [&](const uint32_t* ids, const float* w, size_t n) {
+    for (size_t i = 0; i < n; ++i) o << vocab_words[ids[i]] << "(" << ids[i] << "," << w[i] << ")\t";
+  };
+  for (size_t t = 0; t < pairs.size(); ++t) {
+    const int p = std::get<0>(pairs[t]), q = std::get<1>(pairs[t]);
+    o << "Edge Topic: " << t << "  (" << p << ", " << q << "): " << std::get<2>(pairs[t]) << '\n';
+    o << "Top words in edge_topic: \n";
+    entries(edge_ids + t * n_edge_words, edge_w + t * n_edge_words, n_edge_words);
+    o << "\n";
+    o << "Top words in topic: " << p << "\n";
+    entries(topic_ids + (size_t)p * n_topic_words, topic_w + (size_t)p * n_topic_words, n_topic_words);
+    o << "\n";
+    o << "Top words in topic: " << q << "\n";
+    entries(topic_ids + (size_t)q * n_topic_words, topic_w + (size_t)q * n_topic_words, n_topic_words);
+    o << "\n\n";
+  }
+  return o.str();
+}
 }  // namespace trainer_detail
 
 class ISLETrainer {
@@ -306,7 +345,8 @@ class ISLETrainer {
   FPTYPE* Model = nullptr;  // vocab_size x num_topics, column-major (DenseMatrix<FPTYPE>, include/denseMatrix.h:50-58)
   std::vector<std::tuple<int, int, doc_id_t>> top_topic_pairs;
   std::vector<std::tuple<int, int, uint64_t>> selected_pairs;
-  std::vector<FPTYPE> EdgeModel;
+  std::vector<FPTYPE> EdgeModel;  // fetched by get_edge_model()
+  bool edge_model_fetched = false;
   std::vector<std::string> vocab_words;
   std::vector<std::vector<std::pair<word_id_t, FPTYPE>>> topwords;
   std::vector<std::vector<std::pair<word_id_t, FPTYPE>>> avg_topwords;  // output_avg_topic_coherence()
@@ -511,7 +551,9 @@ class ISLETrainer {
     log->next_time_secs("Collecting word freqs in clusters");
     log->next_time_secs("Finding catchwords for clusters");
     Model = new FPTYPE[(size_t)vocab_size * num_topics];
-    B_fl_CSC->construct_topic_model(Model, num_topics, num_docs, flag_construct_edge_topics && flag_print_top_two_topics ? &top_topic_pairs : NULL);  // :648
+    // the documents' top-two topics stay on the device, where train_edge_topics() selects the pairs; the host loop beyond the counting table's limit needs them here
+    B_fl_CSC->construct_topic_model(Model, num_topics, num_docs,
+                                    flag_construct_edge_topics && flag_print_top_two_topics && num_topics > ISLE_EDGE_TABLE_MAX_TOPICS ? &top_topic_pairs : NULL);  // :648
     log->next_time_secs("Constructing topic vectors");
     is_training_complete = true;
   }
@@ -623,17 +665,39 @@ class ISLETrainer {
   // src/trainer.cpp:673-685 -> construct_edge_topics_v2 :1116-1167
   void train_edge_topics() {
     if (!flag_construct_edge_topics) throw std::runtime_error("train_edge_topics() without construct_edge_topics");
-    B_fl_CSC->construct_edge_topics(top_topic_pairs, max_edge_topics, selected_pairs, EdgeModel);
+    // without print_top_two_topics the reference collects no pairs (:648) and selects from none
+    const bool on_host = !flag_print_top_two_topics || num_topics > ISLE_EDGE_TABLE_MAX_TOPICS;
+    B_fl_CSC->construct_edge_topics(on_host ? &top_topic_pairs : nullptr, max_edge_topics, selected_pairs);
+    EdgeModel.clear();
+    edge_model_fetched = false;
     log->next_time_secs("Constructing edge topic model");
+    print_edge_topic_composition();  // :1163-1166 (flag_print_edge_topic_composition, default true)
+    print_edge_topic_top_words(10);
+  }
+  void print_edge_topic_composition() {  // :1169-1194
+    std::ofstream out(log_dir + "/EdgeTopicComposition.txt", std::ios::binary);
+    out << trainer_detail::edge_composition_text(selected_pairs);
+  }
+  // :1196-1245: 2 * num_top_words words of every edge topic, num_top_words of its two basic topics; min(., vocab_size) of each
+  void print_edge_topic_top_words(const int num_top_words) {
+    load_vocab();
+    const word_id_t n_edge = std::min<word_id_t>(2 * (word_id_t)num_top_words, vocab_size), n_topic = std::min<word_id_t>((word_id_t)num_top_words, vocab_size);
+    std::vector<uint32_t> e_ids, t_ids;
+    std::vector<FPTYPE> e_w, t_w;
+    B_fl_CSC->edge_top_words(selected_pairs, n_edge, e_ids, e_w);
+    std::vector<std::vector<std::pair<word_id_t, FPTYPE>>> basic(num_topics);
+    B_fl_CSC->model_top_words(ISLE_MODEL_CATCH, num_topics, n_topic, basic.data());
+    for (doc_id_t t = 0; t < num_topics; ++t)
+      for (auto& tw : basic[t]) {
+        t_ids.push_back((uint32_t)tw.first);
+        t_w.push_back(tw.second);
+      }
+    std::ofstream out(log_dir + "/EdgeTopicTopWords.txt", std::ios::binary);
+    out << trainer_detail::edge_top_words_text(selected_pairs, vocab_words, e_ids.data(), e_w.data(), n_edge, t_ids.data(), t_w.data(), n_topic);
   }
   // src/trainer.cpp:687-693
   void write_edgemodel_to_file() {
-    std::vector<int64_t> pq(2 * selected_pairs.size());
-    for (size_t e = 0; e < selected_pairs.size(); ++e) {
-      pq[2 * e] = std::get<0>(selected_pairs[e]);
-      pq[2 * e + 1] = std::get<1>(selected_pairs[e]);
-    }
-    B_fl_CSC->write_edge_model_text(pq, (FPTYPE)ISLE_EDGE_TOPIC_PRIMARY_RATIO, log_dir + "/EdgeModel_sparse");
+    B_fl_CSC->write_edge_model_text(FPSparseMatrixHip::pair_ids(selected_pairs), (FPTYPE)ISLE_EDGE_TOPIC_PRIMARY_RATIO, log_dir + "/EdgeModel_sparse");
     log->next_time_secs("Output edge model");
   }
   // src/trainer.cpp:705-745, the cluster-average model (no catchwords) on the device; see the header comment for the deviations
@@ -699,7 +763,11 @@ class ISLETrainer {
   // src/trainer.cpp:993-996: vocab_size x num_topics floats, column-major (element (word, topic) at word + topic * vocab_size)
   void get_basic_model(FPTYPE* const basicModel) { std::memcpy(basicModel, Model, (size_t)vocab_size * num_topics * sizeof(FPTYPE)); }
   int get_num_edge_topics() { return (int)selected_pairs.size(); }                                                        // :998-1001
-  void get_edge_model(FPTYPE* const edgeModel) { std::memcpy(edgeModel, EdgeModel.data(), EdgeModel.size() * sizeof(FPTYPE)); }  // :1003-1007
+  void get_edge_model(FPTYPE* const edgeModel) {  // :1003-1007; the vocab_size x #edge matrix exists on the host from the first call on
+    if (!edge_model_fetched) B_fl_CSC->edge_model(selected_pairs, EdgeModel);
+    edge_model_fetched = true;
+    std::memcpy(edgeModel, EdgeModel.data(), EdgeModel.size() * sizeof(FPTYPE));
+  }
   const std::vector<FPTYPE>& eigenvalues() const { return evalues; }
   const std::vector<std::vector<std::pair<word_id_t, FPTYPE>>>& top_words() const { return topwords; }  // after output_cluster_summary()
   const std::vector<std::vector<std::pair<word_id_t, FPTYPE>>>& avg_top_words() const { return avg_topwords; }  // after output_avg_topic_coherence()

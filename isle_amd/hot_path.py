@@ -388,6 +388,60 @@ class HotPath:
         self._chk(self._lib.isle_hip_edge_topics(self._h, _p(pairs), n, float(primary_ratio), _p(E)))
         return E
 
+    def select_edge_pairs(self, max_edge_topics, min_docs=EDGE_TOPIC_MIN_DOCS, top1=None, top2=None, num_topics=None):
+        """select_edge_pairs() on the device (isle_hip_select_edge_pairs), bit-equal to it: over the resident top-two topics of the last
+        construct_topic_model (top1 and top2 None; nothing is fetched), or over the given int32 arrays with num_topics given (every id in
+        -1 .. num_topics - 1).  -> (int64 (n, 3): primary, secondary, documents; dict(candidates, threshold)), threshold the count of
+        the first candidate cut off, None when nothing was cut."""
+        if top1 is None and top2 is None:
+            docs = getattr(self, "_a_shape", (0, 0))[1]
+            k = getattr(self, "_post_k", 0) if num_topics is None else int(num_topics)
+            t1 = t2 = None
+        else:
+            if num_topics is None:
+                raise ValueError("num_topics is needed with top1 / top2")
+            t1 = None if top1 is None else np.ascontiguousarray(top1, np.int32).reshape(-1)
+            t2 = None if top2 is None else np.ascontiguousarray(top2, np.int32).reshape(-1)
+            if t1 is not None and t2 is not None and t1.size != t2.size:
+                raise ValueError("top1 and top2 differ in length")
+            docs = int((t1 if t1 is not None else t2).size)
+            k = int(num_topics)
+        cap = max(min(int(max_edge_topics), k * k, docs), 0)
+        pairs = np.empty((cap, 3), np.int64)
+        nsel, ncand, thr = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        # (an empty array still hands the library a non-null pointer: which of top1 / top2 was given is what it sees)
+        one = np.zeros(1, np.int32)
+        self._chk(self._lib.isle_hip_select_edge_pairs(self._h, None if t1 is None else _p(t1 if t1.size else one),
+                                                       None if t2 is None else _p(t2 if t2.size else one), docs, k, int(max_edge_topics),
+                                                       int(min_docs), _p(pairs) if cap else None, cap, C.byref(nsel), C.byref(ncand), C.byref(thr)))
+        n = int(nsel.value)
+        cut = int(ncand.value) > n
+        return pairs[:n], dict(candidates=int(ncand.value), threshold=int(thr.value) if cut else None)
+
+    def edge_top_words(self, pairs, n, primary_ratio=EDGE_TOPIC_PRIMARY_RATIO, model="catch"):
+        """The n heaviest words of the edge topics primary_ratio * M[:, p] + (1 - primary_ratio) * M[:, s], by the rule of top_words()
+        and with the entries of edge_topics() (bit-equal to both), formed on the device from the model's two columns: no (V, n_edge)
+        matrix exists anywhere.  pairs: (n_edge, 2) or the (n_edge, 3) of select_edge_pairs; model as in model_top_words.
+        -> (ids uint32 (n_edge, n), weights float32 (n_edge, n))."""
+        pairs = np.asarray(pairs, np.int64)
+        if pairs.ndim != 2 or pairs.shape[1] not in (2, 3):
+            pairs = pairs.reshape(-1, 2)
+        pq = np.ascontiguousarray(pairs[:, :2])
+        ne = pq.shape[0]
+        if isinstance(model, str):
+            which, host = self._MODELS[model], None
+            V, cols = self._resident_shape(model)
+        else:
+            host = np.asfortranarray(model, np.float32)
+            if host.ndim != 2:
+                raise ValueError("model must be (V, cols)")
+            which, (V, cols) = 2, host.shape
+        ids = np.empty((ne, int(n)), np.uint32)
+        w = np.empty((ne, int(n)), np.float32)
+        self._chk(self._lib.isle_hip_edge_top_words(self._h, which, _p(host), int(V), int(cols), _p(pq) if ne else None, ne, float(primary_ratio),
+                                                    int(n), _p(ids), _p(w)))
+        return ids, w
+
     def topic_coherence(self, top_words, eps=DEFAULT_COHERENCE_EPS, fetch_counts=True):
         """UMass coherence of each topic's top words over the count matrix A (SparseMatrix::topic_coherence,
         src/sparseMatrix.cpp:841-1016; the formula, the NaN rule and the deviations: include/isle_hip.h).  top_words: (num_topics, M)
