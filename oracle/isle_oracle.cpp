@@ -468,6 +468,7 @@ struct BlockKs {
   size_t nconv = 0, n_restarts = 0;
   Rng rng;
   bool ok = true;
+  const float* start = nullptr;  // optional dim x blk start block: the first try of init()'s draw loop
 
   BlockKs(Op* op_, size_t nev_, size_t ncv_, size_t maxit_, size_t blk_, float tol_, uint64_t seed)
       : op(op_), nev(nev_), ncv(ncv_), maxit(maxit_), blk(blk_ < nev_ ? blk_ : 1),  // :198
@@ -503,8 +504,11 @@ struct BlockKs {
     V.assign(dim * (ncv + blk), 0.f);
     fvec F, Q, R;
     int rank;
+    bool first = true;
     do {
-      randu(F, blk);
+      if (first && start) F.assign(start, start + dim * blk);
+      else randu(F, blk);
+      first = false;
       rank = compute_qr(F.data(), dim, blk, Q, R);
     } while ((size_t)rank < blk);
     std::memcpy(V.data(), Q.data(), dim * blk * sizeof(float));
@@ -976,8 +980,9 @@ int orc_gram_apply(void* h, const float* X, int b, float* Z) {
 }
 
 static int run_ks(Op& op, int nev, int ncv, int maxit, int blk, float tol, uint64_t seed, float* evals, float* U,
-                  int* nconv, int* restarts, int* napplies) {
+                  int* nconv, int* restarts, int* napplies, const float* start = nullptr) {
   BlockKs ks(&op, nev, ncv, maxit, blk, tol, seed);
+  ks.start = start;
   ks.init();
   ks.compute();
   for (int i = 0; i < nev; ++i) evals[i] = ks.H(i, i);  // src/sparseMatrix.cpp:1212-1213
@@ -1000,6 +1005,13 @@ int orc_block_ks_dense(const float* A, uint64_t n, int nev, int ncv, int maxit, 
                        float* evals, float* U, int* nconv, int* restarts, int* napplies) {
   DenseOp op(A, n);
   return run_ks(op, nev, ncv, maxit, blk, tol, seed, evals, U, nconv, restarts, napplies);
+}
+
+// the same from a given n x blk start block (blk as BlockKs takes it: 1 unless blk < nev)
+int orc_block_ks_dense_start(const float* A, uint64_t n, int nev, int ncv, int maxit, int blk, float tol, uint64_t seed,
+                             const float* start, float* evals, float* U, int* nconv, int* restarts, int* napplies) {
+  DenseOp op(A, n);
+  return run_ks(op, nev, ncv, maxit, blk, tol, seed, evals, U, nconv, restarts, napplies, start);
 }
 
 int orc_eig_sym(const float* S, uint64_t n, float* evals_desc, float* vecs) {

@@ -143,13 +143,19 @@ def lift(U, C_lowd):
     return out
 
 
-def block_ks_dense(A, nev, blk=10, ncv=None, maxit=100, tol=1e-4, seed=1):
+def block_ks_dense(A, nev, blk=10, ncv=None, maxit=100, tol=1e-4, seed=1, start_block=None):
     A = np.asfortranarray(A, dtype=np.float32)
     n = A.shape[0]
     ncv = 2 * nev + 10 if ncv is None else ncv
     ev = np.empty(nev, np.float32)
     U = np.empty((n, nev), np.float32, order="F")
     nconv, rst, nap = C.c_int(), C.c_int(), C.c_int()
+    if start_block is not None:
+        sb = np.asfortranarray(start_block, dtype=np.float32)
+        assert sb.shape == (n, blk if blk < nev else 1)
+        rc = lib().orc_block_ks_dense_start(_p(A), C.c_uint64(n), nev, ncv, maxit, blk, C.c_float(tol), C.c_uint64(seed), _p(sb), _p(ev),
+                                            _p(U), C.byref(nconv), C.byref(rst), C.byref(nap))
+        return dict(rc=rc, evals=ev, U=U, nconv=nconv.value, restarts=rst.value, napplies=nap.value)
     rc = lib().orc_block_ks_dense(_p(A), C.c_uint64(n), nev, ncv, maxit, blk, C.c_float(tol), C.c_uint64(seed), _p(ev),
                                   _p(U), C.byref(nconv), C.byref(rst), C.byref(nap))
     return dict(rc=rc, evals=ev, U=U, nconv=nconv.value, restarts=rst.value, napplies=nap.value)

@@ -28,7 +28,11 @@ def test_seed_spectra_are_recovered(hp, kind, n, k):
     from oracle.oracle import block_ks_dense
     A, evs = seed_matrix(n, kind, 100 * kind + k)
     A32 = A.astype(np.float32)
-    r = hp.block_ks_dense(A32, k, allow_noconv=True)
+    # n = 300, kinds 1 and 2 (the runs that converge, whose counts are compared below): both sides start from the same block (seed 2: every
+    # residual estimate the loop reads stays 17 % or more away from tol in the fp64 restatement of tests/ks_certificate.py, so the converged
+    # counts do not hinge on rounding).  Kind 3 uses up maxit on either side and keeps each side's own draw.
+    S = np.random.default_rng(2).uniform(size=(n, 10)).astype(np.float32) if n == 300 and kind != 3 else None
+    r = hp.block_ks_dense(A32, k, start_block=S, allow_noconv=True)
     top = evs[:k]
     assert np.max(np.abs(r["evals"] - top) / top) <= 2e-4
     U = r["U"].astype(np.float64)
@@ -36,11 +40,11 @@ def test_seed_spectra_are_recovered(hp, kind, n, k):
     # Ritz residuals against the true matrix (kind 3 at k = 200 exhausts maxit in the reference too: gap 1/n)
     res = np.linalg.norm(A @ U - U * r["evals"].astype(np.float64), axis=0)
     assert res.max() <= (2e-3 if kind == 3 else 5e-4) * top[0]
-    if n == 300:  # same control flow as the CPU restatement: restart and application counts agree when both converge
-        o = block_ks_dense(A32, k)
+    if n == 300:  # same control flow as the CPU restatement from the same start block: restart and application counts are equal when both converge
+        o = block_ks_dense(A32, k, start_block=S)
         assert np.max(np.abs(r["evals"] - o["evals"]) / top) <= 2e-4
         if r["rc"] == 0 and o["nconv"] == k and o["restarts"] < 100:
-            assert abs(r["restarts"] - o["restarts"]) <= max(1, o["restarts"] // 4)  # different start blocks: a few restarts either way
+            assert r["restarts"] == o["restarts"] and r["napplies"] == o["napplies"]
 
 
 def test_rank_repair_in_init_and_expand(hp):
