@@ -542,6 +542,38 @@ int isle_hip_get_infer_entries(isle_ctx* ctx, int64_t* doc_offsets, uint32_t* to
 int isle_hip_infer_text(isle_ctx* ctx, int what, uint64_t row_begin, uint64_t row_end, uint64_t number_base, isle_text_sink_fn sink,
                         void* user, uint64_t* nbytes, uint64_t* nlines);
 int isle_hip_doc_line_text(uint64_t doc_number, uint64_t topic_number, float w, char* out40);
+/* The trainer's three per-document report files, formatted on the device (isle_amd/csrc/doc_report.hip) from what isle_hip_catchwords and
+ * isle_hip_topic_model left resident, for documents [doc_begin, doc_end) of A.  All are MMappedOutput text: integers in plain decimal
+ * (concat_int), the weight exactly the <weight> of ISLE_TEXT_SPARSE; documents, words and topics are printed 1-based.
+ * trainer_detail::doc_catchword_text / doc_topic_sums_text / top_two_text (isle_amd/host/trainer_hip.h) restate the bytes on the host.
+ *   ISLE_DOCREPORT_CATCHWORDS         DocCatchword.tsv (ISLETrainer::output_doc_topic, src/trainer.cpp:946-964): documents ascending, the
+ *                                     entries of a document in stored order; every entry of A whose word is a catchword gives
+ *                                     "<doc + 1>\t<word + 1>\t<normalised value>\n"
+ *   ISLE_DOCREPORT_TOPIC_SUMS         DocTopicCatchwordSums.tsv (:979-983): every non-zero (document, topic) catchword sum of the documents
+ *                                     gives "<doc + 1>\t<topic + 1>\t<sum>\n", in the order construct_topic_model leaves the vector in
+ *                                     (src/sparseMatrix.cpp:715-718): topic ascending, then value descending.  Deviation: the reference's
+ *                                     sort is unstable, so equal (topic, value) pairs come in no stated order there; here they go by
+ *                                     document ascending.  The range selects the documents whose sums are sorted and printed; a range
+ *                                     with >= 2^32 sums is ISLE_E_ARG (write it in parts).
+ *   ISLE_DOCREPORT_TOPIC_SUMS_BY_DOC  the same lines in the resident order: document ascending, then topic ascending
+ *   ISLE_DOCREPORT_TOP_TWO            TopTwoTopicsPerDoc.txt (ISLETrainer::print_top_two_topics, :1029-1035): documents ascending; every
+ *                                     document with top1 >= 0 and top2 >= 0 gives "<doc + 1>\t<top1 + 1>\t<top2 + 1>\n"
+ * Domain, delivery, the size query (sink == NULL), a non-zero sink return and "no lines: no sink call" are isle_hip_infer_text's: a
+ * printed number >= 0x7fffffff, or a printed weight that is negative, NaN, infinite or >= 2^31, fails the call with ISLE_E_ARG naming the
+ * first such line before any byte is delivered; pieces of at most 16 MiB, each non-empty and ending at a line end.
+ * ISLE_E_ARG also for: an unknown `what`, doc_begin > doc_end, doc_end > docs(A), world > 1, no count matrix, a call before
+ * isle_hip_catchwords (CATCHWORDS) or before isle_hip_topic_model (the other kinds), a call after a new count matrix.
+ * The call changes nothing resident: a second call gives the same bytes.  Device time is booked under ISLE_T_POST.
+ * isle_hip_top_two_line_text (host only, no context): one TOP_TWO line for the numbers as printed into out40 (NUL-terminated); returns its
+ * length, -1 for a number >= 0x7fffffff or a null out40.  It compiles the functions the kernels compile.  The lines of the other three
+ * kinds are isle_hip_doc_line_text's. */
+#define ISLE_DOCREPORT_CATCHWORDS 0
+#define ISLE_DOCREPORT_TOPIC_SUMS 1        /* reference order */
+#define ISLE_DOCREPORT_TOPIC_SUMS_BY_DOC 2 /* resident order */
+#define ISLE_DOCREPORT_TOP_TWO 3
+int isle_hip_doc_report_text(isle_ctx* ctx, int what, uint64_t doc_begin, uint64_t doc_end, isle_text_sink_fn sink, void* user,
+                             uint64_t* nbytes, uint64_t* nlines);
+int isle_hip_top_two_line_text(uint64_t doc_number, uint64_t t1_number, uint64_t t2_number, char* out40);
 /* The avg_doc_sz of the resident count matrix as the context holds it (see above; computed on first use).  ISLE_E_ARG: no count matrix,
  * world > 1, out null. */
 int isle_hip_avg_doc_sz(isle_ctx* ctx, float* out);

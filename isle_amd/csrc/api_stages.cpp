@@ -943,6 +943,26 @@ extern "C" int isle_hip_infer_text(isle_ctx* c, int what, uint64_t row_begin, ui
   return k_infer_text(c, what, row_begin, row_end, number_base, sink, user, nbytes, nlines);
 }
 
+// The trainer's per-document report files formatted on the device (doc_report.hip) from what the catchword and topic-model stages left
+// resident
+extern "C" int isle_hip_doc_report_text(isle_ctx* c, int what, uint64_t doc_begin, uint64_t doc_end, isle_text_sink_fn sink, void* user,
+                                        uint64_t* nbytes, uint64_t* nlines) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  if (nbytes) *nbytes = 0;
+  if (nlines) *nlines = 0;
+  ISLECHK(post_prepare(c, "doc_report_text"));
+  if (what != ISLE_DOCREPORT_CATCHWORDS && what != ISLE_DOCREPORT_TOPIC_SUMS && what != ISLE_DOCREPORT_TOPIC_SUMS_BY_DOC && what != ISLE_DOCREPORT_TOP_TWO)
+    return isle_fail(c, ISLE_E_ARG, "doc_report_text: unknown kind %d", what);
+  if (what == ISLE_DOCREPORT_CATCHWORDS ? !c->p_catch_ready : !c->p_model_ready)
+    return isle_fail(c, ISLE_E_ARG, "doc_report_text: run %s first (a new count matrix voids its result)",
+                     what == ISLE_DOCREPORT_CATCHWORDS ? "isle_hip_catchwords" : "isle_hip_topic_model");
+  if (doc_begin > doc_end || doc_end > c->a_D)
+    return isle_fail(c, ISLE_E_ARG, "doc_report_text: documents [%llu, %llu) of %llu", (unsigned long long)doc_begin, (unsigned long long)doc_end,
+                     (unsigned long long)c->a_D);
+  return k_doc_report_text(c, what, doc_begin, doc_end, sink, user, nbytes, nlines);
+}
+
 extern "C" int isle_hip_avg_doc_sz(isle_ctx* c, float* out) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));

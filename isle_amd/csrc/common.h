@@ -645,6 +645,12 @@ int k_text_pump(isle_ctx* c, const char* who, const uint64_t* offs_dev, uint64_t
 int k_infer_text(isle_ctx* c, int what, uint64_t row_begin, uint64_t row_end, uint64_t base, isle_text_sink_fn sink, void* user, uint64_t* nbytes,
                  uint64_t* nlines);
 
+// doc_report.hip: the trainer's per-document report files (ISLE_DOCREPORT_*) for documents [doc_begin, doc_end) of A from the resident
+// catchword map, (document, topic) sums and top-two topics, delivered as k_model_text delivers.  The caller has checked the range and
+// that the stage that made the source has run.
+int k_doc_report_text(isle_ctx* c, int what, uint64_t doc_begin, uint64_t doc_end, isle_text_sink_fn sink, void* user, uint64_t* nbytes,
+                      uint64_t* nlines);
+
 // model_load.hip: the text of a model file (n bytes on the device, ISLE_TEXT_SPARSE / ISLE_TEXT_DENSE) parsed into model_dev (V x ncols
 // column-major).  *err_key: ~0 = none, else (byte position << 3) | kind of the first offending byte (isle_hip_load_model_text names them);
 // *nentries: lines parsed (SPARSE), tokens (DENSE)

@@ -8,7 +8,7 @@
 //   ISLE_DOCTEXT_ENTRIES  L = an entry of [off[row_begin], off[row_end]); every candidate is printed
 //   ISLE_DOCTEXT_TOP      L = 5 (row - row_begin) + slot; slot i of a row is printed while slots 0 .. i hold a topic >= 0, else its
 //                         length is 0
-// An entry does not store its row.  Per tile, thread 0 finds the row of the tile's first entry by an upper-bound search in the
+// An entry does not store its row (doc_text.h, shared with doc_report.hip).  Per tile, thread 0 finds the row of the tile's first entry by an upper-bound search in the
 // offsets, the block stages the IT_WIN offsets that follow it in LDS (relative to the tile's first entry, clamped), and every line
 // finds its row by a search in that window.  A tile of 1024 entries spans at most 1024 non-empty rows, but any number of empty ones:
 // where the window's last offset does not lie beyond the tile (a run of empty documents longer than the window), the lines of that
@@ -24,16 +24,13 @@
 #include <vector>
 
 #include "common.h"
+#include "doc_text.h"
 #include "scan.h"
 #include "text_format.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-constexpr int IT_WIN = 1024;               // offsets staged per tile
-constexpr uint64_t IT_NUM_END = 0x7fffffffull;  // concat_int: assert(num < 0x7fffffff)
-static_assert(10 + 1 + 10 + 1 + 13 + 1 <= MT_MAX_ENTRY, "a line fits the LDS budget of a tile");
 
 // Where the lines come from.  Other per-document files of the reference (two integers and a weight per line) fit the same descriptor:
 // a CSR of (column, value) over the rows, or a fixed number of slots per row.
@@ -54,30 +51,10 @@ struct ItLine {
   bool present;
 };
 
-// the row r of [lo, hi) with off[r] <= e < off[r + 1]; the caller knows off[lo] <= e < off[hi]
-__device__ inline uint64_t it_row_of(const int64_t* __restrict__ off, uint64_t lo, uint64_t hi, uint64_t e) {
-  while (hi - lo > 1) {
-    const uint64_t mid = lo + ((hi - lo) >> 1);
-    if ((uint64_t)off[mid] <= e) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// ENTRIES: the tile's first row into *row0 and win[j] = min(off[row0 + 1 + j] - (the tile's first entry), MT_TILE), j < IT_WIN (MT_TILE
-// beyond row_end).  Every thread of the block calls it.
+// ENTRIES: the tile's first row and the offsets that follow it, staged (doc_text.h).  Every thread of the block calls it.
 __device__ inline void it_stage(const ItSrc& s, uint64_t tile, uint32_t* win, uint64_t* row0) {
   if (s.what != ISLE_DOCTEXT_ENTRIES) return;
-  const uint64_t e0 = s.first + tile * MT_TILE;
-  __syncthreads();  // the previous tile's searches are over
-  if (threadIdx.x == 0) *row0 = it_row_of(s.off, s.row_begin, s.row_end, e0);
-  __syncthreads();
-  const uint64_t r0 = *row0;
-  for (int j = threadIdx.x; j < IT_WIN; j += MT) {
-    const uint64_t r = r0 + 1 + (uint64_t)j;
-    win[j] = r <= s.row_end ? (uint32_t)min((uint64_t)s.off[r] - e0, (uint64_t)MT_TILE) : (uint32_t)MT_TILE;
-  }
-  __syncthreads();
+  it_stage_window(s.off, s.row_begin, s.row_end, s.first + tile * MT_TILE, win, row0);
 }
 
 // candidate l < nl of the tile (nl = the tile's candidates)
@@ -85,22 +62,7 @@ __device__ inline ItLine it_line(const ItSrc& s, uint64_t tile, uint32_t l, uint
   ItLine x;
   const uint64_t at = s.first + tile * MT_TILE + l;
   if (s.what == ISLE_DOCTEXT_ENTRIES) {
-    uint64_t row;
-    if (win[IT_WIN - 1] >= nl) {  // the window reaches beyond the tile: the rows before the first offset > l
-      uint32_t lo = 0, n = IT_WIN;
-      while (n) {  // upper bound of l
-        const uint32_t h = n >> 1;
-        if (win[lo + h] <= l) {
-          lo += h + 1;
-          n -= h + 1;
-        } else {
-          n = h;
-        }
-      }
-      row = row0 + lo;
-    } else {
-      row = it_row_of(s.off, row0, s.row_end, at);
-    }
+    const uint64_t row = it_window_row(s.off, s.row_end, at, l, nl, win, row0);
     x.number = row + s.base;
     x.topic1 = (uint64_t)s.topic[at] + 1u;
     x.w = s.weight[at];
@@ -120,7 +82,7 @@ __device__ inline bool it_in_domain(const ItSrc& s, const ItLine& x) {
   return s.base < IT_NUM_END && x.number < IT_NUM_END && x.topic1 < IT_NUM_END && mt_weight_in_domain(x.w);
 }
 __device__ inline uint32_t it_len(const ItLine& x) {
-  return (uint32_t)(mt_ndigits((uint32_t)x.number) + 1 + mt_ndigits((uint32_t)x.topic1) + 1 + mt_whole_digits(x.w) + 7 + 1);
+  return it_line_len((uint32_t)x.number, (uint32_t)x.topic1, x.w);
 }
 
 // stat[0] += lines printed; stat[1] = min over the offending printed candidates of L
@@ -188,12 +150,7 @@ __global__ __launch_bounds__(MT) void it_write_k(ItSrc src, uint64_t tile0, uint
 #pragma unroll
     for (int i = 0; i < MT_ITEMS; ++i) {
       if (!x[i].present) continue;
-      p = mt_put_uint(p, (uint32_t)x[i].number, mt_ndigits((uint32_t)x[i].number));
-      *p++ = '\t';
-      p = mt_put_uint(p, (uint32_t)x[i].topic1, mt_ndigits((uint32_t)x[i].topic1));
-      *p++ = '\t';
-      p = mt_weight(x[i].w, p);
-      *p++ = '\n';
+      p = it_put_line(p, (uint32_t)x[i].number, (uint32_t)x[i].topic1, x[i].w);
     }
     mt_store_tile(lines, shift, nbytes, out, dst0);
   }
@@ -283,12 +240,7 @@ extern "C" int isle_hip_doc_line_text(uint64_t doc_number, uint64_t topic_number
   if (!out40) return -1;
   out40[0] = 0;
   if (doc_number >= IT_NUM_END || topic_number >= IT_NUM_END || !mt_weight_in_domain(w)) return -1;
-  char* p = mt_put_uint(out40, (uint32_t)doc_number, mt_ndigits((uint32_t)doc_number));
-  *p++ = '\t';
-  p = mt_put_uint(p, (uint32_t)topic_number, mt_ndigits((uint32_t)topic_number));
-  *p++ = '\t';
-  p = mt_weight(w, p);
-  *p++ = '\n';
+  char* p = it_put_line(out40, (uint32_t)doc_number, (uint32_t)topic_number, w);
   *p = 0;
   return (int)(p - out40);
 }

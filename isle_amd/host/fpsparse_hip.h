@@ -428,6 +428,37 @@ class FPSparseMatrixHip {
     check(isle_hip_infer_text(ctx_, what, row_begin, row_end, number_base, nullptr, nullptr, &nbytes, nlines), "infer_text_size");
     return nbytes;
   }
+  // A per-document report file of the trainer for every document of A, formatted on the device from what find_catchwords /
+  // construct_topic_model left resident (isle_hip_doc_report_text) and streamed to the file: what = ISLE_DOCREPORT_CATCHWORDS
+  // (DocCatchword.tsv), ISLE_DOCREPORT_TOPIC_SUMS (DocTopicCatchwordSums.tsv; _BY_DOC: the same lines in resident order) or
+  // ISLE_DOCREPORT_TOP_TWO (TopTwoTopicsPerDoc.txt).  Returns the bytes written; nlines nullable.
+  uint64_t write_doc_report(const std::string& filename, const int what, uint64_t* nlines = nullptr) {
+    FILE* fp = std::fopen(filename.c_str(), "wb");
+    if (!fp) throw std::runtime_error("cannot open " + filename);
+    uint64_t nbytes = 0;
+    const int rc = isle_hip_doc_report_text(ctx_, what, 0, a_docs_, text_to_file, fp, &nbytes, nlines);
+    std::fclose(fp);
+    check(rc, "write_doc_report");
+    return nbytes;
+  }
+  // What those files print, fetched: the count matrix A (CSC over its documents) with the corpus' avg_doc_sz, and the (document, topic)
+  // catchword sums of the last construct_topic_model as CSR over A's documents.  For the host statements of the files
+  // (trainer_detail::doc_catchword_text / doc_topic_sums_text / top_two_text) and their yardstick isle_amd/host/doc_report_main.cpp.
+  void get_count_matrix(std::vector<FPTYPE>& counts, std::vector<uint32_t>& rows, std::vector<int64_t>& offs, float* avg_doc_sz) {
+    offs.assign((size_t)a_docs_ + 1, 0);
+    check(isle_hip_get_A(ctx_, nullptr, nullptr, offs.data()), "get_A");
+    counts.assign((size_t)offs[a_docs_], 0.0f);
+    rows.assign((size_t)offs[a_docs_], 0);
+    check(isle_hip_get_A(ctx_, counts.data(), rows.data(), nullptr), "get_A");
+    if (avg_doc_sz) check(isle_hip_avg_doc_sz(ctx_, avg_doc_sz), "avg_doc_sz");
+  }
+  void get_doc_topic_sums(std::vector<int64_t>& offs, std::vector<uint32_t>& topic, std::vector<FPTYPE>& val) {
+    offs.assign((size_t)a_docs_ + 1, 0);
+    check(isle_hip_get_doc_topic_sums(ctx_, offs.data(), nullptr, nullptr), "get_doc_topic_sums");
+    topic.assign((size_t)offs[a_docs_], 0);
+    val.assign((size_t)offs[a_docs_], 0.0f);
+    check(isle_hip_get_doc_topic_sums(ctx_, nullptr, topic.data(), val.data()), "get_doc_topic_sums");
+  }
   doc_id_t count_docs() const { return a_docs_; }  // documents of the count matrix A (B may hold fewer after sampling)
   // DenseMatrix::write_to_file_as_sparse (format = ISLE_TEXT_SPARSE) / write_to_file (ISLE_TEXT_DENSE), src/denseMatrix.cpp:124-186, of a
   // resident model (ISLE_MODEL_CATCH / ISLE_MODEL_AVG), or with ISLE_MODEL_HOST of model_host (vocab x ncols column-major): the text is

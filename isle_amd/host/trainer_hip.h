@@ -33,8 +33,14 @@
 // the edge topics' words selected on the device from the catch model's columns (isle_hip_edge_top_words).  No vocab x #edge matrix is
 // kept on the host: get_edge_model() fetches it on first use.  Deviation: with fewer than 20 (10) words in the vocabulary the blocks
 // print min(., vocab_size) entries; the reference reads out of range there.
+// Per-document reports: output_doc_topic() writes DocCatchword.tsv and DocTopicCatchwordSums.tsv, print_top_two_topics() writes
+// TopTwoTopicsPerDoc.txt (src/trainer.cpp:874-991, :1008-1040), all three formatted on the device from the resident catchword map, the
+// (document, topic) sums and the top-two topics (FPSparseMatrixHip::write_doc_report -> isle_hip_doc_report_text); trainer_detail::
+// doc_catchword_text / doc_topic_sums_text / top_two_text state their bytes.  With print_doctopic set, write_model_to_file() calls
+// output_doc_topic() (the call the reference left commented out at :664-667); the flag defaults to false.  Deviation: equal (topic, value)
+// pairs of DocTopicCatchwordSums.tsv go by document ascending (the reference's sort is unstable).
 // Not mirrored (dead under the shipped hyper-parameters or outside the path): load_preprocessed_data_from_file,
-// print_doctopic (accepted, unused: the reference's use is commented out), compute_input_svd, construct_edge_topics_v1.
+// compute_input_svd, construct_edge_topics_v1.
 #pragma once
 #include <sys/stat.h>
 
@@ -221,6 +227,85 @@ void write_doc_topic_lines(FILE* fp, const int64_t* offs, const TopicT* topic, c
       for (int i = 0; i < 5 && topic[row * 5 + i] >= 0; ++i) put(row, (int64_t)(row * 5 + i));
   }
   std::fwrite(pending.data(), 1, pending.size(), fp);
+}
+// One line of TopTwoTopicsPerDoc.txt: three concat_int decimals, the numbers as printed.  Returns the length (at most 33).
+inline size_t top_two_line_text(uint64_t doc_number, uint64_t t1_number, uint64_t t2_number, char* out) {
+  size_t len = 0;
+  const uint64_t v[3] = {doc_number, t1_number, t2_number};
+  for (int i = 0; i < 3; ++i) {
+    const std::string digits = std::to_string(v[i]);
+    std::memcpy(out + len, digits.data(), digits.size());
+    len += digits.size();
+    out[len++] = i < 2 ? '\t' : '\n';
+  }
+  return len;
+}
+// The three host loops the device formatter (isle_hip_doc_report_text) replaces, kept as the statement of its bytes.  Everything is
+// printed 1-based.
+// DocCatchword.tsv (ISLETrainer::output_doc_topic, src/trainer.cpp:946-964): documents ascending; beside every column of A (rows
+// ascending) the walk over the catchwords sorted by word, a line for every entry whose word is one.  catchword_words: ascending.
+// nv: the normalised values of A (normalized_vals_CSC).
+inline std::string doc_catchword_text(const std::vector<uint32_t>& catchword_words, const int64_t* offs, const uint32_t* rows, const float* nv,
+                                      uint64_t docs) {
+  std::string out;
+  char text[40];
+  for (uint64_t doc = 0; doc < docs; ++doc) {
+    auto w_iter = catchword_words.begin();
+    for (int64_t pos = offs[doc]; pos < offs[doc + 1]; ++pos) {
+      while (w_iter != catchword_words.end() && *w_iter < rows[pos]) ++w_iter;
+      if (w_iter == catchword_words.end()) continue;
+      if (rows[pos] == *w_iter) out.append(text, doc_line_text(doc + 1, (uint64_t)*w_iter + 1, nv[pos], text));
+    }
+  }
+  return out;
+}
+// DocTopicCatchwordSums.tsv (:979-983): the (document, topic, sum) triples (given as CSR over the documents, topics ascending) in the
+// order construct_topic_model leaves them in (src/sparseMatrix.cpp:715-718): topic ascending, then value descending.  The reference's
+// parallel_sort is unstable; here equal (topic, value) pairs go by document ascending (a stable sort of the (document, topic) order).
+// by_doc: the resident order instead (ISLE_DOCREPORT_TOPIC_SUMS_BY_DOC).
+inline std::string doc_topic_sums_text(const int64_t* offs, const uint32_t* topic, const float* val, uint64_t docs, bool by_doc = false) {
+  std::vector<std::tuple<uint64_t, uint32_t, float>> sums;
+  for (uint64_t doc = 0; doc < docs; ++doc)
+    for (int64_t i = offs[doc]; i < offs[doc + 1]; ++i) sums.emplace_back(doc, topic[i], val[i]);
+  if (!by_doc)
+    std::stable_sort(sums.begin(), sums.end(), [](const std::tuple<uint64_t, uint32_t, float>& l, const std::tuple<uint64_t, uint32_t, float>& r) {
+      return std::get<1>(l) < std::get<1>(r) || (std::get<1>(l) == std::get<1>(r) && std::get<2>(l) > std::get<2>(r));
+    });
+  std::string out;
+  char text[40];
+  for (const auto& s : sums) out.append(text, doc_line_text(std::get<0>(s) + 1, (uint64_t)std::get<1>(s) + 1, std::get<2>(s), text));
+  return out;
+}
+// The top-two topics of a document from its sums (src/sparseMatrix.cpp:687-708): -1 where it has fewer than two.
+inline void top_two_from_sums(const int64_t* offs, const uint32_t* topic, const float* val, uint64_t docs, std::vector<int32_t>& top1,
+                              std::vector<int32_t>& top2) {
+  top1.assign(docs, -1);
+  top2.assign(docs, -1);
+  for (uint64_t doc = 0; doc < docs; ++doc) {
+    float max = 0.0f, max2 = 0.0f;
+    int max_topic = -1, max2_topic = -1;
+    for (int64_t i = offs[doc]; i < offs[doc + 1]; ++i) {
+      if (val[i] > max) {
+        max2 = max;
+        max2_topic = max_topic;
+        max = val[i];
+        max_topic = (int)topic[i];
+      } else if (val[i] > max2) {
+        max2 = val[i];
+        max2_topic = (int)topic[i];
+      }
+    }
+    top1[doc] = max_topic;
+    top2[doc] = max2_topic;
+  }
+}
+// TopTwoTopicsPerDoc.txt (ISLETrainer::print_top_two_topics, :1029-1035): documents ascending, those that have both topics.
+inline std::string top_two_text(const int32_t* top1, const int32_t* top2, uint64_t docs) {
+  std::string out;
+  char text[40];
+  for (uint64_t doc = 0; doc < docs; ++doc)
+    if (top1[doc] >= 0 && top2[doc] >= 0) out.append(text, top_two_line_text(doc + 1, (uint64_t)top1[doc] + 1, (uint64_t)top2[doc] + 1, text));
+  return out;
 }
 // The rule of ITERATIVE_DATA_LOAD on the host (src/trainer.cpp:232-371): the fed entries (zero counts already left out) sorted stably by
 // (doc, word), the first fed of equal pairs kept, the CSC of A with its empty documents.  The trainer's data goes through the device feed
@@ -661,7 +746,26 @@ class ISLETrainer {
     log->next_time_secs("Output model");
     output_top_words();
     log->next_time_secs("Output topwords");
+    if (flag_print_doctopic) output_doc_topic();  // :664-667, commented out in the reference
   }
+  // src/trainer.cpp:874-991: DocCatchword.tsv and DocTopicCatchwordSums.tsv, formatted on the device (isle_hip_doc_report_text);
+  // trainer_detail::doc_catchword_text / doc_topic_sums_text state the bytes
+  void output_doc_topic() {
+    if (!is_training_complete) throw std::runtime_error("output_doc_topic() before train()");
+    uint64_t ncatch = 0;
+    for (doc_id_t t = 0; t < num_topics; ++t) ncatch += catchwords[t].size();
+    log->print("Total number of catchwords: " + std::to_string(ncatch) + "\n");
+    B_fl_CSC->write_doc_report(log_dir + "/DocCatchword.tsv", ISLE_DOCREPORT_CATCHWORDS);
+    B_fl_CSC->write_doc_report(log_dir + "/DocTopicCatchwordSums.tsv", ISLE_DOCREPORT_TOPIC_SUMS);
+    log->next_time_secs("Writing document catchword weights");
+  }
+  // src/trainer.cpp:1008-1040: TopTwoTopicsPerDoc.txt from the resident top-two topics; trainer_detail::top_two_text states the bytes
+  void print_top_two_topics() {
+    if (!is_training_complete) throw std::runtime_error("print_top_two_topics() before train()");
+    B_fl_CSC->write_doc_report(log_dir + "/TopTwoTopicsPerDoc.txt", ISLE_DOCREPORT_TOP_TWO);
+  }
+  const std::vector<word_id_t>* catchword_lists() const { return catchwords; }  // after train(): [num_topics], words ascending
+  FPSparseMatrixHip* matrix() { return B_fl_CSC; }
   // src/trainer.cpp:673-685 -> construct_edge_topics_v2 :1116-1167
   void train_edge_topics() {
     if (!flag_construct_edge_topics) throw std::runtime_error("train_edge_topics() without construct_edge_topics");

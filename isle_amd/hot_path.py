@@ -116,6 +116,17 @@ def doc_line_text(doc_number, topic_number, w):
     return -1 if n < 0 else buf.raw[:n]
 
 
+DOC_REPORT_KINDS = {"catchwords": 0, "topic_sums": 1, "topic_sums_by_doc": 2, "top_two": 3}   # ISLE_DOCREPORT_*
+
+
+def top_two_line_text(doc_number, t1_number, t2_number):
+    """One line "<doc>\\t<top1>\\t<top2>\\n" of TopTwoTopicsPerDoc.txt for the numbers as printed (isle_hip_top_two_line_text, the host
+    copy of what the kernels of doc_report.hip compile) -> bytes, or -1 for a number >= 0x7fffffff.  No GPU needed."""
+    buf = C.create_string_buffer(40)
+    n = load_library().isle_hip_top_two_line_text(int(doc_number), int(t1_number), int(t2_number), buf)
+    return -1 if n < 0 else buf.raw[:n]
+
+
 def parse_weight(token, format="sparse"):
     """One weight token of a model file as the library's readers take it (isle_hip_parse_weight, the host copy of the rule the loader's
     kernels compile): <digits>[.<digits>] -> np.float32; "nan" under "dense" -> the quiet NaN.  None for a token outside the grammar.
@@ -795,6 +806,34 @@ class HotPath:
     def infer_text_size(self, what="entries", rows=None, base=1):
         """The counting pass alone.  -> (nbytes, nlines)."""
         return self._infer_text_call(what, rows, base, None)
+
+    # ---- the trainer's per-document report files formatted on the device (include/isle_hip.h, isle_hip_doc_report_text) -----------
+    def _doc_report_call(self, what, docs, consume):
+        kind = DOC_REPORT_KINDS[what] if isinstance(what, str) else int(what)
+        b, e = (0, getattr(self, "_a_shape", (0, 0, 0))[1]) if docs is None else (int(docs[0]), int(docs[1]))
+        return self._text_call(lambda sink, nb, nl: self._lib.isle_hip_doc_report_text(self._h, kind, b, e, sink, None, nb, nl), consume)
+
+    def doc_report_text(self, what, docs=None):
+        """A per-document report file of the trainer for documents docs (None: all of A; or (begin, end)), formatted on the device from
+        what find_catchwords / construct_topic_model left resident; every number is printed 1-based:
+          "catchwords"         DocCatchword.tsv: "<doc>\\t<word>\\t<normalised value>\\n" for every entry of A whose word is a catchword
+          "topic_sums"         DocTopicCatchwordSums.tsv: "<doc>\\t<topic>\\t<sum>\\n", topic ascending, then value descending, ties by
+                               document ascending (the reference's order up to its unstable ties)
+          "topic_sums_by_doc"  the same lines, (document, topic) ascending
+          "top_two"            TopTwoTopicsPerDoc.txt: "<doc>\\t<top1>\\t<top2>\\n" for every document that has both
+        -> bytes."""
+        parts = []
+        self._doc_report_call(what, docs, lambda mv: parts.append(bytes(mv)))
+        return b"".join(parts)
+
+    def write_doc_report(self, path, what, docs=None):
+        """doc_report_text streamed into a file piece by piece; the whole text is never held.  -> (nbytes, nlines)."""
+        with open(path, "wb") as f:
+            return self._doc_report_call(what, docs, f.write)
+
+    def doc_report_size(self, what, docs=None):
+        """The counting pass alone.  -> (nbytes, nlines)."""
+        return self._doc_report_call(what, docs, None)
 
     def avg_doc_sz(self):
         """avg_doc_sz of the resident count matrix (populate_CSC, src/sparseMatrix.cpp:87-98: floor(tokens / non-empty documents))."""
