@@ -259,7 +259,7 @@ struct isle_ctx {
   DevBuf<float> p_model;           // V x k col-major
   DevBuf<uint64_t> p_avg_acc;      // V x k (lo, hi) pairs: exact fixed-point sums of the average model (avg_model.hip)
   DevBuf<float> p_avg_model;       // V x k col-major, the cluster-average model
-  DevBuf<uint32_t> mt_sizes;       // the text formatters (model_text.hip, infer_text.hip): bytes per tile
+  DevBuf<uint32_t> mt_sizes;       // the text formatters (model_text.hip, text_tiles.h): bytes per tile
   DevBuf<uint64_t> mt_offs, mt_blk, mt_stat;  // their exclusive scan (+ its scratch); entries emitted, first entry outside the domain
   DevBuf<unsigned char> mt_text[2];  // one chunk of text each (<= ISLE_TEXT_CHUNK_BYTES), formatted while the other one is copied and consumed
   PinBuf mt_pin[2];
@@ -633,7 +633,7 @@ int k_post_edge(isle_ctx* c, const int64_t* pairs_dev, int n, float a, float b, 
 constexpr uint64_t ISLE_TEXT_CHUNK_BYTES = 16ull << 20;
 int k_model_text(isle_ctx* c, const float* model_dev, uint64_t V, uint64_t ncols, const int64_t* pairs_dev, float a, float b, int format,
                  isle_text_sink_fn sink, void* user, uint64_t* nbytes, uint64_t* nentries);
-// ... and the delivery both text formatters share: a text of `total` > 0 bytes whose ntiles tiles lie at offs_dev (ntiles + 1 offsets on
+// ... and the delivery every text formatter shares: a text of `total` > 0 bytes whose ntiles tiles lie at offs_dev (ntiles + 1 offsets on
 // the device) goes to `sink` in chunks of at most ISLE_TEXT_CHUNK_BYTES cut between tiles (at multiples of `group` tiles where possible);
 // write(t0, n, out) launches the formatting of tiles [t0, t0 + n) into out on the context's stream
 int k_text_pump(isle_ctx* c, const char* who, const uint64_t* offs_dev, uint64_t ntiles, uint64_t total, uint64_t group, isle_text_sink_fn sink,

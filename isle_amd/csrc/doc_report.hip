@@ -5,7 +5,7 @@
 // those of doc_text.h: two integers and a weight (isle_hip_doc_line_text), or three integers (isle_hip_top_two_line_text); every number is
 // printed 1-based.
 //
-// A line is a candidate index L of the call, cut into tiles of MT_TILE = 1024 consecutive candidates (infer_text.hip's scheme):
+// A line is a candidate index L of the call, cut into tiles of MT_TILE = 1024 consecutive candidates:
 //   ISLE_DOCREPORT_CATCHWORDS         L = an entry of A in [a_offs[doc_begin], a_offs[doc_end]); printed iff p_catch[a_rows] >= 0 (the
 //                                     reference's merge walk beside the column, :946-964: a word is a catchword of at most one topic)
 //   ISLE_DOCREPORT_TOPIC_SUMS_BY_DOC  L = an entry of the (document, topic) sums p_dts_* of the documents; every candidate is printed
@@ -20,13 +20,10 @@
 // comes from a search of its entry in the global offsets (it_row_of), about log2(documents) dependent loads per line; the alternative, a
 // second payload carried through the sort, is NOT measured against it.
 // Whether p_catch should be staged in LDS is not measured either (400 KB at 100 k words: it lives in L2); it is read where it lies.
-//   dr_count_k   which candidates print (a tile that prints nothing gets the size 0 here and stages no offsets), then bytes per tile,
-//                lines printed (64-bit) and the first printed candidate outside the writers' domain (a number >= 0x7fffffff; a weight
-//                that is negative, NaN, infinite or >= 2^31)
-//   the 64-bit exclusive scan of scan.h
-//   dr_write_k   tiles of size 0 are skipped before anything is read; else it_write_k's scheme (lengths, a block scan, the characters
-//                into LDS at the tile's alignment modulo 16, mt_store_tile)
-// and the text leaves through k_text_pump (model_text.hip).  Nothing resident is written: the sort works in buffers of the call.
+// The tiles are counted, placed and written by the skeleton of text_tiles.h, of which DrSrc below is the source: its probe says which
+// candidates print, so a tile that prints nothing stages no offsets.  A printed candidate is refused where it lies outside the writers'
+// domain (a number >= 0x7fffffff; a weight that is negative, NaN, infinite or >= 2^31).  Nothing resident is written: the sort works in
+// buffers of the call.
 #include <algorithm>
 #include <vector>
 
@@ -34,12 +31,15 @@
 #include "doc_text.h"
 #include "scan.h"
 #include "text_format.h"
+#include "text_tiles.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 struct DrSrc {
+  static constexpr int kWindow = IT_WIN;
+  static constexpr bool kSkipEmpty = true;  // most entries of A are no catchwords
   int what;
   const int64_t* off;      // CATCHWORDS: a_offs; the sums: p_dts_off (documents + 1)
   const uint32_t* col;     // CATCHWORDS: a_rows; the sums: p_dts_topic
@@ -50,54 +50,63 @@ struct DrSrc {
   uint64_t row_begin, row_end;
   uint64_t first;          // off[row_begin]; TOP_TWO: row_begin — candidate L is element first + L
   uint64_t ncand;
-};
-struct DrLine {
-  uint64_t a, b, c;  // as printed; c: TOP_TWO only
-  float w;
-  bool present;
-};
-
-__device__ inline bool dr_windowed(const DrSrc& s) { return s.what == ISLE_DOCREPORT_CATCHWORDS || s.what == ISLE_DOCREPORT_TOPIC_SUMS_BY_DOC; }
-
-// candidate L of the call: whether it prints, and everything of its line that needs no row search
-__device__ inline DrLine dr_probe(const DrSrc& s, uint64_t L) {
-  DrLine x;
-  x.a = x.b = x.c = 1u;
-  x.w = 0.f;
-  if (s.what == ISLE_DOCREPORT_TOP_TWO) {
-    const uint64_t row = s.first + L;
-    const int32_t t1 = s.top1[row], t2 = s.top2[row];
-    x.present = t1 >= 0 && t2 >= 0;
+  struct Tile {
+    uint32_t n;
+    uint64_t L0;  // the tile's first candidate
+  };
+  struct Line {
+    uint64_t a, b, c;  // as printed; c: TOP_TWO only
+    float w;
+    bool present;
+  };
+  __device__ bool windowed() const { return what == ISLE_DOCREPORT_CATCHWORDS || what == ISLE_DOCREPORT_TOPIC_SUMS_BY_DOC; }
+  __device__ Tile open(uint64_t tile) const { return Tile{(uint32_t)min((uint64_t)MT_TILE, ncand - tile * MT_TILE), tile * MT_TILE}; }
+  __device__ void stage(const Tile& t, uint32_t* win, uint64_t* row0) const {
+    if (windowed()) it_stage_window(off, row_begin, row_end, first + t.L0, win, row0);
+  }
+  // whether the candidate prints, and everything of its line that needs no row search
+  __device__ Line probe(const Tile& t, uint32_t l) const {
+    Line x;
+    x.a = x.b = x.c = 1u;
+    x.w = 0.f;
+    if (what == ISLE_DOCREPORT_TOP_TWO) {
+      const uint64_t row = first + t.L0 + l;
+      const int32_t t1 = top1[row], t2 = top2[row];
+      x.present = t1 >= 0 && t2 >= 0;
+      if (x.present) {
+        x.a = row + 1u;
+        x.b = (uint64_t)t1 + 1u;
+        x.c = (uint64_t)t2 + 1u;
+      }
+      return x;
+    }
+    const uint64_t at = first + (what == ISLE_DOCREPORT_TOPIC_SUMS ? (uint64_t)perm[t.L0 + l] : t.L0 + l);
+    const uint32_t cl = col[at];
+    x.present = what != ISLE_DOCREPORT_CATCHWORDS || catchw[cl] >= 0;
     if (x.present) {
-      x.a = row + 1u;
-      x.b = (uint64_t)t1 + 1u;
-      x.c = (uint64_t)t2 + 1u;
+      x.b = (uint64_t)cl + 1u;
+      x.w = val[at];
     }
     return x;
   }
-  const uint64_t at = s.first + (s.what == ISLE_DOCREPORT_TOPIC_SUMS ? (uint64_t)s.perm[L] : L);
-  const uint32_t col = s.col[at];
-  x.present = s.what != ISLE_DOCREPORT_CATCHWORDS || s.catchw[col] >= 0;
-  if (x.present) {
-    x.b = (uint64_t)col + 1u;
-    x.w = s.val[at];
+  // ... and the document of a printed entry
+  __device__ void place(const Tile& t, uint32_t l, const uint32_t* win, const uint64_t* row0, Line& x) const {
+    if (windowed()) {
+      x.a = it_window_row(off, row_end, first + t.L0 + l, l, t.n, win, *row0) + 1u;
+    } else if (what == ISLE_DOCREPORT_TOPIC_SUMS) {
+      x.a = it_row_of(off, row_begin, row_end, first + (uint64_t)perm[t.L0 + l]) + 1u;
+    }
   }
-  return x;
-}
-// ... and the document of a printed entry: candidate l < nl of the tile
-__device__ inline void dr_place(const DrSrc& s, uint64_t tile, uint32_t l, uint32_t nl, const uint32_t* win, uint64_t row0, DrLine& x) {
-  if (dr_windowed(s)) {
-    x.a = it_window_row(s.off, s.row_end, s.first + tile * MT_TILE + l, l, nl, win, row0) + 1u;
-  } else if (s.what == ISLE_DOCREPORT_TOPIC_SUMS) {
-    x.a = it_row_of(s.off, s.row_begin, s.row_end, s.first + (uint64_t)s.perm[tile * MT_TILE + l]) + 1u;
+  __device__ bool in_domain(const Line& x) const { return x.a < IT_NUM_END && x.b < IT_NUM_END && x.c < IT_NUM_END && mt_weight_in_domain(x.w); }
+  __device__ uint32_t len(const Tile&, uint32_t, const Line& x) const {
+    return what == ISLE_DOCREPORT_TOP_TWO ? it_line3_len((uint32_t)x.a, (uint32_t)x.b, (uint32_t)x.c) : it_line_len((uint32_t)x.a, (uint32_t)x.b, x.w);
   }
-}
-__device__ inline bool dr_in_domain(const DrSrc& s, const DrLine& x) {
-  return x.a < IT_NUM_END && x.b < IT_NUM_END && x.c < IT_NUM_END && mt_weight_in_domain(x.w);
-}
-__device__ inline uint32_t dr_len(const DrSrc& s, const DrLine& x) {
-  return s.what == ISLE_DOCREPORT_TOP_TWO ? it_line3_len((uint32_t)x.a, (uint32_t)x.b, (uint32_t)x.c) : it_line_len((uint32_t)x.a, (uint32_t)x.b, x.w);
-}
+  __device__ char* put(const Tile&, uint32_t, const Line& x, char* p) const {
+    return what == ISLE_DOCREPORT_TOP_TWO ? it_put_line3(p, (uint32_t)x.a, (uint32_t)x.b, (uint32_t)x.c) : it_put_line(p, (uint32_t)x.a, (uint32_t)x.b, x.w);
+  }
+  __device__ char extra(const Tile&) const { return 0; }
+  __device__ uint64_t key(const Tile& t, uint32_t l) const { return t.L0 + l; }
+};
 
 // key[i] = (topic << 32) | ~bits(value) of entry first + i, payload i
 __global__ __launch_bounds__(MT) void dr_key_k(const uint32_t* __restrict__ topic, const float* __restrict__ val, uint64_t first, uint64_t n,
@@ -105,93 +114,6 @@ __global__ __launch_bounds__(MT) void dr_key_k(const uint32_t* __restrict__ topi
   for (uint64_t i = (uint64_t)blockIdx.x * MT + threadIdx.x; i < n; i += (uint64_t)gridDim.x * MT) {
     key[i] = ((uint64_t)topic[first + i] << 32) | (uint64_t)(~__float_as_uint(val[first + i]));
     idx[i] = (uint32_t)i;
-  }
-}
-
-// stat[0] += lines printed; stat[1] = min over the offending printed candidates of L
-__global__ __launch_bounds__(MT) void dr_count_k(DrSrc src, uint64_t ntiles, uint32_t* __restrict__ sizes, unsigned long long* __restrict__ stat) {
-  __shared__ uint32_t win[IT_WIN];
-  __shared__ uint64_t row0;
-  __shared__ uint32_t shb[MT / ISLE_WAVE], shc[MT / ISLE_WAVE];
-  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const uint32_t nl = (uint32_t)min((uint64_t)MT_TILE, src.ncand - tile * MT_TILE);
-    DrLine x[MT_ITEMS];
-    uint32_t cand = 0;
-#pragma unroll
-    for (int i = 0; i < MT_ITEMS; ++i) {
-      const uint32_t l = threadIdx.x * MT_ITEMS + i;
-      x[i].present = false;
-      if (l < nl) x[i] = dr_probe(src, tile * MT_TILE + l);
-      cand += x[i].present ? 1u : 0u;
-    }
-    if (mt_block_sum(cand, shc) == 0) {  // the same for every thread of the block: nothing to place, nothing to store
-      if (threadIdx.x == 0) sizes[tile] = 0;
-      continue;
-    }
-    if (dr_windowed(src)) it_stage_window(src.off, src.row_begin, src.row_end, src.first + tile * MT_TILE, win, &row0);
-    uint32_t bytes = 0, cnt = 0;
-    unsigned long long bad = ~0ull;
-#pragma unroll
-    for (int i = 0; i < MT_ITEMS; ++i) {
-      if (!x[i].present) continue;
-      const uint32_t l = threadIdx.x * MT_ITEMS + i;
-      dr_place(src, tile, l, nl, win, row0, x[i]);
-      if (!dr_in_domain(src, x[i])) {
-        bad = min(bad, (unsigned long long)(tile * MT_TILE + l));
-      } else {
-        ++cnt;
-        bytes += dr_len(src, x[i]);
-      }
-    }
-    if (bad != ~0ull) atomicMin(&stat[1], bad);
-    const uint32_t tb = mt_block_sum(bytes, shb), tc = mt_block_sum(cnt, shc);
-    if (threadIdx.x == 0) {
-      sizes[tile] = tb;
-      if (tc) atomicAdd(&stat[0], (unsigned long long)tc);
-    }
-  }
-}
-
-// tiles [tile0, tile0 + n) -> out[offs[tile] - offs[tile0] ...); out is 16-byte aligned
-__global__ __launch_bounds__(MT) void dr_write_k(DrSrc src, uint64_t tile0, uint64_t n, const uint64_t* __restrict__ offs, unsigned char* __restrict__ out) {
-  __shared__ uint4 lines[MT_LDS_LINES];
-  __shared__ uint32_t sh[MT];
-  __shared__ uint32_t win[IT_WIN];
-  __shared__ uint64_t row0;
-  char* const text = reinterpret_cast<char*>(lines);
-  const uint64_t base = offs[tile0];
-  for (uint64_t tile = tile0 + blockIdx.x; tile < tile0 + n; tile += gridDim.x) {
-    const uint64_t dst0 = offs[tile] - base;
-    const uint32_t nbytes = (uint32_t)(offs[tile + 1] - offs[tile]);
-    if (nbytes == 0) continue;  // the same for every thread of the block
-    const uint32_t shift = (uint32_t)(dst0 & 15u);  // LDS position == position in out, modulo 16
-    const uint32_t nl = (uint32_t)min((uint64_t)MT_TILE, src.ncand - tile * MT_TILE);
-    if (dr_windowed(src)) it_stage_window(src.off, src.row_begin, src.row_end, src.first + tile * MT_TILE, win, &row0);
-    DrLine x[MT_ITEMS];
-    uint32_t mine = 0;
-#pragma unroll
-    for (int i = 0; i < MT_ITEMS; ++i) {
-      const uint32_t l = threadIdx.x * MT_ITEMS + i;
-      x[i].present = false;
-      if (l < nl) {
-        x[i] = dr_probe(src, tile * MT_TILE + l);
-        if (x[i].present) {
-          dr_place(src, tile, l, nl, win, row0, x[i]);
-          if (!dr_in_domain(src, x[i])) x[i].present = false;  // (the counting pass has refused such a call)
-        }
-      }
-      if (x[i].present) mine += dr_len(src, x[i]);
-    }
-    uint32_t total;
-    const uint32_t at = isle_scan::block_exclusive<uint32_t>(mine, sh, &total);
-    char* p = text + shift + at;
-#pragma unroll
-    for (int i = 0; i < MT_ITEMS; ++i) {
-      if (!x[i].present) continue;
-      p = src.what == ISLE_DOCREPORT_TOP_TWO ? it_put_line3(p, (uint32_t)x[i].a, (uint32_t)x[i].b, (uint32_t)x[i].c)
-                                             : it_put_line(p, (uint32_t)x[i].a, (uint32_t)x[i].b, x[i].w);
-    }
-    mt_store_tile(lines, shift, nbytes, out, dst0);
   }
 }
 
@@ -263,26 +185,9 @@ int k_doc_report_text(isle_ctx* c, int what, uint64_t doc_begin, uint64_t doc_en
     ISLECHK(k_sort_pairs_u64(c, key_a.p, idx_a.p, key_b.p, idx_b.p, src.ncand, key_bits, &in_a));
     src.perm = in_a ? idx_a.p : idx_b.p;
   }
-  HIPCHK(c, c->mt_sizes.reserve(ntiles));
-  HIPCHK(c, c->mt_offs.reserve(ntiles + 1));
-  HIPCHK(c, c->mt_blk.reserve(isle_scan::scan_scratch_elems(ntiles)));
-  HIPCHK(c, c->mt_stat.reserve(2));
-  unsigned long long* stat = (unsigned long long*)c->mt_stat.p;
-  const uint64_t init[2] = {0, ~0ull};
-  uint64_t h[3] = {0, ~0ull, 0};
-  {
-    TimeScope ts(c, ISLE_T_POST);
-    HIPCHK(c, hipMemcpyAsync(stat, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(dr_count_k, dim3((unsigned)std::min<uint64_t>(ntiles, cap)), dim3(MT), 0, c->stream, src, ntiles, c->mt_sizes.p, stat);
-    LAUNCH_CHECK(c);
-    HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, uint64_t>(c->stream, c->mt_sizes.p, ntiles, c->mt_offs.p, c->mt_blk.p)));
-  }
-  HIPCHK(c, hipMemcpyAsync(h, stat, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h + 2, c->mt_offs.p + ntiles, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (h[1] != ~0ull) {
+  return k_text_tiles(c, "doc_report_text", ISLE_T_POST, src, ntiles, 1, sink, user, nbytes, nlines, [&](uint64_t key) -> int {
     // name the line (its document: a search in the offsets, fetched for this message only)
-    uint64_t doc = src.first + h[1];
+    uint64_t doc = src.first + key;
     if (what == ISLE_DOCREPORT_TOP_TWO) {
       int32_t t[2] = {0, 0};
       HIPCHK(c, hipMemcpy(&t[0], src.top1 + doc, sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -290,10 +195,10 @@ int k_doc_report_text(isle_ctx* c, int what, uint64_t doc_begin, uint64_t doc_en
       return isle_fail(c, ISLE_E_ARG, "doc_report_text(top_two): the line of document %llu, topics %d and %d (0-based) is outside the writers' domain: a number >= 0x7fffffff",
                        (unsigned long long)doc, (int)t[0], (int)t[1]);
     }
-    uint64_t at = src.first + h[1];
+    uint64_t at = src.first + key;
     if (what == ISLE_DOCREPORT_TOPIC_SUMS) {
       uint32_t e = 0;
-      HIPCHK(c, hipMemcpy(&e, src.perm + h[1], sizeof(e), hipMemcpyDeviceToHost));
+      HIPCHK(c, hipMemcpy(&e, src.perm + key, sizeof(e), hipMemcpyDeviceToHost));
       at = src.first + e;
     }
     std::vector<int64_t> off(doc_end - doc_begin + 1);
@@ -307,16 +212,6 @@ int k_doc_report_text(isle_ctx* c, int what, uint64_t doc_begin, uint64_t doc_en
                      "doc_report_text(%s): the line of document %llu, %s %u (0-based), value %g is outside the writers' domain: a number >= 0x7fffffff, "
                      "or a weight that is negative, NaN, infinite or >= 2^31",
                      dr_name(what), (unsigned long long)doc, what == ISLE_DOCREPORT_CATCHWORDS ? "word" : "topic", col, (double)w);
-  }
-  const uint64_t total = h[2];
-  if (nbytes) *nbytes = total;
-  if (nlines) *nlines = h[0];
-  if (!sink || total == 0) return 0;
-  return k_text_pump(c, "doc_report_text", c->mt_offs.p, ntiles, total, 1, sink, user, [&](uint64_t t0, uint64_t n, unsigned char* out) -> int {
-    TimeScope ts(c, ISLE_T_POST);
-    hipLaunchKernelGGL(dr_write_k, dim3((unsigned)std::min<uint64_t>(n, cap)), dim3(MT), 0, c->stream, src, t0, n, c->mt_offs.p, out);
-    LAUNCH_CHECK(c);
-    return 0;
   });
 }
 

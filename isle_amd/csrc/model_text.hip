@@ -22,7 +22,9 @@
 // Floating-point contraction is switched off for this whole file, host and device (text_format.h gives the reason); mt_weight there is
 // the one copy of the digit rule for both sides.  The only fused operation left is the explicit fmaf of the edge entries.
 //
-// k_text_pump below is the delivery both text formatters share (infer_text.hip is the other one).
+// mt_count_k / mt_write_k and the driver below are this file's own copy of the count / scan / write scheme that text_tiles.h holds for
+// the per-document formatters: on that skeleton the sparse file-sink case measured above the largest repetition of these kernels
+// (profiles/model_text_c2_*.jsonl), so this formatter keeps them.  k_text_pump below is the delivery every text formatter shares.
 #include <algorithm>
 #include <cstring>
 #include <functional>

@@ -1,6 +1,7 @@
-// isle_amd/csrc/text_format.h — what the text formatters (model_text.hip, infer_text.hip) share: the library's one copy of the digit
-// rule (mt_weight, host and device), the decimal integers of MMappedOutput::concat_int, the tile geometry, the block sum and the way a
-// tile leaves LDS as whole 16-byte lines.  The chunk pump both formatters deliver through is k_text_pump (model_text.hip, common.h).
+// isle_amd/csrc/text_format.h — what the text formatters (model_text.hip, infer_text.hip, doc_report.hip) share below their count and
+// write kernels (model_text.hip's own, text_tiles.h for the other two): the library's one copy of the digit rule (mt_weight, host and
+// device), the decimal integers of MMappedOutput::concat_int, the tile geometry, the block sum and the way a tile leaves LDS as whole
+// 16-byte lines.  The chunk pump they all deliver through is k_text_pump (model_text.hip, common.h).
 //
 // Floating-point contraction: hipcc contracts a * b - c into an fma by default, which would take the fraction digits from an unrounded
 // product, and this toolchain's __fmul_rn / __fsub_rn are plain operators that contract all the same (seen in the ISA).  Contraction is

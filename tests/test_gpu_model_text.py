@@ -80,6 +80,32 @@ def test_host_model_both_formats(hp, shape, content):
         assert len(dense_text_np(M)) > 2 * CHUNK                         # several whole-column pieces
 
 
+def one_row_columns():
+    """a 1 x 64 dense model of exact zeros, NaN and weights of one to seven whole digits: every column is one tile of 5 or 10 to 15 bytes"""
+    vals = np.array([0.0, np.nan, 0.5, 12.25, 345.125, 6789.5, 12345.75, 999999.9, 1000001.5], np.float32)
+    return np.asfortranarray(vals[np.random.default_rng(3).integers(0, vals.size, size=64)][None, :])
+
+
+def test_every_store_alignment_of_the_smallest_tiles(hp):
+    """The store path out of LDS (mt_store_tile, isle_amd/csrc/text_format.h) at every alignment of a tile's first byte modulo 16, and
+    for a tile that owns no whole 16-byte line and shares its only one with both neighbours."""
+    M = one_row_columns()
+    want = dense_text_np(M)
+    ends = np.flatnonzero(np.frombuffer(want, np.uint8) == ord("\n")) + 1   # V = 1: a column is a tile is a line
+    starts = np.concatenate([[0], ends[:-1]])
+    assert len(ends) == 64 and set(ends - starts) <= {5, 10, 11, 12, 13, 14, 15}
+    assert set(int(x) % 16 for x in starts) == set(range(16))
+    inside = (starts // 16 == (ends - 1) // 16) & (starts % 16 != 0) & (ends % 16 != 0)
+    assert inside[1:-1].any()
+    assert hp.model_text(M, "dense") == want
+
+
+@pytest.mark.parametrize("fmt", ["sparse", "dense"])
+def test_a_second_tile_of_one_row_in_every_column(hp, fmt):
+    M = torture(1025, 3, seed=11)
+    assert hp.model_text(M, fmt) == RESTATE[fmt](M)
+
+
 def test_all_skipped_model_gives_no_bytes_and_no_sink_call(hp):
     M = np.asfortranarray(np.full((3000, 5), 1e-9, np.float32))
     M[::3] = 0

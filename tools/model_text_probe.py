@@ -53,7 +53,7 @@ def device_case(hp, case, call, **extra):
             if rep:
                 walls.append(wall)
                 devs.append(tg[0])
-        out.update({"wall_ms_" + name: med(walls), "device_ms_" + name: med(devs), "launches_" + name: tg[1]})
+        out.update({"wall_ms_" + name: med(walls), "device_ms_" + name: med(devs), "device_ms_all_" + name: [round(d, 3) for d in devs], "launches_" + name: tg[1]})
     out.update(bytes=nb, entries=ne, **extra)
     hp.timing_enable(0)
     return out
