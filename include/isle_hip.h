@@ -129,6 +129,39 @@ int isle_hip_feed_entries(isle_ctx* ctx, uint64_t n, const uint32_t* docs, const
 int isle_hip_feed_entries_pieces(isle_ctx* ctx, uint64_t n, const uint32_t* docs, const uint32_t* words, const uint32_t* counts,
                                  uint64_t piece_entries);
 int isle_hip_feed_finalize(isle_ctx* ctx, uint64_t doc_offset, uint64_t docs_global, uint64_t* entries_fed, uint64_t* nnz);
+/* The count matrix from tdf text that arrives in pieces: isle_hip_ingest_tdf without holding the text, on the host or on the device.
+ * Let T be the concatenation of all bytes committed or written between tdf_begin and tdf_finalize.  Pieces may be cut anywhere: inside a
+ * field, between '\r' and '\n', inside a run of blanks, one byte at a time.  After a successful tdf_finalize the context's count matrix,
+ * entries_read and nnz are exactly what isle_hip_ingest_tdf(T, ..., max_entries) would have produced; where that call would fail, the stream
+ * fails with ISLE_E_ARG, the same wording of the kind and the same 1-based line number of T ("<kind> on line <n>": lines are counted over
+ * every '\n' since tdf_begin, blank lines included), and a max_entries mismatch reads as it does there.  A line may be of any length,
+ * longer than a piece or than many; such a line is scanned again with every piece it outlasts, so its cost grows with the square of its
+ * length.  Single rank only; vocab_size and num_docs 1 .. 0xfffffff0.
+ * tdf_begin opens a stream, discarding an open stream or an open feed of triples (isle_hip_feed_begin likewise discards an open stream):
+ * the two share one entry store and exclude each other, so isle_hip_feed_entries / feed_finalize on a text stream, and the tdf calls on a
+ * feed or with no stream open, are ISLE_E_ARG.  reserve_entries: capacity hint for the store (0 allowed; it doubles when a piece might not
+ * fit).  piece_bytes: 0 = the library's own piece size (16 MiB); a smaller value is honoured down to 1 (the result does not depend on it:
+ * it exists so that tests can put cuts everywhere), a larger one means the library's own.  The context's current count matrix stays valid
+ * until tdf_finalize succeeds: every check (last line, max_entries) comes before the sort installs anything.
+ * tdf_acquire hands out one of the stream's two page-locked buffers, *cap = the piece size, for the caller to read or copy text into;
+ * tdf_commit(nbytes) gives it back with its first nbytes bytes as the next piece (0: nothing is added).  At most one buffer is outstanding:
+ * a second acquire, a commit without one and nbytes > cap are ISLE_E_ARG and leave the stream as it was.  tdf_commit queues the copy and the
+ * piece's kernels and returns without waiting for them; it waits for the piece BEFORE, whose line, entry and carry counts (read back through
+ * page-locked memory) size this one.  So one piece is on the device while the caller fills the other buffer, and tdf_acquire never waits
+ * for more than that.  tdf_write is acquire, memcpy, commit in a loop for bytes that are elsewhere; they are the caller's again when it
+ * returns.
+ * Because the device trails the calls, the first bad line is reported by whichever of commit, write or finalize learns of it first, by
+ * finalize at the latest; it is always the first bad line of T (pieces are parsed in order, the error word is an atomic minimum over
+ * (line, kind)).  After an error, or an allocation or device failure, the stream is discarded: later tdf calls find no open stream.
+ * tdf_finalize parses what stands behind the last '\n' as the last line, checks max_entries (0 = do not), then sorts, de-duplicates (the
+ * first in T of equal (doc, word) pairs stays) and builds the offsets as isle_hip_feed_finalize does.  entries_read / nnz: nullable.  An empty
+ * stream gives num_docs empty columns.  Device memory beyond the entry store (12 bytes an entry) and the sort's twin depends on the piece
+ * size alone, about 34 bytes per byte of a piece: a piece of n bytes may hold n lines, and the host cannot ask how many without waiting. */
+int isle_hip_tdf_begin(isle_ctx* ctx, uint64_t vocab_size, uint64_t num_docs, uint64_t reserve_entries, uint64_t piece_bytes);
+int isle_hip_tdf_acquire(isle_ctx* ctx, char** buf, uint64_t* cap);
+int isle_hip_tdf_commit(isle_ctx* ctx, uint64_t nbytes);
+int isle_hip_tdf_write(isle_ctx* ctx, const char* bytes, uint64_t nbytes);
+int isle_hip_tdf_finalize(isle_ctx* ctx, uint64_t max_entries, uint64_t* entries_read, uint64_t* nnz);
 /* Copies the context's count matrix to the host (any pointer may be NULL); nnz via the call above
  * or offsets[num_docs]. */
 int isle_hip_get_A(isle_ctx* ctx, float* counts, uint32_t* rows, int64_t* offsets);

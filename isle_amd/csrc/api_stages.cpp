@@ -46,6 +46,10 @@ extern "C" int isle_hip_upload_counts_u32(isle_ctx* c, uint64_t V, uint64_t D, u
   return 0;
 }
 
+// what is wrong with a line of tdf text, by the kind ing_parse_line returns (ingest.hip)
+static const char* const kTdfKind[] = {"", "bad character", "more than three fields", "fewer than three fields", "doc/word id is 0 or exceeds <num_docs>/<vocab_size>",
+                                       "count is 0", "count exceeds 4294967295"};
+
 extern "C" int isle_hip_ingest_tdf(isle_ctx* c, const char* text, uint64_t nbytes, uint64_t V, uint64_t D, uint64_t max_entries,
                                    uint64_t* entries_read, uint64_t* nnz) {
   if (!c) return ISLE_E_ARG;
@@ -65,9 +69,7 @@ extern "C" int isle_hip_ingest_tdf(isle_ctx* c, const char* text, uint64_t nbyte
   HIPCHK(c, he);
   ISLECHK(rc);
   if (err[0]) {
-    static const char* what[] = {"", "bad character", "more than three fields", "fewer than three fields", "doc/word id is 0 or exceeds <num_docs>/<vocab_size>",
-                                 "count is 0", "count exceeds 4294967295"};
-    return isle_fail(c, ISLE_E_ARG, "ingest_tdf: %s on line %llu", what[err[0] < 7 ? err[0] : 0], (unsigned long long)(err[1] + 1));
+    return isle_fail(c, ISLE_E_ARG, "ingest_tdf: %s on line %llu", kTdfKind[err[0] < 7 ? err[0] : 0], (unsigned long long)(err[1] + 1));
   }
   if (max_entries && nread != max_entries)  // include/utils.h:227
     return isle_fail(c, ISLE_E_ARG, "ingest_tdf: file has %llu entries, <max_entries> says %llu", (unsigned long long)nread, (unsigned long long)max_entries);
@@ -84,7 +86,7 @@ extern "C" int isle_hip_ingest_tdf(isle_ctx* c, const char* text, uint64_t nbyte
 extern "C" int isle_hip_feed_begin(isle_ctx* c, uint64_t V, uint64_t D, uint64_t reserve_entries) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  c->feed.release();  // an open feed is discarded
+  c->feed.release();  // an open feed, or an open text stream, is discarded
   if (V == 0 || V > 0xfffffff0ull || D == 0 || D > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "feed_begin: vocab/doc count out of range");
   if (reserve_entries) {
     hipError_t e = c->feed.key.reserve(reserve_entries);
@@ -107,7 +109,7 @@ extern "C" int isle_hip_feed_entries_pieces(isle_ctx* c, uint64_t n, const uint3
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
   IsleFeed& f = c->feed;
-  if (!f.open) return isle_fail(c, ISLE_E_ARG, "feed_entries: no open feed (isle_hip_feed_begin)");
+  if (!f.open || f.text) return isle_fail(c, ISLE_E_ARG, "feed_entries: no open feed (isle_hip_feed_begin)");
   if (n == 0) return 0;
   if (!docs || !words || !counts) return isle_fail(c, ISLE_E_ARG, "feed_entries: null array");
   const uint64_t piece = (piece_entries && piece_entries < ISLE_FEED_CHUNK) ? piece_entries : ISLE_FEED_CHUNK;
@@ -133,7 +135,7 @@ extern "C" int isle_hip_feed_entries_pieces(isle_ctx* c, uint64_t n, const uint3
 extern "C" int isle_hip_feed_finalize(isle_ctx* c, uint64_t doc_offset, uint64_t docs_global, uint64_t* entries_fed, uint64_t* nnz) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  if (!c->feed.open) return isle_fail(c, ISLE_E_ARG, "feed_finalize: no open feed (isle_hip_feed_begin)");
+  if (!c->feed.open || c->feed.text) return isle_fail(c, ISLE_E_ARG, "feed_finalize: no open feed (isle_hip_feed_begin)");
   c->a_ready = false;  // a_cnt / a_rows / a_offs are rewritten from here
   const uint64_t fed = c->feed.n, D = c->feed.D;
   const int rc = k_feed_finalize(c);
@@ -145,6 +147,123 @@ extern "C" int isle_hip_feed_finalize(isle_ctx* c, uint64_t doc_offset, uint64_t
   c->a_ready = true;
   isle_void_derived_from_A(c);
   if (entries_fed) *entries_fed = fed;
+  if (nnz) *nnz = c->a_nnz;
+  return 0;
+}
+
+// ---- tdf text in pieces cut anywhere -> A (ingest.hip: tdf_parse_k / tdf_pack_k / tdf_advance_k per piece, then the feed's tail)
+#define TDF_STREAM(who)                                                                                             \
+  if (!c) return ISLE_E_ARG;                                                                                        \
+  ISLECHK(isle_enter(c));                                                                                           \
+  IsleFeed& f = c->feed;                                                                                            \
+  if (!f.open || !f.text) return isle_fail(c, ISLE_E_ARG, who ": no open text stream (isle_hip_tdf_begin)")
+
+// a device or allocation failure inside the stream: nothing of the caller's is in a queue any more when the stream goes
+static int tdf_discard(isle_ctx* c, int rc) {
+  (void)hipStreamSynchronize(c->stream);
+  c->feed.release();
+  return rc;
+}
+
+// Waits for the piece in flight; ISLE_E_ARG naming the first bad line of the text so far, if there is one (the stream is discarded).
+static int tdf_settle(isle_ctx* c, const char* who) {
+  const int rc = k_tdf_wait(c);
+  if (rc) return tdf_discard(c, rc);
+  const uint64_t bad = c->feed.known.err;
+  if (bad == ~0ull) return 0;
+  c->feed.release();
+  return isle_fail(c, ISLE_E_ARG, "%s: %s on line %llu", who, kTdfKind[(bad & 7ull) < 7 ? (bad & 7ull) : 0], (unsigned long long)((bad >> 3) + 1));
+}
+
+extern "C" int isle_hip_tdf_begin(isle_ctx* c, uint64_t V, uint64_t D, uint64_t reserve_entries, uint64_t piece_bytes) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  IsleFeed& f = c->feed;
+  f.release();  // an open text stream, or an open feed, is discarded
+  if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "tdf_begin: single-rank only");
+  if (V == 0 || V > 0xfffffff0ull || D == 0 || D > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "tdf_begin: vocab/doc count out of range");
+  f.V = V;
+  f.D = D;
+  f.piece = (piece_bytes && piece_bytes < ISLE_TDF_PIECE) ? piece_bytes : ISLE_TDF_PIECE;
+  hipError_t e = hipSuccess;
+  if (reserve_entries) {  // with the headroom of one piece's bound (k_tdf_piece): a hint that is exact never makes the store grow
+    const uint64_t room = reserve_entries + f.piece / 6 + 1;
+    e = f.key.reserve(room);
+    if (e == hipSuccess) e = f.cnt.reserve(room);
+  }
+  for (int i = 0; i < 2 && e == hipSuccess; ++i) e = f.t_pin[i].reserve(f.piece);
+  int rc = 0;
+  if (e == hipSuccess) rc = k_tdf_open(c);
+  if (e != hipSuccess || rc) f.release();
+  HIPCHK(c, e);
+  ISLECHK(rc);
+  f.open = f.text = true;
+  return 0;
+}
+
+extern "C" int isle_hip_tdf_acquire(isle_ctx* c, char** buf, uint64_t* cap) {
+  TDF_STREAM("tdf_acquire");
+  if (!buf || !cap) return isle_fail(c, ISLE_E_ARG, "tdf_acquire: null argument");
+  if (f.acquired) return isle_fail(c, ISLE_E_ARG, "tdf_acquire: the buffer handed out before has not been committed");
+  // t_pin[pieces & 1] was the source of piece `pieces - 2`, which the commit of piece `pieces - 1` waited for: free by now
+  f.acquired = true;
+  *buf = f.t_pin[f.pieces & 1].p;
+  *cap = f.piece;
+  return 0;
+}
+
+extern "C" int isle_hip_tdf_commit(isle_ctx* c, uint64_t nbytes) {
+  TDF_STREAM("tdf_commit");
+  if (!f.acquired) return isle_fail(c, ISLE_E_ARG, "tdf_commit: no buffer acquired (isle_hip_tdf_acquire)");
+  if (nbytes > f.piece) return isle_fail(c, ISLE_E_ARG, "tdf_commit: %llu bytes in a buffer of %llu", (unsigned long long)nbytes, (unsigned long long)f.piece);
+  f.acquired = false;
+  if (nbytes == 0) return 0;
+  ISLECHK(tdf_settle(c, "tdf_commit"));  // the piece before: its counts size this one, its carry says where this one lands
+  const int rc = k_tdf_piece(c, f.t_pin[f.pieces & 1].p, nbytes, false);
+  return rc ? tdf_discard(c, rc) : 0;
+}
+
+extern "C" int isle_hip_tdf_write(isle_ctx* c, const char* bytes, uint64_t nbytes) {
+  TDF_STREAM("tdf_write");
+  if (nbytes && !bytes) return isle_fail(c, ISLE_E_ARG, "tdf_write: null text");
+  if (f.acquired) return isle_fail(c, ISLE_E_ARG, "tdf_write: a buffer is acquired and not committed");
+  for (uint64_t at = 0; at < nbytes;) {
+    char* buf = nullptr;
+    uint64_t cap = 0;
+    ISLECHK(isle_hip_tdf_acquire(c, &buf, &cap));
+    const uint64_t n = std::min<uint64_t>(cap, nbytes - at);
+    memcpy(buf, bytes + at, n);
+    ISLECHK(isle_hip_tdf_commit(c, n));
+    at += n;
+  }
+  return 0;
+}
+
+extern "C" int isle_hip_tdf_finalize(isle_ctx* c, uint64_t max_entries, uint64_t* entries_read, uint64_t* nnz) {
+  TDF_STREAM("tdf_finalize");
+  ISLECHK(tdf_settle(c, "tdf_finalize"));
+  if (f.known.carry) {  // the text does not end in '\n': what is left is its last line
+    const int rc = k_tdf_piece(c, nullptr, 0, true);
+    if (rc) return tdf_discard(c, rc);
+    ISLECHK(tdf_settle(c, "tdf_finalize"));
+  }
+  const uint64_t nread = f.known.entries, D = f.D;
+  if (max_entries && nread != max_entries) {  // include/utils.h:227
+    f.release();
+    return isle_fail(c, ISLE_E_ARG, "tdf_finalize: file has %llu entries, <max_entries> says %llu", (unsigned long long)nread, (unsigned long long)max_entries);
+  }
+  c->a_ready = false;  // a_cnt / a_rows / a_offs are rewritten from here
+  f.n = nread;
+  k_tdf_release_text(c);
+  const int rc = k_feed_finalize(c);
+  (void)hipStreamSynchronize(c->stream);
+  f.release();
+  ISLECHK(rc);
+  c->a_doc_offset = 0;
+  c->a_D_global = D;
+  c->a_ready = true;
+  isle_void_derived_from_A(c);
+  if (entries_read) *entries_read = nread;
   if (nnz) *nnz = c->a_nnz;
   return 0;
 }

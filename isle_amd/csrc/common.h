@@ -94,12 +94,15 @@ struct PinBuf {
     if (e == hipSuccess) cap = n;
     return e;
   }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+  }
   PinBuf() = default;
   PinBuf(const PinBuf&) = delete;
   PinBuf& operator=(const PinBuf&) = delete;
-  ~PinBuf() {
-    if (p) (void)hipHostFree(p);
-  }
+  ~PinBuf() { release(); }
 };
 
 // ------------------------------------------------------------------------------------------
@@ -157,9 +160,34 @@ struct IslePinSmall {
 
 // An open feed of (doc, word, count) triples (isle_hip_feed_begin ... isle_hip_feed_finalize; ingest.hip): the entries kept so far as
 // sort keys (doc << wbits) | word and counts, in the order they were offered, and the staging of one chunk of a batch.
+//
+// The same store behind a stream of tdf text (isle_hip_tdf_begin ... isle_hip_tdf_finalize; `text` set): the text arrives in pieces cut
+// anywhere.  One piece is on the device at a time: t_text[i & 1] holds [carry | piece i], the carry being the bytes behind the last '\n'
+// of everything before, which piece i - 1's last kernel left at the front of that buffer.  What the kernels need of the stream's past is
+// in t_state on the device; the host learns it one piece late, from the page-locked copy (t_back) that each piece ends with.
 constexpr uint64_t ISLE_FEED_CHUNK = 1ull << 26;  // entries per upload + launch: larger batches are cut into these
+constexpr uint64_t ISLE_TDF_PIECE = 16ull << 20;  // bytes of text per piece: of 1, 4, 16 and 64 MiB the best wall, level with 4 MiB, at less device time (profiles/tdf_stream_c2.jsonl)
+struct IsleTdfState {
+  unsigned long long lines;    // '\n' seen since tdf_begin: the 0-based number of the line the carry begins
+  unsigned long long entries;  // entries in the store
+  unsigned long long carry;    // bytes of the unfinished last line
+  unsigned long long err;      // all ones, or (0-based line << 3) | kind of the first bad line (ing_parse_k)
+};
 struct IsleFeed {
   bool open = false;
+  bool text = false;           // the open feed is a text stream: the isle_hip_feed_* calls refuse it, and the other way round
+  uint64_t piece = 0;          // text stream: capacity of t_pin[i]
+  uint64_t pieces = 0;         // non-empty pieces committed
+  bool acquired = false;       // t_pin[pieces & 1] is with the caller
+  bool in_flight = false;      // a piece is queued whose state has not been read back
+  IsleTdfState known = {0, 0, 0, ~0ull};  // t_state after the last piece that was waited for
+  PinBuf t_pin[2], t_back;
+  hipEvent_t t_done = nullptr;
+  DevBuf<unsigned char> t_text[2];
+  DevBuf<IsleTdfState> t_state;
+  DevBuf<uint32_t> t_tile_cnt;
+  DevBuf<int64_t> t_tile_off;
+  DevBuf<uint64_t> t_line_start;
   uint64_t V = 0, D = 0;
   uint64_t n = 0;        // entries held (zero counts are not)
   uint64_t offered = 0;  // entries offered since feed_begin, skipped ones included: the ordinal an error names
@@ -169,6 +197,7 @@ struct IsleFeed {
   DevBuf<uint64_t> t_key, t_err;
   DevBuf<int64_t> t_at, t_scratch;
   void release();
+  ~IsleFeed() { release(); }
 };
 
 struct isle_ctx {
@@ -598,6 +627,10 @@ int k_sort_pairs_u64(isle_ctx* c, uint64_t* key_a, uint32_t* val_a, uint64_t* ke
 int k_ingest_tdf(isle_ctx* c, const unsigned char* text_dev, uint64_t n, uint64_t V, uint64_t D, uint64_t* entries_read, uint64_t* err_out);
 int k_feed_chunk(isle_ctx* c, const uint32_t* docs, const uint32_t* words, const uint32_t* counts, uint64_t n, uint64_t* bad);
 int k_feed_finalize(isle_ctx* c);
+int k_tdf_open(isle_ctx* c);                                                      // the device state and the event of a text stream
+int k_tdf_piece(isle_ctx* c, const char* bytes, uint64_t n, bool last_line);      // queues [carry | n bytes from page-locked memory]; last_line: the carry alone
+int k_tdf_wait(isle_ctx* c);                                                      // -> IsleFeed::known is the state after everything queued
+void k_tdf_release_text(isle_ctx* c);
 
 // infer.hip
 int k_infer(isle_ctx* c, uint64_t V, int k, const float* model_by_word, uint64_t D, uint64_t nnz, const float* counts, const uint32_t* rows,

@@ -7,6 +7,8 @@
 //                                    per pass, hand-written (wave-level multisplit)
 //   ing_flag_k / ing_compact_k       drop repeated (doc, word) pairs, first in file order survives    src/trainer.cpp:243-247
 //   ing_offsets_k                    column offsets, empty documents included                         src/sparseMatrix.cpp:58-87
+//   tdf_parse_k / tdf_pack_k /       the same text in pieces cut anywhere (isle_hip_tdf_*): the complete lines of [carry | piece]
+//   tdf_advance_k                    behind the entries held, the rest becomes the next carry
 //
 // Deviations from the reference parser, shared with the host parser of isle_amd/host/prestage.h: trailing blanks do not
 // leak into the next line (the reference keeps its was_whitespace flag across '\n'), blank lines are skipped, a bad
@@ -68,17 +70,12 @@ __global__ __launch_bounds__(IT) void ing_nl_fill_k(const unsigned char* __restr
   }
 }
 
-// kinds: 1 bad character, 2 too many fields, 3 fewer than three fields, 4 doc/word id 0 or out of range, 5 count 0, 6 count above
-// 2^32 - 1.  *err starts as all ones and ends as the smallest (line << 3) | kind over the bad lines: the first bad line, whichever
-// thread gets there first.
-__global__ __launch_bounds__(IT) void ing_parse_k(const unsigned char* __restrict__ text, uint64_t n, const uint64_t* __restrict__ line_start, uint64_t nlines,
-                                                   uint64_t V, uint64_t D, int wbits, uint64_t* __restrict__ key, uint32_t* __restrict__ cnt,
-                                                   uint32_t* __restrict__ valid, unsigned long long* __restrict__ err) {
+// One line, text[s, e) without its '\n'.  -> 0 with *ok = 1 and its (key, count), 0 with *ok = 0 for a line without a digit, or the kind of
+// what is wrong with it: 1 bad character, 2 too many fields, 3 fewer than three fields, 4 doc/word id 0 or out of range, 5 count 0,
+// 6 count above 2^32 - 1.
+__device__ inline int ing_parse_line(const unsigned char* __restrict__ text, uint64_t s, uint64_t e, uint64_t V, uint64_t D, int wbits, uint64_t* key,
+                                     uint32_t* cnt, uint32_t* ok) {
   constexpr unsigned long long FIELD_MAX = 0xffffffffull;
-  const uint64_t l = (uint64_t)blockIdx.x * IT + threadIdx.x;
-  if (l >= nlines) return;
-  const uint64_t s = line_start[l];
-  const uint64_t e = (l + 1 < nlines) ? line_start[l + 1] - 1 : ((n && text[n - 1] == '\n') ? n - 1 : n);
   unsigned long long f[3] = {0, 0, 0};
   int state = 0;
   bool was_ws = false, any = false;
@@ -104,17 +101,36 @@ __global__ __launch_bounds__(IT) void ing_parse_k(const unsigned char* __restric
     f[state] = f[state] * 10ull + (unsigned long long)(ch - '0');
     if (f[state] > FIELD_MAX) f[state] = FIELD_MAX + 1ull;  // saturated: above every id and every count, and 10 * 2^32 + 9 still fits
   }
-  uint32_t ok = 0;
+  *ok = 0;
   if (!bad && any) {
     if (state != 2) bad = 3;
     else if (f[0] == 0 || f[1] == 0 || f[0] > D || f[1] > V) bad = 4;
     else if (f[2] == 0) bad = 5;  // a document made of zero counts would normalise to 0 / 0 (src/sparseMatrix.cpp:136-167)
     else if (f[2] > FIELD_MAX) bad = 6;
     else {
-      ok = 1;
-      key[l] = ((f[0] - 1) << wbits) | (f[1] - 1);
-      cnt[l] = (uint32_t)f[2];
+      *ok = 1;
+      *key = ((f[0] - 1) << wbits) | (f[1] - 1);
+      *cnt = (uint32_t)f[2];
     }
+  }
+  return bad;
+}
+
+// *err starts as all ones and ends as the smallest (line << 3) | kind over the bad lines: the first bad line, whichever thread gets
+// there first.
+__global__ __launch_bounds__(IT) void ing_parse_k(const unsigned char* __restrict__ text, uint64_t n, const uint64_t* __restrict__ line_start, uint64_t nlines,
+                                                   uint64_t V, uint64_t D, int wbits, uint64_t* __restrict__ key, uint32_t* __restrict__ cnt,
+                                                   uint32_t* __restrict__ valid, unsigned long long* __restrict__ err) {
+  const uint64_t l = (uint64_t)blockIdx.x * IT + threadIdx.x;
+  if (l >= nlines) return;
+  const uint64_t s = line_start[l];
+  const uint64_t e = (l + 1 < nlines) ? line_start[l + 1] - 1 : ((n && text[n - 1] == '\n') ? n - 1 : n);
+  uint64_t k = 0;
+  uint32_t x = 0, ok = 0;
+  const int bad = ing_parse_line(text, s, e, V, D, wbits, &k, &x, &ok);
+  if (ok) {
+    key[l] = k;
+    cnt[l] = x;
   }
   valid[l] = ok;
   if (bad) atomicMin(err, ((unsigned long long)l << 3) | (unsigned long long)bad);
@@ -425,8 +441,13 @@ hipError_t grow_keeping(hipStream_t st, DevBuf<T>& b, size_t keep, size_t want) 
 }  // namespace
 
 void IsleFeed::release() {
-  open = false;
-  n = offered = 0;
+  open = text = acquired = in_flight = false;
+  n = offered = piece = pieces = 0;
+  known = {0, 0, 0, ~0ull};
+  if (t_done) (void)hipEventDestroy(t_done);
+  t_done = nullptr;
+  t_text[0].release(); t_text[1].release(); t_state.release(); t_tile_cnt.release(); t_tile_off.release(); t_line_start.release();
+  t_pin[0].release(); t_pin[1].release(); t_back.release();
   key.release(); cnt.release(); in_docs.release(); in_words.release(); in_cnt.release(); t_key.release(); t_cnt.release(); t_valid.release();
   t_at.release(); t_scratch.release(); t_err.release();
 }
@@ -492,4 +513,146 @@ int k_feed_finalize(isle_ctx* c) {
   HIPCHK(c, f.t_key.reserve(f.n ? f.n : 1));
   HIPCHK(c, f.t_cnt.reserve(f.n ? f.n : 1));
   return ing_sort_dedup_install(c, f.V, f.D, wbits, dbits, f.key.p, f.cnt.p, f.t_key.p, f.t_cnt.p, f.n);
+}
+
+// ---------------- tdf text in pieces cut anywhere (isle_hip_tdf_*) ----------------------------------------------------------------------
+namespace {
+
+// The complete lines of text[0, L) = [carry | piece]: line l < *nnl is text[line_start[l], line_start[l + 1] - 1).  last_line: the text
+// is the carry behind the last piece, one line without a '\n'.  valid[] is written for every l < nmax, the host's bound on the lines,
+// so that the scan behind needs no count from the device.  The error word is the stream's: lines are numbered from tdf_begin.
+__global__ __launch_bounds__(IT) void tdf_parse_k(const unsigned char* __restrict__ text, uint64_t L, const uint64_t* __restrict__ line_start,
+                                                   const int64_t* __restrict__ nnl, uint64_t nmax, int last_line, uint64_t V, uint64_t D, int wbits,
+                                                   uint64_t* __restrict__ key, uint32_t* __restrict__ cnt, uint32_t* __restrict__ valid,
+                                                   IsleTdfState* __restrict__ st) {
+  const uint64_t l = (uint64_t)blockIdx.x * IT + threadIdx.x;
+  if (l >= nmax) return;
+  const uint64_t nlines = last_line ? 1ull : (uint64_t)*nnl;
+  if (l >= nlines) {
+    valid[l] = 0;
+    return;
+  }
+  const uint64_t s = last_line ? 0 : line_start[l];
+  const uint64_t e = last_line ? L : line_start[l + 1] - 1;
+  uint64_t k = 0;
+  uint32_t x = 0, ok = 0;
+  const int bad = ing_parse_line(text, s, e, V, D, wbits, &k, &x, &ok);
+  if (ok) {
+    key[l] = k;
+    cnt[l] = x;
+  }
+  valid[l] = ok;
+  if (bad) atomicMin(&st->err, ((st->lines + l) << 3) | (unsigned long long)bad);
+}
+
+// ing_pack_k behind the entries the store holds (the count is on the device)
+__global__ __launch_bounds__(IT) void tdf_pack_k(const uint64_t* __restrict__ key, const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ valid,
+                                                  const int64_t* __restrict__ at, uint64_t nmax, uint64_t* __restrict__ okey, uint32_t* __restrict__ ocnt,
+                                                  const IsleTdfState* __restrict__ st) {
+  const uint64_t l = (uint64_t)blockIdx.x * IT + threadIdx.x;
+  if (l < nmax && valid[l]) {
+    const uint64_t j = st->entries + (uint64_t)at[l];
+    okey[j] = key[l];
+    ocnt[j] = cnt[l];
+  }
+}
+
+// What stands behind the last '\n' of text[0, L) goes to the front of the other text buffer, and the stream's state moves on: the last
+// kernel of a piece, the only one that writes the state's counts (no other thread of it reads them).
+__global__ __launch_bounds__(IT) void tdf_advance_k(const unsigned char* __restrict__ text, uint64_t L, const uint64_t* __restrict__ line_start,
+                                                     const int64_t* __restrict__ nnl, const int64_t* __restrict__ nvalid, int last_line,
+                                                     unsigned char* __restrict__ next, IsleTdfState* __restrict__ st) {
+  const uint64_t from = last_line ? L : line_start[*nnl];
+  const uint64_t len = L - from;
+  for (uint64_t i = (uint64_t)blockIdx.x * IT + threadIdx.x; i < len; i += (uint64_t)gridDim.x * IT) next[i] = text[from + i];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    st->lines += last_line ? 1ull : (unsigned long long)*nnl;
+    st->entries += (unsigned long long)*nvalid;
+    st->carry = len;
+  }
+}
+
+// capacity to ask for when `need` elements do not fit: at least twice what there is
+inline size_t grown(size_t cap, size_t need) { return need <= cap ? cap : std::max(need, 2 * cap); }
+
+}  // namespace
+
+int k_tdf_open(isle_ctx* c) {
+  IsleFeed& f = c->feed;
+  HIPCHK(c, f.t_state.reserve(1));
+  HIPCHK(c, f.t_back.reserve(sizeof(IsleTdfState)));
+  HIPCHK(c, hipEventCreateWithFlags(&f.t_done, hipEventDisableTiming));
+  f.known = {0, 0, 0, ~0ull};
+  HIPCHK(c, hipMemcpyAsync(f.t_state.p, &f.known, sizeof(IsleTdfState), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int k_tdf_wait(isle_ctx* c) {
+  IsleFeed& f = c->feed;
+  if (!f.in_flight) return 0;
+  HIPCHK(c, hipEventSynchronize(f.t_done));
+  f.known = *reinterpret_cast<const IsleTdfState*>(f.t_back.p);
+  f.in_flight = false;
+  return 0;
+}
+
+void k_tdf_release_text(isle_ctx* c) {
+  IsleFeed& f = c->feed;
+  f.t_text[0].release(); f.t_text[1].release(); f.t_tile_cnt.release(); f.t_tile_off.release(); f.t_line_start.release();
+}
+
+// Queues one piece: n bytes from page-locked memory behind the carry, the kernels over [carry | piece], the copy of the state to t_back,
+// the event.  No piece is in flight (k_tdf_wait), so f.known is exact and every size below is either known or bounded by n: a piece of n
+// bytes ends at most n lines (the carry holds no '\n') and holds at most n / 6 + 1 entries ("1 1 1\n", the first may begin in the carry).
+int k_tdf_piece(isle_ctx* c, const char* bytes, uint64_t n, bool last_line) {
+  IsleFeed& f = c->feed;
+  int wbits, dbits;
+  ing_key_bits(f.V, f.D, &wbits, &dbits);
+  const int s = (int)(f.pieces & 1);
+  const uint64_t carry = f.known.carry, L = carry + n;
+  const uint64_t nmax = last_line ? 1 : n, ntiles = (L + TILE_BYTES - 1) / TILE_BYTES;
+  HIPCHK(c, grow_keeping(c->stream, f.t_text[s], carry, grown(f.t_text[s].cap, L + 16)));  // (fits unless a line outgrows its pieces)
+  HIPCHK(c, f.t_text[s ^ 1].reserve(grown(f.t_text[s ^ 1].cap, L + 16)));                  // the next carry: at most all of this text
+  const size_t store = (size_t)(f.known.entries + n / 6 + 1);
+  HIPCHK(c, grow_keeping(c->stream, f.key, f.known.entries, grown(f.key.cap, store)));
+  HIPCHK(c, grow_keeping(c->stream, f.cnt, f.known.entries, grown(f.cnt.cap, store)));
+  HIPCHK(c, f.t_tile_cnt.reserve(ntiles));
+  HIPCHK(c, f.t_tile_off.reserve(ntiles + 1));
+  HIPCHK(c, f.t_line_start.reserve(n + 2));
+  HIPCHK(c, f.t_key.reserve(nmax));
+  HIPCHK(c, f.t_cnt.reserve(nmax));
+  HIPCHK(c, f.t_valid.reserve(nmax));
+  HIPCHK(c, f.t_at.reserve(nmax + 1));
+  HIPCHK(c, f.t_scratch.reserve(isle_scan_scratch(L + 16) + 8));
+  unsigned char* text = f.t_text[s].p;
+  if (n) HIPCHK(c, hipMemcpyAsync(text + carry, bytes, n, hipMemcpyHostToDevice, c->stream));
+  {
+    TimeScope ts(c, ISLE_T_INGEST);
+    const int64_t* nnl = f.t_tile_off.p + ntiles;
+    if (!last_line) {
+      hipLaunchKernelGGL(ing_nl_count_k, dim3((unsigned)ntiles), dim3(IT), 0, c->stream, text, L, f.t_tile_cnt.p);
+      LAUNCH_CHECK(c);
+      HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, f.t_tile_cnt.p, ntiles, f.t_tile_off.p, f.t_scratch.p)));
+      HIPCHK(c, hipMemsetAsync(f.t_line_start.p, 0, sizeof(uint64_t), c->stream));
+      hipLaunchKernelGGL(ing_nl_fill_k, dim3((unsigned)ntiles), dim3(IT), 0, c->stream, text, L, f.t_tile_off.p, f.t_line_start.p);
+      LAUNCH_CHECK(c);
+    }
+    hipLaunchKernelGGL(tdf_parse_k, dim3(cdiv((long)nmax, IT)), dim3(IT), 0, c->stream, text, L, f.t_line_start.p, nnl, nmax, (int)last_line, f.V, f.D, wbits,
+                       f.t_key.p, f.t_cnt.p, f.t_valid.p, f.t_state.p);
+    LAUNCH_CHECK(c);
+    HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, f.t_valid.p, nmax, f.t_at.p, f.t_scratch.p)));
+    hipLaunchKernelGGL(tdf_pack_k, dim3(cdiv((long)nmax, IT)), dim3(IT), 0, c->stream, f.t_key.p, f.t_cnt.p, f.t_valid.p, f.t_at.p, nmax, f.key.p, f.cnt.p,
+                       f.t_state.p);
+    LAUNCH_CHECK(c);
+    const unsigned nb = (unsigned)std::min<uint64_t>((L + IT - 1) / IT, 1024);
+    hipLaunchKernelGGL(tdf_advance_k, dim3(nb), dim3(IT), 0, c->stream, text, L, f.t_line_start.p, nnl, f.t_at.p + nmax, (int)last_line, f.t_text[s ^ 1].p,
+                       f.t_state.p);
+    LAUNCH_CHECK(c);
+  }
+  HIPCHK(c, hipMemcpyAsync(f.t_back.p, f.t_state.p, sizeof(IsleTdfState), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipEventRecord(f.t_done, c->stream));
+  f.in_flight = true;
+  ++f.pieces;
+  return 0;
 }

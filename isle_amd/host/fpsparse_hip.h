@@ -6,6 +6,8 @@
 // this class exists so that the call sequence of ISLETrainer::train() (src/trainer.cpp:490-571) can be
 // compiled and run against the GPU library without the reference's MKL-dependent sources.
 #pragma once
+#include <sys/stat.h>
+
 #include <cassert>
 #include <cstdint>
 #include <cstdio>
@@ -19,6 +21,7 @@
 
 #include "../../include/isle_hip.h"
 #include "model_read.h"
+#include "tdf_pump.h"
 
 namespace ISLE {
 
@@ -207,6 +210,30 @@ class FPSparseMatrixHip {
     FPSparseMatrixHip* B = new FPSparseMatrixHip(vocab_size, 0, device);
     try {
       B->check(isle_hip_ingest_tdf(B->ctx_, text, nbytes, vocab_size, num_docs, (uint64_t)max_entries, nullptr, entries_in_A), "ingest_tdf");
+      B->a_docs_ = num_docs;
+      B->threshold_on_device(num_topics, sample_rate, original_cols, nullptr, entries_above_threshold, avg_doc_sz);
+    } catch (...) {
+      delete B;
+      throw;
+    }
+    return B;
+  }
+
+  // The same from the file itself, never held whole: tdf_pump.h reads it piece by piece into the library's page-locked buffers
+  // (isle_hip_tdf_acquire / _commit), each piece is copied and parsed while the next is read.  A equals from_tdf's on the file's bytes.
+  static FPSparseMatrixHip* from_tdf_file(word_id_t vocab_size, doc_id_t num_docs, const std::string& path, offset_t max_entries, doc_id_t num_topics,
+                                          double sample_rate, std::vector<doc_id_t>& original_cols, uint64_t* entries_in_A = nullptr,
+                                          uint64_t* entries_above_threshold = nullptr, float* avg_doc_sz = nullptr, int device = 0, uint64_t piece_bytes = 0) {
+    FPSparseMatrixHip* B = new FPSparseMatrixHip(vocab_size, 0, device);
+    try {
+      struct stat st;  // room for max_entries at once, where the file can hold that many ("1 1 1\n" is six bytes)
+      const uint64_t room = ::stat(path.c_str(), &st) == 0 ? (uint64_t)st.st_size / 6 + 1 : 0;
+      B->check(isle_hip_tdf_begin(B->ctx_, vocab_size, num_docs, std::min<uint64_t>((uint64_t)max_entries, room), piece_bytes), "tdf_begin");
+      isle_ctx* ctx = B->ctx_;
+      B->check(tdf_pump::file(path, [ctx](char** buf, uint64_t* cap) { return isle_hip_tdf_acquire(ctx, buf, cap); },
+                              [ctx](uint64_t n) { return isle_hip_tdf_commit(ctx, n); }),
+               "tdf stream");
+      B->check(isle_hip_tdf_finalize(B->ctx_, (uint64_t)max_entries, nullptr, entries_in_A), "tdf_finalize");
       B->a_docs_ = num_docs;
       B->threshold_on_device(num_topics, sample_rate, original_cols, nullptr, entries_above_threshold, avg_doc_sz);
     } catch (...) {

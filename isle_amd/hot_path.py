@@ -307,6 +307,58 @@ class HotPath:
         self._a_shape = self._feed_shape + (int(nz.value),)
         return int(fed.value), int(nz.value)
 
+    # ---- tdf text in pieces cut anywhere -> A (isle_hip_tdf_*) -------------------------------
+    def tdf_begin(self, vocab_size, num_docs, reserve_entries=0, _piece_bytes=0):
+        """Opens a text stream for a vocab_size x num_docs count matrix (an open stream or feed is discarded; the current A stays until
+        tdf_finalize succeeds).  _piece_bytes (tests): the size of the pieces the text travels in, 0 = the library's own."""
+        self._chk(self._lib.isle_hip_tdf_begin(self._h, int(vocab_size), int(num_docs), int(reserve_entries), int(_piece_bytes)))
+        self._feed_shape = (int(vocab_size), int(num_docs))
+
+    def tdf_write(self, data):
+        """The next bytes of the text (bytes, bytearray, memoryview or a uint8 array), cut anywhere.  The first bad line of the text so far
+        raises here or in tdf_finalize, whichever learns of it first; the stream is gone then."""
+        if isinstance(data, np.ndarray):
+            if data.dtype != np.uint8:
+                raise ValueError("tdf_write takes bytes: a uint8 array, not %s (nothing is cast)" % data.dtype)
+            buf = np.ascontiguousarray(data)
+        else:
+            buf = np.frombuffer(data, dtype=np.uint8)
+        self._chk(self._lib.isle_hip_tdf_write(self._h, _p(buf) if buf.size else None, int(buf.size)))
+
+    def tdf_finalize(self, max_entries=0):
+        """-> dict(entries_read, nnz); the context's count matrix is what ingest_tdf of all the bytes written would have made it."""
+        nr, nz = C.c_uint64(), C.c_uint64()
+        self._chk(self._lib.isle_hip_tdf_finalize(self._h, int(max_entries), C.byref(nr), C.byref(nz)))
+        self._a_shape = self._feed_shape + (int(nz.value),)
+        return dict(entries_read=int(nr.value), nnz=int(nz.value))
+
+    def ingest_tdf_file(self, path, vocab_size, num_docs, max_entries=0, _piece_bytes=0):
+        """ingest_tdf of a file's bytes without holding them: the file is read straight into the stream's page-locked buffers (readinto,
+        no copy in between), piece by piece, each piece parsed on the device while the next is read.  -> dict(entries_read, nnz).
+        A file that cannot be opened opens no stream; after a read error the stream stays open, holding what was read, until the next
+        tdf_begin or feed_begin discards it."""
+        buf, cap = C.c_void_p(), C.c_uint64()
+        with open(path, "rb", buffering=0) as f:      # before tdf_begin: a file that is not there opens no stream and discards no feed
+            self.tdf_begin(vocab_size, num_docs, _piece_bytes=_piece_bytes)
+            eof = False
+            while not eof:
+                self._chk(self._lib.isle_hip_tdf_acquire(self._h, C.byref(buf), C.byref(cap)))
+                got = 0
+                try:
+                    view = memoryview((C.c_char * cap.value).from_address(buf.value)).cast("B")
+                    while got < cap.value:      # a read may return fewer bytes than asked for; only 0 is the end of the file
+                        r = f.readinto(view[got:])
+                        if not r:
+                            eof = True
+                            break
+                        got += r
+                    del view
+                except BaseException:           # a read error: the buffer goes back; the stream stays open until the next begin discards it
+                    self._lib.isle_hip_tdf_commit(self._h, 0)
+                    raise
+                self._chk(self._lib.isle_hip_tdf_commit(self._h, got))
+        return self.tdf_finalize(max_entries)
+
     def upload_coo(self, V, D, docs, words, counts, batch=None):
         """feed_begin + feed + feed_finalize for triples held in arrays, fed in slices of `batch` entries (None: one call).
         -> (entries_fed, nnz)."""
