@@ -13,11 +13,51 @@
 // ------------------------------------------------------------------------------------------
 // upstream stage: A -> B on the device
 // ------------------------------------------------------------------------------------------
+// ---- what the four ways to a count matrix share (upload_counts, ingest_tdf, the feed, the text stream)
+// who: the call's prefix of the message, colon included; upload_counts has none and takes a matrix without documents
+static int shape_ok(isle_ctx* c, const char* who, uint64_t V, uint64_t D, bool no_docs_ok) {
+  if (V == 0 || V > 0xfffffff0ull || (D == 0 && !no_docs_ok) || D > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "%svocab/doc count out of range", who);
+  return 0;
+}
+
+static int entries_ok(isle_ctx* c, const char* who, uint64_t nread, uint64_t max_entries) {
+  if (max_entries && nread != max_entries)  // include/utils.h:227
+    return isle_fail(c, ISLE_E_ARG, "%s: file has %llu entries, <max_entries> says %llu", who, (unsigned long long)nread, (unsigned long long)max_entries);
+  return 0;
+}
+
+// a_cnt / a_rows / a_offs and a_V / a_D / a_nnz are written: they become A, and what was derived from the A before is void
+static int install_A(isle_ctx* c, uint64_t doc_offset, uint64_t docs_global, uint64_t entries, uint64_t* entries_out, uint64_t* nnz_out) {
+  c->a_doc_offset = doc_offset;
+  c->a_D_global = docs_global ? docs_global : c->a_D;
+  c->a_ready = true;
+  isle_void_derived_from_A(c);
+  if (entries_out) *entries_out = entries;
+  if (nnz_out) *nnz_out = c->a_nnz;
+  return 0;
+}
+
+// The open feed or text stream goes, with rc: a device or allocation failure inside it, or its end.  Nothing of the caller's is in a
+// queue any more when it does.
+static int feed_discard(isle_ctx* c, int rc) {
+  (void)hipStreamSynchronize(c->stream);
+  c->feed.release();
+  return rc;
+}
+
+// the entry of every call on an open feed (is_text false) or an open text stream (true): each refuses the other's
+#define FEED_OPEN(who, is_text)                                                                                     \
+  if (!c) return ISLE_E_ARG;                                                                                        \
+  ISLECHK(isle_enter(c));                                                                                           \
+  IsleFeed& f = c->feed;                                                                                            \
+  if (!f.open || f.text != (is_text))                                                                               \
+    return isle_fail(c, ISLE_E_ARG, "%s: no open %s", who, (is_text) ? "text stream (isle_hip_tdf_begin)" : "feed (isle_hip_feed_begin)")
+
 extern "C" int isle_hip_upload_counts_u32(isle_ctx* c, uint64_t V, uint64_t D, uint64_t nnz, const float* counts, const uint32_t* rows,
                                           const int64_t* offs, uint64_t doc_offset, uint64_t docs_global) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  if (V == 0 || V > 0xfffffff0ull || D > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "vocab/doc count out of range");
+  ISLECHK(shape_ok(c, "", V, D, true));
   if (offs[0] != 0 || (uint64_t)offs[D] != nnz) return isle_fail(c, ISLE_E_ARG, "offsets[0] != 0 or offsets[D] != nnz");
   for (uint64_t d = 0; d < D; ++d) {
     if (offs[d + 1] < offs[d]) return isle_fail(c, ISLE_E_ARG, "offsets not monotone at column %llu", (unsigned long long)d);
@@ -31,8 +71,6 @@ extern "C" int isle_hip_upload_counts_u32(isle_ctx* c, uint64_t V, uint64_t D, u
   c->a_V = V;
   c->a_D = D;
   c->a_nnz = nnz;
-  c->a_doc_offset = doc_offset;
-  c->a_D_global = docs_global ? docs_global : D;
   HIPCHK(c, c->a_cnt.reserve(nnz ? nnz : 1));
   HIPCHK(c, c->a_rows.reserve(nnz ? nnz : 1));
   HIPCHK(c, c->a_offs.reserve(D + 1));
@@ -41,9 +79,7 @@ extern "C" int isle_hip_upload_counts_u32(isle_ctx* c, uint64_t V, uint64_t D, u
     HIPCHK(c, hipMemcpy(c->a_rows.p, rows, nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
   }
   HIPCHK(c, hipMemcpy(c->a_offs.p, offs, (D + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  c->a_ready = true;
-  isle_void_derived_from_A(c);
-  return 0;
+  return install_A(c, doc_offset, docs_global, nnz, nullptr, nullptr);
 }
 
 // what is wrong with a line of tdf text, by the kind ing_parse_line returns (ingest.hip)
@@ -55,7 +91,7 @@ extern "C" int isle_hip_ingest_tdf(isle_ctx* c, const char* text, uint64_t nbyte
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
   if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "ingest_tdf: single-rank only");
-  if (V == 0 || V > 0xfffffff0ull || D == 0 || D > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "ingest_tdf: vocab/doc count out of range");
+  ISLECHK(shape_ok(c, "ingest_tdf: ", V, D, false));
   if (nbytes && !text) return isle_fail(c, ISLE_E_ARG, "ingest_tdf: null text");
   c->a_ready = false;
   DevBuf<unsigned char> td;
@@ -71,15 +107,8 @@ extern "C" int isle_hip_ingest_tdf(isle_ctx* c, const char* text, uint64_t nbyte
   if (err[0]) {
     return isle_fail(c, ISLE_E_ARG, "ingest_tdf: %s on line %llu", kTdfKind[err[0] < 7 ? err[0] : 0], (unsigned long long)(err[1] + 1));
   }
-  if (max_entries && nread != max_entries)  // include/utils.h:227
-    return isle_fail(c, ISLE_E_ARG, "ingest_tdf: file has %llu entries, <max_entries> says %llu", (unsigned long long)nread, (unsigned long long)max_entries);
-  c->a_doc_offset = 0;
-  c->a_D_global = D;
-  c->a_ready = true;
-  isle_void_derived_from_A(c);
-  if (entries_read) *entries_read = nread;
-  if (nnz) *nnz = c->a_nnz;
-  return 0;
+  ISLECHK(entries_ok(c, "ingest_tdf", nread, max_entries));
+  return install_A(c, 0, 0, nread, entries_read, nnz);
 }
 
 // ---- (doc, word, count) triples in batches -> A (ingest.hip: feed_key_k, then the tail tdf ingest runs)
@@ -87,7 +116,7 @@ extern "C" int isle_hip_feed_begin(isle_ctx* c, uint64_t V, uint64_t D, uint64_t
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
   c->feed.release();  // an open feed, or an open text stream, is discarded
-  if (V == 0 || V > 0xfffffff0ull || D == 0 || D > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "feed_begin: vocab/doc count out of range");
+  ISLECHK(shape_ok(c, "feed_begin: ", V, D, false));
   if (reserve_entries) {
     hipError_t e = c->feed.key.reserve(reserve_entries);
     if (e == hipSuccess) e = c->feed.cnt.reserve(reserve_entries);
@@ -106,10 +135,7 @@ extern "C" int isle_hip_feed_entries(isle_ctx* c, uint64_t n, const uint32_t* do
 
 extern "C" int isle_hip_feed_entries_pieces(isle_ctx* c, uint64_t n, const uint32_t* docs, const uint32_t* words, const uint32_t* counts,
                                             uint64_t piece_entries) {
-  if (!c) return ISLE_E_ARG;
-  ISLECHK(isle_enter(c));
-  IsleFeed& f = c->feed;
-  if (!f.open || f.text) return isle_fail(c, ISLE_E_ARG, "feed_entries: no open feed (isle_hip_feed_begin)");
+  FEED_OPEN("feed_entries", false);
   if (n == 0) return 0;
   if (!docs || !words || !counts) return isle_fail(c, ISLE_E_ARG, "feed_entries: null array");
   const uint64_t piece = (piece_entries && piece_entries < ISLE_FEED_CHUNK) ? piece_entries : ISLE_FEED_CHUNK;
@@ -117,11 +143,7 @@ extern "C" int isle_hip_feed_entries_pieces(isle_ctx* c, uint64_t n, const uint3
   for (uint64_t at = 0; at < n; at += piece) {
     uint64_t bad = ~0ull;
     const int rc = k_feed_chunk(c, docs + at, words + at, counts + at, std::min<uint64_t>(piece, n - at), &bad);
-    if (rc) {  // allocation or device failure: the feed is discarded, once no copy from the caller's arrays is queued any more
-      (void)hipStreamSynchronize(c->stream);
-      f.release();
-      return rc;
-    }
+    if (rc) return feed_discard(c, rc);  // once no copy from the caller's arrays is queued any more
     if (bad != ~0ull) {
       f.n = n0;
       f.offered = offered0;
@@ -133,42 +155,18 @@ extern "C" int isle_hip_feed_entries_pieces(isle_ctx* c, uint64_t n, const uint3
 }
 
 extern "C" int isle_hip_feed_finalize(isle_ctx* c, uint64_t doc_offset, uint64_t docs_global, uint64_t* entries_fed, uint64_t* nnz) {
-  if (!c) return ISLE_E_ARG;
-  ISLECHK(isle_enter(c));
-  if (!c->feed.open || c->feed.text) return isle_fail(c, ISLE_E_ARG, "feed_finalize: no open feed (isle_hip_feed_begin)");
+  FEED_OPEN("feed_finalize", false);
   c->a_ready = false;  // a_cnt / a_rows / a_offs are rewritten from here
-  const uint64_t fed = c->feed.n, D = c->feed.D;
-  const int rc = k_feed_finalize(c);
-  (void)hipStreamSynchronize(c->stream);
-  c->feed.release();
-  ISLECHK(rc);
-  c->a_doc_offset = doc_offset;
-  c->a_D_global = docs_global ? docs_global : D;
-  c->a_ready = true;
-  isle_void_derived_from_A(c);
-  if (entries_fed) *entries_fed = fed;
-  if (nnz) *nnz = c->a_nnz;
-  return 0;
+  const uint64_t fed = f.n;
+  ISLECHK(feed_discard(c, k_feed_finalize(c)));
+  return install_A(c, doc_offset, docs_global, fed, entries_fed, nnz);
 }
 
-// ---- tdf text in pieces cut anywhere -> A (ingest.hip: tdf_parse_k / tdf_pack_k / tdf_advance_k per piece, then the feed's tail)
-#define TDF_STREAM(who)                                                                                             \
-  if (!c) return ISLE_E_ARG;                                                                                        \
-  ISLECHK(isle_enter(c));                                                                                           \
-  IsleFeed& f = c->feed;                                                                                            \
-  if (!f.open || !f.text) return isle_fail(c, ISLE_E_ARG, who ": no open text stream (isle_hip_tdf_begin)")
-
-// a device or allocation failure inside the stream: nothing of the caller's is in a queue any more when the stream goes
-static int tdf_discard(isle_ctx* c, int rc) {
-  (void)hipStreamSynchronize(c->stream);
-  c->feed.release();
-  return rc;
-}
-
+// ---- tdf text in pieces cut anywhere -> A (ingest.hip: the whole text's kernels and tdf_advance_k per piece, then the feed's tail)
 // Waits for the piece in flight; ISLE_E_ARG naming the first bad line of the text so far, if there is one (the stream is discarded).
 static int tdf_settle(isle_ctx* c, const char* who) {
   const int rc = k_tdf_wait(c);
-  if (rc) return tdf_discard(c, rc);
+  if (rc) return feed_discard(c, rc);
   const uint64_t bad = c->feed.known.err;
   if (bad == ~0ull) return 0;
   c->feed.release();
@@ -181,7 +179,7 @@ extern "C" int isle_hip_tdf_begin(isle_ctx* c, uint64_t V, uint64_t D, uint64_t 
   IsleFeed& f = c->feed;
   f.release();  // an open text stream, or an open feed, is discarded
   if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "tdf_begin: single-rank only");
-  if (V == 0 || V > 0xfffffff0ull || D == 0 || D > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "tdf_begin: vocab/doc count out of range");
+  ISLECHK(shape_ok(c, "tdf_begin: ", V, D, false));
   f.V = V;
   f.D = D;
   f.piece = (piece_bytes && piece_bytes < ISLE_TDF_PIECE) ? piece_bytes : ISLE_TDF_PIECE;
@@ -202,7 +200,7 @@ extern "C" int isle_hip_tdf_begin(isle_ctx* c, uint64_t V, uint64_t D, uint64_t 
 }
 
 extern "C" int isle_hip_tdf_acquire(isle_ctx* c, char** buf, uint64_t* cap) {
-  TDF_STREAM("tdf_acquire");
+  FEED_OPEN("tdf_acquire", true);
   if (!buf || !cap) return isle_fail(c, ISLE_E_ARG, "tdf_acquire: null argument");
   if (f.acquired) return isle_fail(c, ISLE_E_ARG, "tdf_acquire: the buffer handed out before has not been committed");
   // t_pin[pieces & 1] was the source of piece `pieces - 2`, which the commit of piece `pieces - 1` waited for: free by now
@@ -213,18 +211,18 @@ extern "C" int isle_hip_tdf_acquire(isle_ctx* c, char** buf, uint64_t* cap) {
 }
 
 extern "C" int isle_hip_tdf_commit(isle_ctx* c, uint64_t nbytes) {
-  TDF_STREAM("tdf_commit");
+  FEED_OPEN("tdf_commit", true);
   if (!f.acquired) return isle_fail(c, ISLE_E_ARG, "tdf_commit: no buffer acquired (isle_hip_tdf_acquire)");
   if (nbytes > f.piece) return isle_fail(c, ISLE_E_ARG, "tdf_commit: %llu bytes in a buffer of %llu", (unsigned long long)nbytes, (unsigned long long)f.piece);
   f.acquired = false;
   if (nbytes == 0) return 0;
   ISLECHK(tdf_settle(c, "tdf_commit"));  // the piece before: its counts size this one, its carry says where this one lands
   const int rc = k_tdf_piece(c, f.t_pin[f.pieces & 1].p, nbytes, false);
-  return rc ? tdf_discard(c, rc) : 0;
+  return rc ? feed_discard(c, rc) : 0;
 }
 
 extern "C" int isle_hip_tdf_write(isle_ctx* c, const char* bytes, uint64_t nbytes) {
-  TDF_STREAM("tdf_write");
+  FEED_OPEN("tdf_write", true);
   if (nbytes && !bytes) return isle_fail(c, ISLE_E_ARG, "tdf_write: null text");
   if (f.acquired) return isle_fail(c, ISLE_E_ARG, "tdf_write: a buffer is acquired and not committed");
   for (uint64_t at = 0; at < nbytes;) {
@@ -240,32 +238,24 @@ extern "C" int isle_hip_tdf_write(isle_ctx* c, const char* bytes, uint64_t nbyte
 }
 
 extern "C" int isle_hip_tdf_finalize(isle_ctx* c, uint64_t max_entries, uint64_t* entries_read, uint64_t* nnz) {
-  TDF_STREAM("tdf_finalize");
+  FEED_OPEN("tdf_finalize", true);
   ISLECHK(tdf_settle(c, "tdf_finalize"));
   if (f.known.carry) {  // the text does not end in '\n': what is left is its last line
     const int rc = k_tdf_piece(c, nullptr, 0, true);
-    if (rc) return tdf_discard(c, rc);
+    if (rc) return feed_discard(c, rc);
     ISLECHK(tdf_settle(c, "tdf_finalize"));
   }
-  const uint64_t nread = f.known.entries, D = f.D;
-  if (max_entries && nread != max_entries) {  // include/utils.h:227
+  const uint64_t nread = f.known.entries;
+  const int refused = entries_ok(c, "tdf_finalize", nread, max_entries);
+  if (refused) {
     f.release();
-    return isle_fail(c, ISLE_E_ARG, "tdf_finalize: file has %llu entries, <max_entries> says %llu", (unsigned long long)nread, (unsigned long long)max_entries);
+    return refused;
   }
   c->a_ready = false;  // a_cnt / a_rows / a_offs are rewritten from here
   f.n = nread;
   k_tdf_release_text(c);
-  const int rc = k_feed_finalize(c);
-  (void)hipStreamSynchronize(c->stream);
-  f.release();
-  ISLECHK(rc);
-  c->a_doc_offset = 0;
-  c->a_D_global = D;
-  c->a_ready = true;
-  isle_void_derived_from_A(c);
-  if (entries_read) *entries_read = nread;
-  if (nnz) *nnz = c->a_nnz;
-  return 0;
+  ISLECHK(feed_discard(c, k_feed_finalize(c)));
+  return install_A(c, 0, 0, nread, entries_read, nnz);
 }
 
 extern "C" int isle_hip_get_A(isle_ctx* c, float* counts, uint32_t* rows, int64_t* offs) {

@@ -1,14 +1,15 @@
 // isle_amd/csrc/ingest.hip — tdf text -> count matrix A (CSC) in HBM.
 //
 //   ing_nl_count_k / ing_nl_fill_k   line starts (one '\n' scan over the text)
-//   ing_parse_k                      one thread per line: "<doc> <word> <count>", 1-based ids,        include/utils.h:158-228
-//                                    blanks / tabs between fields, '\r' ignored                       (DocWordEntriesReader)
+//   ing_parse_k / ing_pack_k         one thread per line: "<doc> <word> <count>", 1-based ids,        include/utils.h:158-228
+//                                    blanks / tabs between fields, '\r' ignored; the entries packed   (DocWordEntriesReader)
 //   rs_hist_k / rs_scatter_k         stable LSD radix sort of the entries by (doc, word), 8 bits      src/trainer.cpp:236-241
 //                                    per pass, hand-written (wave-level multisplit)
 //   ing_flag_k / ing_compact_k       drop repeated (doc, word) pairs, first in file order survives    src/trainer.cpp:243-247
 //   ing_offsets_k                    column offsets, empty documents included                         src/sparseMatrix.cpp:58-87
-//   tdf_parse_k / tdf_pack_k /       the same text in pieces cut anywhere (isle_hip_tdf_*): the complete lines of [carry | piece]
-//   tdf_advance_k                    behind the entries held, the rest becomes the next carry
+//   feed_key_k                       binary (doc, word, count) triples in batches (isle_hip_feed_*) instead of lines
+//   tdf_advance_k                    the same text in pieces cut anywhere (isle_hip_tdf_*): the same kernels over the complete lines of
+//                                    [carry | piece], the entries packed behind those held; the rest becomes the next carry
 //
 // Deviations from the reference parser, shared with the host parser of isle_amd/host/prestage.h: trailing blanks do not
 // leak into the next line (the reference keeps its was_whitespace flag across '\n'), blank lines are skipped, a bad
@@ -116,15 +117,24 @@ __device__ inline int ing_parse_line(const unsigned char* __restrict__ text, uin
   return bad;
 }
 
+// The lines of text[0, n): the nnl lines that end in '\n', line l being text[line_start[l], line_start[l + 1] - 1), and with `tail` the
+// bytes behind the last '\n' as one more line.  nnl is *nnl_dev where the count is on the device only (the stream), else nnl_host.
+// valid[] is written for every l < nmax, the host's bound on the lines, so that the scan behind needs no count from the device.
 // *err starts as all ones and ends as the smallest (line << 3) | kind over the bad lines: the first bad line, whichever thread gets
-// there first.
-__global__ __launch_bounds__(IT) void ing_parse_k(const unsigned char* __restrict__ text, uint64_t n, const uint64_t* __restrict__ line_start, uint64_t nlines,
-                                                   uint64_t V, uint64_t D, int wbits, uint64_t* __restrict__ key, uint32_t* __restrict__ cnt,
-                                                   uint32_t* __restrict__ valid, unsigned long long* __restrict__ err) {
+// there first.  Lines are numbered from *line0 (the stream: from tdf_begin), from 0 where it is null.
+__global__ __launch_bounds__(IT) void ing_parse_k(const unsigned char* __restrict__ text, uint64_t n, const uint64_t* __restrict__ line_start,
+                                                   const int64_t* __restrict__ nnl_dev, uint64_t nnl_host, uint64_t nmax, int tail, uint64_t V, uint64_t D,
+                                                   int wbits, uint64_t* __restrict__ key, uint32_t* __restrict__ cnt, uint32_t* __restrict__ valid,
+                                                   unsigned long long* __restrict__ err, const unsigned long long* __restrict__ line0) {
   const uint64_t l = (uint64_t)blockIdx.x * IT + threadIdx.x;
-  if (l >= nlines) return;
-  const uint64_t s = line_start[l];
-  const uint64_t e = (l + 1 < nlines) ? line_start[l + 1] - 1 : ((n && text[n - 1] == '\n') ? n - 1 : n);
+  if (l >= nmax) return;
+  const uint64_t nnl = nnl_dev ? (uint64_t)*nnl_dev : nnl_host;
+  if (l >= nnl + (uint64_t)tail) {
+    valid[l] = 0;
+    return;
+  }
+  const uint64_t s = l ? line_start[l] : 0;  // (a tail alone, the stream's last line, has no line starts at all)
+  const uint64_t e = l < nnl ? line_start[l + 1] - 1 : n;
   uint64_t k = 0;
   uint32_t x = 0, ok = 0;
   const int bad = ing_parse_line(text, s, e, V, D, wbits, &k, &x, &ok);
@@ -133,15 +143,18 @@ __global__ __launch_bounds__(IT) void ing_parse_k(const unsigned char* __restric
     cnt[l] = x;
   }
   valid[l] = ok;
-  if (bad) atomicMin(err, ((unsigned long long)l << 3) | (unsigned long long)bad);
+  if (bad) atomicMin(err, (((line0 ? *line0 : 0ull) + l) << 3) | (unsigned long long)bad);
 }
 
+// the valid ones of nlines (key, count) pairs to okey / ocnt, behind the *held entries these hold (none where it is null)
 __global__ __launch_bounds__(IT) void ing_pack_k(const uint64_t* __restrict__ key, const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ valid,
-                                                  const int64_t* __restrict__ at, uint64_t nlines, uint64_t* __restrict__ okey, uint32_t* __restrict__ ocnt) {
+                                                  const int64_t* __restrict__ at, uint64_t nlines, uint64_t* __restrict__ okey, uint32_t* __restrict__ ocnt,
+                                                  const unsigned long long* __restrict__ held) {
   const uint64_t l = (uint64_t)blockIdx.x * IT + threadIdx.x;
   if (l < nlines && valid[l]) {
-    okey[at[l]] = key[l];
-    ocnt[at[l]] = cnt[l];
+    const uint64_t j = (held ? (uint64_t)*held : 0ull) + (uint64_t)at[l];
+    okey[j] = key[l];
+    ocnt[j] = cnt[l];
   }
 }
 
@@ -244,22 +257,23 @@ __global__ __launch_bounds__(IT) void ing_offsets_k(const uint32_t* __restrict__
 #define LAUNCH_CHECK(c) HIPCHK(c, hipGetLastError())
 
 // Stable LSD radix sort of n (key, payload) pairs on the low key_bits bits of the keys, ping-ponging between the caller's
-// two buffer pairs; *in_a tells which pair holds the sorted sequence.  Also used by gram_lds.hip to order documents and
-// words by their number of nonzeros.
-int k_sort_pairs_u64(isle_ctx* c, uint64_t* key_a, uint32_t* val_a, uint64_t* key_b, uint32_t* val_b, uint64_t n, int key_bits, bool* in_a) {
+// two buffer pairs; *in_a tells which pair holds the sorted sequence.  The histogram (256 counters per 2048 keys), its offsets
+// and the scan's scratch are the caller's and grow as needed.
+static int rs_sort_pairs(isle_ctx* c, DevBuf<uint32_t>& hist, DevBuf<int64_t>& hist_off, DevBuf<int64_t>& scratch, uint64_t* key_a, uint32_t* val_a,
+                         uint64_t* key_b, uint32_t* val_b, uint64_t n, int key_bits, bool* in_a) {
   *in_a = true;
   if (n < 2) return 0;
   const uint32_t nblocks = (uint32_t)((n + RS_TILE - 1) / RS_TILE);
-  HIPCHK(c, c->rs_hist.reserve((size_t)256 * nblocks));
-  HIPCHK(c, c->rs_hist_off.reserve((size_t)256 * nblocks + 1));
-  HIPCHK(c, c->rs_scratch.reserve(isle_scan_scratch((uint64_t)256 * nblocks) + 8));
+  HIPCHK(c, hist.reserve((size_t)256 * nblocks));
+  HIPCHK(c, hist_off.reserve((size_t)256 * nblocks + 1));
+  HIPCHK(c, scratch.reserve(isle_scan_scratch((uint64_t)256 * nblocks) + 8));
   uint64_t *ka = key_a, *kb = key_b;
   uint32_t *va = val_a, *vb = val_b;
   for (int shift = 0; shift < key_bits; shift += 8) {
-    hipLaunchKernelGGL(rs_hist_k, dim3(nblocks), dim3(IT), 0, c->stream, ka, n, shift, nblocks, c->rs_hist.p);
+    hipLaunchKernelGGL(rs_hist_k, dim3(nblocks), dim3(IT), 0, c->stream, ka, n, shift, nblocks, hist.p);
     LAUNCH_CHECK(c);
-    HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, c->rs_hist.p, (uint64_t)256 * nblocks, c->rs_hist_off.p, c->rs_scratch.p)));
-    hipLaunchKernelGGL(rs_scatter_k, dim3(nblocks), dim3(IT), 0, c->stream, ka, va, n, shift, nblocks, c->rs_hist_off.p, kb, vb);
+    HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, hist.p, (uint64_t)256 * nblocks, hist_off.p, scratch.p)));
+    hipLaunchKernelGGL(rs_scatter_k, dim3(nblocks), dim3(IT), 0, c->stream, ka, va, n, shift, nblocks, hist_off.p, kb, vb);
     LAUNCH_CHECK(c);
     std::swap(ka, kb);
     std::swap(va, vb);
@@ -268,32 +282,26 @@ int k_sort_pairs_u64(isle_ctx* c, uint64_t* key_a, uint32_t* val_a, uint64_t* ke
   return 0;
 }
 
-// The part both front ends share: ne (key, count) pairs in offered order in (key_a, cnt_a), keys (doc << wbits) | word; (key_b, cnt_b) is
+// The same with the context's scratch, which stays: also used by gram_lds.hip to order documents and words by their number of
+// nonzeros, and by spmm.hip, kmeans.hip, corpus_stats.hip, edge_select.hip and doc_report.hip.
+int k_sort_pairs_u64(isle_ctx* c, uint64_t* key_a, uint32_t* val_a, uint64_t* key_b, uint32_t* val_b, uint64_t n, int key_bits, bool* in_a) {
+  return rs_sort_pairs(c, c->rs_hist, c->rs_hist_off, c->rs_scratch, key_a, val_a, key_b, val_b, n, key_bits, in_a);
+}
+
+// The part all front ends share: ne (key, count) pairs in offered order in (key_a, cnt_a), keys (doc << wbits) | word; (key_b, cnt_b) is
 // the other half of the sort's ping-pong, ne elements each.  Stable sort by (doc, word), the first of equal pairs kept, offsets with the
-// empty documents: the result becomes the context's a_cnt / a_rows / a_offs, a_V, a_D, a_nnz.
+// empty documents: the result becomes the context's a_cnt / a_rows / a_offs, a_V, a_D, a_nnz.  The sort's scratch is local: a histogram
+// of 256 counters per 2048 entries is not to outlive the ingest.
 static int ing_sort_dedup_install(isle_ctx* c, uint64_t V, uint64_t D, int wbits, int dbits, uint64_t* key_a, uint32_t* cnt_a, uint64_t* key_b,
                                   uint32_t* cnt_b, uint64_t ne) {
   DevBuf<uint32_t> flag, docs, hist;
   DevBuf<int64_t> at, hist_off, scratch;
   // ---- sort by (doc, word)
-  uint64_t *ka = key_a, *kb = key_b;
-  uint32_t *va = cnt_a, *vb = cnt_b;
   HIPCHK(c, scratch.reserve(isle_scan_scratch(ne + 16) + 8));
-  if (ne > 1) {
-    const uint32_t nblocks = (uint32_t)((ne + RS_TILE - 1) / RS_TILE);
-    HIPCHK(c, hist.reserve((size_t)256 * nblocks));
-    HIPCHK(c, hist_off.reserve((size_t)256 * nblocks + 1));
-    HIPCHK(c, scratch.reserve(isle_scan_scratch((uint64_t)256 * nblocks) + 8));
-    for (int shift = 0; shift < wbits + dbits; shift += 8) {
-      hipLaunchKernelGGL(rs_hist_k, dim3(nblocks), dim3(IT), 0, c->stream, ka, ne, shift, nblocks, hist.p);
-      LAUNCH_CHECK(c);
-      HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, hist.p, (uint64_t)256 * nblocks, hist_off.p, scratch.p)));
-      hipLaunchKernelGGL(rs_scatter_k, dim3(nblocks), dim3(IT), 0, c->stream, ka, va, ne, shift, nblocks, hist_off.p, kb, vb);
-      LAUNCH_CHECK(c);
-      std::swap(ka, kb);
-      std::swap(va, vb);
-    }
-  }
+  bool in_a = true;
+  ISLECHK(rs_sort_pairs(c, hist, hist_off, scratch, key_a, cnt_a, key_b, cnt_b, ne, wbits + dbits, &in_a));
+  const uint64_t* ka = in_a ? key_a : key_b;
+  const uint32_t* va = in_a ? cnt_a : cnt_b;
   // ---- drop repeated pairs, build the CSC
   HIPCHK(c, flag.reserve(ne ? ne : 1));
   HIPCHK(c, at.reserve(ne + 1));
@@ -325,80 +333,79 @@ static void ing_key_bits(uint64_t V, uint64_t D, int* wbits, int* dbits) {
   while ((1ull << *dbits) < D) ++*dbits;
 }
 
-// text_dev: n bytes on the device.  On success the context's count matrix is set (a_cnt / a_rows / a_offs, a_nnz).
+// The line starts of text[0, n): the '\n' of each 4096-byte tile counted and scanned (tile_off[ntiles] is their number, nnl, and stays on
+// the device), line_start[0] = 0, line_start[j + 1] = the position behind the j-th '\n'.  With nnl_back the count and the text's last byte
+// are read back behind the scan and line_start gets nnl + 2 elements; without, the caller has sized it by a bound and nothing is read back.
+static int ing_line_starts(isle_ctx* c, const unsigned char* text, uint64_t n, uint32_t* tile_cnt, int64_t* tile_off, int64_t* scratch,
+                           DevBuf<uint64_t>& line_start, int64_t* nnl_back, unsigned char* last_back) {
+  const uint64_t ntiles = (n + TILE_BYTES - 1) / TILE_BYTES;
+  if (ntiles) hipLaunchKernelGGL(ing_nl_count_k, dim3((unsigned)ntiles), dim3(IT), 0, c->stream, text, n, tile_cnt);
+  LAUNCH_CHECK(c);
+  HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, tile_cnt, ntiles, tile_off, scratch)));
+  if (nnl_back) {
+    HIPCHK(c, hipMemcpyAsync(nnl_back, tile_off + ntiles, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (n) HIPCHK(c, hipMemcpyAsync(last_back, text + n - 1, 1, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, line_start.reserve(*nnl_back + 2));
+  }
+  HIPCHK(c, hipMemsetAsync(line_start.p, 0, sizeof(uint64_t), c->stream));
+  if (ntiles) hipLaunchKernelGGL(ing_nl_fill_k, dim3((unsigned)ntiles), dim3(IT), 0, c->stream, text, n, tile_off, line_start.p);
+  LAUNCH_CHECK(c);
+  return 0;
+}
+
+// text_dev: n bytes on the device.  On success the context's count matrix is set (a_cnt / a_rows / a_offs, a_nnz).  Every buffer is the
+// call's own and goes at scope exit, on every return: an open feed or text stream keeps its staging.
 int k_ingest_tdf(isle_ctx* c, const unsigned char* text_dev, uint64_t n, uint64_t V, uint64_t D, uint64_t* entries_read, uint64_t* err_out /*2*/) {
   TimeScope ts(c, ISLE_T_INGEST);
   err_out[0] = err_out[1] = 0;
   int wbits, dbits;
   ing_key_bits(V, D, &wbits, &dbits);
-  // ---- line starts
   const uint64_t ntiles = (n + TILE_BYTES - 1) / TILE_BYTES;
   DevBuf<uint32_t> tile_cnt, valid, cnt0, cnt1;
   DevBuf<int64_t> tile_off, at, scratch;
   DevBuf<uint64_t> line_start, key0, key1, errd;
-  auto cleanup = [&]() {
-    tile_cnt.release(); valid.release(); cnt0.release(); cnt1.release();
-    tile_off.release(); at.release(); scratch.release();
-    line_start.release(); key0.release(); key1.release(); errd.release();
-  };
-#define ING(call)            \
-  do {                       \
-    hipError_t ing_e = (call); \
-    if (ing_e != hipSuccess) { \
-      cleanup();               \
-      HIPCHK(c, ing_e);        \
-    }                          \
-  } while (0)
-  ING(tile_cnt.reserve(ntiles ? ntiles : 1));
-  ING(tile_off.reserve(ntiles + 1));
-  ING(scratch.reserve(isle_scan_scratch(n + 16) + 8));  // every scan below is over at most n elements
-  if (ntiles) hipLaunchKernelGGL(ing_nl_count_k, dim3((unsigned)ntiles), dim3(IT), 0, c->stream, text_dev, n, tile_cnt.p);
-  ING(hipGetLastError());
-  ING((isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, tile_cnt.p, ntiles, tile_off.p, scratch.p)));
+  // ---- line starts
+  HIPCHK(c, tile_cnt.reserve(ntiles ? ntiles : 1));
+  HIPCHK(c, tile_off.reserve(ntiles + 1));
+  HIPCHK(c, scratch.reserve(isle_scan_scratch(n + 16) + 8));  // every scan below is over at most n elements
   int64_t nnl = 0;
   unsigned char last = '\n';
-  ING(hipMemcpyAsync(&nnl, tile_off.p + ntiles, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  if (n) ING(hipMemcpyAsync(&last, text_dev + n - 1, 1, hipMemcpyDeviceToHost, c->stream));
-  ING(hipStreamSynchronize(c->stream));
-  const uint64_t nlines = (uint64_t)nnl + ((n && last != '\n') ? 1 : 0);
-  ING(line_start.reserve(nnl + 2));
-  ING(hipMemsetAsync(line_start.p, 0, sizeof(uint64_t), c->stream));
-  if (ntiles) hipLaunchKernelGGL(ing_nl_fill_k, dim3((unsigned)ntiles), dim3(IT), 0, c->stream, text_dev, n, tile_off.p, line_start.p);
-  ING(hipGetLastError());
+  ISLECHK(ing_line_starts(c, text_dev, n, tile_cnt.p, tile_off.p, scratch.p, line_start, &nnl, &last));
+  const int tail = (n && last != '\n') ? 1 : 0;  // the last line's end is n - 1 if the text ends in '\n', else n
+  const uint64_t nlines = (uint64_t)nnl + tail;
   // ---- parse
-  ING(key0.reserve(nlines ? nlines : 1));
-  ING(cnt0.reserve(nlines ? nlines : 1));
-  ING(valid.reserve(nlines ? nlines : 1));
-  ING(at.reserve(nlines + 1));
-  ING(errd.reserve(1));
-  ING(hipMemsetAsync(errd.p, 0xff, sizeof(uint64_t), c->stream));
+  HIPCHK(c, key0.reserve(nlines ? nlines : 1));
+  HIPCHK(c, cnt0.reserve(nlines ? nlines : 1));
+  HIPCHK(c, valid.reserve(nlines ? nlines : 1));
+  HIPCHK(c, at.reserve(nlines + 1));
+  HIPCHK(c, errd.reserve(1));
+  HIPCHK(c, hipMemsetAsync(errd.p, 0xff, sizeof(uint64_t), c->stream));
   if (nlines)
-    hipLaunchKernelGGL(ing_parse_k, dim3(cdiv((long)nlines, IT)), dim3(IT), 0, c->stream, text_dev, n, line_start.p, nlines, V, D, wbits, key0.p, cnt0.p,
-                       valid.p, (unsigned long long*)errd.p);
-  ING(hipGetLastError());
-  ING((isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, valid.p, nlines, at.p, scratch.p)));
+    hipLaunchKernelGGL(ing_parse_k, dim3(cdiv((long)nlines, IT)), dim3(IT), 0, c->stream, text_dev, n, line_start.p, nullptr, (uint64_t)nnl, nlines,
+                       tail, V, D, wbits, key0.p, cnt0.p, valid.p, (unsigned long long*)errd.p, nullptr);
+  LAUNCH_CHECK(c);
+  HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, valid.p, nlines, at.p, scratch.p)));
   int64_t nent = 0;
-  ING(hipMemcpyAsync(&nent, at.p + nlines, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&nent, at.p + nlines, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   uint64_t first_bad = ~0ull;
-  ING(hipMemcpyAsync(&first_bad, errd.p, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  ING(hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpyAsync(&first_bad, errd.p, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   *entries_read = (uint64_t)nent;
   if (first_bad != ~0ull) {
     err_out[0] = first_bad & 7ull;  // kind
     err_out[1] = first_bad >> 3;    // 0-based line
-    cleanup();
     return 0;  // the caller formats the message
   }
   const uint64_t ne = (uint64_t)nent;
-  ING(key1.reserve(ne ? ne : 1));
-  ING(cnt1.reserve(ne ? ne : 1));
-  if (nlines) hipLaunchKernelGGL(ing_pack_k, dim3(cdiv((long)nlines, IT)), dim3(IT), 0, c->stream, key0.p, cnt0.p, valid.p, at.p, nlines, key1.p, cnt1.p);
-  ING(hipGetLastError());
+  HIPCHK(c, key1.reserve(ne ? ne : 1));
+  HIPCHK(c, cnt1.reserve(ne ? ne : 1));
+  if (nlines)
+    hipLaunchKernelGGL(ing_pack_k, dim3(cdiv((long)nlines, IT)), dim3(IT), 0, c->stream, key0.p, cnt0.p, valid.p, at.p, nlines, key1.p, cnt1.p,
+                       nullptr);
+  LAUNCH_CHECK(c);
   // ---- sort by (doc, word), drop repeated pairs, build the CSC: keys in key1/cnt1, ping-pong with key0/cnt0
-  const int rc = ing_sort_dedup_install(c, V, D, wbits, dbits, key1.p, cnt1.p, key0.p, cnt0.p, ne);
-  cleanup();
-#undef ING
-  return rc;
+  return ing_sort_dedup_install(c, V, D, wbits, dbits, key1.p, cnt1.p, key0.p, cnt0.p, ne);
 }
 
 // ---------------- binary (doc, word, count) triples in batches (isle_hip_feed_*) --------------------------------------------------------
@@ -419,14 +426,16 @@ __global__ __launch_bounds__(IT) void feed_key_k(const uint32_t* __restrict__ do
   if (bad) atomicMin(err, ((unsigned long long)(ordinal0 + i) << 3) | (unsigned long long)bad);
 }
 
-// a buffer of at least `want` elements whose first `keep` elements are those it held
+// a buffer of at least `need` elements whose first `keep` elements are those it held; where it grows, to at least twice what it was
 template <class T>
-hipError_t grow_keeping(hipStream_t st, DevBuf<T>& b, size_t keep, size_t want) {
-  if (want <= b.cap) return hipSuccess;
+hipError_t grow_keeping(hipStream_t st, DevBuf<T>& b, size_t keep, size_t need) {
+  if (need <= b.cap) return hipSuccess;
+  const size_t want = std::max(need, 2 * b.cap);
+  if (!keep) return b.reserve(want);
   T* q = nullptr;
   hipError_t e = hipMalloc((void**)&q, want * sizeof(T));
   if (e != hipSuccess) return e;
-  if (keep) e = hipMemcpyAsync(q, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice, st);
+  e = hipMemcpyAsync(q, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) {
     (void)hipFree(q);
@@ -436,6 +445,22 @@ hipError_t grow_keeping(hipStream_t st, DevBuf<T>& b, size_t keep, size_t want) 
   b.p = q;
   b.cap = want;
   return hipSuccess;
+}
+
+// room for m more entries behind the `held` entries of the feed's store
+hipError_t feed_room(hipStream_t st, IsleFeed& f, uint64_t held, uint64_t m) {
+  const hipError_t e = grow_keeping(st, f.key, (size_t)held, (size_t)(held + m));
+  return e != hipSuccess ? e : grow_keeping(st, f.cnt, (size_t)held, (size_t)(held + m));
+}
+
+// the staging of m lines or entries ahead of their compaction, with scratch for a scan over scan_n inputs
+hipError_t feed_stage(IsleFeed& f, uint64_t m, uint64_t scan_n) {
+  hipError_t e = f.t_key.reserve(m);
+  if (e == hipSuccess) e = f.t_cnt.reserve(m);
+  if (e == hipSuccess) e = f.t_valid.reserve(m);
+  if (e == hipSuccess) e = f.t_at.reserve(m + 1);
+  if (e == hipSuccess) e = f.t_scratch.reserve(isle_scan_scratch(scan_n) + 8);
+  return e;
 }
 
 }  // namespace
@@ -463,11 +488,7 @@ int k_feed_chunk(isle_ctx* c, const uint32_t* docs, const uint32_t* words, const
   HIPCHK(c, f.in_docs.reserve(n));
   HIPCHK(c, f.in_words.reserve(n));
   HIPCHK(c, f.in_cnt.reserve(n));
-  HIPCHK(c, f.t_key.reserve(n));
-  HIPCHK(c, f.t_cnt.reserve(n));
-  HIPCHK(c, f.t_valid.reserve(n));
-  HIPCHK(c, f.t_at.reserve(n + 1));
-  HIPCHK(c, f.t_scratch.reserve(isle_scan_scratch(n) + 8));
+  HIPCHK(c, feed_stage(f, n, n));
   HIPCHK(c, f.t_err.reserve(1));
   HIPCHK(c, hipMemcpyAsync(f.in_docs.p, docs, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(f.in_words.p, words, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
@@ -485,18 +506,14 @@ int k_feed_chunk(isle_ctx* c, const uint32_t* docs, const uint32_t* words, const
   HIPCHK(c, hipMemcpyAsync(bad, f.t_err.p, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));  // (the host arrays are the caller's again from here)
   if (*bad != ~0ull) return 0;
-  const uint64_t need = f.n + (uint64_t)nvalid;
-  if (need > f.key.cap) {
-    const size_t want = (size_t)std::max<uint64_t>(need, 2 * (uint64_t)f.key.cap);
-    HIPCHK(c, grow_keeping(c->stream, f.key, f.n, want));
-    HIPCHK(c, grow_keeping(c->stream, f.cnt, f.n, want));
-  }
+  HIPCHK(c, feed_room(c->stream, f, f.n, (uint64_t)nvalid));
   if (nvalid) {
     TimeScope ts(c, ISLE_T_INGEST);
-    hipLaunchKernelGGL(ing_pack_k, dim3(cdiv((long)n, IT)), dim3(IT), 0, c->stream, f.t_key.p, f.t_cnt.p, f.t_valid.p, f.t_at.p, n, f.key.p + f.n, f.cnt.p + f.n);
+    hipLaunchKernelGGL(ing_pack_k, dim3(cdiv((long)n, IT)), dim3(IT), 0, c->stream, f.t_key.p, f.t_cnt.p, f.t_valid.p, f.t_at.p, n, f.key.p + f.n, f.cnt.p + f.n,
+                       nullptr);
     LAUNCH_CHECK(c);
   }
-  f.n = need;
+  f.n += (uint64_t)nvalid;
   f.offered += n;
   return 0;
 }
@@ -516,46 +533,9 @@ int k_feed_finalize(isle_ctx* c) {
 }
 
 // ---------------- tdf text in pieces cut anywhere (isle_hip_tdf_*) ----------------------------------------------------------------------
+// The complete lines of text[0, L) = [carry | piece] go through ing_parse_k / ing_pack_k with the stream's state: lines numbered from
+// tdf_begin, entries packed behind those the store holds.  last_line: the text is the carry behind the last piece, one line without a '\n'.
 namespace {
-
-// The complete lines of text[0, L) = [carry | piece]: line l < *nnl is text[line_start[l], line_start[l + 1] - 1).  last_line: the text
-// is the carry behind the last piece, one line without a '\n'.  valid[] is written for every l < nmax, the host's bound on the lines,
-// so that the scan behind needs no count from the device.  The error word is the stream's: lines are numbered from tdf_begin.
-__global__ __launch_bounds__(IT) void tdf_parse_k(const unsigned char* __restrict__ text, uint64_t L, const uint64_t* __restrict__ line_start,
-                                                   const int64_t* __restrict__ nnl, uint64_t nmax, int last_line, uint64_t V, uint64_t D, int wbits,
-                                                   uint64_t* __restrict__ key, uint32_t* __restrict__ cnt, uint32_t* __restrict__ valid,
-                                                   IsleTdfState* __restrict__ st) {
-  const uint64_t l = (uint64_t)blockIdx.x * IT + threadIdx.x;
-  if (l >= nmax) return;
-  const uint64_t nlines = last_line ? 1ull : (uint64_t)*nnl;
-  if (l >= nlines) {
-    valid[l] = 0;
-    return;
-  }
-  const uint64_t s = last_line ? 0 : line_start[l];
-  const uint64_t e = last_line ? L : line_start[l + 1] - 1;
-  uint64_t k = 0;
-  uint32_t x = 0, ok = 0;
-  const int bad = ing_parse_line(text, s, e, V, D, wbits, &k, &x, &ok);
-  if (ok) {
-    key[l] = k;
-    cnt[l] = x;
-  }
-  valid[l] = ok;
-  if (bad) atomicMin(&st->err, ((st->lines + l) << 3) | (unsigned long long)bad);
-}
-
-// ing_pack_k behind the entries the store holds (the count is on the device)
-__global__ __launch_bounds__(IT) void tdf_pack_k(const uint64_t* __restrict__ key, const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ valid,
-                                                  const int64_t* __restrict__ at, uint64_t nmax, uint64_t* __restrict__ okey, uint32_t* __restrict__ ocnt,
-                                                  const IsleTdfState* __restrict__ st) {
-  const uint64_t l = (uint64_t)blockIdx.x * IT + threadIdx.x;
-  if (l < nmax && valid[l]) {
-    const uint64_t j = st->entries + (uint64_t)at[l];
-    okey[j] = key[l];
-    ocnt[j] = cnt[l];
-  }
-}
 
 // What stands behind the last '\n' of text[0, L) goes to the front of the other text buffer, and the stream's state moves on: the last
 // kernel of a piece, the only one that writes the state's counts (no other thread of it reads them).
@@ -571,9 +551,6 @@ __global__ __launch_bounds__(IT) void tdf_advance_k(const unsigned char* __restr
     st->carry = len;
   }
 }
-
-// capacity to ask for when `need` elements do not fit: at least twice what there is
-inline size_t grown(size_t cap, size_t need) { return need <= cap ? cap : std::max(need, 2 * cap); }
 
 }  // namespace
 
@@ -612,38 +589,25 @@ int k_tdf_piece(isle_ctx* c, const char* bytes, uint64_t n, bool last_line) {
   const int s = (int)(f.pieces & 1);
   const uint64_t carry = f.known.carry, L = carry + n;
   const uint64_t nmax = last_line ? 1 : n, ntiles = (L + TILE_BYTES - 1) / TILE_BYTES;
-  HIPCHK(c, grow_keeping(c->stream, f.t_text[s], carry, grown(f.t_text[s].cap, L + 16)));  // (fits unless a line outgrows its pieces)
-  HIPCHK(c, f.t_text[s ^ 1].reserve(grown(f.t_text[s ^ 1].cap, L + 16)));                  // the next carry: at most all of this text
-  const size_t store = (size_t)(f.known.entries + n / 6 + 1);
-  HIPCHK(c, grow_keeping(c->stream, f.key, f.known.entries, grown(f.key.cap, store)));
-  HIPCHK(c, grow_keeping(c->stream, f.cnt, f.known.entries, grown(f.cnt.cap, store)));
+  HIPCHK(c, grow_keeping(c->stream, f.t_text[s], carry, L + 16));  // (fits unless a line outgrows its pieces)
+  HIPCHK(c, grow_keeping(c->stream, f.t_text[s ^ 1], 0, L + 16));  // the next carry: at most all of this text
+  HIPCHK(c, feed_room(c->stream, f, f.known.entries, n / 6 + 1));
   HIPCHK(c, f.t_tile_cnt.reserve(ntiles));
   HIPCHK(c, f.t_tile_off.reserve(ntiles + 1));
   HIPCHK(c, f.t_line_start.reserve(n + 2));
-  HIPCHK(c, f.t_key.reserve(nmax));
-  HIPCHK(c, f.t_cnt.reserve(nmax));
-  HIPCHK(c, f.t_valid.reserve(nmax));
-  HIPCHK(c, f.t_at.reserve(nmax + 1));
-  HIPCHK(c, f.t_scratch.reserve(isle_scan_scratch(L + 16) + 8));
+  HIPCHK(c, feed_stage(f, nmax, L + 16));
   unsigned char* text = f.t_text[s].p;
   if (n) HIPCHK(c, hipMemcpyAsync(text + carry, bytes, n, hipMemcpyHostToDevice, c->stream));
   {
     TimeScope ts(c, ISLE_T_INGEST);
-    const int64_t* nnl = f.t_tile_off.p + ntiles;
-    if (!last_line) {
-      hipLaunchKernelGGL(ing_nl_count_k, dim3((unsigned)ntiles), dim3(IT), 0, c->stream, text, L, f.t_tile_cnt.p);
-      LAUNCH_CHECK(c);
-      HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, f.t_tile_cnt.p, ntiles, f.t_tile_off.p, f.t_scratch.p)));
-      HIPCHK(c, hipMemsetAsync(f.t_line_start.p, 0, sizeof(uint64_t), c->stream));
-      hipLaunchKernelGGL(ing_nl_fill_k, dim3((unsigned)ntiles), dim3(IT), 0, c->stream, text, L, f.t_tile_off.p, f.t_line_start.p);
-      LAUNCH_CHECK(c);
-    }
-    hipLaunchKernelGGL(tdf_parse_k, dim3(cdiv((long)nmax, IT)), dim3(IT), 0, c->stream, text, L, f.t_line_start.p, nnl, nmax, (int)last_line, f.V, f.D, wbits,
-                       f.t_key.p, f.t_cnt.p, f.t_valid.p, f.t_state.p);
+    const int64_t* nnl = f.t_tile_off.p + ntiles;  // on the device only; the last line is the carry, a tail without line starts
+    if (!last_line) ISLECHK(ing_line_starts(c, text, L, f.t_tile_cnt.p, f.t_tile_off.p, f.t_scratch.p, f.t_line_start, nullptr, nullptr));
+    hipLaunchKernelGGL(ing_parse_k, dim3(cdiv((long)nmax, IT)), dim3(IT), 0, c->stream, text, L, f.t_line_start.p, last_line ? nullptr : nnl, (uint64_t)0, nmax,
+                       (int)last_line, f.V, f.D, wbits, f.t_key.p, f.t_cnt.p, f.t_valid.p, &f.t_state.p->err, &f.t_state.p->lines);
     LAUNCH_CHECK(c);
     HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, f.t_valid.p, nmax, f.t_at.p, f.t_scratch.p)));
-    hipLaunchKernelGGL(tdf_pack_k, dim3(cdiv((long)nmax, IT)), dim3(IT), 0, c->stream, f.t_key.p, f.t_cnt.p, f.t_valid.p, f.t_at.p, nmax, f.key.p, f.cnt.p,
-                       f.t_state.p);
+    hipLaunchKernelGGL(ing_pack_k, dim3(cdiv((long)nmax, IT)), dim3(IT), 0, c->stream, f.t_key.p, f.t_cnt.p, f.t_valid.p, f.t_at.p, nmax, f.key.p, f.cnt.p,
+                       &f.t_state.p->entries);
     LAUNCH_CHECK(c);
     const unsigned nb = (unsigned)std::min<uint64_t>((L + IT - 1) / IT, 1024);
     hipLaunchKernelGGL(tdf_advance_k, dim3(nb), dim3(IT), 0, c->stream, text, L, f.t_line_start.p, nnl, f.t_at.p + nmax, (int)last_line, f.t_text[s ^ 1].p,

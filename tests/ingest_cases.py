@@ -110,7 +110,7 @@ fixed("nl-last-line-trailing-blanks", 5, 5, b"1 1 1\n2 2 2  \t ")
 fixed("nl-line-longer-than-a-tile", 5, 5, b" " * 5000 + b"1 2 3\n" + b"2 1 1\n")
 
 
-# ---------------------------------------------------------------- line counts (parse grid, the scan of `valid`, ing_pack_k)
+# ---------------------------------------------------------------- line counts (ing_parse_k's grid, the scan of `valid`, ing_pack_k)
 def _lines_case(nlines):
     def make():
         n = nlines - nlines // 3                       # every third line is blank

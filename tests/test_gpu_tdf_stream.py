@@ -1,7 +1,8 @@
 """The tdf text stream (isle_hip_tdf_begin / _acquire / _commit / _write / _finalize, HotPath.tdf_* and ingest_tdf_file) against the plain
 rule of tests/ingest_rule.py on the whole text, whatever the cuts: every cut of small texts, the case table of tests/ingest_cases.py at
 piece sizes from 1 byte to 4097, the error-order texts and the million-line text over many pieces, the library's own piece size through
-both of its buffers more than once, the states of a stream, and isle_amd/host/tdf_stream_main as a real process.  Every comparison is exact:
+both of its buffers more than once, the states of a stream, isle_amd/host/tdf_stream_main as a real process, and a whole-text ingest
+between the parts of an open stream or feed, which share its kernels but none of its buffers.  Every comparison is exact:
 counts, rows, offsets, entries_read, nnz; an error by its kind's wording and its 1-based line in the whole text."""
 import ctypes as C
 import os
@@ -11,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from feed_rule import BASE_D, BASE_V, base_corpus, feed_rule
 from ingest_cases import CASES
 from ingest_rule import KINDS, ingest_rule, text_from_entries
 from isle_amd import IsleHipError
@@ -284,3 +286,39 @@ def test_the_driver_finds_the_two_refusals_equal(files):
     r = subprocess.run([EXE, bad, str(case.V), str(case.D), "1000"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.strip() == "both refuse: %s on line %d" % (KINDS[1], want[2])
+
+
+# ---------------------------------------------------------------- 8. a whole-text ingest between the parts of a stream, or of a feed
+def _between():
+    """The stream's text and its cut, inside a line; another text of more lines than one 4096-byte tile holds and of more entries than the
+    stream has taken by the cut, with its own V and D."""
+    ours, other = (next(c for c in CASES if c.id == i) for i in ("passes-2", "passes-4"))
+    text, cut = ours.build()[0], 10001
+    assert b"\n" not in text[cut - 2:cut + 2] and text[:cut].count(b"\n") < 4400 < other.build()[0].count(b"\n") + 1
+    return ours, text, cut, other, other.build()[0]
+
+
+@pytest.mark.parametrize("refused", [False, True], ids=["taken", "refused"])
+def test_a_whole_text_ingest_inside_an_open_stream_disturbs_neither(hp, refused):
+    ours, text, cut, other, text2 = _between()
+    hp.tdf_begin(ours.V, ours.D, _piece_bytes=1000)
+    hp.tdf_write(text[:cut])
+    if refused:
+        with pytest.raises(IsleHipError, match=re.escape("%s on line 4401" % KINDS[5]) + r"\b"):
+            hp.ingest_tdf(text2 + b"1 1 0\n", other.V, other.D)
+    else:
+        assert_exact(hp, hp.ingest_tdf(text2, other.V, other.D), ingest_rule(text2, other.V, other.D))
+    hp.tdf_write(text[cut:])
+    assert_exact(hp, hp.tdf_finalize(), ingest_rule(text, ours.V, ours.D))
+
+
+def test_a_whole_text_ingest_inside_an_open_feed_disturbs_neither(hp):
+    _, _, _, other, text2 = _between()
+    d, w, c = base_corpus()
+    hp.feed_begin(BASE_V, BASE_D)
+    hp.feed(d[:1000], w[:1000], c[:1000])
+    assert_exact(hp, hp.ingest_tdf(text2, other.V, other.D), ingest_rule(text2, other.V, other.D))
+    hp.feed(d[1000:], w[1000:], c[1000:])
+    assert hp.feed_finalize() == (int(np.count_nonzero(c)), len(feed_rule(d, w, c, BASE_D)[0]))
+    for got, want in zip(hp.get_A(), feed_rule(d, w, c, BASE_D)):
+        np.testing.assert_array_equal(got, want)
