@@ -11,6 +11,8 @@
 #include <thread>
 #include <vector>
 
+#include "gl_plan.h"
+
 // ------------------------------------------------------------------------------------------
 // Launch guard.  On this stack a kernel launch of 2^32 threads or more (grid x block) does not run and reports NO error — round 3's
 // yy2_scan_k at 10 M documents left collapsed partitions that way.  Every launch of the library goes through this redefinition of
@@ -126,9 +128,7 @@ struct IsleKnobInfo {
 extern const IsleKnobInfo isle_knob_table[KN_COUNT];
 
 // One side of the LDS-banded Gram apply (gram_lds.hip): a sliced-ELL stream of band-local u16 source ids.
-struct GlDesc {  // one workgroup: 16 waves wave0 + i*wstride (i < nw), source bands [b0, b1), output slab
-  uint32_t wave0, wstride, nw, b0, b1, slab, pos_base, pad;
-};
+// (GlDesc, one workgroup of gl_apply_k, and the host plan that fills it: gl_plan.h)
 struct GlSide {
   uint32_t n_out = 0, n_src = 0, NB = 0, nslice = 0, nwv = 0, ndesc = 0;
   int G = 4;                  // groups of a wave = output items per lane (4 ... 8)

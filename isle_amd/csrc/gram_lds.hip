@@ -41,17 +41,8 @@
 
 namespace {
 
-constexpr int GL_WAVES = 16;
+// (GL_WAVES, GL_GMAX, GL_RB, GL_APPLY_WAVES, GL_NONE and GL_BAND_COST: gl_plan.h, with the host plan that shares them)
 constexpr int GL_THREADS = GL_WAVES * 64;
-constexpr int GL_GMAX = 8;  // groups (output items per lane) of a wave: 4 ... 8, GlSide::G; count records are GL_GMAX wide
-#ifndef GL_RB_V
-#define GL_RB_V 4078
-#endif
-#ifndef GL_APPLY_WAVES_V
-#define GL_APPLY_WAVES_V 16
-#endif
-constexpr uint32_t GL_RB = GL_RB_V;  // source rows per band (even: the half plane is whole float4)
-constexpr uint32_t GL_APPLY_WAVES = GL_APPLY_WAVES_V;  // most waves of a workgroup of gl_apply_k (experiment builds: 8 with bands of half the height, two workgroups per CU)
 constexpr uint32_t GL_NZ = 16;    // zero rows behind every plane of the band, one per residue class mod 16 (= per 16-byte bank group of the plane):
                                   // a padding slot reads the zero row of a class no real lane of its ds_read_b128 lane group uses in that slot (gl_place_k)
 constexpr uint32_t GL_PS = GL_RB + GL_NZ;   // rows of a plane in LDS
@@ -71,12 +62,10 @@ __host__ __device__ inline size_t gl_planar_off(uint32_t row, int l, int LPE, bo
 }
 constexpr int GL_PLACE_MAXN = 8;  // slices of up to 8 super-rounds (32 slots per lane) are placed; longer ones keep their ascending order
 constexpr int GL_PF = 4;  // super-rounds in flight per wave (4 x 512 B)
-constexpr uint32_t GL_NONE = 0xffffffffu;
 constexpr uint32_t GL_OUT_PLANAR = 0xffffffffu;  // gl_apply_k out_n2: the output is a packed (planar, banded) operand
 constexpr uint32_t GL_VP = 81920;  // words per vocabulary part of the LDS histograms (two u16 counters per dword: 160 KiB)
 constexpr uint32_t GL_HLDS = GL_VP / 2 * 4;
 constexpr int GL_SUB = 8;  // lanes per document in the histogram kernels
-constexpr double GL_BAND_COST = 256.0;  // cost of staging one 160 KB band from HBM in pass 2, in super-rounds (measured by sweep at C2)
 
 // ---------------------------------------------------------------------------------------------------------------
 // does every row hold a single value?
@@ -779,16 +768,10 @@ __device__ inline void add4(float4& a, const float4 b) {
       float4 v[GL_STEP][NFA];                                                                                           \
       float2 h[GL_STEP];                                                                                                \
       _Pragma("unroll") for (int t = 0; t < GL_STEP; ++t) {                                                             \
-        const uint32_t a8x = (GL_ABLATE & 4) ? (a8[t2 + t] & 8u) : a8[t2 + t];                                          \
+        const uint32_t a8x = a8[t2 + t];                                                                                \
         const uint32_t b16 = (a8x << 1) + p0s;                                                                          \
-        if (GL_ABLATE & 16) {                                                                                           \
-          const float f = __builtin_bit_cast(float, a8x);                                                               \
-          _Pragma("unroll") for (int l = 0; l < NF; ++l) v[t][l] = make_float4(f, f, f, f);                             \
-          h[t] = make_float2(f, f);                                                                                     \
-        } else {                                                                                                        \
-          _Pragma("unroll") for (int l = 0; l < NF; ++l) v[t][l] = gl_lds_f4(b16 + l * GL_PSB);                         \
-          if (HALF) h[t] = gl_lds_f2(a8x);                                                                              \
-        }                                                                                                               \
+        _Pragma("unroll") for (int l = 0; l < NF; ++l) v[t][l] = gl_lds_f4(b16 + l * GL_PSB);                           \
+        if (HALF) h[t] = gl_lds_f2(a8x);                                                                                \
       }                                                                                                                 \
       _Pragma("unroll") for (int t = 0; t < GL_STEP; ++t) {                                                             \
         _Pragma("unroll") for (int l = 0; l < NF; ++l) add4(acc[g][l], v[t][l]);                                        \
@@ -816,9 +799,6 @@ __device__ inline float2 gl_lds_f2(uint32_t addr) {
 // pass and should not push the staged operand (X: 4 MB, read by every workgroup; the band columns of Y) out of the XCD's L2
 #ifndef GL_IDS_NT
 #define GL_IDS_NT 1
-#endif
-#ifndef GL_ABLATE
-#define GL_ABLATE 0  // timing experiments only (tools/build_variant.sh): 1 no band staging, 2 no band barriers, 4 every gather reads row 0, 8 ids re-read from one place, 16 no LDS reads, 32 half the id loads, 64 loaded ids never consumed, 256 every fifth (band, group) of a wave skipped with its ids (round 6: the ceiling of a form with 0.8x the slots)
 #endif
 // (a macro, not a function: with the plain load behind an inline function hipcc 7.2 allocated the kernel's registers differently and
 // the 10-column kernels at 6 and 7 items per lane spilled 10 / 74 registers — pass 1 of config 3 on one GPU 1.60 -> 2.77 ms)
@@ -901,28 +881,26 @@ __global__ __launch_bounds__(GL_THREADS) void gl_apply_k(const float4* __restric
     // the band's count record (GL_GMAX u16 super-round counts of this wave): asked for before the band is staged, used behind it (it used to be
     // loaded behind the second barrier: one exposed memory round trip per band and wave)
     const uint4 cc = *reinterpret_cast<const uint4*>(cnt + (wv * NB + band) * GL_GMAX);
-    if (!(GL_ABLATE & 2)) __syncthreads();  // every wave is done with the previous band
+    __syncthreads();  // every wave is done with the previous band
     GL_STAMP(t1);
-    if (!(GL_ABLATE & 1)) {
-      // stage the band: up to ten 1-KiB LDS-DMA pieces per wave (global_load_lds_dwordx4: no VGPR round trip, all in flight at once)
-      const uint32_t nrow = min(GL_RB, n_src - band * GL_RB);
-      const char* src = reinterpret_cast<const char*>(In) + (size_t)band * IMG;
+    // stage the band: up to ten 1-KiB LDS-DMA pieces per wave (global_load_lds_dwordx4: no VGPR round trip, all in flight at once)
+    const uint32_t nrow = min(GL_RB, n_src - band * GL_RB);
+    const char* src = reinterpret_cast<const char*>(In) + (size_t)band * IMG;
 #pragma nounroll
-      for (int q = w; q < NPIECE; q += nwaves) {  // wave-uniform piece; rolled: unrolled, the address pairs stayed live beside the accumulators (spills)
-          const bool hp = q >= NF * 64;  // a piece of the half plane
-          const int plane = hp ? NF : q >> 6;
-          const uint32_t i = (uint32_t)(hp ? q - NF * 64 : q & 63) * 64u + lane;  // float4 of the plane
-          // lanes past the band's rows stay masked: they must not land on the zero rows
-          if (i < (hp ? (nrow + 1) / 2 : nrow)) {
-            const char* gp = src + (size_t)plane * GL_RB * 16u + (size_t)i * 16u;
-            char* lp = lb + (hp ? 0u : P0 + plane * GL_PSB) + (i - lane) * 16u;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp, (__attribute__((address_space(3))) void*)lp, 16, 0, 0);
-          }
+    for (int q = w; q < NPIECE; q += nwaves) {  // wave-uniform piece; rolled: unrolled, the address pairs stayed live beside the accumulators (spills)
+      const bool hp = q >= NF * 64;  // a piece of the half plane
+      const int plane = hp ? NF : q >> 6;
+      const uint32_t i = (uint32_t)(hp ? q - NF * 64 : q & 63) * 64u + lane;  // float4 of the plane
+      // lanes past the band's rows stay masked: they must not land on the zero rows
+      if (i < (hp ? (nrow + 1) / 2 : nrow)) {
+        const char* gp = src + (size_t)plane * GL_RB * 16u + (size_t)i * 16u;
+        char* lp = lb + (hp ? 0u : P0 + plane * GL_PSB) + (i - lane) * 16u;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp, (__attribute__((address_space(3))) void*)lp, 16, 0, 0);
       }
-      __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): this wave's pieces have landed
     }
+    __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): this wave's pieces have landed
     GL_STAMP(t2);
-    if (!(GL_ABLATE & 2)) __syncthreads();
+    __syncthreads();
     GL_STAMP(t3);
     uint32_t cw[4] = {(uint32_t)__builtin_amdgcn_readfirstlane(cc.x), (uint32_t)__builtin_amdgcn_readfirstlane(cc.y),
                       (uint32_t)__builtin_amdgcn_readfirstlane(cc.z), (uint32_t)__builtin_amdgcn_readfirstlane(cc.w)};
@@ -931,12 +909,8 @@ __global__ __launch_bounds__(GL_THREADS) void gl_apply_k(const float4* __restric
     for (int g = 0; g < G; ++g) {
       const uint32_t nf = (uint32_t)__builtin_amdgcn_readfirstlane((int)((cw[g >> 1] >> (16 * (g & 1))) & 0xffffu));
       // bit 15 (gl_place_k / gl_scale_ids_k): every lane's last two slots of the group's last super-round are padding — only its first two are read
-      const bool half_last = (GL_ABLATE & 128) ? (nf & 0x7fffu) != 0u : (nf >> 15) != 0u;
+      const bool half_last = (nf >> 15) != 0u;
       const uint32_t n = nf & 0x7fffu;  // a scalar loop count
-      if ((GL_ABLATE & 256) && (band * (uint32_t)G + (uint32_t)g) % 5u == 4u) {  // timing build only: a stream with a fifth fewer slots (and ids)
-        p += (size_t)64 * n;
-        continue;
-      }
       // two super-rounds per step: the ring moves by PAIRS (q0 = q2; q1 = q3; two loads), so the moves read entries loaded one whole step
       // = two super-rounds earlier.  (Rotating by one — q0 = q1; ... q3 = *p — the move reads the load issued the step before and every
       // step waits for it, s_waitcnt vmcnt(0) at the head of the loop: one load in flight where the ring was meant to keep four.  A C3
@@ -945,18 +919,11 @@ __global__ __launch_bounds__(GL_THREADS) void gl_apply_k(const float4* __restric
       uint32_t r = 0;
       for (; r + 2 <= n; r += 2) {
         const uint2 ua = q0, ub = q1;
-        if (!(GL_ABLATE & 64)) {  // 64: the loaded ids are never consumed (no wait for them at all; the first super-rounds are walked again and again)
-          q0 = q2;
-          q1 = q3;
-        }
+        q0 = q2;
+        q1 = q3;
         q2 = gl_ld_ids(p);
-        if (GL_ABLATE & 32) {
-          q3 = q2;
-          p += 64;
-        } else {
-          q3 = gl_ld_ids(p + 64);
-          if (!(GL_ABLATE & 8)) p += 128;
-        }
+        q3 = gl_ld_ids(p + 64);
+        p += 128;
         GL_ROWS(ua)
         if (half_last && r + 2 == n) {
           GL_ROWS_N(ub, 2)
@@ -966,13 +933,11 @@ __global__ __launch_bounds__(GL_THREADS) void gl_apply_k(const float4* __restric
       }
       if (r < n) {
         const uint2 ua = q0;
-        if (!(GL_ABLATE & 64)) {
-          q0 = q1;
-          q1 = q2;
-          q2 = q3;
-        }
+        q0 = q1;
+        q1 = q2;
+        q2 = q3;
         q3 = gl_ld_ids(p);
-        if (!(GL_ABLATE & 8)) p += 64;
+        p += 64;
         if (half_last) {
           GL_ROWS_N(ua, 2)
         } else {
@@ -1005,7 +970,6 @@ __global__ __launch_bounds__(GL_THREADS) void gl_apply_k(const float4* __restric
   }
 #endif
   if (!wvalid) return;
-  if ((GL_ABLATE & 64) && (q2.x ^ q3.y) == 0x12345u) acc[0][0].x += 1.f;  // keeps the loads of the ablated ring alive
   float4* out = Out + (size_t)ds.slab * slab_stride;
 #pragma unroll
   for (int g = 0; g < G; ++g) {
@@ -1223,88 +1187,121 @@ int sort_by_key(isle_ctx* c, uint64_t n, uint64_t maxlen, uint32_t* perm) {
   return 0;
 }
 
-// counts -> offsets -> ids for one side; the per-lane entry source differs per pass (fill kernel chosen by PASS)
+// ---- the id stream of one side (GlStream<PASS>::build below), in steps.  Shorthands over a side whose geometry is set:
+inline size_t gl_nwb(const GlSide& s) { return (size_t)s.nwv * s.NB; }  // its (wave, band) cells
+inline uint16_t* gl_ids16(const GlSide& s) { return reinterpret_cast<uint16_t*>(s.ids.p); }
+// the prefetch ring reads up to GL_PF super-rounds past the end: that slack, and in pass 2 every slot no entry lands in,
+// holds the padding id (the zero row behind the band)
+inline size_t gl_n16_body(const GlSide& s) { return (size_t)s.total_sr * 64 * 4; }
+inline size_t gl_n16_all(const GlSide& s) { return ((size_t)s.total_sr + 2 * GL_PF) * 64 * 4; }
+
+// counts -> offsets -> ids for one side; the per-lane entry source differs per pass.  The steps are members of a class template, instantiated
+// per pass: the template kernels they name (gl_cnt_k<PASS>, the scan's, gl_place_k) are then emitted where a pass first needs them, behind
+// gl_apply_k — the order the code object has always had (profiles/gl_build_refactor.md compares it byte for byte).
 template <int PASS>
-int build_side(isle_ctx* c, GlSide& s, const std::vector<uint32_t>& slice_of_host) {
-  HIPCHK(c, s.slice_of.reserve(slice_of_host.size()));
-  HIPCHK(c, hipMemcpyAsync(s.slice_of.p, slice_of_host.data(), slice_of_host.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  const size_t nwb = (size_t)s.nwv * s.NB;
-  if (nwb * 64 * GL_GMAX >= (1ull << 32))  // gl_fill1_k / gl_sort2_k take one workgroup per (wave, band): a launch of 2^32 threads does not run
-    return isle_fail(c, ISLE_E_ARG, "operator build: %zu (wave, band) cells exceed one launch", nwb);
-  HIPCHK(c, s.cnt.reserve(nwb * GL_GMAX));
-  HIPCHK(c, s.roff.reserve(nwb + 1));
-  HIPCHK(c, c->gl_srsum.reserve(nwb));
-  HIPCHK(c, c->gl_scan.reserve(isle_scan::scan_scratch_elems(nwb) + 8));
-  HIPCHK(c, c->gl_flag.reserve(4));
-  HIPCHK(c, hipMemsetAsync(c->gl_flag.p, 0, sizeof(int), c->stream));
-  hipLaunchKernelGGL((gl_cnt_k<PASS>), dim3(s.nwv), dim3(64 * s.G), 0, c->stream, s.slice_of.p, s.G, s.n_out, s.NB, c->gl_bst.p, c->gl_cellcnt.p,
-                     c->wperm.p, s.cnt.p, c->gl_srsum.p, c->gl_flag.p);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, c->gl_srsum.p, nwb, s.roff.p, c->gl_scan.p)));
-  int overflow = 0;
-  HIPCHK(c, hipMemcpyAsync(&overflow, c->gl_flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&s.total_sr, s.roff.p + nwb, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (overflow) return isle_fail(c, ISLE_E_NUMERIC, "operator build: more than 65535 super-rounds in one (wave, band) cell");
-  if (s.total_sr >= 0xfffffff0ll) return isle_fail(c, ISLE_E_ARG, "operator build: id stream too long (%lld super-rounds)", (long long)s.total_sr);
-  HIPCHK(c, s.ids.reserve(((size_t)s.total_sr + 2 * GL_PF) * 64));
-  // the prefetch ring reads up to GL_PF super-rounds past the end: that slack, and in pass 2 every slot no entry lands in,
-  // holds the padding id (the zero row behind the band)
-  const size_t n16_all = ((size_t)s.total_sr + 2 * GL_PF) * 64 * 4, n16_body = (size_t)s.total_sr * 64 * 4;
-  uint16_t* ids16 = reinterpret_cast<uint16_t*>(s.ids.p);
-  if (PASS == 1) {
-    HIPCHK(c, hipMemsetD16Async((hipDeviceptr_t)(ids16 + n16_body), (unsigned short)GL_RB, n16_all - n16_body, c->stream));
+struct GlStream {
+  // counts -> offsets -> checks: the super-rounds of every (wave, band, group), where each (wave, band) starts in the stream, and a stream
+  // that can be launched over and addressed
+  static int counts(isle_ctx* c, GlSide& s, const std::vector<uint32_t>& slice_of_host) {
+    HIPCHK(c, s.slice_of.reserve(slice_of_host.size()));
+    HIPCHK(c, hipMemcpyAsync(s.slice_of.p, slice_of_host.data(), slice_of_host.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    const size_t nwb = gl_nwb(s);
+    if (nwb * 64 * GL_GMAX >= (1ull << 32))  // gl_fill1_k / gl_sort2_k take one workgroup per (wave, band): a launch of 2^32 threads does not run
+      return isle_fail(c, ISLE_E_ARG, "operator build: %zu (wave, band) cells exceed one launch", nwb);
+    HIPCHK(c, s.cnt.reserve(nwb * GL_GMAX));
+    HIPCHK(c, s.roff.reserve(nwb + 1));
+    HIPCHK(c, c->gl_srsum.reserve(nwb));
+    HIPCHK(c, c->gl_scan.reserve(isle_scan::scan_scratch_elems(nwb) + 8));
+    HIPCHK(c, c->gl_flag.reserve(4));
+    HIPCHK(c, hipMemsetAsync(c->gl_flag.p, 0, sizeof(int), c->stream));
+    hipLaunchKernelGGL((gl_cnt_k<PASS>), dim3(s.nwv), dim3(64 * s.G), 0, c->stream, s.slice_of.p, s.G, s.n_out, s.NB, c->gl_bst.p, c->gl_cellcnt.p,
+                       c->wperm.p, s.cnt.p, c->gl_srsum.p, c->gl_flag.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, c->gl_srsum.p, nwb, s.roff.p, c->gl_scan.p)));
+    int overflow = 0;
+    HIPCHK(c, hipMemcpyAsync(&overflow, c->gl_flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&s.total_sr, s.roff.p + nwb, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (overflow) return isle_fail(c, ISLE_E_NUMERIC, "operator build: more than 65535 super-rounds in one (wave, band) cell");
+    if (s.total_sr >= 0xfffffff0ll) return isle_fail(c, ISLE_E_ARG, "operator build: id stream too long (%lld super-rounds)", (long long)s.total_sr);
+    HIPCHK(c, s.ids.reserve(((size_t)s.total_sr + 2 * GL_PF) * 64));
+    return 0;
+  }
+
+  // pass 1: a lane's entries of a band are a run of its document's column (gl_bst): written in place, padding included
+  static int fill_pass1(isle_ctx* c, GlSide& s) {
+    const size_t nwb = gl_nwb(s);
+    HIPCHK(c, hipMemsetD16Async((hipDeviceptr_t)(gl_ids16(s) + gl_n16_body(s)), (unsigned short)GL_RB, gl_n16_all(s) - gl_n16_body(s), c->stream));
     if (nwb)
       hipLaunchKernelGGL(gl_fill1_k, dim3((unsigned)(8 * cdiv((long)nwb, 8))), dim3(64 * s.G), 0, c->stream, s.slice_of.p, s.G, s.n_out, s.NB, c->gl_bst.p, c->dperm.p,
                          c->rows.p, c->offs.p, c->nnz, s.cnt.p, s.roff.p, s.ids.p, (size_t)nwb);
     HIPCHK(c, hipGetLastError());
-  } else {
-    HIPCHK(c, hipMemsetD16Async((hipDeviceptr_t)ids16, (unsigned short)GL_RB, n16_all, c->stream));
+    return 0;
+  }
+
+  // pass 2, by buckets of word positions: gl_fb_count_k -> scan -> gl_fb_scatter_k -> gl_fb_fill_k (the comment above gl_fb_count_k)
+  static int fill2_bucketed(isle_ctx* c, GlSide& s) {
+    const uint32_t V = s.n_out;
+    // buckets of about 1024 word positions, 16 ... 128 of them (W <= 8192 while V <= 2^20): at config 3 a bucket's part of a band's stream
+    // region is 13 KB, and the 256 workgroups in flight on an XCD write into 3.4 MB — with 16 buckets (81 KB each) they thrashed the L2 as
+    // the direct scatter does (gl_fb_fill_k 14.9 ms)
+    // (W a multiple of 64: a bucket holds whole slices — gl_fb_fill_k writes a slice's super-rounds as one run)
+    const uint32_t NBK0 = std::min<uint32_t>(128u, std::max<uint32_t>(16u, (V + 1023) / 1024)), W = ((V + NBK0 - 1) / NBK0 + 63) / 64 * 64, NBK = (V + W - 1) / W;
+    const size_t nbb = (size_t)s.NB * NBK;
+    HIPCHK(c, c->gl_fb_cnt.reserve(nbb));
+    HIPCHK(c, c->gl_fb_off.reserve(nbb + 1));
+    HIPCHK(c, c->gl_scan.reserve(isle_scan::scan_scratch_elems(nbb) + 8));
+    HIPCHK(c, c->gl_fb_tmp.reserve(c->nnz));
+    hipLaunchKernelGGL(gl_fb_count_k, dim3(s.NB), dim3(GL_THREADS), 0, c->stream, c->gl_cellcnt.p, c->wperm.p, V, W, NBK, c->gl_fb_cnt.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, c->gl_fb_cnt.p, nbb, c->gl_fb_off.p, c->gl_scan.p)));
+    hipLaunchKernelGGL(gl_fb_scatter_k, dim3(s.NB), dim3(GL_THREADS), 0, c->stream, c->rows.p, c->offs.p, c->dperm.p, s.n_src, c->wpos.p, W, NBK,
+                       c->gl_fb_off.p, c->gl_fb_tmp.p);
+    const size_t fb_head = ((size_t)W + 2 * (W / 64 + 2) + 1 + 3) / 4 * 4 * sizeof(uint32_t);  // cursors, slice bases, offsets: a multiple of 16 bytes
+    const size_t fb_lds = std::max<size_t>(32u << 10, fb_head + 8 * 512);                          // 32 KB: five workgroups per CU
+    ISLECHK(isle_max_lds(c, (const void*)gl_fb_fill_k, (int)fb_lds));
+    hipLaunchKernelGGL(gl_fb_fill_k, dim3(s.NB, NBK), dim3(256), fb_lds, c->stream, c->gl_fb_tmp.p, c->gl_fb_off.p, V, s.NB, W, NBK, c->gl_sbase.p,
+                       c->gl_scnt.p, gl_ids16(s), (uint32_t)((fb_lds - fb_head) / 512));
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  }
+  // pass 2, direct: every entry scattered straight into its slot of the stream
+  static int fill2_direct(isle_ctx* c, GlSide& s) {
+    const uint32_t nvp = (s.n_out + GL_VP - 1) / GL_VP;
+    hipLaunchKernelGGL(gl_hist_fill_k, dim3(s.NB, nvp), dim3(GL_THREADS), GL_HLDS, c->stream, c->rows.p, c->offs.p, c->dperm.p, s.n_src, s.n_out,
+                       s.NB, c->wpos.p, c->gl_sbase.p, gl_ids16(s));
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  }
+  // pass 2: the whole stream is padding until an entry lands; the slices' bases, then the entries by buckets or directly
+  static int fill_pass2(isle_ctx* c, GlSide& s) {
+    const size_t nwb = gl_nwb(s);
+    HIPCHK(c, hipMemsetD16Async((hipDeviceptr_t)gl_ids16(s), (unsigned short)GL_RB, gl_n16_all(s), c->stream));
     HIPCHK(c, c->gl_sbase.reserve((size_t)s.nslice * s.NB));
     HIPCHK(c, c->gl_scnt.reserve((size_t)s.nslice * s.NB));
     if (nwb) hipLaunchKernelGGL(gl_sbase_k, dim3(cdiv((long)nwb, 256)), dim3(256), 0, c->stream, s.slice_of.p, s.G, s.cnt.p, s.roff.p, nwb, s.NB,
                                 c->gl_sbase.p, c->gl_scnt.p);
     HIPCHK(c, hipGetLastError());
     static_assert(GL_RB <= 4096, "the packed entries of the bucketed fill hold the document in 12 bits");
-    if (s.n_out <= (1u << 20) && c->nnz && !c->knob_zero(KN_GL_FILL_BUCKETS)) {  // (word positions in 20 bits)
-      const uint32_t V = s.n_out;
-      // buckets of about 1024 word positions, 16 ... 128 of them (W <= 8192 while V <= 2^20): at config 3 a bucket's part of a band's stream
-      // region is 13 KB, and the 256 workgroups in flight on an XCD write into 3.4 MB — with 16 buckets (81 KB each) they thrashed the L2 as
-      // the direct scatter does (gl_fb_fill_k 14.9 ms)
-      // (W a multiple of 64: a bucket holds whole slices — gl_fb_fill_k writes a slice's super-rounds as one run)
-      const uint32_t NBK0 = std::min<uint32_t>(128u, std::max<uint32_t>(16u, (V + 1023) / 1024)), W = ((V + NBK0 - 1) / NBK0 + 63) / 64 * 64, NBK = (V + W - 1) / W;
-      const size_t nbb = (size_t)s.NB * NBK;
-      HIPCHK(c, c->gl_fb_cnt.reserve(nbb));
-      HIPCHK(c, c->gl_fb_off.reserve(nbb + 1));
-      HIPCHK(c, c->gl_scan.reserve(isle_scan::scan_scratch_elems(nbb) + 8));
-      HIPCHK(c, c->gl_fb_tmp.reserve(c->nnz));
-      hipLaunchKernelGGL(gl_fb_count_k, dim3(s.NB), dim3(GL_THREADS), 0, c->stream, c->gl_cellcnt.p, c->wperm.p, V, W, NBK, c->gl_fb_cnt.p);
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, c->gl_fb_cnt.p, nbb, c->gl_fb_off.p, c->gl_scan.p)));
-      hipLaunchKernelGGL(gl_fb_scatter_k, dim3(s.NB), dim3(GL_THREADS), 0, c->stream, c->rows.p, c->offs.p, c->dperm.p, s.n_src, c->wpos.p, W, NBK,
-                         c->gl_fb_off.p, c->gl_fb_tmp.p);
-      const size_t fb_head = ((size_t)W + 2 * (W / 64 + 2) + 1 + 3) / 4 * 4 * sizeof(uint32_t);  // cursors, slice bases, offsets: a multiple of 16 bytes
-      const size_t fb_lds = std::max<size_t>(32u << 10, fb_head + 8 * 512);                          // 32 KB: five workgroups per CU
-      ISLECHK(isle_max_lds(c, (const void*)gl_fb_fill_k, (int)fb_lds));
-      hipLaunchKernelGGL(gl_fb_fill_k, dim3(s.NB, NBK), dim3(256), fb_lds, c->stream, c->gl_fb_tmp.p, c->gl_fb_off.p, V, s.NB, W, NBK, c->gl_sbase.p,
-                         c->gl_scnt.p, ids16, (uint32_t)((fb_lds - fb_head) / 512));
-      HIPCHK(c, hipGetLastError());
-    } else {
-      const uint32_t nvp = (s.n_out + GL_VP - 1) / GL_VP;
-      hipLaunchKernelGGL(gl_hist_fill_k, dim3(s.NB, nvp), dim3(GL_THREADS), GL_HLDS, c->stream, c->rows.p, c->offs.p, c->dperm.p, s.n_src, s.n_out,
-                         s.NB, c->wpos.p, c->gl_sbase.p, ids16);
-      HIPCHK(c, hipGetLastError());
-    }
-    if (nwb) {
-      HIPCHK(c, c->gl_biglist.reserve(nwb * GL_GMAX + 1));
-      HIPCHK(c, hipMemsetAsync(c->gl_biglist.p, 0, sizeof(uint32_t), c->stream));
-      hipLaunchKernelGGL(gl_sort2_k, dim3((unsigned)nwb), dim3(64 * s.G), 0, c->stream, s.NB, s.cnt.p, s.roff.p, s.ids.p, c->gl_biglist.p);
-      hipLaunchKernelGGL(gl_sort2_big_k, dim3(2 * c->num_cus), dim3(128), 0, c->stream, s.NB, s.cnt.p, s.roff.p, s.ids.p, c->gl_biglist.p);
-      HIPCHK(c, hipGetLastError());
-    }
+    if (s.n_out <= (1u << 20) && c->nnz && !c->knob_zero(KN_GL_FILL_BUCKETS)) return fill2_bucketed(c, s);  // (word positions in 20 bits)
+    return fill2_direct(c, s);
   }
-  if (nwb) {
-    const size_t nsl = nwb * (size_t)s.G;
+
+  // pass 2: the ids of every (word, document band) cell in ascending order (the comment above gl_sort_regs)
+  static int sort_pass2(isle_ctx* c, GlSide& s) {
+    const size_t nwb = gl_nwb(s);
+    if (!nwb) return 0;
+    HIPCHK(c, c->gl_biglist.reserve(nwb * GL_GMAX + 1));
+    HIPCHK(c, hipMemsetAsync(c->gl_biglist.p, 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(gl_sort2_k, dim3((unsigned)nwb), dim3(64 * s.G), 0, c->stream, s.NB, s.cnt.p, s.roff.p, s.ids.p, c->gl_biglist.p);
+    hipLaunchKernelGGL(gl_sort2_big_k, dim3(2 * c->num_cus), dim3(128), 0, c->stream, s.NB, s.cnt.p, s.roff.p, s.ids.p, c->gl_biglist.p);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  }
+
+  // bank-aware placement of the short slices (ISLE_GL_PLACE=0: none), and every id in the form gl_apply_k reads (8 * id)
+  static int place_and_scale(isle_ctx* c, GlSide& s) {
+    const size_t nsl = gl_nwb(s) * (size_t)s.G;
     const bool place = !c->knob_zero(KN_GL_PLACE);
     // at most 2^22 workgroups of 512 threads per launch (a launch of 2^32 threads or more does not run, and says nothing)
     for (size_t sid0 = 0; sid0 < nsl; sid0 += (size_t)8 << 22) {
@@ -1316,11 +1313,27 @@ int build_side(isle_ctx* c, GlSide& s, const std::vector<uint32_t>& slice_of_hos
       hipLaunchKernelGGL(gl_scale_ids_k, grid, dim3(512), 0, c->stream, s.G, sid0, nsl, place ? (uint32_t)GL_PLACE_MAXN : 0u, s.cnt.p, s.roff.p, s.ids.p);
       HIPCHK(c, hipGetLastError());
     }
+    return 0;
   }
+
   // the prefetch slack behind the stream: the padding id in the stream's final form
-  HIPCHK(c, hipMemsetD16Async((hipDeviceptr_t)(ids16 + n16_body), (unsigned short)(GL_RB * 8), n16_all - n16_body, c->stream));
-  return 0;
-}
+  static int prefetch_slack(isle_ctx* c, GlSide& s) {
+    HIPCHK(c, hipMemsetD16Async((hipDeviceptr_t)(gl_ids16(s) + gl_n16_body(s)), (unsigned short)(GL_RB * 8), gl_n16_all(s) - gl_n16_body(s), c->stream));
+    return 0;
+  }
+
+  static int build(isle_ctx* c, GlSide& s, const std::vector<uint32_t>& slice_of_host) {
+    ISLECHK(counts(c, s, slice_of_host));
+    if (PASS == 1) {
+      ISLECHK(fill_pass1(c, s));
+    } else {
+      ISLECHK(fill_pass2(c, s));
+      ISLECHK(sort_pass2(c, s));
+    }
+    ISLECHK(place_and_scale(c, s));
+    return prefetch_slack(c, s);
+  }
+};
 
 template <int LPE, bool HALF, int G>
 int launch_apply_g(isle_ctx* c, const GlSide& s, const float4* In, float4* Out, size_t slab_stride, const uint32_t* rowmap, uint32_t out_ld4,
@@ -1390,14 +1403,31 @@ int k_gl_detect(isle_ctx* c) {
   return 0;
 }
 
-int k_gl_ablate_skip(isle_ctx* c);
-int k_gl_build(isle_ctx* c) {
-  const uint32_t D = (uint32_t)c->D, V = (uint32_t)c->V;
-  GlSide& s1 = c->gl1;
-  GlSide& s2 = c->gl2;
-  ISLECHK(isle_max_lds(c, (const void*)gl_hist_count_k, GL_HLDS));
-  ISLECHK(isle_max_lds(c, (const void*)gl_hist_fill_k, GL_HLDS));
-  // ---- documents by decreasing length
+// ---- the operator build (k_gl_build below), in steps.  The host arithmetic between them — which slices a wave owns, which waves and
+// bands a workgroup takes — is gl_plan.h; here are the device steps, in stream order.
+
+// every switch the plan depends on, read once
+static GlPlanOpts gl_options(const isle_ctx* c) {
+  GlPlanOpts o;
+  if (c->knob(KN_GL_G1)) o.g1 = gl_forced_g(atoi(c->knob(KN_GL_G1)));
+  if (c->knob(KN_GL_G2)) o.g2 = gl_forced_g(atoi(c->knob(KN_GL_G2)));
+  o.rounds = !c->knob_zero(KN_GL_ROUNDS);
+  o.columns = !c->knob_zero(KN_GL_COLUMNS);
+  if (c->knob(KN_GL_TEST_CUS)) o.test_cus = (uint32_t)std::max(1, atoi(c->knob(KN_GL_TEST_CUS)));  // test hook
+  return o;
+}
+static void gl_set_side(GlSide& s, uint32_t n_out, uint32_t n_src, const GlGeom& g) {
+  s.n_out = n_out;
+  s.n_src = n_src;
+  s.NB = g.NB;
+  s.nslice = g.nslice;
+  s.G = g.G;
+  s.nwv = g.nwv;
+  s.wpg = g.wpg;
+}
+
+// documents by decreasing length: dperm (position -> document) and dpos
+static int gl_order_documents(isle_ctx* c, uint32_t D, uint32_t V) {
   HIPCHK(c, c->dperm.reserve(D));
   HIPCHK(c, c->dpos.reserve(D));
   ISLECHK(reserve_sort(c, std::max(D, V)));
@@ -1407,311 +1437,153 @@ int k_gl_build(isle_ctx* c) {
   ISLECHK(sort_by_key(c, D, V, c->dperm.p));
   hipLaunchKernelGGL(gl_invert_k, dim3(cdiv(D, 256)), dim3(256), 0, c->stream, c->dperm.p, (uint64_t)D, c->dpos.p);
   HIPCHK(c, hipGetLastError());
+  return 0;
+}
 
-  // ---- pass 1: outputs = documents (position order), sources = words
-  s1.n_out = D;
-  s1.n_src = V;
-  s1.NB = (V + GL_RB - 1) / GL_RB;
-  s1.nslice = (D + 63) / 64;
-  // items per lane G and waves per workgroup: the makespan model  rounds x (waves x G x LDS time of a slice + staging of all bands)
-  // over G = 4..8 and 1..16 waves.  Every workgroup stages every word band, so a shard whose documents need more than one round of
-  // workgroups at G = 4 (a C3 shard: 306 workgroups on 256 CUs, 0.44 ms per pass) runs one fuller round at G = 5 (245 workgroups,
-  // 0.31 ms), and all of config 3 on one GPU five rounds at G = 8 instead of ten (2.69 -> 2.34 ms); small matrices keep G = 4 and
-  // take fewer waves per workgroup so that all CUs stay busy.  The model's figures against the measured ones, pass 1 with 10 columns:
-  // C3 shard G = 5: 312 / 313 us; config 3 on one GPU G = 4 / 6 / 8: 2610 / 2530 / 2310 against 2690 / 2490 / 2336 us.
-  // ISLE_GL_G1 = 4..8 forces G.
-  const uint32_t maxw = GL_APPLY_WAVES;
-  uint32_t wpw = maxw;
-  const uint32_t cus = c->knob(KN_GL_TEST_CUS) ? (uint32_t)std::max(1, atoi(c->knob(KN_GL_TEST_CUS))) : (uint32_t)c->num_cus;  // test hook: the geometry of a larger problem on a small one
-  {
-    const double t_slice = 0.05 * 2.5 * (double)c->nnz / 256.0 / std::max<uint32_t>(1u, s1.nslice);  // us: ~50 ns per super-round, ~2.5x padded
-    const double t_stage = 2.0 * s1.NB;                                                               // us: ~2 us per band from L2
-    const char* e_g = c->knob(KN_GL_G1);
-    const int g_lo = e_g ? std::max(4, std::min(GL_GMAX, atoi(e_g))) : 4, g_hi = e_g ? g_lo : GL_GMAX - 1;  // 8: the 10-column kernel spills there
-    double best = 1e300;
-    for (int G = g_lo; G <= g_hi; ++G) {
-      const uint32_t nwv = (s1.nslice + G - 1) / G;
-      for (uint32_t cand = maxw; cand >= 1; --cand) {
-        const uint32_t wgs = (nwv + cand - 1) / cand;
-        const double fewer = 1.0 + 0.25 * (double)(GL_WAVES - cand) / GL_WAVES;  // fewer waves hide less of the id-stream latency
-        const uint32_t rounds = (wgs + cus - 1) / cus;
-        // more than one round: the workgroups are spread over WHOLE rounds (below), a wave then owns nslice / (rounds x CUs x waves) slices
-        const double per_wave = rounds > 1 ? (double)s1.nslice / ((double)rounds * cus * cand) : (double)G;
-        const double cost = (double)rounds * (cand * per_wave * t_slice * fewer + t_stage);
-        if (cost < best * 0.97) {  // prefer fewer items per lane and more waves per workgroup unless clearly worse
-          best = cost;
-          wpw = cand;
-          s1.G = G;
-        }
-      }
-    }
-  }
-  s1.nwv = (s1.nslice + s1.G - 1) / s1.G;
-  s1.wpg = wpw;
-  // More than one round of workgroups: their number is rounded up to whole rounds of the CUs — the waves of the last quantile range
-  // then own one slice less — and a workgroup takes ADJACENT waves (slices of neighbouring lengths: its waves reach the barrier of a band
-  // together; the workgroups differ by the length of their documents, the longest are launched first).  5.45 rounds of 7 slices per wave
-  // ran like 6 (all of config 3 on one GPU, pass 1); 6 rounds of 6.36 do the same work with the CUs busy to the end.  One round (a C3
-  // shard: 244 workgroups): the workgroups must finish together, so they take waves strided over the whole length order as before.
-  bool adjacent = false;
-  {
-    const uint32_t nwg0 = (s1.nwv + wpw - 1) / wpw;
-    if (nwg0 > cus && !c->knob_zero(KN_GL_ROUNDS)) {
-      const uint32_t nwg_r = (nwg0 + cus - 1) / cus * cus;
-      s1.nwv = nwg_r * wpw;
-      adjacent = true;
-    }
-  }
-  {
-    // serpentine over G quantile ranges of the length-ordered slices: every wave gets long, middle and short slices alike
-    const int G = s1.G;
-    std::vector<uint32_t> so((size_t)s1.nwv * G);
-    const uint64_t n = s1.nwv;
-    for (uint64_t wv = 0; wv < n; ++wv)
-      for (int g = 0; g < G; ++g) {
-        const uint64_t cand = (g & 1) ? (uint64_t)(g + 1) * n - 1 - wv : (uint64_t)g * n + wv;
-        so[wv * G + g] = cand < s1.nslice ? (uint32_t)cand : GL_NONE;
-      }
-    HIPCHK(c, c->gl_bst.reserve((size_t)D * (s1.NB + 1)));
-    const uint64_t nb = (uint64_t)D * (s1.NB + 1);
-    hipLaunchKernelGGL(gl_bst_k, dim3(cdiv((long)nb, 256)), dim3(256), 0, c->stream, c->rows.p, c->offs.p, c->dperm.p, (uint64_t)D, s1.NB,
-                       c->gl_bst.p);
-    HIPCHK(c, hipGetLastError());
-    ISLECHK(build_side<1>(c, s1, so));
-    // workgroup j = waves j, j + nwg, j + 2 nwg, ... : equal totals, one slab (Y itself)
-    const uint32_t nwg = (s1.nwv + wpw - 1) / wpw;
-    std::vector<GlDesc> ds(nwg);
-    for (uint32_t j = 0; j < nwg; ++j) {
-      uint32_t nw = 0;
-      while (nw < wpw && (uint64_t)j + (uint64_t)nw * nwg < s1.nwv) ++nw;
-      ds[j] = adjacent ? GlDesc{j * wpw, 1u, (uint32_t)std::min<uint64_t>(wpw, s1.nwv - (uint64_t)j * wpw), 0u, s1.NB, 0u, 0u, 0u} : GlDesc{j, nwg, nw, 0u, s1.NB, 0u, 0u, 0u};
-    }
-    s1.ndesc = nwg;
-    HIPCHK(c, s1.desc.reserve(nwg));
-    HIPCHK(c, hipMemcpyAsync(s1.desc.p, ds.data(), ds.size() * sizeof(GlDesc), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // ds / so are stack-owned
-  }
+// where every word band starts inside every document's column (gl_bst: the lanes' entry runs of pass 1)
+static int gl_band_starts(isle_ctx* c, uint32_t D, uint32_t NB1) {
+  HIPCHK(c, c->gl_bst.reserve((size_t)D * (NB1 + 1)));
+  const uint64_t nb = (uint64_t)D * (NB1 + 1);
+  hipLaunchKernelGGL(gl_bst_k, dim3(cdiv((long)nb, 256)), dim3(256), 0, c->stream, c->rows.p, c->offs.p, c->dperm.p, (uint64_t)D, NB1,
+                     c->gl_bst.p);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
 
-  // ---- (word, document band) cell sizes: one LDS histogram per band and vocabulary part
-  s2.n_out = V;
-  s2.n_src = D;
-  s2.NB = (D + GL_RB - 1) / GL_RB;
-  const size_t ncell = (size_t)V * s2.NB;
+// pass 1: outputs = documents (position order), sources = words.  The stream, then the plan's workgroups
+static int gl_pass1_streams(isle_ctx* c, uint32_t D, uint32_t V, const GlPlan1& p) {
+  GlSide& s1 = c->gl1;
+  gl_set_side(s1, D, V, p);
+  ISLECHK(GlStream<1>::build(c, s1, p.slice_of));
+  s1.ndesc = (uint32_t)p.desc.size();
+  HIPCHK(c, s1.desc.reserve(p.desc.size()));
+  HIPCHK(c, hipMemcpyAsync(s1.desc.p, p.desc.data(), p.desc.size() * sizeof(GlDesc), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the copies above read the plan's host memory
+  return 0;
+}
+
+// (word, document band) cell sizes: one LDS histogram per band and vocabulary part
+static int gl_cell_histogram(isle_ctx* c, uint32_t D, uint32_t V, uint32_t NB2) {
+  const size_t ncell = (size_t)V * NB2;
   const uint32_t nvp = (V + GL_VP - 1) / GL_VP;
   HIPCHK(c, c->gl_cellcnt.reserve(ncell));
-  hipLaunchKernelGGL(gl_hist_count_k, dim3(s2.NB, nvp), dim3(GL_THREADS), GL_HLDS, c->stream, c->rows.p, c->offs.p, c->dperm.p, D, V, s2.NB,
+  hipLaunchKernelGGL(gl_hist_count_k, dim3(NB2, nvp), dim3(GL_THREADS), GL_HLDS, c->stream, c->rows.p, c->offs.p, c->dperm.p, D, V, NB2,
                      c->gl_cellcnt.p);
   HIPCHK(c, hipGetLastError());
+  return 0;
+}
 
-  // ---- words by decreasing row length
+// words by decreasing row length: wperm (position -> word) and wpos
+static int gl_order_words(isle_ctx* c, uint32_t D, uint32_t V, uint32_t NB2) {
   HIPCHK(c, c->wperm.reserve(V));
   HIPCHK(c, c->wpos.reserve(V));
-  hipLaunchKernelGGL(gl_rowlen_key_k, dim3(cdiv(V, 256)), dim3(256), 0, c->stream, c->gl_cellcnt.p, V, s2.NB, (uint64_t)D, c->gl_key_a.p,
+  hipLaunchKernelGGL(gl_rowlen_key_k, dim3(cdiv(V, 256)), dim3(256), 0, c->stream, c->gl_cellcnt.p, V, NB2, (uint64_t)D, c->gl_key_a.p,
                      c->gl_val_a.p);
   HIPCHK(c, hipGetLastError());
   ISLECHK(sort_by_key(c, V, D, c->wperm.p));
   hipLaunchKernelGGL(gl_invert_k, dim3(cdiv(V, 256)), dim3(256), 0, c->stream, c->wperm.p, (uint64_t)V, c->wpos.p);
   HIPCHK(c, hipGetLastError());
+  return 0;
+}
 
-  // ---- pass 2: outputs = words (position order), sources = documents (position order)
-  s2.nslice = (V + 63) / 64;
-  // a word block = wpb waves = 4 wpb consecutive slices; 16 waves unless the vocabulary is so small that blocks x bands would
-  // leave CUs idle
-  {
-    const char* e_g = c->knob(KN_GL_G2);  // items per lane in pass 2 (4 ... 8)
-    // 4; 6 beyond 1024 document bands (more than 4 M documents): fewer word blocks, and every block stages every band of its columns.
-    // Measured with the final kernels, pass 2: config 3 on one GPU (2452 bands) 2.41 / 2.40 / 2.26 / 3.07 ms at 4 / 5 / 6 / 8; a C3 shard
-    // (307 bands) 0.309 / 0.334 / 0.314 at 4 / 5 / 6
-    s2.G = e_g ? std::max(4, std::min(GL_GMAX, atoi(e_g))) : (s2.NB > 1024 ? 6 : 4);
+// pass 2: outputs = words (position order), sources = documents (position order)
+static int gl_pass2_streams(isle_ctx* c, uint32_t D, uint32_t V, const GlGeom2& g) {
+  gl_set_side(c->gl2, V, D, g);
+  c->gl_block_items = g.bitems;
+  return GlStream<2>::build(c, c->gl2, g.slice_of);
+}
+
+// the super-rounds of every (word block, document band) — or of every word block, without band columns: the weights of the schedule
+static int gl_block_totals(isle_ctx* c, const GlGeom2& g, bool columns, std::vector<unsigned long long>& tot) {
+  const uint32_t nzones = columns ? g.NB : 1u;
+  HIPCHK(c, c->gl_blocktot.reserve((size_t)g.nblk * nzones));
+  hipLaunchKernelGGL(gl_blocktot_k, dim3(g.nblk, nzones), dim3(256), 0, c->stream, c->gl_srsum.p, g.nwv, g.wpg, g.NB, nzones, c->gl_blocktot.p);
+  HIPCHK(c, hipGetLastError());
+  tot.resize((size_t)g.nblk * nzones);
+  HIPCHK(c, hipMemcpyAsync(tot.data(), c->gl_blocktot.p, tot.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// the workgroups of pass 2, the word blocks' slab ranges, and room for the slabs
+static int gl_upload_schedule(isle_ctx* c, const GlGeom2& g, const GlSched2& sch) {
+  GlSide& s2 = c->gl2;
+  s2.ndesc = (uint32_t)sch.desc.size();
+  HIPCHK(c, s2.desc.reserve(sch.desc.size()));
+  HIPCHK(c, c->gl_slab0.reserve(g.nblk));
+  HIPCHK(c, c->gl_nch.reserve(g.nblk));
+  HIPCHK(c, hipMemcpyAsync(s2.desc.p, sch.desc.data(), sch.desc.size() * sizeof(GlDesc), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->gl_slab0.p, sch.slab0.data(), g.nblk * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->gl_nch.p, sch.nch.data(), g.nblk * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, c->gl_part.reserve((size_t)sch.nslab * g.bitems * 12));  // sized for the widest panel (BP = 12)
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ISLE_GL_VERBOSE: the word blocks' weights and chunks, per pass how many (wave, band, group) slices end in a half super-round and the
+// slices' lengths, and the geometry
+static int gl_report(isle_ctx* c, const GlGeom2& g, const GlSched2& sch, const std::vector<unsigned long long>& tot) {
+  const GlSide &s1 = c->gl1, &s2 = c->gl2;
+  fprintf(stderr, "[gram_lds] pass-2 %s, word blocks (super-rounds, chunks):", sch.columns ? "band columns shared per XCD" : "per-block band chunks");
+  const size_t per = sch.columns ? s2.NB : 1;
+  for (uint32_t ob = 0; ob < g.nblk; ++ob) {
+    unsigned long long t = 0;
+    for (size_t z = 0; z < per; ++z) t += tot[(size_t)ob * per + z];
+    fprintf(stderr, " %llu/%u", t, sch.nch[ob]);
   }
-  const uint32_t G2 = (uint32_t)s2.G;
-  uint32_t wpb = maxw;
-  while (wpb > 1 && (uint64_t)((s2.nslice + G2 * wpb - 1) / (G2 * wpb)) * s2.NB < 2ull * c->num_cus) wpb /= 2;
-  const uint32_t bslices = G2 * wpb, bitems = 64 * bslices;
-  const uint32_t nblk = (s2.nslice + bslices - 1) / bslices;
-  s2.nwv = nblk * wpb;
-  s2.wpg = wpb;
-  c->gl_block_items = bitems;
-  {
-    // serpentine inside the block keeps its waves level
-    std::vector<uint32_t> so((size_t)s2.nwv * G2);
-    for (uint32_t ob = 0; ob < nblk; ++ob)
-      for (uint32_t w = 0; w < wpb; ++w)
-        for (uint32_t g = 0; g < G2; ++g) {
-          const uint32_t cand = (g & 1u) ? (g + 1) * wpb - 1 - w : g * wpb + w;
-          const uint64_t sl = (uint64_t)ob * bslices + cand;
-          so[((size_t)ob * wpb + w) * G2 + g] = sl < s2.nslice ? (uint32_t)sl : GL_NONE;
-        }
-    ISLECHK(build_side<2>(c, s2, so));
-    const double bc = GL_BAND_COST, wgs_per_cu = 2.0;  // measured by sweeps at C2
-    std::vector<uint32_t> slab0(nblk), nch(nblk, 0);
-    std::vector<GlDesc> ds;
-    uint32_t nslab = 0;
-    const char* e_col = c->knob(KN_GL_COLUMNS);
-    const bool columns = !(e_col && atoi(e_col) == 0) && s2.NB >= 16;  // ISLE_GL_COLUMNS=0: per-block chunking only
-    std::vector<unsigned long long> tot;
-    if (columns) {
-      // Band columns shared through L2.  Every word block walks every document band, so Y (48 MB at C2) is staged from HBM once
-      // per word block (13 x 48 MB = 0.62 GB of the 1.2 GB pass 2 moves; 25 x 60 MB = 1.5 of 2.6 GB at a C3 shard, where pass 2 runs
-      // at the HBM rate).  Here the document bands are cut into NC "columns" of equal total cost — at most GL_COL_BANDS bands, 1.3 MB
-      // of Y — the SAME cut for all word blocks, and all workgroups of a column are queued back to back on ONE XCD (workgroup i
-      // runs on XCD i % 8), so the column's bands are fetched from HBM once and found in that XCD's 4 MB L2 by the other word
-      // blocks (measured with one workgroup per (block, column): FETCH_SIZE of pass 2 1.11 -> 0.66 GB).  Inside a column a word
-      // block is cut into sub-chunks of about the same cost as everybody else's (the word blocks differ 5x in cost; with whole
-      // columns per workgroup the heavy ones set the makespan: 0.301 -> 0.349 ms at C2).
-      const uint32_t NB = s2.NB;
-      HIPCHK(c, c->gl_blocktot.reserve((size_t)nblk * NB));
-      hipLaunchKernelGGL(gl_blocktot_k, dim3(nblk, NB), dim3(256), 0, c->stream, c->gl_srsum.p, s2.nwv, wpb, NB, NB, c->gl_blocktot.p);
-      HIPCHK(c, hipGetLastError());
-      tot.resize((size_t)nblk * NB);
-      HIPCHK(c, hipMemcpyAsync(tot.data(), c->gl_blocktot.p, tot.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      std::vector<double> bcost(NB, 0.0);
-      double all = 0;
-      for (uint32_t bnd = 0; bnd < NB; ++bnd) {
-        for (uint32_t ob = 0; ob < nblk; ++ob) bcost[bnd] += (double)tot[(size_t)ob * NB + bnd] + bc;
-        all += bcost[bnd];
-      }
-      // <= 12 bands (1.9 MB of Y) per column: measured at C2 / C3 shard, pass 2 in ms — per-block chunks 0.291 / 0.474, columns of
-      // <= 8 bands 0.294 / 0.459, <= 12 bands 0.283 / 0.436, <= 16 bands 0.282 / 0.464
-      // with the planar bands and the final kernels (round 3), all of config 3 on one GPU (2452 bands): 8 / 12 / 16 / 24 / 32 / 48 / 64 bands
-      // 2.42 / 2.28 / 2.20 / 2.15 / 2.16 / 2.26 / 2.43 ms; a C3 shard and C2 do not depend on it (their column count is set by the other term)
-      const uint32_t colbands = 24u;
-      const double W = wgs_per_cu * c->num_cus;
-      uint32_t NC = 8u * (uint32_t)std::ceil(std::max(W / (1.25 * nblk), (double)NB / colbands) / 8.0);
-      NC = std::max(8u, std::min(NC, (NB / 8u) * 8u));
-      std::vector<uint32_t> cut(NC + 1, 0);  // column cc = bands [cut[cc], cut[cc + 1])
-      {
-        double pre = 0;
-        uint32_t cc = 1;
-        for (uint32_t bnd = 0; bnd < NB && cc < NC; ++bnd) {
-          pre += bcost[bnd];
-          // close column cc - 1 behind this band once its share of the cost is reached, leaving at least one band per later column
-          while (cc < NC && (pre >= all * cc / NC || NB - (bnd + 1) <= NC - cc) && bnd + 1 > cut[cc - 1]) cut[cc++] = bnd + 1;
-        }
-        while (cc <= NC) cut[cc++] = NB;
-        cut[NC] = NB;
-      }
-      for (uint32_t cc = 0; cc < NC; ++cc)
-        if (cut[cc + 1] <= cut[cc]) return isle_fail(c, ISLE_E_NUMERIC, "operator build: empty band column");
-      const double target = std::max(1.0, all / W);
-      // sub-chunks per (block, column), then the blocks' slab ranges, then the descriptors in XCD queues
-      std::vector<uint32_t> nsub((size_t)nblk * NC);
-      for (uint32_t ob = 0; ob < nblk; ++ob) {
-        slab0[ob] = nslab;
-        for (uint32_t cc = 0; cc < NC; ++cc) {
-          double cost = 0;
-          for (uint32_t bnd = cut[cc]; bnd < cut[cc + 1]; ++bnd) cost += (double)tot[(size_t)ob * NB + bnd] + bc;
-          const uint32_t nb = cut[cc + 1] - cut[cc];
-          const uint32_t n = (uint32_t)std::min<double>((double)nb, std::max(1.0, std::floor(cost / target + 0.5)));
-          nsub[(size_t)ob * NC + cc] = n;
-          nch[ob] += n;
-          nslab += n;
-        }
-      }
-      std::vector<std::vector<GlDesc>> xq(8);
-      std::vector<std::pair<double, uint32_t>> order(nblk);
-      std::vector<uint32_t> next(nblk);
-      for (uint32_t ob = 0; ob < nblk; ++ob) next[ob] = slab0[ob];
-      for (uint32_t cc = 0; cc < NC; ++cc) {
-        const uint32_t b0 = cut[cc], b1 = cut[cc + 1], nb = b1 - b0;
-        for (uint32_t ob = 0; ob < nblk; ++ob) {
-          double t = 0;
-          for (uint32_t bnd = b0; bnd < b1; ++bnd) t += (double)tot[(size_t)ob * NB + bnd];
-          order[ob] = {-t / nsub[(size_t)ob * NC + cc], ob};
-        }
-        std::sort(order.begin(), order.end());  // heaviest workgroups of the column first
-        for (auto& o : order) {
-          const uint32_t ob = o.second, n = nsub[(size_t)ob * NC + cc];
-          for (uint32_t q = 0; q < n; ++q)
-            xq[cc % 8].push_back(GlDesc{ob * wpb, 1u, wpb, b0 + (uint32_t)((uint64_t)q * nb / n), b0 + (uint32_t)((uint64_t)(q + 1) * nb / n), next[ob]++,
-                                        ob * bitems, 0u});
-        }
-      }
-      size_t qmax = 0;
-      for (auto& q : xq) qmax = std::max(qmax, q.size());
-      ds.reserve(qmax * 8);
-      for (size_t j = 0; j < qmax; ++j)
-        for (uint32_t x = 0; x < 8; ++x) ds.push_back(j < xq[x].size() ? xq[x][j] : GlDesc{0u, 1u, 0u, 0u, 0u, 0u, 0u, 0u});  // empty: no wave is valid
-    } else {
-      // per word block: band chunks in proportion to the block's cost (round 1's form; small matrices, or ISLE_GL_COLUMNS=0).
-      // Cost = super-rounds (LDS-bound, ~50 ns of CU time each) + GL_BAND_COST per band staged; without the second term a block
-      // of rare words would walk all bands in a single workgroup
-      HIPCHK(c, c->gl_blocktot.reserve((size_t)nblk));
-      hipLaunchKernelGGL(gl_blocktot_k, dim3(nblk, 1), dim3(256), 0, c->stream, c->gl_srsum.p, s2.nwv, wpb, s2.NB, 1u, c->gl_blocktot.p);
-      HIPCHK(c, hipGetLastError());
-      tot.resize(nblk);
-      HIPCHK(c, hipMemcpyAsync(tot.data(), c->gl_blocktot.p, tot.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      double all = 0;
-      for (auto t : tot) all += (double)t;
-      all += bc * (double)s2.NB * nblk;
-      const double target = std::max(1.0, all / (wgs_per_cu * c->num_cus));
-      for (uint32_t ob = 0; ob < nblk; ++ob) {
-        slab0[ob] = nslab;
-        const uint32_t nzb = s2.NB;
-        const double cost = (double)tot[ob] + bc * nzb;
-        const uint32_t n = (uint32_t)std::min<double>((double)nzb, std::max(1.0, std::ceil(cost / target)));
-        for (uint32_t ch = 0; ch < n; ++ch) {
-          const uint32_t b0 = (uint32_t)((uint64_t)ch * nzb / n), b1 = (uint32_t)((uint64_t)(ch + 1) * nzb / n);
-          ds.push_back(GlDesc{ob * wpb, 1u, wpb, b0, b1, nslab, ob * bitems, 0u});
-          ++nslab;
-          ++nch[ob];
-        }
-      }
+  fprintf(stderr, "\n");
+  for (const GlSide* sd : {&s1, &s2}) {
+    const size_t ncnt = (size_t)sd->nwv * sd->NB * GL_GMAX;
+    std::vector<uint16_t> h(ncnt);
+    HIPCHK(c, hipMemcpy(h.data(), sd->cnt.p, ncnt * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    unsigned long long nsl = 0, nhalf = 0, sr = 0, hist[6] = {0, 0, 0, 0, 0, 0};
+    for (size_t i = 0; i < ncnt; ++i) {
+      const uint32_t n = h[i] & 0x7fffu;
+      if (!n) continue;
+      ++nsl;
+      nhalf += h[i] >> 15;
+      sr += n;
+      ++hist[n < 5 ? n : 5];
     }
-    s2.ndesc = (uint32_t)ds.size();
-    HIPCHK(c, s2.desc.reserve(ds.size()));
-    HIPCHK(c, c->gl_slab0.reserve(nblk));
-    HIPCHK(c, c->gl_nch.reserve(nblk));
-    HIPCHK(c, hipMemcpyAsync(s2.desc.p, ds.data(), ds.size() * sizeof(GlDesc), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->gl_slab0.p, slab0.data(), nblk * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->gl_nch.p, nch.data(), nblk * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, c->gl_part.reserve((size_t)nslab * bitems * 12));  // sized for the widest panel (BP = 12)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->knob_on(KN_GL_VERBOSE)) {
-      fprintf(stderr, "[gram_lds] pass-2 %s, word blocks (super-rounds, chunks):", columns ? "band columns shared per XCD" : "per-block band chunks");
-      const size_t per = columns ? s2.NB : 1;
-      for (uint32_t ob = 0; ob < nblk; ++ob) {
-        unsigned long long t = 0;
-        for (size_t z = 0; z < per; ++z) t += tot[(size_t)ob * per + z];
-        fprintf(stderr, " %llu/%u", t, nch[ob]);
-      }
-      fprintf(stderr, "\n");
-    }
-    if (c->knob_on(KN_GL_VERBOSE)) {  // how many (wave, band, group) slices end in a half super-round, and the slices' lengths
-      for (const GlSide* sd : {&s1, &s2}) {
-        const size_t ncnt = (size_t)sd->nwv * sd->NB * GL_GMAX;
-        std::vector<uint16_t> h(ncnt);
-        HIPCHK(c, hipMemcpy(h.data(), sd->cnt.p, ncnt * sizeof(uint16_t), hipMemcpyDeviceToHost));
-        unsigned long long nsl = 0, nhalf = 0, sr = 0, hist[6] = {0, 0, 0, 0, 0, 0};
-        for (size_t i = 0; i < ncnt; ++i) {
-          const uint32_t n = h[i] & 0x7fffu;
-          if (!n) continue;
-          ++nsl;
-          nhalf += h[i] >> 15;
-          sr += n;
-          ++hist[n < 5 ? n : 5];
-        }
-        fprintf(stderr, "[gram_lds] pass %d: %llu slices, %llu super-rounds, %.1f %% end in a half one; slices of 1/2/3/4/5+ super-rounds: %.1f %.1f %.1f %.1f %.1f %%\n",
-                sd == &s1 ? 1 : 2, nsl, sr, 100.0 * nhalf / std::max(1ull, nsl), 100.0 * hist[1] / std::max(1ull, nsl), 100.0 * hist[2] / std::max(1ull, nsl),
-                100.0 * hist[3] / std::max(1ull, nsl), 100.0 * hist[4] / std::max(1ull, nsl), 100.0 * hist[5] / std::max(1ull, nsl));
-      }
-    }
-    if (c->knob_on(KN_GL_VERBOSE))
-      fprintf(stderr,
-              "[gram_lds] V=%u D=%u nnz=%llu | pass1: bands=%u items/lane=%d waves=%u wgs=%u padded=%.2fx | pass2: bands=%u items/lane=%d blocks=%u wgs=%u slabs=%u "
-              "padded=%.2fx\n",
-              V, D, (unsigned long long)c->nnz, s1.NB, s1.G, s1.nwv, s1.ndesc, (double)s1.total_sr * 256.0 / (double)c->nnz, s2.NB, s2.G, nblk, s2.ndesc,
-              nslab, (double)s2.total_sr * 256.0 / (double)c->nnz);
+    fprintf(stderr, "[gram_lds] pass %d: %llu slices, %llu super-rounds, %.1f %% end in a half one; slices of 1/2/3/4/5+ super-rounds: %.1f %.1f %.1f %.1f %.1f %%\n",
+            sd == &s1 ? 1 : 2, nsl, sr, 100.0 * nhalf / std::max(1ull, nsl), 100.0 * hist[1] / std::max(1ull, nsl), 100.0 * hist[2] / std::max(1ull, nsl),
+            100.0 * hist[3] / std::max(1ull, nsl), 100.0 * hist[4] / std::max(1ull, nsl), 100.0 * hist[5] / std::max(1ull, nsl));
   }
+  fprintf(stderr,
+          "[gram_lds] V=%u D=%u nnz=%llu | pass1: bands=%u items/lane=%d waves=%u wgs=%u padded=%.2fx | pass2: bands=%u items/lane=%d blocks=%u wgs=%u slabs=%u "
+          "padded=%.2fx\n",
+          s2.n_out, s1.n_out, (unsigned long long)c->nnz, s1.NB, s1.G, s1.nwv, s1.ndesc, (double)s1.total_sr * 256.0 / (double)c->nnz, s2.NB, s2.G, g.nblk, s2.ndesc,
+          sch.nslab, (double)s2.total_sr * 256.0 / (double)c->nnz);
+  return 0;
+}
+
+int k_gl_ablate_skip(isle_ctx* c);
+int k_gl_build(isle_ctx* c) {
+  const uint32_t D = (uint32_t)c->D, V = (uint32_t)c->V, cus = (uint32_t)c->num_cus;
+  ISLECHK(isle_max_lds(c, (const void*)gl_hist_count_k, GL_HLDS));
+  ISLECHK(isle_max_lds(c, (const void*)gl_hist_fill_k, GL_HLDS));
+  const GlPlanOpts o = gl_options(c);
+  ISLECHK(gl_order_documents(c, D, V));
+  const GlPlan1 p1 = gl_plan_pass1(c->nnz, D, V, cus, o);
+  ISLECHK(gl_band_starts(c, D, p1.NB));
+  ISLECHK(gl_pass1_streams(c, D, V, p1));
+  const GlGeom2 g2 = gl_plan_pass2_geometry(D, V, cus, o);
+  ISLECHK(gl_cell_histogram(c, D, V, g2.NB));
+  ISLECHK(gl_order_words(c, D, V, g2.NB));
+  ISLECHK(gl_pass2_streams(c, D, V, g2));
+  std::vector<unsigned long long> tot;
+  ISLECHK(gl_block_totals(c, g2, gl_use_columns(g2.NB, o), tot));
+  const GlSched2 sch = gl_plan_pass2_schedule(tot, g2.nblk, g2.NB, g2.wpg, g2.bitems, cus, gl_use_columns(g2.NB, o));
+  if (sch.error) return isle_fail(c, ISLE_E_NUMERIC, "operator build: %s", sch.error);
+  ISLECHK(gl_upload_schedule(c, g2, sch));
+  if (c->knob_on(KN_GL_VERBOSE)) ISLECHK(gl_report(c, g2, sch, tot));
   return k_gl_ablate_skip(c);
 }
 
 // TIMING EXPERIMENT (ISLE_GL_ABLATE_SKIP=m, round 6): the count records of every m-th (band, group) of every wave are zeroed behind the
 // build, so that the unchanged apply kernel walks (1 - 1/m) of its super-rounds and reads as much of its id stream (the waves then read
 // the ids of other cells: valid rows, wrong sums — Z is wrong by construction).  Prices a form with that many fewer padded slots at no
-// other cost; the in-kernel variant of the same cut (GL_ABLATE 256) moves the register allocation and spills.
+// other cost; an in-kernel variant of the same cut (a compile-time flag, since removed) moved the register allocation and spilled.
 __global__ __launch_bounds__(256) void gl_ablate_cnt_k(uint16_t* __restrict__ cnt, size_t n, uint32_t NB, int G, uint32_t m) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;

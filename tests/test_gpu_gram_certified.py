@@ -42,7 +42,7 @@ def pattern(name):
 
 
 def _mid():
-    # >= 30 000 documents: several rounds of pass-1 workgroups under ISLE_GL_TEST_CUS (gram_lds.hip:1459)
+    # >= 30 000 documents: several rounds of pass-1 workgroups under ISLE_GL_TEST_CUS (gl_plan.h gl_plan_pass1)
     return 6000, *pattern_random(6000, 30000, 5, 60, 101, must=(0, 4077, 4078, 5999))
 
 
@@ -51,18 +51,18 @@ _BUILDERS = {
     "ragged": lambda: (4500, *pattern_ragged(4500, 3000, 11)),
     "other": lambda: (3000, *pattern_random(3000, 2000, 1, 30, 102)),
     "place": lambda: (GL_RB, *pattern_place(103)),
-    # G2 = 6 beyond 1024 document bands (s2.NB > 1024, gram_lds.hip:1525): 1025 bands and more
+    # G2 = 6 beyond 1024 document bands (s2.NB > 1024, gl_plan.h gl_plan_pass2_geometry): 1025 bands and more
     "G2six": lambda: (5000, *pattern_random(5000, 4_180_000, 1, 3, 104, must=(4999,))),
 }
-for _V in (4077, 4078, 4079, 8156, 8157):  # word bands of GL_RB = 4078 rows (pass 1's sources, gram_lds.hip:1414)
+for _V in (4077, 4078, 4079, 8156, 8157):  # word bands of GL_RB = 4078 rows (pass 1's sources, gl_plan.h gl_plan_pass1)
     _BUILDERS["V%d" % _V] = (lambda V: lambda: (V, *pattern_random(V, 3000, 1, 12, V, must=tuple(sorted({4076, min(4077, V - 1), min(4078, V - 1), V - 1})))))(_V)
-for _D in (1, 63, 64, 65, 4078, 4079):  # slices of 64 outputs and document bands of GL_RB (pass 2's sources, gram_lds.hip:1498)
+for _D in (1, 63, 64, 65, 4078, 4079):  # slices of 64 outputs and document bands of GL_RB (pass 2's sources, gl_plan.h gl_plan_pass2_geometry)
     _BUILDERS["D%d" % _D] = (lambda D: lambda: (3000, *pattern_random(3000, D, 1, 200, D)))(_D)
-for _D in (61170, 61171):  # 15 and 16 document bands: band columns need s2.NB >= 16 (gram_lds.hip:1551)
+for _D in (61170, 61171):  # 15 and 16 document bands: band columns need s2.NB >= 16 (gl_plan.h gl_use_columns)
     _BUILDERS["D%d" % _D] = (lambda D: lambda: (3000, *pattern_random(3000, D, 1, 6, D)))(_D)
-for _V in (GL_VP - 1, GL_VP, GL_VP + 1, 2 * GL_VP + 1):  # vocabulary parts of the LDS histograms (gl_hist_count_k grid, gram_lds.hip:1500)
+for _V in (GL_VP - 1, GL_VP, GL_VP + 1, 2 * GL_VP + 1):  # vocabulary parts of the LDS histograms (gl_hist_count_k grid, gram_lds.hip gl_cell_histogram)
     _BUILDERS["V%d" % _V] = (lambda V: lambda: (V, *pattern_random(V, 3000, 20, 60, V, must=(GL_VP - 2, GL_VP - 1, min(GL_VP, V - 1), V - 1))))(_V)
-for _V in (1 << 20, (1 << 20) + 1):  # the pass-2 stream is filled by buckets only for V <= 2^20 (gram_lds.hip:1269)
+for _V in (1 << 20, (1 << 20) + 1):  # the pass-2 stream is filled by buckets only for V <= 2^20 (gram_lds.hip GlStream::fill_pass2)
     _BUILDERS["V%d" % _V] = (lambda V: lambda: (V, *pattern_random(V, 20000, 1, 5, V, must=((1 << 20) - 2, (1 << 20) - 1, V - 1))))(_V)
 
 
@@ -150,14 +150,14 @@ def test_document_slices_and_bands(hp, D):
 
 @pytest.mark.parametrize("D,columns", [(61170, None), (61171, None), (61171, "0")])
 def test_band_columns(hp, monkeypatch, D, columns):
-    # 15 bands: per-block chunking; 16: band columns shared through L2 (gram_lds.hip:1551); ISLE_GL_COLUMNS=0 at 16
+    # 15 bands: per-block chunking; 16: band columns shared through L2 (gl_plan.h gl_use_columns); ISLE_GL_COLUMNS=0 at 16
     if columns is not None:
         monkeypatch.setenv("ISLE_GL_COLUMNS", columns)
     certify_case(hp, "D%d" % D, 1, label="form 1, ISLE_GL_COLUMNS=%s" % (columns or "default"))
 
 
 def test_more_than_1024_document_bands_take_six_items_per_lane(hp):
-    # 4 180 000 documents = 1026 bands: s2.G = 6 by default (gram_lds.hip:1525); once with non-dyadic values
+    # 4 180 000 documents = 1026 bands: s2.G = 6 by default (gl_plan.h gl_plan_pass2_geometry); once with non-dyadic values
     certify_case(hp, "G2six", 1, label="form 1, G2 = 6 (1026 document bands)")
 
 
@@ -168,7 +168,7 @@ def test_vocabulary_parts_of_the_histograms(hp, V):
 
 @pytest.mark.parametrize("V,buckets", [(1 << 20, None), ((1 << 20) + 1, None), (1 << 20, "0")])
 def test_fill_by_buckets_up_to_2_pow_20_words(hp, monkeypatch, V, buckets):
-    # gram_lds.hip:1269: buckets of word positions for V <= 2^20, the direct scatter above and under ISLE_GL_FILL_BUCKETS=0
+    # gram_lds.hip GlStream::fill_pass2: buckets of word positions for V <= 2^20, the direct scatter above and under ISLE_GL_FILL_BUCKETS=0
     if buckets is not None:
         monkeypatch.setenv("ISLE_GL_FILL_BUCKETS", buckets)
     certify_case(hp, "V%d" % V, 1, b=2, label="form 1, ISLE_GL_FILL_BUCKETS=%s" % (buckets or "default"))
@@ -186,7 +186,7 @@ def test_placement_and_register_sorts(hp, monkeypatch, place):
 @pytest.mark.parametrize("cus", ["3", "7"])
 @pytest.mark.parametrize("rounds", [None, "0"])
 def test_rounds_of_workgroups(hp, monkeypatch, cus, rounds):
-    # pass 1 laid out for a device of 3 or 7 CUs: whole rounds of adjacent waves, or strided under ISLE_GL_ROUNDS=0 (gram_lds.hip:1459)
+    # pass 1 laid out for a device of 3 or 7 CUs: whole rounds of adjacent waves, or strided under ISLE_GL_ROUNDS=0 (gl_plan.h gl_plan_pass1)
     monkeypatch.setenv("ISLE_GL_TEST_CUS", cus)
     if rounds is not None:
         monkeypatch.setenv("ISLE_GL_ROUNDS", rounds)
@@ -226,7 +226,7 @@ def test_chunk_sizes_of_the_gather_form_in_fresh_contexts(monkeypatch, chunk):
         h.close()
 
 
-# ---- reproducibility: Z depends on B alone (the id sort, gram_lds.hip:473) in every form -------------------------------------------
+# ---- reproducibility: Z depends on B alone (the id sort, gram_lds.hip gl_sort2_k) in every form -------------------------------------------
 @pytest.mark.parametrize("switch,value", [(None, None)] + SWEEP_CASES)
 def test_reupload_gives_the_same_bits(hp, monkeypatch, switch, value):
     from isle_amd import HotPath

@@ -8,7 +8,7 @@ SRCS=${@:-gram_lds.hip}
 HERE=$(cd "$(dirname "$0")" && pwd); CS=$HERE/../isle_amd/csrc; OUT=$HERE/variants; mkdir -p $OUT/obj_$NAME
 make -s -C $CS ../libisle_hip.so
 OBJS=""
-for o in api api_ks api_kmeans api_stages spmm gram_lds evd_tridiag dense kmeans threshold post ingest infer; do
+for o in $(make -s -C $CS print-objs | sed 's/\.o//g'); do
   src=""; for s in $SRCS; do [ "${s%.*}" = "$o" ] && src=$s; done
   if [ -n "$src" ]; then
     x=""; [ "${src##*.}" = "cpp" ] && x="-x hip"
@@ -16,5 +16,5 @@ for o in api api_ks api_kmeans api_stages spmm gram_lds evd_tridiag dense kmeans
     OBJS="$OBJS $OUT/obj_$NAME/$o.o"
   else OBJS="$OBJS $CS/$o.o"; fi
 done
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib -o $OUT/libisle_$NAME.so $OBJS
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -L/opt/rocm/lib -lrccl -ldl -Wl,-rpath,/opt/rocm/lib -o $OUT/libisle_$NAME.so $OBJS
 echo built $OUT/libisle_$NAME.so

@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """Timing probe for the Gram apply at C2 size: device ms of pass 1 / pass 2 / operator build for a list of environment
-settings (each setting re-uploads B, which rebuilds the operator).  usage: gram_probe.py ['ENV=VAL,ENV=VAL' ...]
-(GRAM_PROBE_WORKLOAD=c3shard: vocab 100k, 1.25M documents instead)"""
+settings (each setting re-uploads B, which rebuilds the operator), and the CRC-32 of Z's bits: two builds of the library that print the same
+CRC computed the same operator.  usage: gram_probe.py ['ENV=VAL,ENV=VAL' ...]
+(GRAM_PROBE_WORKLOAD=c3shard: vocab 100k, 1.25M documents instead)
+What the library writes to stderr (the "[gram_lds]" lines under ISLE_GL_VERBOSE=1) is not touched: a "== <setting>" line on stdout and on
+stderr goes before every setting, so that those lines can be told apart when both streams go to one file."""
 import os
 import sys
+import zlib
 
 import numpy as np
 
@@ -25,6 +29,8 @@ for setting in (sys.argv[1:] or [""]):
     kv = [s.split("=") for s in setting.split(",") if s]
     for a, b in kv:
         os.environ[a] = b
+    for f in (sys.stdout, sys.stderr):
+        print("== %s" % (setting or "(default)"), file=f, flush=True)
     hp.timing_enable(True)
     hp.timing_reset()
     hp.upload_csc(V, B["vals"], B["rows"], B["offs"])
@@ -40,7 +46,7 @@ for setting in (sys.argv[1:] or [""]):
         for _ in range(reps):
             hp.gram_apply(X)
         t = hp.timing_get()
-        print("%-40s form=%d pass1 %.4f ms  pass2 %.4f ms  op_build %.1f ms (relerr vs first %.1e)" % (setting or "(default)", hp.operator_form(),
-              t["gram_pass1"][0] / reps, t["gram_pass2"][0] / reps, op_build, err), flush=True)
+        print("%-40s form=%d pass1 %.4f ms  pass2 %.4f ms  op_build %.1f ms (relerr vs first %.1e) crc32(Z) %08x" % (setting or "(default)", hp.operator_form(),
+              t["gram_pass1"][0] / reps, t["gram_pass2"][0] / reps, op_build, err, zlib.crc32(np.ascontiguousarray(Z).tobytes())), flush=True)
     for a, b in kv:
         del os.environ[a]
