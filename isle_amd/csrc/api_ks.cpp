@@ -11,37 +11,15 @@
 #include <numeric>
 
 #include "api_internal.h"
+#include "ks_host.h"
 
-constexpr int KS_AGREE = 40;  // int slots [40, 43) of the expand mailbox: max rank, -min rank, max status over all ranks
 __global__ void ks_agree_pack_k(int* meta) {
   if (threadIdx.x == 0) {
-    meta[KS_AGREE] = meta[0];
-    meta[KS_AGREE + 1] = -meta[0];
-    meta[KS_AGREE + 2] = meta[1];
+    meta[KS_AGREE_MAX_RANK] = meta[0];
+    meta[KS_AGREE_NEG_MIN_RANK] = -meta[0];
+    meta[KS_AGREE_STATUS] = meta[1];
   }
 }
-
-namespace {
-
-struct HMat {  // small col-major float matrix on the host (the projected matrix H)
-  size_t r = 0, c = 0, ld = 0, cap_c = 0;  // r x c in use inside an ld x cap_c allocation (zero outside what was written)
-  std::vector<float> a;
-  HMat() {}
-  HMat(size_t r_, size_t c_) : r(r_), c(c_), ld(r_), cap_c(c_), a(r_ * c_, 0.f) {}
-  // room to grow: the Krylov expansion appends blocks of rows and columns in place (at ncv = 2010 the matrix is 16 MB, and every
-  // fresh copy of it cost the host 2 - 6 ms with the GPU idle)
-  HMat(size_t r_, size_t c_, size_t cap_r_, size_t cap_c_) : r(r_), c(c_), ld(std::max(r_, cap_r_)), cap_c(std::max(c_, cap_c_)), a(ld * cap_c, 0.f) {}
-  float& operator()(size_t i, size_t j) { return a[j * ld + i]; }
-  float operator()(size_t i, size_t j) const { return a[j * ld + i]; }
-};
-HMat hsub(const HMat& m, size_t r0, size_t c0, size_t r1, size_t c1) {  // inclusive bounds (arma submat)
-  HMat o(r1 - r0 + 1, c1 - c0 + 1);
-  for (size_t j = c0; j <= c1; ++j)
-    for (size_t i = r0; i <= r1; ++i) o(i - r0, j - c0) = m(i, j);
-  return o;
-}
-}  // namespace
-
 
 // ------------------------------------------------------------------------------------------
 // Panel QR: rank-revealing CholQR2 on an fp64 Gram matrix.
@@ -101,9 +79,8 @@ struct Ks {
       }
       return 0;
     }
-    const uint64_t nloc = (((dim + c->world - 1) / c->world) + 3) & ~3ull;  // rows per rank, a multiple of 4 (16-byte aligned slices)
-    const uint64_t r0 = std::min<uint64_t>(dim, (uint64_t)c->rank * nloc), r1 = std::min<uint64_t>(dim, r0 + nloc);
-    const uint64_t nl = r1 - r0;
+    const KsSlice my = ks_row_slice(dim, c->world, c->rank);
+    const uint64_t nloc = my.nloc, r0 = my.r0, nl = my.r1 - my.r0;
     for (int p = 0; p < passes; ++p) {
       float* cf = base + (size_t)p * m * w;
       ISLECHK(k_vtf(c, Vb() + r0, nl, (int)m, F + r0, w, cf, dim));
@@ -118,8 +95,8 @@ struct Ks {
       ISLECHK(isle_allgather(c, mine, c->ks_gather.p, nloc * (size_t)w, ISLE_DT_F32));
     }
     for (int r = 0; r < c->world; ++r) {
-      const uint64_t q0 = std::min<uint64_t>(dim, (uint64_t)r * nloc), q1 = std::min<uint64_t>(dim, q0 + nloc);
-      if (r != c->rank && q1 > q0) ISLECHK(k_slice_rows(c, F, dim, w, q0, q1 - q0, nloc, c->ks_gather.p + (size_t)r * nloc * w, false));
+      const KsSlice q = ks_row_slice(dim, c->world, r);
+      if (r != c->rank && q.r1 > q.r0) ISLECHK(k_slice_rows(c, F, dim, w, q.r0, q.r1 - q.r0, nloc, c->ks_gather.p + (size_t)r * nloc * w, false));
     }
     return 0;
   }
@@ -166,212 +143,196 @@ struct Ks {
     std::vector<float> hc(2 * blk * blk);
     HIPCHK(c, hipMemcpyAsync(hc.data(), c->coef.p, hc.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     ISLECHK(dev_qr(c, V1, dim, (int)blk, col(blk), R, &rank));  // synchronises the stream
-    H = HMat(2 * blk, blk, std::max<size_t>(ncv, 2 * blk) + blk, blk + (std::max<size_t>(ncv, 2 * blk) + blk - 2 * blk));
-    for (size_t j = 0; j < blk; ++j) {
-      for (size_t i = 0; i < blk; ++i) H(i, j) = hc[j * blk + i] + hc[blk * blk + j * blk + i];
-      for (int i = 0; i < rank; ++i) H(blk + i, j) = R[j * rank + i];
-    }
+    H = ks_h_start(blk, ncv, hc.data(), R.data(), rank);
     vcols = blk + rank;
     if ((size_t)rank < blk) ISLECHK(repair(vcols, 2 * blk, blk - rank));
     vcols = 2 * blk;
     return 0;
   }
 
-  int expand() {  // :62-136
-    // H grows by blk rows and columns per step; it is kept in a work matrix of the final size while the loop runs (copying
-    // the whole of H at every step cost ~10 ms of host time per solve at ncv = 410, with the GPU idle behind the QR's sync)
-    isle_host_mark("expand: entry");
-    const size_t cap_r = std::max<size_t>(ncv, H.r) + blk, cap_c = H.c + (cap_r - H.r);
-    if (H.ld < cap_r || H.cap_c < cap_c) {  // init() and truncate() allocate with this room, so this copy is the exception
-      HMat W(H.r, H.c, cap_r, cap_c);
-      for (size_t j = 0; j < H.c; ++j)
-        for (size_t i = 0; i < H.r; ++i) W(i, j) = H(i, j);
-      H = std::move(W);
-    }
-    HMat& W = H;  // grows in place: rows hr.. and columns hcn.. are zero until a step writes them
-    size_t hr = H.r, hcn = H.c;
-    auto shrink = [&]() {
-      H.r = hr;
-      H.c = hcn;
-    };
-    // Pipelined: after the QR of step i is enqueued, the operator application and orthogonalisation of step i + 1 are
-    // enqueued too (they only need Q on the device, assuming full rank), and the host then waits for an event recorded
-    // behind the QR to fold R and the coefficients into H.  Everything the host needs from a step — rank and status of the QR,
-    // R, the three coefficient blocks — is written into one device mailbox and comes back as ONE copy (every small copy
-    // costs ~20 us of queue time).  A rank-deficient panel (never seen on thresholded matrices) discards the speculative
-    // work and repairs, as the synchronous form (ISLE_KS_SYNC=1) does.
-    // Round 6: the copy runs on a stream of its own behind an event — in the main stream it held the next step's kernels back for the ~10 us
-    // a 160 kB transfer over PCIe takes, 300 times per solve — and the device mailbox is double-buffered by slot, so that the next step's
-    // coefficients (written by the speculative orthogonalisation) never land in a mailbox whose copy may still be reading it: a slot is
-    // written again only after the host has waited for its copy.
-    const bool pipelined = !c->knob_on(KN_KS_SYNC);
-    // Passes of block Gram-Schmidt against the basis per step.  The reference makes three (CGS + 2 DGKS, :83-91); the second
-    // already leaves coefficients at rounding level ("twice is enough"), so two are made here and the third
-    // block of coefficients that the reference adds into H is zero.  ISLE_KS_ORTHO_PASSES=3 restores the reference's count.
-    int npass = 2;
-    if (const char* e = c->knob(KN_KS_ORTHO_PASSES)) npass = std::max(2, std::min(3, atoi(e)));
-    constexpr size_t MB_R = 64, MB_COEF = 64 + 32 * 32;  // mailbox offsets (floats): [meta ints | R | coefficients]
-    const size_t mb_floats = MB_COEF + 3 * cap_r * blk;
+  // ---- expand (:62-136) --------------------------------------------------------------------------------------------------------------------
+  // Pipelined: after the QR of step i is enqueued, the operator application and orthogonalisation of step i + 1 are
+  // enqueued too (they only need Q on the device, assuming full rank), and the host then waits for an event recorded
+  // behind the QR to fold R and the coefficients into H.  Everything the host needs from a step — rank and status of the QR,
+  // R, the three coefficient blocks — is written into one device mailbox (ks_host.h) and comes back as ONE copy (every small copy
+  // costs ~20 us of queue time).  A rank-deficient panel (never seen on thresholded matrices) discards the speculative
+  // work and repairs, as the synchronous form (ISLE_KS_SYNC=1) does.
+  // Round 6: the copy runs on a stream of its own behind an event — in the main stream it held the next step's kernels back for the ~10 us
+  // a 160 kB transfer over PCIe takes, 300 times per solve — and the device mailbox is double-buffered by slot, so that the next step's
+  // coefficients (written by the speculative orthogonalisation) never land in a mailbox whose copy may still be reading it: a slot is
+  // written again only after the host has waited for its copy.
+  struct Expand {
+    KsCap cap;              // rows / columns the work matrix has room for
+    int npass;              // passes of block Gram-Schmidt per step (2, or 3 under ISLE_KS_ORTHO_PASSES)
+    bool pipelined;         // step i + 1 is enqueued before the host waits for step i (not under ISLE_KS_SYNC)
+    float* mail[2];         // the two device mailboxes
+    float* host_mail[2];    // where their copies land: page-locked when they fit the context's slots, else host_mail_pageable
+    std::vector<float> host_mail_pageable[2];
+    size_t hr, hcn;         // rows / columns of H written so far; H.r / H.c take them in shrink()
+    bool spec = false;      // apply + ortho of the step that comes next are already enqueued, into mailbox `slot`
+    int slot = 0;           // mailbox, landing area and events of the current step; a speculative step writes the other one
+  };
+
+  // mailboxes, events, the copy stream and the host landing slots
+  int expand_prepare(Expand& e) {
+    e.pipelined = !c->knob_on(KN_KS_SYNC);
+    e.npass = ks_ortho_passes(c->knob(KN_KS_ORTHO_PASSES));
+    const size_t mb_floats = ks_mail_floats(e.cap.r, blk);
     HIPCHK(c, c->ks_mail.reserve(2 * mb_floats));
     for (int i = 0; i < 2; ++i) {
       if (!c->ks_ev[i]) HIPCHK(c, hipEventCreateWithFlags(&c->ks_ev[i], hipEventDisableTiming));
       if (!c->ks_ev_ready[i]) HIPCHK(c, hipEventCreateWithFlags(&c->ks_ev_ready[i], hipEventDisableTiming));
     }
     if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    std::vector<float> host_mail_pageable[2];
-    float* host_mail[2];
     for (int i = 0; i < 2; ++i) {
-      if (mb_floats * sizeof(float) <= isle_ctx::PIN_MAIL_SLOT) {  // page-locked: the copy below then really is asynchronous
-        host_mail[i] = reinterpret_cast<float*>(c->pin + isle_ctx::PIN_MAIL + (size_t)i * isle_ctx::PIN_MAIL_SLOT);
+      if (mb_floats * sizeof(float) <= isle_ctx::PIN_MAIL_SLOT) {  // page-locked: the copy of qr_and_post then really is asynchronous
+        e.host_mail[i] = reinterpret_cast<float*>(c->pin + isle_ctx::PIN_MAIL + (size_t)i * isle_ctx::PIN_MAIL_SLOT);
       } else {
-        host_mail_pageable[i].resize(mb_floats);
-        host_mail[i] = host_mail_pageable[i].data();
+        e.host_mail_pageable[i].resize(mb_floats);
+        e.host_mail[i] = e.host_mail_pageable[i].data();
       }
+      e.mail[i] = c->ks_mail.p + (size_t)i * mb_floats;
     }
+    return 0;
+  }
+
+  // operator application to basis columns [from_col, from_col + blk) and orthogonalisation against the first m basis vectors, the
+  // coefficients into `mailbox`: the step itself, or the speculative next one
+  int enqueue_step(const Expand& e, size_t m, size_t from_col, float* mailbox) {
+    ISLECHK(apply(col(from_col), c->Fbuf.p));
+    return ortho(c->Fbuf.p, (int)blk, m, e.npass, mailbox + KS_MB_COEF);
+  }
+
+  // panel QR of the step into basis columns [hcn + blk, ..), the ranks' agreement on it, and the mailbox's copy to the host posted on the copy stream
+  int qr_and_post(const Expand& e, size_t m) {
+    float* mail = e.mail[e.slot];
+    ISLECHK(k_panel_qr_kernels(c, c->Fbuf.p, dim, (int)blk, col(e.hcn + blk), reinterpret_cast<int*>(mail), mail + KS_MB_R));
+    if (c->multi()) {  // the ranks' verdicts on this block travel with the mailbox (see agree_i32)
+      hipLaunchKernelGGL(ks_agree_pack_k, dim3(1), dim3(64), 0, c->stream, reinterpret_cast<int*>(mail));
+      HIPCHK(c, hipGetLastError());
+      TimeScope ts(c, ISLE_T_COMM);
+      ISLECHK(isle_allreduce(c, reinterpret_cast<int*>(mail) + KS_AGREE, 3, ISLE_DT_I32, true));
+    }
+    HIPCHK(c, hipEventRecord(c->ks_ev_ready[e.slot], c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ks_ev_ready[e.slot], 0));
+    HIPCHK(c, hipMemcpyAsync(e.host_mail[e.slot], mail, ks_mail_copied(e.npass, m, blk) * sizeof(float), hipMemcpyDeviceToHost, c->copy_stream));
+    HIPCHK(c, hipEventRecord(c->ks_ev[e.slot], c->copy_stream));
+    return 0;
+  }
+
+  // the step's mailbox has landed: the two failure verdicts, else the rank of its panel
+  int wait_and_check(const Expand& e, int* rk) {
+    HIPCHK(c, hipEventSynchronize(c->ks_ev[e.slot]));
+    const int* meta = reinterpret_cast<const int*>(e.host_mail[e.slot]);
+    if (c->multi() && meta[KS_AGREE_MAX_RANK] != -meta[KS_AGREE_NEG_MIN_RANK])
+      return isle_fail(c, ISLE_E_COMM, "ranks disagree on the rank of a Krylov block (min %d, max %d): replicated state diverged",
+                       -meta[KS_AGREE_NEG_MIN_RANK], meta[KS_AGREE_MAX_RANK]);
+    if (meta[1] || (c->multi() && meta[KS_AGREE_STATUS]))
+      return isle_fail(c, ISLE_E_NUMERIC, "CholQR2: second Gram matrix not positive definite");
+    *rk = meta[0];
+    return 0;
+  }
+
+  void shrink(const Expand& e) {
+    H.r = e.hr;
+    H.c = e.hcn;
+  }
+
+  // a panel of rank rk < blk: the speculative step used columns that are about to be replaced
+  int repair_after(Expand& e, int rk) {
+    if (e.spec) {
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      e.spec = false;
+      napplies--;
+    }
+    shrink(e);  // repair() reads H.r / H.c
+    size_t nvecs = H.c + rk;
+    return repair(nvecs, H.r, blk - rk);
+  }
+
+  int expand() {
+    isle_host_mark("expand: entry");
+    Expand e;
+    e.cap = ks_h_reserve(H, ncv, blk);  // H grows in place: rows hr.. and columns hcn.. are zero until a step writes them
+    e.hr = H.r;
+    e.hcn = H.c;
+    ISLECHK(expand_prepare(e));
     isle_host_mark("expand: work matrix ready");
-    float* const mail2[2] = {c->ks_mail.p, c->ks_mail.p + mb_floats};
-    bool spec = false;  // apply + ortho of the current step already enqueued
-    int slot = 0;
-    while (hr < ncv) {
-      const size_t m = hr;
-      float* F = c->Fbuf.p;
-      float* mail = mail2[slot];
-      if (!spec) {
-        ISLECHK(apply(col(hcn), F));
-        ISLECHK(ortho(F, (int)blk, m, npass, mail + MB_COEF));
+    while (e.hr < ncv) {
+      const size_t m = e.hr;
+      if (!e.spec) ISLECHK(enqueue_step(e, m, e.hcn, e.mail[e.slot]));
+      e.spec = false;
+      if (m + blk > e.cap.r || e.hcn + blk > e.cap.c) return isle_fail(c, ISLE_E_NUMERIC, "expand: projected matrix outgrew its work space");
+      ISLECHK(qr_and_post(e, m));
+      if (e.pipelined && m + blk < ncv) {  // speculate: full rank -> next step works on the blk new columns with m + blk basis vectors
+        ISLECHK(enqueue_step(e, m + blk, e.hcn + blk, e.mail[e.slot ^ 1]));  // the other slot's mailbox: its last copy has been waited for
+        e.spec = true;
       }
-      spec = false;
-      if (m + blk > cap_r || hcn + blk > cap_c) return isle_fail(c, ISLE_E_NUMERIC, "expand: projected matrix outgrew its work space");
-      ISLECHK(k_panel_qr_kernels(c, F, dim, (int)blk, col(hcn + blk), reinterpret_cast<int*>(mail), mail + MB_R));
-      if (c->multi()) {  // the ranks' verdicts on this block travel with the mailbox (see agree_i32)
-        hipLaunchKernelGGL(ks_agree_pack_k, dim3(1), dim3(64), 0, c->stream, reinterpret_cast<int*>(mail));
-        HIPCHK(c, hipGetLastError());
-        TimeScope ts(c, ISLE_T_COMM);
-        ISLECHK(isle_allreduce(c, reinterpret_cast<int*>(mail) + KS_AGREE, 3, ISLE_DT_I32, true));
-      }
-      float* hm = host_mail[slot];
-      HIPCHK(c, hipEventRecord(c->ks_ev_ready[slot], c->stream));
-      HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ks_ev_ready[slot], 0));
-      HIPCHK(c, hipMemcpyAsync(hm, mail, (MB_COEF + (size_t)npass * m * blk) * sizeof(float), hipMemcpyDeviceToHost, c->copy_stream));
-      HIPCHK(c, hipEventRecord(c->ks_ev[slot], c->copy_stream));
-      const bool more = m + blk < ncv;
-      if (pipelined && more) {  // speculate: full rank -> next step works on the blk new columns with m + blk basis vectors
-        ISLECHK(apply(col(hcn + blk), F));
-        ISLECHK(ortho(F, (int)blk, m + blk, npass, mail2[slot ^ 1] + MB_COEF));  // the other slot's mailbox: its last copy has been waited for
-        spec = true;
-      }
-      HIPCHK(c, hipEventSynchronize(c->ks_ev[slot]));
-      const int* meta = reinterpret_cast<const int*>(hm);
-      if (c->multi() && meta[KS_AGREE] != -meta[KS_AGREE + 1])
-        return isle_fail(c, ISLE_E_COMM, "ranks disagree on the rank of a Krylov block (min %d, max %d): replicated state diverged",
-                         -meta[KS_AGREE + 1], meta[KS_AGREE]);
-      if (meta[1] || (c->multi() && meta[KS_AGREE + 2]))
-        return isle_fail(c, ISLE_E_NUMERIC, "CholQR2: second Gram matrix not positive definite");
-      const int rk = meta[0];
-      const float* hc = hm + MB_COEF;
-      const float* Rfull = hm + MB_R;
-      for (size_t j = 0; j < blk; ++j)
-        for (size_t i = 0; i < m; ++i) {
-          float h = hc[j * m + i];
-          h = h + hc[m * blk + j * m + i];
-          if (npass > 2) h = h + hc[2 * m * blk + j * m + i];
-          W(i, hcn + j) = h;
-        }
-      for (size_t j = 0; j < blk; ++j)
-        for (int i = 0; i < rk; ++i) W(m + i, hcn + j) = Rfull[j * rk + i];
-      hr = m + blk;
-      hcn += blk;
-      if ((size_t)rk < blk) {
-        if (spec) {  // the speculative step used columns that are about to be replaced
-          HIPCHK(c, hipStreamSynchronize(c->stream));
-          spec = false;
-          napplies--;
-        }
-        shrink();  // repair() reads H.r / H.c
-        size_t nvecs = H.c + rk;
-        ISLECHK(repair(nvecs, H.r, blk - rk));
-      }
-      slot ^= 1;
+      int rk = 0;
+      ISLECHK(wait_and_check(e, &rk));
+      ks_fold_step(H, m, e.hcn, blk, e.npass, e.host_mail[e.slot] + KS_MB_COEF, e.host_mail[e.slot] + KS_MB_R, rk);
+      e.hr = m + blk;
+      e.hcn += blk;
+      if ((size_t)rk < blk) ISLECHK(repair_after(e, rk));
+      e.slot ^= 1;
     }
     isle_host_mark("expand: loop done");
     HIPCHK(c, hipStreamSynchronize(c->stream));
     isle_host_mark("expand: synchronised");
-    shrink();
+    shrink(e);
     isle_host_mark("expand: shrink");
     vcols = H.r;
     return 0;
   }
 
-  int truncate() {  // :138-187
-    isle_host_mark("truncate: entry");
-    const size_t n = H.c - nconv;
-    const size_t keep = nev - nconv;  // only the leading `keep` eigenvectors are used below
-    // Everything that crosses the bus here lives in the context's page-locked staging area — [subH n x n | vH n x keep | locked
-    // rows of H nconv x n | top nconv x keep], 36 MB at k = 1000: copies from freshly allocated pageable vectors blocked the host
-    // (registration with the driver) and made their release slow, with the GPU idle in between.
-    HIPCHK(c, c->pin_stage.reserve((n * n + n * keep + nconv * n + nconv * keep) * sizeof(float)));
-    float* subH = reinterpret_cast<float*>(c->pin_stage.p);
-    float* vH = subH + n * n;
-    float* blkH = vH + n * keep;
-    float* top = blkH + nconv * n;
-    for (size_t j = 0; j < n; ++j) memcpy(subH + j * n, &H(nconv, nconv + j), n * sizeof(float));  // H(nconv:, nconv:), square
-    isle_host_mark("truncate: subH extracted");
-    std::vector<float> eH(n);
-    HIPCHK(c, c->Wf.reserve(n * n));
-    ISLECHK(k_eig_small(c, subH, (int)n, eH.data(), c->Wf.p, (int)keep));
-    isle_host_mark("truncate: eig_small returned");
-    HIPCHK(c, hipMemcpyAsync(vH, c->Wf.p, n * keep * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    // V = [ V(:, :nconv) | V(:, nconv : ncols-blk) * vH(:, :keep) | V(:, tail blk) ]
+  // ---- truncate (:138-187) -----------------------------------------------------------------------------------------------------------------
+  // Everything that crosses the bus here lives in the context's page-locked staging area (ks_stage_layout): copies from freshly
+  // allocated pageable vectors blocked the host (registration with the driver) and made their release slow, with the GPU idle in between.
+  struct Stage {
+    float *subH, *vH, *blkH, *top;
+  };
+
+  // V = [ V(:, :nconv) | V(:, nconv : ncols-blk) * vH(:, :keep) | V(:, tail blk) ] with the Ritz rotation in Wf (n x keep); vH and,
+  // with locked pairs, top come back to the staging area.  Ends synchronised.
+  int rotate_basis(const Stage& st, size_t n, size_t keep) {
+    HIPCHK(c, hipMemcpyAsync(st.vH, c->Wf.p, n * keep * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     ISLECHK(k_gemm_nn(c, col(nconv), dim, (int)n, c->Wf.p, (int)n, (int)keep, c->Tmp.p));
     // top = H(0:nconv, nconv:) * vH(:, :keep)  (:176-178), the coupling of the locked columns with the rotated block: nconv x n x keep
     // multiply-adds — 0.3 G at k = 1000 with 600 pairs locked, 31 ms of host time with the GPU idle when it was a host loop
     if (nconv > 0) {
       HIPCHK(c, c->ks_top.reserve(nconv * n + nconv * keep));
-      for (size_t t = 0; t < n; ++t) memcpy(blkH + t * nconv, &H(0, nconv + t), nconv * sizeof(float));
-      HIPCHK(c, hipMemcpyAsync(c->ks_top.p, blkH, nconv * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+      ks_h_extract_locked(H, nconv, st.blkH);
+      HIPCHK(c, hipMemcpyAsync(c->ks_top.p, st.blkH, nconv * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
       ISLECHK(k_gemm_nn(c, c->ks_top.p, nconv, (int)n, c->Wf.p, (int)n, (int)keep, c->ks_top.p + nconv * n));
-      HIPCHK(c, hipMemcpyAsync(top, c->ks_top.p + nconv * n, nconv * keep * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(st.top, c->ks_top.p + nconv * n, nconv * keep * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipMemcpyAsync(c->Fbuf.p, col(vcols - blk), blk * dim * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(col(nconv), c->Tmp.p, keep * dim * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(col(nev), c->Fbuf.p, blk * dim * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     vcols = nev + blk;
-    isle_host_mark("truncate: device part synchronised");
-    // Transform H (:169-184)
-    auto vh = [&](size_t i, size_t j) { return vH[j * n + i]; };
-    HMat last = hsub(H, H.r - blk, H.c - blk, H.r - 1, H.c - 1);  // blk x blk
-    HMat newrows(blk, keep);
-    for (size_t j = 0; j < keep; ++j)
-      for (size_t t = 0; t < blk; ++t) {
-        const float v = vh(n - blk + t, j);
-        for (size_t i = 0; i < blk; ++i) newrows(i, j) += last(i, t) * v;
-      }
-    const size_t grow_r = std::max<size_t>(ncv, nev + blk) + blk;  // what the next expand() asks for
-    HMat Hn(nev + blk, nev, grow_r, nev + (grow_r - (nev + blk)));
-    for (size_t j = 0; j < nconv; ++j) {  // locked columns keep their entries (rows < nev from the old H; residual rows too)
-      for (size_t i = 0; i < nev; ++i) Hn(i, j) = H(i, j);
-      for (size_t i = 0; i < blk; ++i) Hn(nev + i, j) = H(nev + i, j);
-    }
-    for (size_t j = nconv; j < nev; ++j) {
-      Hn(j, j) = eH[j - nconv];
-      for (size_t i = 0; i < blk; ++i) Hn(nev + i, j) = newrows(i, j - nconv);
-      for (size_t i = 0; i < nconv; ++i) Hn(i, j) = top[(j - nconv) * nconv + i];
-    }
-    H = std::move(Hn);
-    isle_host_mark("truncate: H transformed");
     return 0;
   }
 
-  size_t first_unconverged(bool divide) const {  // :278-293
-    for (size_t j = 0; j < H.c; ++j) {
-      float s = 0.f;
-      for (size_t i = H.r - blk; i < H.r; ++i) s += H(i, j) * H(i, j);
-      float nrm = std::sqrt(s);
-      if (divide) nrm = nrm / H(j, j);
-      if (nrm >= tol) return j;
-    }
-    return H.c;
+  int truncate() {
+    isle_host_mark("truncate: entry");
+    const size_t n = H.c - nconv;
+    const size_t keep = nev - nconv;  // only the leading `keep` eigenvectors are used below
+    const KsStage lay = ks_stage_layout(n, keep, nconv);
+    HIPCHK(c, c->pin_stage.reserve(lay.bytes));
+    float* base = reinterpret_cast<float*>(c->pin_stage.p);
+    const Stage st{base + lay.subH, base + lay.vH, base + lay.blkH, base + lay.top};
+    ks_h_extract_sub(H, nconv, st.subH);
+    isle_host_mark("truncate: subH extracted");
+    std::vector<float> eH(n);
+    HIPCHK(c, c->Wf.reserve(n * n));
+    ISLECHK(k_eig_small(c, st.subH, (int)n, eH.data(), c->Wf.p, (int)keep));
+    isle_host_mark("truncate: eig_small returned");
+    ISLECHK(rotate_basis(st, n, keep));
+    isle_host_mark("truncate: device part synchronised");
+    H = ks_h_truncate(H, nev, ncv, blk, nconv, eH.data(), st.vH, st.top);
+    isle_host_mark("truncate: H transformed");
+    return 0;
   }
 
   int compute() {  // :261-321
@@ -380,7 +341,7 @@ struct Ks {
     ISLECHK(expand());
     while (n_restarts < maxit) {
       ISLECHK(truncate());
-      const size_t j = first_unconverged(true);
+      const size_t j = ks_first_unconverged(H, blk, tol, true);  // :278-293
       ISLECHK(agree_i32(c, (int)j, "the number of converged Ritz pairs"));
       last_j = j;
       if (j == H.c) {
@@ -419,15 +380,15 @@ int install_U(isle_ctx* c, const float* Ucm_dev, int k) {
 // ncv + blk - 1 vectors.
 static int ks_solve(isle_ctx* c, Ks& ks, int nev, int ncv, int maxit, int blk, float tol, uint64_t seed, float* evals, int* nconv,
                     int* restarts, int* napplies, int* nconv_ref_rule) {
-  if (nev < 1 || blk < 1 || blk > 32 || maxit < 1) return isle_fail(c, ISLE_E_ARG, "bad nev/blk/maxit (nev >= 1, 1 <= blk <= 32, maxit >= 1)");
+  if (ks_check_counts(nev, blk, maxit) != KS_ARGS_OK) return isle_fail(c, ISLE_E_ARG, "bad nev/blk/maxit (nev >= 1, 1 <= blk <= 32, maxit >= 1)");
   ks.c = c;
   ks.nev = nev;
   ks.ncv = ncv;
   ks.maxit = maxit;
-  ks.blk = (blk < nev) ? blk : 1;  // block-ks/restarted_block_ks.h:198
+  ks.blk = ks_effective_blk(nev, blk);
   ks.tol = tol;
   ks.seed = seed;
-  if ((size_t)ncv < (size_t)nev + 2 * ks.blk || (uint64_t)ncv + ks.blk > ks.dim)
+  if (ks_check_range(nev, ncv, ks.blk, ks.dim) != KS_ARGS_OK)
     return isle_fail(c, ISLE_E_ARG, "need nev + 2*blk <= ncv and ncv + blk <= operator dimension (nev=%d ncv=%d blk=%zu dim=%llu)", nev, ncv,
                      ks.blk, (unsigned long long)ks.dim);
   HIPCHK(c, c->basis.reserve((size_t)ks.dim * (ncv + 2 * ks.blk)));
@@ -438,19 +399,9 @@ static int ks_solve(isle_ctx* c, Ks& ks, int nev, int ncv, int maxit, int blk, f
   isle_host_mark("ks_solve: init done");
   ISLECHK(ks.compute());
   isle_host_mark("ks_solve: compute done");
-  int rc = 0;
-  size_t nc = ks.nconv, nc_ref = ks.nconv;
-  if (ks.n_restarts == (size_t)maxit) {
-    // The reference recomputes residuals from the EXPANDED H without dividing by the Ritz value (:303-317); the last blk rows of
-    // an expanded H are [0 ... 0 R], so that rule reports min(first column of the last block, nev) = nev whatever happened
-    // (SURVEY App. C #7).  Here: the count of the last restart's residual test, status ISLE_E_NOCONV, and the same Ritz pairs;
-    // the reference's figure is available through nconv_ref_rule.
-    nc_ref = ks.first_unconverged(false);
-    nc = std::min(ks.last_j, (size_t)nev);
-    if (nc < (size_t)nev) rc = ISLE_E_NOCONV;
-  }
-  nc = std::min(nc, (size_t)nev);
-  nc_ref = std::min(nc_ref, (size_t)nev);
+  const KsCounts k = ks_final_counts(ks.H, ks.blk, ks.tol, ks.nconv, ks.last_j, ks.n_restarts, maxit, nev);
+  const int rc = k.noconv ? ISLE_E_NOCONV : 0;
+  const size_t nc = k.nc, nc_ref = k.nc_ref;
   for (int i = 0; i < nev; ++i) evals[i] = ks.H(i, i);  // src/sparseMatrix.cpp:1212-1213
   if (nconv) *nconv = (int)nc;
   if (nconv_ref_rule) *nconv_ref_rule = (int)nc_ref;
@@ -484,7 +435,7 @@ extern "C" int isle_hip_block_ks_dense(isle_ctx* c, const float* A, uint64_t n, 
   if (!c || !A || !evals || n < 2 || n > 46340) return isle_fail(c, ISLE_E_ARG, "block_ks_dense: bad arguments (2 <= n <= 46340)");
   ISLECHK(isle_enter(c));
   if (c->multi()) return isle_fail(c, ISLE_E_ARG, "block_ks_dense: the dense operator is not sharded (single rank only)");
-  const int b_eff = (blk < nev) ? blk : 1;
+  const int b_eff = (int)ks_effective_blk(nev, blk);
   DevBuf<float> Adev, Sdev;
   HIPCHK(c, Adev.reserve((size_t)n * n));
   HIPCHK(c, hipMemcpy(Adev.p, A, (size_t)n * n * sizeof(float), hipMemcpyHostToDevice));

@@ -1,9 +1,9 @@
-"""Plain restatement of the restarted block Krylov-Schur loop of isle_amd/csrc/api_ks.cpp on a dense operator, the cases built for the
+"""Plain restatement of the restarted block Krylov-Schur loop of isle_amd/csrc/api_ks.cpp / ks_host.h on a dense operator, the cases built for the
 dispatch edges of dense.hip, and the bounds of the fp64 certificate (no GPU, no oracle library; numpy only).
 
-reference_run: init (api_ks.cpp:153-178) from a given start block, expand (:180-303) in whole blocks to at least ncv rows, truncate
-(:305-364) through the small symmetric EVD of the UPPER triangle of H (evd_tridiag.hip:839-840), the residual test (:366-375), maxit
-restarts (:377-395) and the counters of ks_solve (:441-458).  One body, the dtype a parameter: float64 is the reference, float32 measures
+reference_run: init (Ks::init, ks_h_start) from a given start block, expand (Ks::expand, ks_fold_step) in whole blocks to at least ncv rows,
+truncate (Ks::truncate, ks_h_truncate) through the small symmetric EVD of the UPPER triangle of H (evd_tridiag.hip:839-840), the residual
+test (ks_first_unconverged), maxit restarts (Ks::compute) and the counters of ks_solve (ks_final_counts).  One body, the dtype a parameter: float64 is the reference, float32 measures
 what the same algorithm loses in the device's number format.  numpy.linalg.qr stands where the device has CholQR2 and numpy.linalg.eigh
 where it has tridiagonalisation and bisection: the factors differ in sign and basis, so only quantities that do not depend on the basis
 are compared (`measure`): the Ritz values, and of the returned vectors the orthonormality, the Rayleigh quotients, the residual norms and
@@ -11,7 +11,7 @@ the distance from the Krylov space of the fp64 run.  The counters must be equal.
 
 Determinism.  Every case fixes the start block; the spectrum (`spectrum`) is simple and of full rank, ||A||_2 = 1.  The data-dependent
 decisions of the loop are the rank of every panel (dense.hip:562-564: a pivot below 1e-6, or its square below 1e-13 w of the column's
-own square), the number of converged pairs (api_ks.cpp:372) and with it how many vectors truncation rotates (:307-308).  `decisions`
+own square), the number of converged pairs (ks_first_unconverged) and with it how many vectors truncation rotates (Ks::truncate: keep).  `decisions`
 returns them with their margins: every pivot is at least PIVOT_MARGIN times the drop threshold, every residual estimate that the test
 reads is DECISION_MARGIN away from tol on either side, in the fp32 and in the fp64 run; test_ks_certificate_cpu.py asserts it.
 
@@ -52,7 +52,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # The constants the cases were built from: name -> (file, line, pattern with one group per value, values).
 # test_ks_certificate_cpu.py reads the cited line and fails when the text or the line moved: update the cases, then this table.
 # ---------------------------------------------------------------------------------------------------------------------------------
-DENSE, API = "isle_amd/csrc/dense.hip", "isle_amd/csrc/api_ks.cpp"
+DENSE, KS_HOST = "isle_amd/csrc/dense.hip", "isle_amd/csrc/ks_host.h"
 SOURCE = {
     "VTF_CG": (DENSE, 25, r"constexpr int VTF_CG = (\d+);", (32,)),
     "vtf_rc": (DENSE, 27, r"constexpr int vtf_rc\(int BT\) \{ return BT <= (\d+) \? (\d+) : \(BT <= (\d+) \? (\d+) : (\d+)\); \}", (12, 1024, 16, 512, 256)),
@@ -64,8 +64,8 @@ SOURCE = {
     "PQ_W": (DENSE, 402, r"constexpr int PQ_W = (\d+);", (32,)),
     "PQ_SUB": (DENSE, 403, r"constexpr int PQ_SUB = (\d+);", (2,)),
     "PQ_NSEG": (DENSE, 449, r"constexpr int PQ_NSEG = (\d+);", (4,)),
-    "blk_rule": (API, 427, r"ks\.blk = \(blk < nev\) \? blk : 1;", ()),
-    "ortho_passes": (API, 211, r"int npass = (\d+);", (2,)),
+    "blk_rule": (KS_HOST, 37, r"return \(blk < nev\) \? blk : 1;", ()),  # ks_effective_blk
+    "ortho_passes": (KS_HOST, 52, r"int npass = (\d+);", (2,)),  # ks_ortho_passes
 }
 
 
@@ -117,7 +117,7 @@ def route(n, b, m, num_cus=256):
 # the loop
 # ---------------------------------------------------------------------------------------------------------------------------------
 def effective_blk(nev, blk):
-    """api_ks.cpp:427."""
+    """ks_host.h ks_effective_blk."""
     return blk if blk < nev else 1
 
 
@@ -130,9 +130,9 @@ def reference_run(A, S, nev, blk, ncv, maxit, tol, dtype, wrong=None, passes=2):
     A = np.asarray(A, dt)
     n = A.shape[0]
     b = effective_blk(nev, blk)
-    assert nev >= 1 and 1 <= blk <= 32 and maxit >= 1 and ncv >= nev + 2 * b and ncv + b <= n  # api_ks.cpp:422, :430
+    assert nev >= 1 and 1 <= blk <= 32 and maxit >= 1 and ncv >= nev + 2 * b and ncv + b <= n  # ks_host.h ks_check_counts, ks_check_range
     tol = dt.type(tol)
-    V = np.zeros((n, ncv + 2 * b), dt, order="F")      # :433
+    V = np.zeros((n, ncv + 2 * b), dt, order="F")      # ks_solve: the basis
     H = np.zeros((ncv + 2 * b, ncv + b), dt, order="F")
     tr = dict(ortho=[], pivots=[], tests=[], estimates=[])
     st = dict(napplies=0, step=0, hr=0, hc=0, nconv=0, last_j=0, truncations=0, space=None, m=0, steps_at_truncate=0)
@@ -144,7 +144,7 @@ def reference_run(A, S, nev, blk, ncv, maxit, tol, dtype, wrong=None, passes=2):
         return Q, R
 
     def ortho(F, m):
-        """`passes` times c = V^T F, F -= V c (api_ks.cpp:97-101); H takes the sum of the c (:275-278)."""
+        """`passes` times c = V^T F, F -= V c (Ks::ortho); H takes the sum of the c (ks_fold_step)."""
         step = st["step"]
         st["step"] += 1
         tr["ortho"].append((step, m, F.shape[1]))
@@ -167,7 +167,7 @@ def reference_run(A, S, nev, blk, ncv, maxit, tol, dtype, wrong=None, passes=2):
         st["napplies"] += 1
         return A @ X
 
-    def init():  # :153-178
+    def init():  # Ks::init, ks_h_start
         Q0, _ = qr(np.asarray(S, dt))
         V[:, :b] = Q0
         F, coef = ortho(apply(V[:, :b]), b)
@@ -177,7 +177,7 @@ def reference_run(A, S, nev, blk, ncv, maxit, tol, dtype, wrong=None, passes=2):
         V[:, b:2 * b] = Q1
         st["hr"], st["hc"] = 2 * b, b
 
-    def expand():  # :180-303
+    def expand():  # Ks::expand, ks_fold_step
         while st["hr"] < ncv:
             m, hc = st["hr"], st["hc"]
             F, coef = ortho(apply(V[:, hc:hc + b]), m)
@@ -187,7 +187,7 @@ def reference_run(A, S, nev, blk, ncv, maxit, tol, dtype, wrong=None, passes=2):
             V[:, m:m + b] = Q
             st["hr"], st["hc"] = m + b, hc + b
 
-    def truncate():  # :305-364
+    def truncate():  # Ks::truncate, ks_h_truncate
         hr, hc, nconv = st["hr"], st["hc"], st["nconv"]
         nn, keep = hc - nconv, nev - nconv
         st["m"], st["space"], st["steps_at_truncate"] = hr, V[:, :hc].copy(), st["step"]
@@ -213,7 +213,7 @@ def reference_run(A, S, nev, blk, ncv, maxit, tol, dtype, wrong=None, passes=2):
         st["hr"], st["hc"] = nev + b, nev
         st["truncations"] += 1
 
-    def first_unconverged(divide):  # :366-375 -> (first j at or above tol, the estimates it read, the estimates of all columns)
+    def first_unconverged(divide):  # ks_first_unconverged -> (first j at or above tol, the estimates it read, the estimates of all columns)
         hr, hc = st["hr"], st["hc"]
         est = []
         for j in range(hc):
@@ -230,7 +230,7 @@ def reference_run(A, S, nev, blk, ncv, maxit, tol, dtype, wrong=None, passes=2):
     init()
     restarts = 0
     expand()
-    while restarts < maxit:  # :377-395
+    while restarts < maxit:  # Ks::compute
         truncate()
         j, est, every = first_unconverged(True)
         tr["tests"].append((est, j))
@@ -243,7 +243,7 @@ def reference_run(A, S, nev, blk, ncv, maxit, tol, dtype, wrong=None, passes=2):
         restarts += 1
         expand()
     nc = nc_ref = st["nconv"]
-    if restarts == maxit:  # :443-451
+    if restarts == maxit:  # ks_final_counts
         nc_ref = first_unconverged(False)[0]
         nc = min(st["last_j"], nev)
     out = dict(evals=np.diag(H)[:nev].copy(), U=V[:, :nev].copy(), restarts=restarts, napplies=st["napplies"], nconv=min(nc, nev),

@@ -699,7 +699,7 @@ def test_grouped_projection_at_topic_counts_that_end_inside_a_group(hp, small50,
 
 
 def test_pipelined_expand_equals_the_synchronous_form(hp, small50, monkeypatch):
-    """The expand loop (api_ks.cpp) enqueues step i + 1 behind the panel QR of step i and fetches step i's mailbox on a copy stream of its own
+    """The expand loop (api_ks.cpp Ks::expand: enqueue_step, qr_and_post, wait_and_check) enqueues step i + 1 behind the panel QR of step i and fetches step i's mailbox on a copy stream of its own
     (round 6: double-buffered device mailbox); ISLE_KS_SYNC=1 runs one step at a time with a host synchronisation each.  Same kernels on the same
     data in the same order: eigenvalues, U and the work counts must agree bit for bit — a mailbox read before its step had finished writing it,
     or a coefficient block landing in a mailbox whose copy was still in flight, would show here."""

@@ -35,7 +35,7 @@ def test_case_reaches_its_edge(name):
     eff = _effective(run)
     routes = [kc.route(n, w, m) for m, w in eff]
     assert c["ncv"] <= 135 and n <= 2049 and (n, nev) not in ((2000, 10), (2000, 20), (6000, 50))  # small, and not a workload's own size
-    assert b == blk, "the block width is not overridden (api_ks.cpp:427)"
+    assert b == blk, "the block width is not overridden (ks_host.h ks_effective_blk)"
     edge = c["edge"]
     if edge == "blk":
         bt, rows, upd = {1: (4, 1024, True), 12: (12, 1024, True), 13: (16, 512, True), 16: (16, 512, True), 17: (32, 256, False), 32: (32, 256, False)}[blk]
