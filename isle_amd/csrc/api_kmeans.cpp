@@ -154,7 +154,10 @@ static int kmpp_draw_by_ranks(isle_ctx* c, HostRng& rng, int ndraw, bool injecte
   const KmppScalars sc = kmpp_scalars(c);
   // totals (per rank) -> offsets
   st.my[0] = st.my[1] = 0.0;
-  ISLECHK(k_pack2(c, c->cum.p + D, D > 0 ? c->min_dist.p + (D - 1) : nullptr, sc.totals));
+  // the second scalar is the last distance of the CORPUS: only the rank that holds its last document reports one (the ranks behind it
+  // hold no document at all and report 0, as do the ranks before it)
+  const bool holds_last = D > 0 && c->doc_offset + D == c->D_global;
+  ISLECHK(k_pack2(c, c->cum.p + D, holds_last ? c->min_dist.p + (D - 1) : nullptr, sc.totals));
   HIPCHK(c, hipMemcpyAsync(st.my, sc.totals, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));  // one copy, one round trip for both scalars
   for (int r = 0; r < 2 * c->world; ++r) st.tot[r] = 0.0;
@@ -165,7 +168,8 @@ static int kmpp_draw_by_ranks(isle_ctx* c, HostRng& rng, int ndraw, bool injecte
     if (r == c->rank) my_off = *grand;
     *grand += st.tot[2 * r];
   }
-  *last_md = st.tot[2 * (c->world - 1) + 1];
+  *last_md = 0.0;
+  for (int r = 0; r < c->world; ++r) *last_md += st.tot[2 * r + 1];  // one rank's, whichever holds the last document (not rank world - 1 when its shard is empty)
   if (injected) return 0;
   // all ranks draw the same dice; the owner of the interval searches its local prefix sums
   for (int i = 0; i < ndraw; ++i) {

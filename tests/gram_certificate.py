@@ -128,12 +128,15 @@ def _worst(ratio, k=5):
     return [np.unravel_index(i, ratio.shape) for i in flat]
 
 
-def certify_gram(Z, Z64, M, B):
-    """Every entry within (n_w + max n_d + 2) u M of the fp64 product.  -> {'max_ratio': max |err| / (u M), 'coeff_max': ...}."""
+def certify_gram(Z, Z64, M, B, extra=0):
+    """Every entry within (n_w + max n_d + 2 + extra) u M of the fp64 product.  extra: roundings beyond those of one rank's sums — N - 1
+    for a Z all-reduced over N ranks (each entry is a sum of N partial results, joined by at most N - 1 additions in any order).
+    -> {'max_ratio': max |err| / (u M), 'coeff_max': ...}."""
     Z = np.asarray(Z)
     assert Z.shape == Z64.shape, (Z.shape, Z64.shape)
     assert Z.dtype == np.float32, Z.dtype
     coeff = bound_coeff(B)
+    coeff = np.where(coeff > 0, coeff + extra, 0.0)
     assert coeff.max(initial=0.0) - 2 <= _BOUND_K_MAX, "bound needs n_w + n_d <= %d (got %d)" % (_BOUND_K_MAX, coeff.max() - 2)
     err = np.abs(Z.astype(np.float64) - Z64)
     uM = U_F32 * M

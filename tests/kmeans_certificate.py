@@ -192,3 +192,38 @@ def certify_gemm(A, B, C_gpu, what=""):
     assert ratio.size == 0 or ratio[i, j] <= 1.0, ("%s entry (%d, %d) of %s: %.9g against %.9g, bound %.3g"
                                                    % (what, i, j, C64.shape, C_gpu[i, j], C64[i, j], bound[i, j]))
     return dict(max_ratio=float(ratio[i, j]) if ratio.size else 0.0)
+
+
+# Float centroid sums of a row-constant B (the gather form of the operator on such a B: forced by ISLE_GRAM_LDS=0, or agreed by the ranks
+# when a shard is empty): a centre entry is a sum of n_c copies of one value, whose fp32 roundings do not cancel.  The reference's own
+# sequential fp32 sums reach a Frobenius relative error of 1.0 - 1.6e-6 there (tests/test_kmeans_certificate_cpu.py: the oracle on the same
+# corpus); the library's float sums 1.1 - 1.3e-6.  The per-entry bound holds unchanged; the typical-level bound is the reference's level
+# with a margin.
+FLOAT_SUMS_ROW_CONSTANT_FROB = 4e-6
+
+
+def certify_kmeanspp(c, g, md):
+    """k-means++ with injected seeds.  c: the fp64 side of the case (k, B["X"], U, P64, pn2, seeds); g: seeds and C_lowd as returned; md:
+    get_min_dist() of all documents.  C_lowd = P[seeds] within the product bound; md per document within E = ISLE_SLACK_REL (|p_d|^2 +
+    max_s |p_s|^2) of the fp64 minimum over the seeds folded in (the last batch of the rounds never is: src/sparseMatrix.cpp:2163-2207).
+    -> (d, E): the fp64 minima and their allowances, or None where nothing is folded in."""
+    k, B = c.k, c.B
+    assert np.array_equal(g["seeds"], c.seeds)
+    Bs = B["X"][:, c.seeds.astype(np.int64)].T.toarray()
+    certify_gemm(Bs, c.U, g["C_lowd"], what="k-means++ seeds k=%d:" % k)
+    s, last = 1, 0
+    while s < k:
+        nd = 0
+        while nd < 1 + np.sqrt(max(s - 5, 0)):
+            nd += 1
+        last = min(nd, k - s)
+        s += last
+    folded = c.seeds[:k - last].astype(np.int64)
+    if folded.size == 0 or k == 1:
+        return None
+    Ps = c.P64[folded]
+    d = np.maximum(c.pn2[:, None] + np.einsum("ij,ij->i", Ps, Ps)[None, :] - 2.0 * (c.P64 @ Ps.T), 0.0).min(axis=1)
+    E = ISLE_SLACK_REL * (c.pn2 + c.pn2[folded].max())
+    bad = np.flatnonzero(np.abs(np.asarray(md, np.float64) - d) > E)
+    assert bad.size == 0, ("k=%d: min_dist of document %d is %.9g, fp64 %.9g, E %.3g" % (k, bad[0], md[bad[0]], d[bad[0]], E[bad[0]]))
+    return d, E

@@ -26,7 +26,8 @@ defect of ONE pass: H takes c1 + c2, and whatever the first projection missed th
 of a single step is invisible by construction, on the device as here.  A kernel that is wrong is wrong in every launch of a shape, so the
 rules spoil both passes of one step: "drop_rows" leaves the last n % 256 rows out of both projections of step `step`, "zero_col" zeroes
 column `col` of both V^T F of that step; "one_pass" skips the second pass in every step; "keep_short" rotates one Ritz vector too few at
-every truncation.
+every truncation; "skip_slice" (r0, r1) leaves the rows [r0, r1) of the panel unorthogonalised in every pass of every step (the
+row-sharded step with one rank's update missing).
 """
 import os
 import re
@@ -96,11 +97,18 @@ def vtf_rc(BT):
     return ra if BT <= a else (rb if BT <= b else rc)
 
 
-def route(n, b, m, num_cus=256):
-    """Which kernels one orthogonalisation pass of a b-wide panel against m basis vectors of n rows takes (ld = n in the dense entry;
-    basis and panel are separate allocations, so the 16-byte test of dense.hip:366 holds).
-    -> dict(vtf: "mfma" | "valu", vtf_rows: rows per chunk, update: "mfma" | "valu")."""
+def route(n, b, m, num_cus=256, ld=None):
+    """Which kernels one orthogonalisation pass of a b-wide panel against m basis vectors of n rows takes.  ld: the leading dimension of
+    basis and panel — n in the dense entry and in the replicated step; the row count of the whole block when n is a rank's row slice
+    (Ks::ortho: the slice starts at a multiple of four rows, ks_row_slice, so it is 16-byte aligned exactly when the block is).  Basis
+    and panel are separate allocations, so the 16-byte test of dense.hip:366 rests on ld alone.
+    -> dict(vtf: "mfma" | "valu" | "none", vtf_rows: rows per chunk, vtf_aligned: vtf_mfma_k's float4 path (dense.hip:97),
+    update: "mfma" | "valu" | "none"); "none": a slice of zero rows launches nothing (dense.hip:207, :363)."""
+    ld = n if ld is None else ld
+    if n == 0:
+        return dict(vtf="none", vtf_rows=0, vtf_aligned=False, update="none")
     bmax, mmin = SOURCE["vtf_mfma"][3]
+    ub, um, mask = SOURCE["update_mfma"][3]
     if b <= bmax and m >= mmin:
         rc = VM_RC  # dense.hip:217-218
         cd = lambda a, d: -(-a // d)
@@ -109,8 +117,8 @@ def route(n, b, m, num_cus=256):
         vtf, rows = "mfma", rc
     else:
         vtf, rows = "valu", vtf_rc(bt_of(b))
-    ub, um, mask = SOURCE["update_mfma"][3]
-    return dict(vtf=vtf, vtf_rows=rows, update="mfma" if (b <= ub and m >= um and (n & mask) == 0) else "valu")
+    return dict(vtf=vtf, vtf_rows=rows, vtf_aligned=vtf == "mfma" and (ld & mask) == 0,
+                update="mfma" if (b <= ub and m >= um and (ld & mask) == 0) else "valu")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -158,7 +166,11 @@ def reference_run(A, S, nev, blk, ncv, maxit, tol, dtype, wrong=None, passes=2):
                 c = Vm.T @ F
             if "zero_col" in wrong and wrong["zero_col"][0] == step:
                 c[:, wrong["zero_col"][1]] = 0
-            F = F - Vm @ c
+            Fn = F - Vm @ c
+            if "skip_slice" in wrong:  # the rows of one rank's slice are left as they were, in every pass of every step
+                r0, r1 = wrong["skip_slice"]
+                Fn[r0:r1] = F[r0:r1]
+            F = Fn
             coef = coef + c
         assert F.dtype == dt and coef.dtype == dt
         return F, coef

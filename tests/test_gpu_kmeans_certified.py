@@ -17,7 +17,8 @@ import re
 import numpy as np
 import pytest
 
-from kmeans_certificate import ISLE_SLACK_REL, certify_assignment, certify_centroids, certify_gemm, csc_points
+import kmeans_certificate as kc
+from kmeans_certificate import FLOAT_SUMS_ROW_CONSTANT_FROB, certify_assignment, certify_centroids, certify_gemm, csc_points
 
 pytestmark = pytest.mark.gpu
 
@@ -121,13 +122,6 @@ def _bounded(err, D, tags):
     return [(t, int(i), int(n)) for t, i, n in re.findall(r"\[([^\]]+)\] iter (\d+) active (\d+) of %d\b" % D, err) if t in tags]
 
 
-# Float centroid sums of a row-constant B (the gather form forced by ISLE_GRAM_LDS=0): a centre entry is a sum of n_c copies of one value,
-# whose fp32 roundings do not cancel.  The reference's own sequential fp32 sums reach a Frobenius relative error of 1.0 - 1.6e-6 there
-# (tests/test_kmeans_certificate_cpu.py: the oracle on the same corpus); the library's float sums 1.1 - 1.3e-6.  The per-entry bound holds
-# unchanged; the typical-level bound is the reference's level with a margin.
-FLOAT_SUMS_ROW_CONSTANT_FROB = 4e-6
-
-
 def _group_pruned(err, D):
     """Yinyang's group filter at work in an iteration from the second on: fewer groups scanned per active document than there are groups
     ('group scans n (x per active document, of G)'; by group: 'x per active document, of G' pairs beside the own group's scan, of G - 1)."""
@@ -211,28 +205,8 @@ def sparse_trajectory(c, R, C0=None, lift_from=None, reproducible=True, loop="Ll
 
 
 def certify_kmeanspp(c, g):
-    """C_lowd = P[seeds] within the product bound; get_min_dist() per document within 1e-4 (|p_d|^2 + max_s |p_s|^2) of the fp64
-    minimum over the seeds folded in (the last batch of the rounds never is: src/sparseMatrix.cpp:2163-2207)."""
-    hp, k, B = c.hp, c.k, c.B
-    assert np.array_equal(g["seeds"], c.seeds)
-    Bs = B["X"][:, c.seeds.astype(np.int64)].T.toarray()
-    certify_gemm(Bs, c.U, g["C_lowd"], what="k-means++ seeds k=%d:" % k)
-    s, last = 1, 0
-    while s < k:
-        nd = 0
-        while nd < 1 + np.sqrt(max(s - 5, 0)):
-            nd += 1
-        last = min(nd, k - s)
-        s += last
-    folded = c.seeds[:k - last].astype(np.int64)
-    md = hp.get_min_dist()
-    if folded.size == 0 or k == 1:
-        return
-    Ps = c.P64[folded]
-    d = np.maximum(c.pn2[:, None] + np.einsum("ij,ij->i", Ps, Ps)[None, :] - 2.0 * (c.P64 @ Ps.T), 0.0).min(axis=1)
-    E = ISLE_SLACK_REL * (c.pn2 + c.pn2[folded].max())
-    bad = np.flatnonzero(np.abs(md.astype(np.float64) - d) > E)
-    assert bad.size == 0, ("k=%d: min_dist of document %d is %.9g, fp64 %.9g, E %.3g" % (k, bad[0], md[bad[0]], d[bad[0]], E[bad[0]]))
+    """kmeans_certificate.certify_kmeanspp on this context's min_dist."""
+    kc.certify_kmeanspp(c, g, c.hp.get_min_dist())
 
 
 KS = [1, 7, 8, 9, 63, 64, 65, 224, 225, 255, 256, 257, 1000]
