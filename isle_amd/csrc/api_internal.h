@@ -57,6 +57,16 @@ inline int allgather_host(isle_ctx* c, const T* mine_host, size_t n, T* dev, T* 
   return 0;
 }
 
+// The one ending of a call with device buffers of its own: declared AFTER its local DevBufs, so that whichever return is taken the stream
+// is drained before they are freed.  The result is ignored: the caller gets the call's own status.
+struct StreamDrain {
+  isle_ctx* c;
+  explicit StreamDrain(isle_ctx* c_) : c(c_) {}
+  StreamDrain(const StreamDrain&) = delete;
+  StreamDrain& operator=(const StreamDrain&) = delete;
+  ~StreamDrain() { (void)hipStreamSynchronize(c->stream); }
+};
+
 // what a new count matrix A / a new B voids in the context (api.cpp)
 void isle_void_derived_from_A(isle_ctx* c);
 void isle_void_derived_from_B(isle_ctx* c);

@@ -9,6 +9,7 @@
 #include <numeric>
 
 #include "api_internal.h"
+#include "stage_host.h"
 
 // ------------------------------------------------------------------------------------------
 // upstream stage: A -> B on the device
@@ -95,15 +96,11 @@ extern "C" int isle_hip_ingest_tdf(isle_ctx* c, const char* text, uint64_t nbyte
   if (nbytes && !text) return isle_fail(c, ISLE_E_ARG, "ingest_tdf: null text");
   c->a_ready = false;
   DevBuf<unsigned char> td;
+  StreamDrain drain(c);
   HIPCHK(c, td.reserve(nbytes + 16));
-  hipError_t he = nbytes ? hipMemcpy(td.p, text, nbytes, hipMemcpyHostToDevice) : hipSuccess;
+  if (nbytes) HIPCHK(c, hipMemcpy(td.p, text, nbytes, hipMemcpyHostToDevice));
   uint64_t nread = 0, err[2] = {0, 0};
-  int rc = 0;
-  if (he == hipSuccess) rc = k_ingest_tdf(c, td.p, nbytes, V, D, &nread, err);
-  (void)hipStreamSynchronize(c->stream);
-  td.release();
-  HIPCHK(c, he);
-  ISLECHK(rc);
+  ISLECHK(k_ingest_tdf(c, td.p, nbytes, V, D, &nread, err));
   if (err[0]) {
     return isle_fail(c, ISLE_E_ARG, "ingest_tdf: %s on line %llu", kTdfKind[err[0] < 7 ? err[0] : 0], (unsigned long long)(err[1] + 1));
   }
@@ -269,157 +266,161 @@ extern "C" int isle_hip_get_A(isle_ctx* c, float* counts, uint32_t* rows, int64_
   return 0;
 }
 
+// isle_hip_threshold, A -> B: the scalars its steps hand on.  What the host decides between them is stage_host.h.
+struct Th {
+  isle_ctx* c;
+  const uint64_t num_topics;
+  const double sample_rate;
+  const uint64_t sample_seed;
+  const bool sampling;
+  const uint64_t V, D;
+  uint64_t* st_dev = nullptr;  // two words of a_scan: the statistics, then the scratch of the host values' collectives
+  uint64_t nz_docs = 0;
+  float avg = 0.f;
+  uint32_t maxv = 0;
+  uint64_t bnnz = 0, Db = 0, b_off = 0, b_glob = 0;  // nnz(B), columns of B (local), this shard's first column, columns of B (global)
+
+  Th(isle_ctx* c_, uint64_t num_topics_, double rate, uint64_t seed)
+      : c(c_), num_topics(num_topics_), sample_rate(rate), sample_seed(seed), sampling(rate > 0.0 && rate < 1.0), V(c_->a_V), D(c_->a_D) {}
+
+  int stats(float* avg_out) {  // corpus statistics (src/sparseMatrix.cpp:92-99), global
+    HIPCHK(c, c->a_scan.reserve(isle_scan_scratch(D) + 4));
+    st_dev = (uint64_t*)c->a_scan.p;
+    ISLECHK(k_th_stats(c, st_dev));
+    ISLECHK(allreduce_sum<uint64_t>(c, st_dev, 2));
+    uint64_t st[2];
+    HIPCHK(c, hipMemcpyAsync(st, st_dev, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    nz_docs = st[1];
+    avg = corpus_avg(st[0], nz_docs);
+    if (avg_out) *avg_out = avg;
+    c->a_avg = avg;
+    c->a_avg_valid = true;
+    if (!hist_maxv(avg, &maxv)) return isle_fail(c, ISLE_E_ARG, "threshold: average document size %g too large", (double)avg);
+    return 0;
+  }
+
+  int round_and_histogram() {  // rounded normalised counts + per-word value histogram, global
+    HIPCHK(c, c->a_q.reserve(c->a_nnz ? c->a_nnz : 1));
+    HIPCHK(c, c->a_hist.reserve((size_t)V * (maxv + 1)));
+    ISLECHK(k_th_round_hist(c, avg, maxv));
+    return allreduce_sum<uint32_t>(c, c->a_hist.p, (size_t)V * (maxv + 1));
+  }
+
+  int zetas() {
+    const ThresholdCounts n = threshold_counts(nz_docs, num_topics);
+    HIPCHK(c, c->zetas.reserve(V));
+    return k_th_zetas(c, maxv, n.gr, n.eq);
+  }
+
+  int count_survivors(uint64_t* entries_above) {  // survivors per document
+    HIPCHK(c, c->a_kept.reserve(D ? D : 1));
+    if (sampling) HIPCHK(c, c->a_wgt.reserve(D ? D : 1));
+    ISLECHK(k_th_count(c, sampling));
+    ISLECHK(k_th_scans(c));
+    int64_t above_local = 0;
+    HIPCHK(c, hipMemcpyAsync(&above_local, c->a_off_all.p + D, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (entries_above) {
+      uint64_t g = (uint64_t)above_local;
+      ISLECHK(allreduce_host<uint64_t>(c, &g, 1, st_dev));
+      *entries_above = g;
+    }
+    return 0;
+  }
+
+  // all keys of the corpus on every rank: shards padded with -1 to the largest one.  dice: this shard's keys in, every shard's block out
+  int gather_keys(std::vector<float>& dice) {
+    uint64_t dmax = D;
+    ISLECHK(allreduce_host<uint64_t>(c, &dmax, 1, st_dev, true, false /*not counted among the collectives' time, as before*/));
+    const std::vector<float> mine = sample_pad(dice, dmax);
+    const size_t slots = mine.size();
+    DevBuf<float> keys_all;
+    StreamDrain drain(c);
+    HIPCHK(c, keys_all.reserve((size_t)c->world * slots));
+    HIPCHK(c, hipMemcpy(keys_all.p + (size_t)c->rank * slots, mine.data(), slots * sizeof(float), hipMemcpyHostToDevice));
+    {
+      TimeScope ts(c, ISLE_T_COMM);
+      ISLECHK(isle_allgather(c, keys_all.p + (size_t)c->rank * slots, keys_all.p, slots, ISLE_DT_F32));
+    }
+    dice.assign((size_t)c->world * slots, 0.f);
+    HIPCHK(c, hipMemcpyAsync(dice.data(), keys_all.p, dice.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+  }
+
+  int sample() {  // sampled_threshold_and_copy, src/sparseMatrix.cpp:1383-1415
+    if (!(sampling && (D || c->multi()))) return 0;
+    std::vector<float> wgt(D);
+    if (D) HIPCHK(c, hipMemcpy(wgt.data(), c->a_wgt.p, D * sizeof(float), hipMemcpyDeviceToHost));
+    const std::vector<float> key = sample_keys(sample_seed, c->a_doc_offset, wgt);
+    std::vector<float> dice(key);
+    if (c->multi()) ISLECHK(gather_keys(dice));
+    const std::vector<uint8_t> drop = drop_mask(key, sample_pivot(sample_rate, dice));
+    DevBuf<uint8_t> drop_dev;
+    StreamDrain drain(c);
+    HIPCHK(c, drop_dev.reserve(drop.size()));
+    if (D) HIPCHK(c, hipMemcpy(drop_dev.p, drop.data(), D, hipMemcpyHostToDevice));
+    if (D) ISLECHK(k_th_drop(c, drop_dev.p));
+    return k_th_scans(c);
+  }
+
+  int place_shard() {  // placement of this shard in B's global column numbering
+    int64_t tail[2];  // nnz(B), columns of B (local)
+    HIPCHK(c, hipMemcpyAsync(&tail[0], c->a_off_all.p + D, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&tail[1], c->a_col_of.p + D, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    bnnz = (uint64_t)tail[0];
+    Db = b_glob = (uint64_t)tail[1];
+    if (c->multi()) {
+      DevBuf<uint64_t> all;
+      StreamDrain drain(c);
+      HIPCHK(c, all.reserve((size_t)c->world + 1));
+      std::vector<uint64_t> h(c->world);
+      ISLECHK(allgather_host<uint64_t>(c, &Db, 1, all.p, h.data()));
+      const ShardPlace s = shard_placement(c->rank, h);
+      b_off = s.b_off;
+      b_glob = s.b_glob;
+    }
+    return 0;
+  }
+
+  int emit(uint64_t* docs_kept, uint64_t* nnz_kept) {
+    isle_trim_derived(c, Db, bnnz);
+    c->V = V;
+    c->D = Db;
+    c->nnz = bnnz;
+    c->doc_offset = b_off;
+    c->D_global = b_glob;
+    HIPCHK(c, c->vals.reserve(bnnz ? bnnz : 1));
+    HIPCHK(c, c->rows.reserve(bnnz ? bnnz : 1));
+    HIPCHK(c, c->offs.reserve(Db + 1));
+    HIPCHK(c, c->original_cols.reserve(Db ? Db : 1));
+    if (D == 0) HIPCHK(c, hipMemsetAsync(c->offs.p, 0, sizeof(int64_t), c->stream));
+    ISLECHK(k_th_emit(c, c->a_doc_offset));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    isle_void_derived_from_B(c);
+    c->b_from_threshold = true;
+    if (docs_kept) *docs_kept = Db;
+    if (nnz_kept) *nnz_kept = bnnz;
+    return 0;
+  }
+};
+
 extern "C" int isle_hip_threshold(isle_ctx* c, uint64_t num_topics, double sample_rate, uint64_t sample_seed, uint64_t* docs_kept,
                                   uint64_t* nnz_kept, uint64_t* entries_above, float* avg_out) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
   if (!c->a_ready) return isle_fail(c, ISLE_E_ARG, "threshold: no count matrix uploaded");
   if (num_topics == 0) return isle_fail(c, ISLE_E_ARG, "threshold: num_topics == 0");
-  const bool sampling = sample_rate > 0.0 && sample_rate < 1.0;
-  const uint64_t V = c->a_V, D = c->a_D;
-
-  // corpus statistics (src/sparseMatrix.cpp:92-99), global
-  HIPCHK(c, c->a_scan.reserve(isle_scan_scratch(D) + 4));
-  uint64_t* st_dev = (uint64_t*)c->a_scan.p;
-  ISLECHK(k_th_stats(c, st_dev));
-  ISLECHK(allreduce_sum<uint64_t>(c, st_dev, 2));
-  uint64_t st[2];
-  HIPCHK(c, hipMemcpyAsync(st, st_dev, sizeof(st), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t tokens = st[0], nz_docs = st[1];
-  const float avg = (float)(tokens / std::max<uint64_t>(nz_docs, 1));  // :98, integer division
-  if (avg_out) *avg_out = avg;
-  c->a_avg = avg;
-  c->a_avg_valid = true;
-  const uint64_t maxv64 = (uint64_t)avg + 2;
-  if (maxv64 > 65535) return isle_fail(c, ISLE_E_ARG, "threshold: average document size %g too large", (double)avg);
-  const uint32_t maxv = (uint32_t)maxv64;
-
-  // rounded normalised counts + per-word value histogram, global
-  HIPCHK(c, c->a_q.reserve(c->a_nnz ? c->a_nnz : 1));
-  HIPCHK(c, c->a_hist.reserve((size_t)V * (maxv + 1)));
-  ISLECHK(k_th_round_hist(c, avg, maxv));
-  ISLECHK(allreduce_sum<uint32_t>(c, c->a_hist.p, (size_t)V * (maxv + 1)));
-
-  // thresholds  (src/sparseMatrix.cpp:367-368)
-  uint64_t count_gr = (uint64_t)(1.0 * (float)nz_docs / (2.0 * (float)num_topics));
-  uint64_t count_eq = (uint64_t)std::ceil(3.0 * (1.0 / 60.0) * 1.0 * (float)nz_docs / (float)num_topics);
-  if (count_gr == 0) count_gr = 1;
-  if (count_eq == 0) count_eq = 1;
-  HIPCHK(c, c->zetas.reserve(V));
-  ISLECHK(k_th_zetas(c, maxv, count_gr, count_eq));
-
-  // survivors per document
-  HIPCHK(c, c->a_kept.reserve(D ? D : 1));
-  if (sampling) HIPCHK(c, c->a_wgt.reserve(D ? D : 1));
-  ISLECHK(k_th_count(c, sampling));
-  ISLECHK(k_th_scans(c));
-  int64_t above_local = 0;
-  HIPCHK(c, hipMemcpyAsync(&above_local, c->a_off_all.p + D, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (entries_above) {
-    uint64_t g = (uint64_t)above_local;
-    ISLECHK(allreduce_host<uint64_t>(c, &g, 1, st_dev));
-    *entries_above = g;
-  }
-
-  if (sampling && (D || c->multi())) {  // sampled_threshold_and_copy, src/sparseMatrix.cpp:1383-1415 (keys on the host, like the reference)
-    // Several ranks (round 5): a document's key depends on its GLOBAL number only, the pivot is the (rate x D_global)-th largest key of the
-    // whole corpus — every rank gathers all keys (padded to the largest shard) and selects the same pivot; what a shard keeps is what the
-    // single-rank run keeps of those documents.
-    std::vector<float> wgt(D), key(D), dice(D);
-    if (D) HIPCHK(c, hipMemcpy(wgt.data(), c->a_wgt.p, D * sizeof(float), hipMemcpyDeviceToHost));
-    for (uint64_t dl = 0; dl < D; ++dl) {
-      const uint64_t d = c->a_doc_offset + dl;  // the document's number in the corpus
-      uint64_t z = (sample_seed + 1) * 0x9E3779B97F4A7C15ull ^ (d * 0xD1342543DE82EF95ull);
-      z += 0x9E3779B97F4A7C15ull;
-      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-      z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-      z = z ^ (z >> 31);
-      const double u = (double)(z >> 11) * (1.0 / 9007199254740992.0);
-      key[dl] = (wgt[dl] == 0.f) ? 0.f : (float)std::pow(u, 1.0 / (double)wgt[dl]);
-      dice[dl] = key[dl];
-    }
-    uint64_t Dg = D;
-    if (c->multi()) {  // all keys of the corpus on every rank: shards padded with -1 to the largest one
-      uint64_t dmax = D;
-      ISLECHK(allreduce_host<uint64_t>(c, &dmax, 1, st_dev, true, false /*not counted among the collectives' time, as before*/));
-      if (dmax == 0) dmax = 1;
-      DevBuf<float> keys_all;
-      HIPCHK(c, keys_all.reserve((size_t)c->world * dmax));
-      std::vector<float> mine(dmax, -1.f);
-      std::copy(key.begin(), key.end(), mine.begin());
-      HIPCHK(c, hipMemcpy(keys_all.p + (size_t)c->rank * dmax, mine.data(), dmax * sizeof(float), hipMemcpyHostToDevice));
-      {
-        TimeScope ts(c, ISLE_T_COMM);
-        ISLECHK(isle_allgather(c, keys_all.p + (size_t)c->rank * dmax, keys_all.p, dmax, ISLE_DT_F32));
-      }
-      std::vector<float> all((size_t)c->world * dmax);
-      HIPCHK(c, hipMemcpyAsync(all.data(), keys_all.p, all.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      keys_all.release();
-      dice.clear();
-      for (float v : all)
-        if (v >= 0.f) dice.push_back(v);
-      Dg = dice.size();
-    }
-    float pivot = 2.f;  // (an empty corpus keeps nothing)
-    if (Dg) {
-      const size_t nth = std::min<size_t>((size_t)((float)sample_rate * (float)Dg), Dg - 1);
-      std::nth_element(dice.begin(), dice.begin() + nth, dice.end(), std::greater<float>());
-      pivot = dice[nth];
-    }
-    std::vector<uint8_t> drop(D ? D : 1);
-    for (uint64_t d = 0; d < D; ++d) drop[d] = !(key[d] >= pivot);
-    DevBuf<uint8_t> drop_dev;
-    HIPCHK(c, drop_dev.reserve(D ? D : 1));
-    if (D) HIPCHK(c, hipMemcpy(drop_dev.p, drop.data(), D, hipMemcpyHostToDevice));
-    int rc = D ? k_th_drop(c, drop_dev.p) : 0;
-    if (rc == 0) rc = k_th_scans(c);
-    (void)hipStreamSynchronize(c->stream);
-    drop_dev.release();
-    ISLECHK(rc);
-  }
-
-  int64_t tail[2];  // nnz(B), columns of B (local)
-  HIPCHK(c, hipMemcpyAsync(&tail[0], c->a_off_all.p + D, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&tail[1], c->a_col_of.p + D, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t bnnz = (uint64_t)tail[0], Db = (uint64_t)tail[1];
-
-  // placement of this shard in B's global column numbering
-  uint64_t b_off = 0, b_glob = Db;
-  if (c->multi()) {
-    DevBuf<uint64_t> all;
-    HIPCHK(c, all.reserve((size_t)c->world + 1));
-    std::vector<uint64_t> h(c->world);
-    ISLECHK(allgather_host<uint64_t>(c, &Db, 1, all.p, h.data()));
-    all.release();
-    b_glob = 0;
-    for (int r = 0; r < c->world; ++r) {
-      if (r == c->rank) b_off = b_glob;
-      b_glob += h[r];
-    }
-  }
-
-  isle_trim_derived(c, Db, bnnz);
-  c->V = V;
-  c->D = Db;
-  c->nnz = bnnz;
-  c->doc_offset = b_off;
-  c->D_global = b_glob;
-  HIPCHK(c, c->vals.reserve(bnnz ? bnnz : 1));
-  HIPCHK(c, c->rows.reserve(bnnz ? bnnz : 1));
-  HIPCHK(c, c->offs.reserve(Db + 1));
-  HIPCHK(c, c->original_cols.reserve(Db ? Db : 1));
-  if (D == 0) HIPCHK(c, hipMemsetAsync(c->offs.p, 0, sizeof(int64_t), c->stream));
-  ISLECHK(k_th_emit(c, c->a_doc_offset));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  isle_void_derived_from_B(c);
-  c->b_from_threshold = true;
-  if (docs_kept) *docs_kept = Db;
-  if (nnz_kept) *nnz_kept = bnnz;
-  return 0;
+  Th th(c, num_topics, sample_rate, sample_seed);
+  ISLECHK(th.stats(avg_out));
+  ISLECHK(th.round_and_histogram());
+  ISLECHK(th.zetas());
+  ISLECHK(th.count_survivors(entries_above));
+  ISLECHK(th.sample());
+  ISLECHK(th.place_shard());
+  return th.emit(docs_kept, nnz_kept);
 }
 
 extern "C" int isle_hip_shape(isle_ctx* c, uint64_t* V, uint64_t* D, uint64_t* nnz, uint64_t* doc_offset, uint64_t* docs_global) {
@@ -465,7 +466,7 @@ static int ensure_avg_doc_sz(isle_ctx* c) {
     uint64_t st[2];
     HIPCHK(c, hipMemcpyAsync(st, c->a_scan.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->a_avg = (float)(st[0] / std::max<uint64_t>(st[1], 1));
+    c->a_avg = corpus_avg(st[0], st[1]);
     c->a_avg_valid = true;
   }
   return 0;
@@ -564,21 +565,13 @@ extern "C" int isle_hip_edge_topics(isle_ctx* c, const int64_t* pairs, int n, fl
   ISLECHK(check_topic_pairs(c, pairs, n, "edge_topics"));
   DevBuf<int64_t> pd;
   DevBuf<float> ed;
+  StreamDrain drain(c);
   HIPCHK(c, pd.reserve(2 * (size_t)n));
-  hipError_t e1 = ed.reserve((size_t)c->a_V * n);
-  if (e1 != hipSuccess) {
-    pd.release();
-    HIPCHK(c, e1);
-  }
-  int rc = 0;
-  hipError_t he = hipMemcpy(pd.p, pairs, 2 * (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice);
-  if (he == hipSuccess) rc = k_post_edge(c, pd.p, n, primary_ratio, (float)(1.0 - (double)primary_ratio), ed.p);
-  if (he == hipSuccess && rc == 0) he = hipStreamSynchronize(c->stream);
-  if (he == hipSuccess && rc == 0) he = hipMemcpy(edge, ed.p, (size_t)c->a_V * n * sizeof(float), hipMemcpyDeviceToHost);
-  pd.release();
-  ed.release();
-  ISLECHK(rc);
-  HIPCHK(c, he);
+  HIPCHK(c, ed.reserve((size_t)c->a_V * n));
+  HIPCHK(c, hipMemcpy(pd.p, pairs, 2 * (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+  ISLECHK(k_post_edge(c, pd.p, n, primary_ratio, (float)(1.0 - (double)primary_ratio), ed.p));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(edge, ed.p, (size_t)c->a_V * n * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -604,6 +597,7 @@ extern "C" int isle_hip_select_edge_pairs(isle_ctx* c, const int32_t* top1, cons
   const bool resident = top1 == nullptr;
   const int32_t *t1 = nullptr, *t2 = nullptr;
   DevBuf<int32_t> u1, u2;
+  StreamDrain drain(c);
   if (resident) {
     if (!c->p_model_ready) return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: no resident top topics (run isle_hip_topic_model, or pass top1 / top2)");
     if (n_docs != c->a_D || num_topics != c->p_k)
@@ -622,9 +616,7 @@ extern "C" int isle_hip_select_edge_pairs(isle_ctx* c, const int32_t* top1, cons
     t2 = u2.p;
   }
   uint64_t nsel = 0, ncand = 0, thr = 0, bad = ~0ull;
-  const int rc = k_edge_select(c, t1, t2, n_docs, (uint32_t)num_topics, (uint64_t)max_edge_topics, min_docs, pairs, cap, &nsel, &ncand, &thr, &bad);
-  (void)hipStreamSynchronize(c->stream);  // `u1` and `u2` are freed on return
-  ISLECHK(rc);
+  ISLECHK(k_edge_select(c, t1, t2, n_docs, (uint32_t)num_topics, (uint64_t)max_edge_topics, min_docs, pairs, cap, &nsel, &ncand, &thr, &bad));
   if (bad != ~0ull)
     return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: document %llu: a topic id outside -1 .. %d", (unsigned long long)bad, num_topics - 1);
   if (n_selected) *n_selected = nsel;
@@ -645,58 +637,11 @@ extern "C" int isle_hip_topic_coherence(isle_ctx* c, int num_topics, int M, cons
   if (num_topics < 1) return isle_fail(c, ISLE_E_ARG, "topic_coherence: num_topics < 1");
   if (M < 1 || M > 32) return isle_fail(c, ISLE_E_ARG, "topic_coherence: M = %d outside 1 .. 32", M);
   if (!top_words || !coherence) return isle_fail(c, ISLE_E_ARG, "topic_coherence: null top_words or coherence");
-  const size_t n = (size_t)num_topics, m = (size_t)M, npt = m * (m - 1) / 2;
-  for (size_t t = 0; t < n; ++t) {
-    const uint32_t* w = top_words + t * m;
-    for (size_t i = 0; i < m; ++i) {
-      if (w[i] >= c->a_V) return isle_fail(c, ISLE_E_ARG, "topic_coherence: word %u of topic %zu >= vocab %llu", w[i], t, (unsigned long long)c->a_V);
-      for (size_t j = 0; j < i; ++j)
-        if (w[j] == w[i]) return isle_fail(c, ISLE_E_ARG, "topic_coherence: word %u repeats in topic %zu", w[i], t);
-    }
-  }
-  // U: distinct words ascending, local id = rank; P: distinct (lo, hi) pairs of local ids, sorted, as a CSR keyed by lo
-  std::vector<uint32_t> U(top_words, top_words + n * m);
-  std::sort(U.begin(), U.end());
-  U.erase(std::unique(U.begin(), U.end()), U.end());
-  std::vector<uint32_t> loc(n * m);
-  for (size_t i = 0; i < n * m; ++i) loc[i] = (uint32_t)(std::lower_bound(U.begin(), U.end(), top_words[i]) - U.begin());
-  std::vector<uint64_t> keys;
-  keys.reserve(n * npt);
-  for (size_t t = 0; t < n; ++t)
-    for (size_t i = 1; i < m; ++i)
-      for (size_t j = 0; j < i; ++j) {
-        const uint64_t a = loc[t * m + i], b = loc[t * m + j];
-        keys.push_back(a < b ? (a << 32 | b) : (b << 32 | a));
-      }
-  std::vector<uint64_t> P(keys);
-  std::sort(P.begin(), P.end());
-  P.erase(std::unique(P.begin(), P.end()), P.end());
-  std::vector<uint32_t> part_off(U.size() + 1, 0u), part_hi(P.size());
-  for (size_t p = 0; p < P.size(); ++p) {
-    part_off[(P[p] >> 32) + 1]++;
-    part_hi[p] = (uint32_t)P[p];
-  }
-  for (size_t u = 0; u < U.size(); ++u) part_off[u + 1] += part_off[u];
-
+  const CoherencePlan plan(top_words, (size_t)num_topics, (size_t)M, c->a_V);
+  if (!plan.refused.empty()) return isle_fail(c, ISLE_E_ARG, "%s", plan.refused.c_str());
   std::vector<uint32_t> cnt;
-  ISLECHK(k_coherence_counts(c, U, part_off, part_hi, cnt, nullptr));
-  const uint32_t* du = cnt.data();
-  const uint32_t* dp = cnt.data() + U.size();
-  for (size_t t = 0; t < n; ++t) {
-    double sum = 0.0;
-    bool undefined = false;
-    for (size_t i = 1; i < m; ++i)
-      for (size_t j = 0; j < i; ++j) {
-        const uint64_t key = keys[t * npt + i * (i - 1) / 2 + j];
-        const uint32_t dij = dp[std::lower_bound(P.begin(), P.end(), key) - P.begin()], dj = du[loc[t * m + j]];
-        if (dj == 0) undefined = true;
-        sum += std::log((double)dij + eps) - std::log((double)dj);
-        if (co_doc_freq) co_doc_freq[t * npt + i * (i - 1) / 2 + j] = dij;
-      }
-    coherence[t] = undefined ? std::nan("") : sum;
-    if (doc_freq)
-      for (size_t i = 0; i < m; ++i) doc_freq[t * m + i] = du[loc[t * m + i]];
-  }
+  ISLECHK(k_coherence_counts(c, plan.U, plan.part_off, plan.part_hi, cnt, nullptr));
+  coherence_sums(plan, cnt.data(), eps, coherence, doc_freq, co_doc_freq);
   return 0;
 }
 
@@ -767,12 +712,12 @@ extern "C" int isle_hip_model_top_words(isle_ctx* c, int which, const float* mod
   if (n < 1 || n > 32 || (uint64_t)n > vocab) return isle_fail(c, ISLE_E_ARG, "model_top_words: n = %d outside 1 .. min(vocab, 32)", n);
   if (!ids) return isle_fail(c, ISLE_E_ARG, "model_top_words: null ids");
   const float* dev = nullptr;
-  DevBuf<float> up;
+  DevBuf<float> up, w_d;
+  DevBuf<uint32_t> id_d;
+  StreamDrain drain(c);
   ISLECHK(model_source(c, which, model_host, vocab, ncols, "model_top_words", &up, &dev));
   if (ncols == 0) return 0;
   const size_t m = (size_t)ncols * n;
-  DevBuf<uint32_t> id_d;
-  DevBuf<float> w_d;
   HIPCHK(c, id_d.reserve(m));
   HIPCHK(c, w_d.reserve(m));
   ISLECHK(k_model_top_words(c, dev, vocab, (uint32_t)ncols, n, id_d.p, w_d.p));
@@ -795,29 +740,21 @@ extern "C" int isle_hip_edge_top_words(isle_ctx* c, int which, const float* mode
     if (pairs[e] < 0 || pairs[e] >= ncols)
       return isle_fail(c, ISLE_E_ARG, "edge_top_words: edge topic %d: topic id %lld outside 0 .. %d", e / 2, (long long)pairs[e], ncols - 1);
   const float* dev = nullptr;
-  DevBuf<float> up;
-  ISLECHK(model_source(c, which, model_host, vocab, ncols, "edge_top_words", &up, &dev));
-  if (n_edge == 0) {
-    (void)hipStreamSynchronize(c->stream);  // `up` is freed on return
-    return 0;
-  }
-  const size_t m = (size_t)n_edge * n;
+  DevBuf<float> up, w_d;
   DevBuf<int64_t> pd;
   DevBuf<uint32_t> id_d;
-  DevBuf<float> w_d;
-  int rc = 0;
-  hipError_t he = pd.reserve(2 * (size_t)n_edge);
-  if (he == hipSuccess) he = id_d.reserve(m);
-  if (he == hipSuccess) he = w_d.reserve(m);
-  if (he == hipSuccess) he = hipMemcpyAsync(pd.p, pairs, 2 * (size_t)n_edge * sizeof(int64_t), hipMemcpyHostToDevice, c->stream);
-  if (he == hipSuccess)
-    rc = k_edge_top_words(c, dev, vocab, pd.p, (uint32_t)n_edge, primary_ratio, (float)(1.0 - (double)primary_ratio), n, id_d.p, w_d.p);
-  if (he == hipSuccess && rc == 0) he = hipMemcpyAsync(ids, id_d.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-  if (he == hipSuccess && rc == 0 && weights) he = hipMemcpyAsync(weights, w_d.p, m * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-  const hipError_t hs = hipStreamSynchronize(c->stream);  // the local buffers are freed on return
-  ISLECHK(rc);
-  HIPCHK(c, he);
-  HIPCHK(c, hs);
+  StreamDrain drain(c);
+  ISLECHK(model_source(c, which, model_host, vocab, ncols, "edge_top_words", &up, &dev));
+  if (n_edge == 0) return 0;
+  const size_t m = (size_t)n_edge * n;
+  HIPCHK(c, pd.reserve(2 * (size_t)n_edge));
+  HIPCHK(c, id_d.reserve(m));
+  HIPCHK(c, w_d.reserve(m));
+  HIPCHK(c, hipMemcpyAsync(pd.p, pairs, 2 * (size_t)n_edge * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+  ISLECHK(k_edge_top_words(c, dev, vocab, pd.p, (uint32_t)n_edge, primary_ratio, (float)(1.0 - (double)primary_ratio), n, id_d.p, w_d.p));
+  HIPCHK(c, hipMemcpyAsync(ids, id_d.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (weights) HIPCHK(c, hipMemcpyAsync(weights, w_d.p, m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
 
@@ -834,10 +771,9 @@ extern "C" int isle_hip_model_text(isle_ctx* c, int which, const float* model_ho
   if (ncols < 0 || vocab == 0 || vocab > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "model_text: vocab or ncols out of range");
   const float* dev = nullptr;
   DevBuf<float> up;
+  StreamDrain drain(c);
   ISLECHK(model_source(c, which, model_host, vocab, ncols, "model_text", &up, &dev));
-  const int rc = k_model_text(c, dev, vocab, (uint64_t)ncols, nullptr, 0.f, 0.f, format, sink, user, nbytes, nentries);
-  (void)hipStreamSynchronize(c->stream);  // `up` is freed on return
-  return rc;
+  return k_model_text(c, dev, vocab, (uint64_t)ncols, nullptr, 0.f, 0.f, format, sink, user, nbytes, nentries);
 }
 
 // A model file read on the device (model_load.hip) into a resident model of its own: parsed into scratch, swapped in on success
@@ -855,20 +791,16 @@ extern "C" int isle_hip_load_model_text(isle_ctx* c, const char* text, uint64_t 
     return isle_fail(c, ISLE_E_ARG, "load_model_text: a sparse text of %llu bytes (the line order is kept in 32 bits: at most 2^34 - 16)", (unsigned long long)nbytes);
   DevBuf<unsigned char> td;
   DevBuf<float> next;
+  StreamDrain drain(c);
   HIPCHK(c, td.reserve(nbytes + 16));
   HIPCHK(c, next.reserve(vocab * (size_t)ncols));
   if (nbytes) HIPCHK(c, hipMemcpy(td.p, text, nbytes, hipMemcpyHostToDevice));
   uint64_t n = 0, key = ~0ull;
-  const int rc = k_load_model_text(c, td.p, nbytes, vocab, (uint32_t)ncols, format, base, next.p, &n, &key);
-  (void)hipStreamSynchronize(c->stream);  // `td` and `next` are freed on return
-  ISLECHK(rc);
+  ISLECHK(k_load_model_text(c, td.p, nbytes, vocab, (uint32_t)ncols, format, base, next.p, &n, &key));
   if (key != ~0ull) {
     static const char* what[] = {"", "bad character", "too many fields", "too few fields", "id zero or out of range", "token too long",
                                  "wrong token count", "wrong line count"};
-    const uint64_t pos = key >> 3, upto = std::min<uint64_t>(pos, nbytes ? nbytes - 1 : 0);  // the line an error at the end of the text belongs to
-    uint64_t line = 1;
-    for (uint64_t i = 0; i < upto; ++i) line += text[i] == '\n';
-    return isle_fail(c, ISLE_E_ARG, "load_model_text: line %llu: %s", (unsigned long long)line, what[key & 7]);
+    return isle_fail(c, ISLE_E_ARG, "load_model_text: line %llu: %s", (unsigned long long)line_of_byte(text, nbytes, key >> 3), what[key & 7]);
   }
   std::swap(c->ml_model.p, next.p);  // the previous model leaves with `next`
   std::swap(c->ml_model.cap, next.cap);
@@ -902,12 +834,11 @@ extern "C" int isle_hip_edge_topics_text(isle_ctx* c, const int64_t* pairs, int 
   if (n == 0) return 0;
   ISLECHK(check_topic_pairs(c, pairs, n, "edge_topics_text"));
   DevBuf<int64_t> pd;
+  StreamDrain drain(c);
   HIPCHK(c, pd.reserve(2 * (size_t)n));
   HIPCHK(c, hipMemcpy(pd.p, pairs, 2 * (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
-  const int rc = k_model_text(c, c->p_model.p, c->a_V, (uint64_t)n, pd.p, primary_ratio, (float)(1.0 - (double)primary_ratio), format, sink, user,
-                              nbytes, nentries);
-  (void)hipStreamSynchronize(c->stream);  // `pd` is freed on return
-  return rc;
+  return k_model_text(c, c->p_model.p, c->a_V, (uint64_t)n, pd.p, primary_ratio, (float)(1.0 - (double)primary_ratio), format, sink, user, nbytes,
+                      nentries);
 }
 
 extern "C" int isle_hip_topic_diversity(isle_ctx* c, int which, int num_topics, double* dist, double* avg) {
@@ -922,6 +853,7 @@ extern "C" int isle_hip_topic_diversity(isle_ctx* c, int which, int num_topics, 
   const uint32_t k = (uint32_t)num_topics;
   DevBuf<double> dd, ab;
   DevBuf<int32_t> fin;
+  StreamDrain drain(c);
   HIPCHK(c, dd.reserve(k));
   HIPCHK(c, ab.reserve(V));
   HIPCHK(c, fin.reserve(k));
@@ -930,11 +862,8 @@ extern "C" int isle_hip_topic_diversity(isle_ctx* c, int which, int num_topics, 
   std::vector<double> h(k);
   HIPCHK(c, hipMemcpyAsync(h.data(), dd.p, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  double s = 0.0;
-  for (uint32_t t = 0; t < k; ++t)
-    if (std::isfinite(h[t])) s += h[t];
   if (dist) std::memcpy(dist, h.data(), k * sizeof(double));
-  if (avg) *avg = kp ? s / (double)kp : std::nan("");
+  if (avg) *avg = diversity_average(h.data(), k, kp);
   return 0;
 }
 
@@ -950,22 +879,9 @@ extern "C" int isle_hip_log_combinatorial(isle_ctx* c, float* out, uint64_t* max
 
 extern "C" int isle_hip_top_five_count_rule(const uint64_t* run_lengths, uint64_t n_runs, int32_t m, uint64_t* out) {
   if (!out || (n_runs && !run_lengths) || m < 2) return ISLE_E_ARG;
-  uint64_t n = 0;
-  for (uint64_t r = 0; r < n_runs; ++r) {
+  for (uint64_t r = 0; r < n_runs; ++r)
     if (run_lengths[r] == 0) return ISLE_E_ARG;
-    n += run_lengths[r];
-  }
-  // The loop of src/sparseMatrix.cpp:198-208 moves its mark from p to p + max(rem(p), m), rem(p) = distance from p to the end of
-  // its run, and counts every move that lands before n.  r: the run holding p, rb: the run's first position.
-  uint64_t num = 0, p = 0, r = 0, rb = 0;
-  while (n_runs) {
-    const uint64_t next = std::max(rb + run_lengths[r], p + (uint64_t)m);
-    if (next >= n) break;
-    ++num;
-    p = next;
-    while (rb + run_lengths[r] <= p) rb += run_lengths[r++];
-  }
-  *out = num;
+  *out = top_five_count(run_lengths, n_runs, m);
   return 0;
 }
 
@@ -1016,13 +932,11 @@ extern "C" int isle_hip_infer_resident(isle_ctx* c, int which, const float* mode
     return isle_fail(c, ISLE_E_ARG, "infer_resident: the model has %llu words, the count matrix %llu", (unsigned long long)vocab, (unsigned long long)c->a_V);
   const float* dev = nullptr;
   DevBuf<float> up;
+  StreamDrain drain(c);
   ISLECHK(model_source(c, which, model_host, vocab, ncols, "infer_resident", &up, &dev));
-  int rc = ensure_avg_doc_sz(c);
-  if (rc == 0)
-    rc = k_infer_resident(c, dev, ncols, doc_begin, doc_end, iters, Lf, c->a_avg, min_weight, chunk_docs, top_topic, top_weight, llh, nconverged,
+  ISLECHK(ensure_avg_doc_sz(c));
+  return k_infer_resident(c, dev, ncols, doc_begin, doc_end, iters, Lf, c->a_avg, min_weight, chunk_docs, top_topic, top_weight, llh, nconverged,
                           nentries);
-  (void)hipStreamSynchronize(c->stream);  // `up` is freed on return
-  return rc;
 }
 
 extern "C" int isle_hip_get_infer_entries(isle_ctx* c, int64_t* doc_offsets, uint32_t* topic, float* weight) {
