@@ -67,7 +67,7 @@ const IsleKnobInfo isle_knob_table[KN_COUNT] = {
     {"ISLE_GEMM_EPILOGUE", "form", "0: the D x k x k products of the assignment steps are written to memory and read by dots_assign_cm_k / proj_dots_tiles_k instead of the epilogues inside the product (same bits)"},
     {"ISLE_GEMM_TERMS", "form", "3: the assignment products run once with three bf16 terms per operand (default: two terms first, the rows whose arg-min that leaves open again with three; same assignment)"},
     {"ISLE_GEMM_DMA", "form", "0: the two-term pass of the assignment products splits A on the fly and stages it through registers (gemm_bf16x3_k) instead of reading the projection's pre-split copy by LDS-DMA through a ring of stages (gemm_bf16x2_dma_k; same products in the same order: same bits)"},
-    {"ISLE_YY_MODE", "form", "doc | docg | group: Yinyang iteration by document (row-major / group-major centres) or ordered by group (default: group at k >= 256)"},
+    {"ISLE_YY_MODE", "form", "doc | docg | group: Yinyang iteration by document (row-major / group-major centres) or ordered by group (default: group at k >= 249)"},
     {"ISLE_YY_FUSED", "form", "0: the by-group Yinyang iteration lowers the bounds (yy_filter_k) and tightens the active documents (yy2_tighten_k) in two launches instead of one (same bits)"},
     {"ISLE_YY_MOVERS", "form", "0: every centre's movement lowers its Yinyang group's bound (default: up to ten centres that moved far beyond the rest are bounded by their exact new distances instead)"},
     {"ISLE_YY_REGROUP", "form", "0: a Yinyang group is eight consecutive centres (default at k >= 256 behind the product's first assignment: the centres in the order of their squared norms, so that the few centres every far-off document is near share groups; same partitions, a third of the (document, group) pairs)"},
@@ -92,12 +92,14 @@ const IsleKnobInfo isle_knob_table[KN_COUNT] = {
     {"ISLE_GL_ABLATE_SKIP", "test hook", "m >= 2: TIMING EXPERIMENT, results wrong by construction — every m-th (band, group) of every wave of the LDS-banded passes is not walked and its ids are not read (prices a form with 1/m fewer padded slots; round 6)"},
 };
 void isle_refresh_knobs(isle_ctx* c) {
+  const char* val[KN_COUNT];
   for (int i = 0; i < KN_COUNT; ++i) {
-    const char* e = getenv(isle_knob_table[i].name);
-    c->knob_set[i] = e != nullptr;
-    if (e) c->knob_val[i] = e;
+    val[i] = getenv(isle_knob_table[i].name);
+    c->knob_set[i] = val[i] != nullptr;
+    if (val[i]) c->knob_val[i] = val[i];
     else c->knob_val[i].clear();
   }
+  c->route = route_env(val);
 }
 int isle_enter(isle_ctx* c) {
   HIPCHK(c, hipSetDevice(c->device));
@@ -105,18 +107,14 @@ int isle_enter(isle_ctx* c) {
   return 0;
 }
 
-// May the optional D x k scratch of the GEMM routes be taken?  A function of the problem's size and the device's TOTAL memory only —
-// never of what happens to be free — so that the route, and with it every rounding of the first assignment, is the same run after run
-// and rank after rank: always up to 8 GB; beyond (all of config 3 on one GPU: 40 GB), up to a fifth of the device (57 GB on an MI355X).
-bool isle_scratch_ok(isle_ctx* c, size_t have_elems, double bytes) {
-  (void)have_elems;
-  if (bytes <= 8e9) return true;
+// the device's total memory, for route_scratch_ok: asked for once per context, and only where a route's decision needs it
+bool isle_total_mem(isle_ctx* c) {
   if (c->total_mem == 0) {
     size_t fr = 0, tot = 0;
     if (hipSetDevice(c->device) != hipSuccess || hipMemGetInfo(&fr, &tot) != hipSuccess) return false;
     c->total_mem = tot;
   }
-  return bytes <= 0.2 * (double)c->total_mem;
+  return true;
 }
 
 int isle_max_lds(isle_ctx* c, const void* fn, int bytes) {
@@ -180,7 +178,7 @@ static void roctx_load_once() {
 }
 
 TimeScope::TimeScope(isle_ctx* c_, int fam) : c(c_), on(false) {
-  if (fam >= 0 && fam < ISLE_T_COUNT && c->knob_on(KN_ROCTX) && !c->knob_zero(KN_ROCTX) && !c->roctx_open) {
+  if (fam >= 0 && fam < ISLE_T_COUNT && c->knob_on(KN_ROCTX) && atoi(c->knob(KN_ROCTX)) != 0 && !c->roctx_open) {
     roctx_load_once();
     if (g_roctx_push) {
       g_roctx_push(kFamilyName[fam]);
@@ -280,7 +278,7 @@ static void wd_loop(isle_ctx* c) {
   }
 }
 static int wd_start(isle_ctx* c) {
-  if (const char* e = c->knob(KN_COMM_TIMEOUT)) c->wd_timeout_s = atof(e);
+  c->wd_timeout_s = route_comm_timeout(c->wd_timeout_s, c->route);
   if (!(c->wd_timeout_s > 0.0) || c->wd_thread.joinable()) return 0;
   c->wd_done = &c->pin_small()->wd_done;  // page-locked
   *c->wd_done = 0;
@@ -394,7 +392,7 @@ extern "C" isle_ctx* isle_hip_create(int device_id) {
     return nullptr;
   }
   isle_refresh_knobs(c);
-  if (const char* br = c->knob(KN_CHUNK_COLS)) c->band_rows = (uint32_t)atoi(br);
+  c->band_rows = c->route.chunk_cols;
   if (hipHostMalloc((void**)&c->pin, isle_ctx::PIN_BYTES, hipHostMallocDefault) != hipSuccess) {
     (void)hipStreamDestroy(c->stream);
     delete c;
@@ -500,11 +498,6 @@ static int comm_selftest(isle_ctx* c) {
           std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   return 0;
 }
-static bool comm_selftest_wanted(isle_ctx* c, bool dflt) {
-  if (c->knob_on(KN_COMM_SELFTEST)) return !c->knob_zero(KN_COMM_SELFTEST);
-  return dflt;
-}
-
 extern "C" int isle_hip_comm_init(isle_ctx* c, int world, int rank, const void* uid) {
   if (!c || world < 1 || rank < 0 || rank >= world) return isle_fail(c, ISLE_E_ARG, "bad world/rank");
   c->world = world;
@@ -518,7 +511,7 @@ extern "C" int isle_hip_comm_init(isle_ctx* c, int world, int rank, const void* 
   memcpy(&id, uid, sizeof id);
   NCCLCHK(c, ncclCommInitRank(&c->comm, world, id, rank));
   ISLECHK(wd_start(c));
-  if (comm_selftest_wanted(c, world > 1)) return comm_selftest(c);  // (a forced 1-rank communicator: the collectives are the identity)
+  if (route_comm_selftest(world > 1, c->route)) return comm_selftest(c);  // (a forced 1-rank communicator: the collectives are the identity)
   return 0;
 }
 
@@ -529,7 +522,7 @@ extern "C" int isle_hip_comm_init_host(isle_ctx* c, int world, int rank, isle_ho
   c->rank = rank;
   c->host_xchg = fn;
   c->host_xchg_user = user;
-  if (comm_selftest_wanted(c, false)) {
+  if (route_comm_selftest(false, c->route)) {
     ISLECHK(isle_enter(c));
     return comm_selftest(c);
   }

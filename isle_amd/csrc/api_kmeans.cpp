@@ -57,8 +57,7 @@ static int ensure_P(isle_ctx* c, int k) {
   // Where the assignment products run with their epilogues inside (a large shard) they read the projection's two bf16 terms in the layout
   // the LDS-DMA product stages (gemm_bf16x2_dma_k).  The grouped projection writes that copy on its way, by POSITION (the products map their
   // rows to documents through dperm): no transposition and no split pass behind the projection (round 5: 15 + 15 ms at config 3).
-  const bool want_a2 = c->D && k_gemm_assign_fused_ok(c, c->D, k, k) && !c->knob_zero(KN_GEMM_DMA) &&
-                       !(c->knob(KN_GEMM_TERMS) && atoi(c->knob(KN_GEMM_TERMS)) == 3);
+  const bool want_a2 = route_want_a2(c->D, k, c->route);
   bool a2_done = false;
   if (want_a2) HIPCHK(c, c->Pt2.reserve(k_gemm_split_a_bytes(c->D, k) / sizeof(uint4)));
   ISLECHK(k_spmm_wide_project(c, c->Urm.p, k, c->ldk, c->P.p, c->pnorm.p, want_a2 ? c->Pt2.p : nullptr, &a2_done));
@@ -104,16 +103,6 @@ static void centres_unpack(float* C_lowd, const float* Ch, int k, int ldk) {
 }
 
 namespace {
-// The route decisions of one k-means++ call, taken once at its entry (the switches are read at isle_enter only).
-struct KmppPlan {
-  // k > 224 (Lloyd in span(U) keeps tile bounds): the rounds also keep every document's nearest seed and tile minima, so that Lloyd's
-  // first assignment — a D x k x k pass against exactly these seeds — need not be computed again (kmeans.hip kmpp_min_dots_track_k)
-  bool track;
-  int maxdraw;
-  // one rank, seeds not injected: the device throws the dice of a round itself while they fit its 40 slots (kmpp_draw_on_device); the
-  // switch is for the test that holds both forms to the same seeds
-  bool device_dice;
-};
 // page-locked staging for the per-round scalars (IslePinSmall::kmpp_stage): [my 2 | tot 2 * world | local maxdraw] doubles, then drawn
 // maxdraw u64, then the 42 words of the device's search
 struct KmppStage {
@@ -200,10 +189,7 @@ extern "C" int isle_hip_kmeanspp_projected(isle_ctx* c, int k, const uint64_t* i
   if (!c || !seeds_out || !C_lowd || k < 1) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
   if ((uint64_t)k > c->D_global) return isle_fail(c, ISLE_E_ARG, "k > number of documents");
-  KmppPlan plan;
-  plan.track = k > 224 && (k + 31) / 32 <= 32 && !c->knob_zero(KN_KMPP_TRACK);
-  plan.maxdraw = 2 + (int)std::ceil(std::sqrt((double)k));
-  plan.device_dice = !c->multi() && !inject && !c->knob_on(KN_KMPP_HOST_DICE);
+  const KmppPlan plan = route_kmpp_plan(k, c->multi(), inject != nullptr, c->route);
   isle_host_mark("kmeanspp: entry");
   ISLECHK(ensure_P(c, k));  // compute_projected_docs_l2sq :2144
   isle_host_mark("kmeanspp: projection enqueued");
@@ -372,18 +358,6 @@ static int prepare_movers(isle_ctx* c, const std::vector<float>& delta, int k, i
 // Lloyd in span(U)
 // ------------------------------------------------------------------------------------------
 namespace {
-// The route decisions of one call, taken once behind ensure_P (the switches are read at isle_enter only) and read everywhere below.
-struct ProjPlan {
-  bool hamerly;  // Hamerly bounds (exact skip of documents whose closest centre provably did not change), as in the sparse Lloyd
-  // k > 224 (more than 7 tiles of 32 centres): one lower bound per tile instead of Hamerly's single one, which prunes nothing at
-  // k = 1000 (kmeans.hip PR_TILES, spmm.hip pt_filter_k).  ISLE_PROJ_BOUNDS=hamerly keeps the single bound.
-  bool tiles;
-  int T, TL;
-  bool from_kmpp;   // the first assignment is the one the k-means++ rounds kept
-  bool pt_sorted;   // the active documents are ordered by the tiles they need: the filter walks the documents in their own order
-  bool delta_sums;  // the centroid sums are kept up to date by the documents that changed centre
-  bool movers;      // tile bounds may leave centres that jumped out of their tiles' movements (where the thin product exists: proj_reassign_tiles)
-};
 // device scalars of the loop, behind the previous centres in c->Cold and in c->small
 struct ProjScalars {
   float* delta;  // k movements (Cold + k * ldk)
@@ -392,18 +366,11 @@ struct ProjScalars {
 };
 }  // namespace
 
+// the route decisions of one call (route_host.h ProjPlan), taken once behind ensure_P: the switches are read at isle_enter only
 static ProjPlan proj_plan(isle_ctx* c, int k, const float* C_lowd) {
-  ProjPlan p;
-  p.hamerly = !c->knob_on(KN_NO_HAMERLY) && (c->Pt_ready || c->Pt2_ready);
-  p.T = (k + 31) / 32;
-  p.TL = (p.T + 3) & ~3;
-  p.tiles = p.hamerly && k > 224 && p.T <= 32 && !c->knob_is(KN_PROJ_BOUNDS, "hamerly");
-  p.from_kmpp = p.tiles && c->kmpp_track_k == k && c->kmpp_P_gen == c->P_gen && c->P_ready && !c->knob_zero(KN_KMPP_TRACK) &&
-                c->kmpp_C_host.size() == (size_t)k * k && memcmp(c->kmpp_C_host.data(), C_lowd, (size_t)k * k * sizeof(float)) == 0;
-  p.pt_sorted = !c->knob_zero(KN_PT_SORT);
-  p.delta_sums = !c->knob_is(KN_PROJ_SUMS, "fresh") && c->D < (1ull << 31);
-  p.movers = !c->knob_zero(KN_YY_MOVERS) && c->D > 0;
-  return p;
+  const bool seeds_kept = c->kmpp_C_host.size() == (size_t)k * k && memcmp(c->kmpp_C_host.data(), C_lowd, (size_t)k * k * sizeof(float)) == 0;
+  const ProjFacts f = {c->D, c->Pt_ready, c->Pt2_ready, c->P_ready, c->kmpp_track_k, c->kmpp_P_gen == c->P_gen, seeds_kept};
+  return route_proj_plan(f, k, c->route);
 }
 
 static int proj_reserve(isle_ctx* c, const ProjPlan& p, int k, ProjScalars* sc) {
@@ -451,7 +418,7 @@ static int debug_tile_stats(isle_ctx* c, int it, uint32_t na, int T) {
   std::vector<uint32_t> act(na), need(D);
   if (na) HIPCHK(c, hipMemcpy(act.data(), c->active.p, na * sizeof(uint32_t), hipMemcpyDeviceToHost));
   if (D) HIPCHK(c, hipMemcpy(need.data(), c->pneed.p, D * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (na > 256 && !c->knob_zero(KN_PT_SORT))  // the order k_proj_assign_tiles gives the list
+  if (route_pt_sort(true, na, c->route))  // the order k_proj_assign_tiles gives the list
     std::stable_sort(act.begin(), act.end(), [&](uint32_t a, uint32_t b) { return need[a] < need[b]; });
   double tiles_sum = 0, union_sum = 0;
   for (uint32_t i = 0; i < na; i += 128) {
@@ -649,30 +616,6 @@ extern "C" int isle_hip_lift_centers(isle_ctx* c, const float* in, int ld_in, in
 }
 
 namespace {
-// The route decisions of one call of Lloyd on B, taken once (the switches are read at isle_enter only) and read everywhere below.
-struct SparsePlan {
-  // Distance bounds: exact accelerations of the assignment step (documents whose bounds prove "unchanged" are skipped).
-  // Default: Yinyang group bounds (groups of 8 centres); ISLE_KMEANS_BOUNDS=hamerly|none selects the others.
-  bool hamerly /*any bound-based mode*/, yinyang;
-  int G;
-  // form of the Yinyang iteration: 0 = by document over the row-major centres, 1 = by document over the group-major copy, 2 = by group.
-  // The forms that visit documents in member order (docg, group) hold a document's group bounds four per lane: at most 256 groups
-  // (k <= 2048); beyond, by document over the row-major centres, whatever ISLE_YY_MODE asks for
-  int yy_mode;
-  // by group: the bounds are lowered and the active documents tightened in one launch (the D x G bounds read once), ISLE_YY_FUSED=0: in two
-  bool fused;
-  // Visiting order of the assignment step: the member lists of the previous iteration, which are then made every iteration (the
-  // Hamerly and plain forms: cache locality of the centre rows; results are order-independent).  The fused by-group launch takes the
-  // documents in their own order since the end of round 5 (its first phase then streams the bounds as one run per workgroup; once that
-  // phase kept sixteen loads in flight the member order's gain in the second phase — neighbours share the own group's table — no longer
-  // paid for its scattered rows: sparse_assign 177 -> 170 ms at config 3): nothing reads the lists then, and they are not made (a sort
-  // of D keys per iteration).  ISLE_YY_ORDER = doc | member forces either.
-  bool by_members;
-  bool fused_first;     // the product's epilogue forms the first assignment: no D x k scratch
-  bool via_projection;  // the first assignment is the dense product on the projection (where its scratch is had: first_scratch_had)
-  bool regroup;         // the Yinyang groups are formed from the centres in the order of their squared norms (sparse_regroup_tables)
-  bool movers;          // centres that jumped may be left out of their groups' movements (where the thin product exists: sparse_reassign_yinyang)
-};
 // device scalars of the loop in c->Csum (2 k + 16 + G floats)
 struct SparseScalars {
   float* delta;   // k movements
@@ -690,7 +633,7 @@ static SparseScalars sparse_scalars(isle_ctx* c, int k) {
   return {c->Csum.p, c->Csum.p + 2 * k + 8, reinterpret_cast<HamTop*>(c->Csum.p + 2 * k + 12), c->Csum.p + 2 * k + 16};
 }
 
-// The D x k scratch of the first assignment's product.  The route is chosen from sizes alone (isle_scratch_ok), but on a device shared with
+// The D x k scratch of the first assignment's product.  The route is chosen from sizes alone (route_scratch_ok), but on a device shared with
 // other work the scratch may still not be had: the sparse product gives the same assignment up to dot-product rounding, so take it
 // instead of failing the call
 static bool first_scratch_had(isle_ctx* c, int k) {
@@ -701,38 +644,10 @@ static bool first_scratch_had(isle_ctx* c, int k) {
   return false;
 }
 
+// the route decisions of one call (route_host.h SparsePlan)
 static SparsePlan sparse_plan(isle_ctx* c, int k, int ld) {
-  const uint64_t D = c->D;
-  SparsePlan p;
-  p.hamerly = !c->knob_on(KN_NO_HAMERLY) && !c->knob_is(KN_KMEANS_BOUNDS, "none");
-  p.yinyang = p.hamerly && !c->knob_is(KN_KMEANS_BOUNDS, "hamerly");
-  p.G = (k + 7) / 8;
-  int yy_mode_env = -1;
-  if (const char* e = c->knob(KN_YY_MODE)) yy_mode_env = !strcmp(e, "doc") ? 0 : !strcmp(e, "docg") ? 1 : !strcmp(e, "group") ? 2 : -1;
-  p.yy_mode = !p.yinyang ? 0 : p.G > 256 ? 0 : yy_mode_env >= 0 ? yy_mode_env : (p.G >= 32 ? 2 : 0);
-  p.fused = p.yy_mode == 2 && !c->knob_zero(KN_YY_FUSED);
-  const char* yord = c->knob(KN_YY_ORDER);
-  p.by_members = !p.yinyang || !p.yy_mode || (yord ? strcmp(yord, "doc") != 0 : !p.fused);
-  p.movers = p.fused && !c->knob_zero(KN_YY_MOVERS);
-  // first assignment through the projection: only for centres that came from isle_hip_lift_centers (lift_valid) with the current U and P, and
-  // while the dense product is cheaper than the sparse one: always up to k = 384; beyond, by the measured rates — the D x k x k
-  // product runs at ~130 TFLOP/s (rocBLAS), a panel pass of the sparse product takes ~2.8 ps per nonzero (C3 shard, k = 1000: 19 against
-  // 44 ms) — and while its D x k scratch can be had (isle_scratch_ok; first_scratch_had at run time) (ISLE_FIRST_ASSIGN=sparse|projection forces)
-  const double t_dense = 2.0 * (double)D * k * k / 130e12, t_sparse = (double)((k + 7) / 8) * (double)c->nnz * 2.8e-12;
-  p.fused_first = p.yinyang && k_gemm_assign_fused_ok(c, D, k, k);
-  const bool dense_pays = k <= 384 || (t_dense < t_sparse && (p.fused_first || isle_scratch_ok(c, c->dotsT.cap, (double)D * k * sizeof(float))));
-  p.via_projection = c->lift_valid && c->lift_k == k && c->U_k == k && c->P_ready && (c->Pt_ready || c->Pt2_ready) && c->ldk == ld && D > 0 &&
-                     (dense_pays || c->knob_is(KN_FIRST_ASSIGN, "projection")) && !c->knob_is(KN_FIRST_ASSIGN, "sparse");
-  // Regrouping (round 5).  A Yinyang group's bound is the distance to its CLOSEST member, so one centre every document is near spoils the
-  // bound of its whole group — and the centres of small squared norm (the large, diffuse clusters) are near every document that lies
-  // far from everything else: with groups of eight consecutive labels those few centres sit in as many groups and an undecided document
-  // scans them all (config 3: 10 - 15 groups per active document in the first iterations).  The groups are therefore formed from the
-  // centres in the order of their squared norms at the loop's entry (stable: equal norms keep their labels' order), through slot
-  // tables (YyMap); labels, ties and everything outside the by-group kernels stay in the centres' own numbering.  Config 3 on one GPU:
-  // 137 M -> 39 M (document, group) pairs per step, Lloyd on B 296 -> 199 ms, same partition (tools/yy_probe.py, profiles/r05_d_*).
-  // Taken with the by-group form behind the product's first assignment; ISLE_YY_REGROUP=0 keeps groups of consecutive labels.
-  p.regroup = p.yinyang && p.yy_mode == 2 && p.via_projection && p.fused_first && !c->knob_zero(KN_YY_REGROUP);
-  return p;
+  const SparseFacts f = {c->D, c->nnz, c->lift_valid, c->lift_k, c->U_k, c->ldk, c->P_ready, c->Pt_ready, c->Pt2_ready};
+  return isle_route_mem(c, [&](uint64_t total_mem, bool* ask) { return route_sparse_plan(f, k, ld, c->route, total_mem, ask); });
 }
 
 // the slot tables, from the norms just computed (the same on every rank: the centres are replicated)
@@ -918,7 +833,7 @@ static int sparse_update_centres(isle_ctx* c, const SparsePlan& p, int k, int ld
   const uint64_t D = c->D, V = c->V;
   // documents grouped by centre: visiting order of the next assignment (SparsePlan::by_members), and what the FRESH counting centroid
   // update walks (the first of a run; later ones go by the documents that changed centre)
-  if (it == 0 || p.by_members || c->gl_mode != 1 || c->knob_on(KN_CENTERS_FRESH)) {
+  if (route_member_lists(it, p.by_members, c->gl_mode, c->route)) {
     TimeScope ts(c, ISLE_T_SPARSE_ASSIGN);
     ISLECHK(k_member_lists_dev(c, c->assign.p, D, k, c->counts.p));
   } else {

@@ -70,7 +70,7 @@ struct Ks {
     // the replicated panel QR.  The step is HBM-bound on reading the basis (0.15 s of a 1.15 s C3-shard step): it now divides by
     // the number of ranks at the price of passes + 1 small collectives per step.  Default with several ranks since round 5 (a collective
     // that never completes is turned into ISLE_E_COMM by the watchdog, api.cpp); ISLE_KS_ROWSHARD=0 keeps it replicated.
-    const bool shard = c->multi() && !dense_A && !c->knob_zero(KN_KS_ROWSHARD);
+    const bool shard = route_ks_rowshard(c->multi(), dense_A, c->route);
     if (!shard) {
       for (int p = 0; p < passes; ++p) {
         float* cf = base + (size_t)p * m * w;
@@ -175,8 +175,8 @@ struct Ks {
 
   // mailboxes, events, the copy stream and the host landing slots
   int expand_prepare(Expand& e) {
-    e.pipelined = !c->knob_on(KN_KS_SYNC);
-    e.npass = ks_ortho_passes(c->knob(KN_KS_ORTHO_PASSES));
+    e.pipelined = route_ks_pipelined(c->route);
+    e.npass = c->route.ks_ortho_passes;
     const size_t mb_floats = ks_mail_floats(e.cap.r, blk);
     HIPCHK(c, c->ks_mail.reserve(2 * mb_floats));
     for (int i = 0; i < 2; ++i) {

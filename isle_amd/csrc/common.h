@@ -12,6 +12,8 @@
 #include <vector>
 
 #include "gl_plan.h"
+#include "knobs.h"
+#include "route_host.h"
 
 // ------------------------------------------------------------------------------------------
 // Launch guard.  On this stack a kernel launch of 2^32 threads or more (grid x block) does not run and reports NO error — round 3's
@@ -107,26 +109,6 @@ struct PinBuf {
   ~PinBuf() { release(); }
 };
 
-// ------------------------------------------------------------------------------------------
-// Environment switches.  Every switch the library honours is in this table; they are read into the context when it is created and
-// again at the entry of every C-ABI call (isle_enter, api.cpp) — never inside a loop or a launch path — and the code asks the context
-// (isle_ctx::knob).  DESIGN.md section "Environment switches" is this table with the measurements behind the defaults.
-// ------------------------------------------------------------------------------------------
-enum IsleKnob {
-  KN_GRAM_LDS, KN_GL_G1, KN_GL_G2, KN_GL_PLACE, KN_GL_FILL_BUCKETS, KN_GL_ROUNDS, KN_GL_COLUMNS, KN_GL_PANEL, KN_GL_WIDE_GROUPED, KN_WIDE_GATHER, KN_WIDE_LDS,
-  KN_KS_ROWSHARD, KN_KS_SYNC, KN_KS_ORTHO_PASSES, KN_UPDATE_MFMA, KN_EVD_JACOBI, KN_TD_CHAIN, KN_TD_BAR, KN_TD_BACK, KN_EVD_SPLIT,
-  KN_KMPP_HOST_DICE, KN_KMPP_SPARSE, KN_KMPP_TRACK, KN_NO_HAMERLY, KN_KMEANS_BOUNDS, KN_PROJ_BOUNDS, KN_PROJ_FULL, KN_FIRST_ASSIGN, KN_GEMM_BF16X3, KN_GEMM_EPILOGUE, KN_GEMM_TERMS, KN_GEMM_DMA, KN_YY_MODE, KN_YY_FUSED, KN_YY_MOVERS, KN_YY_REGROUP, KN_YY_ORDER, KN_PT_SORT, KN_PROJ_ACTIVE, KN_PROJ_SUMS, KN_CENTERS_FRESH,
-  KN_INFER_CAP_ROWS, KN_CHUNK_COLS, KN_COMM_TIMEOUT, KN_COMM_SELFTEST, KN_FORCE_COMM, KN_TEST_STALL_MS,
-  KN_ROCTX, KN_HOST_TRACE, KN_DEBUG_HAMERLY, KN_DEBUG_EVD, KN_GL_VERBOSE, KN_TD_FORCE_BAIL_RANK, KN_GL_TEST_CUS, KN_GL_ABLATE_SKIP,
-  KN_COUNT
-};
-struct IsleKnobInfo {
-  const char* name;
-  const char* kind;  // "form" (selects between exact forms of a computation), "tuning", "diagnostic", "test hook"
-  const char* what;
-};
-extern const IsleKnobInfo isle_knob_table[KN_COUNT];
-
 // One side of the LDS-banded Gram apply (gram_lds.hip): a sliced-ELL stream of band-local u16 source ids.
 // (GlDesc, one workgroup of gl_apply_k, and the host plan that fills it: gl_plan.h)
 struct GlSide {
@@ -201,15 +183,15 @@ struct IsleFeed {
 };
 
 struct isle_ctx {
-  // environment switches as read at the last C-ABI entry (isle_refresh_knobs)
+  // environment switches as read at the last C-ABI entry (isle_refresh_knobs): the typed values of the switches that select or tune a form
+  // (what the rules of route_host.h read), and the strings for the diagnostics and the test hooks
+  RouteEnv route;
   std::string knob_val[KN_COUNT];
   bool knob_set[KN_COUNT] = {};
   const char* knob(int id) const { return knob_set[id] ? knob_val[id].c_str() : nullptr; }
-  bool knob_on(int id) const { return knob_set[id]; }                                         // set at all (any value)
-  bool knob_is(int id, const char* v) const { return knob_set[id] && knob_val[id] == v; }
-  bool knob_zero(int id) const { return knob_set[id] && atoi(knob_val[id].c_str()) == 0; }
+  bool knob_on(int id) const { return knob_set[id]; }  // set at all (any value)
   int device = 0;
-  size_t total_mem = 0;  // bytes of device memory (isle_scratch_ok)
+  size_t total_mem = 0;  // bytes of device memory (isle_total_mem); 0: not asked yet
   hipStream_t stream = nullptr;
   std::string err;
   int num_cus = 256;
@@ -333,7 +315,7 @@ struct isle_ctx {
   DevBuf<uint32_t> gl_fb_cnt, gl_fb_tmp;  // pass-2 fill by buckets of word positions: entries per (band, bucket); the packed entries (nnz words = 4 GB at config 3).
                                           // KEPT between builds, like gl_pscratch below (7.7 GB at 10 M documents): every solve builds the operator again and a
                                           // hipFree / hipMalloc pair of that size per step costs more than the memory is worth on a 288 GB device; both count
-                                          // against what isle_scratch_ok sees as free — it decides from the device's TOTAL memory, so the routes do not depend on them
+                                          // against what route_scratch_ok sees as free — it decides from the device's TOTAL memory, so the routes do not depend on them
   DevBuf<int64_t> gl_fb_off;
   DevBuf<uint16_t> gl_scnt;  // super-rounds of (slice, band) of pass 2 (gl_sbase's indexing)
   DevBuf<uint32_t> gl_biglist;   // [count | (wave, band, group) triples whose pass-2 cells are too long for the register sort]
@@ -480,7 +462,15 @@ int isle_fail(isle_ctx* c, int code, const char* fmt, ...);
 void isle_trim_derived(isle_ctx* c, uint64_t D, uint64_t nnz);
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (context = device, kernel, size): api.cpp
 int isle_max_lds(isle_ctx* c, const void* fn, int bytes);
-bool isle_scratch_ok(isle_ctx* c, size_t have_elems, double bytes);
+bool isle_total_mem(isle_ctx* c);  // asks the device for its total memory, once (c->total_mem); false: it could not be asked
+// A rule of route_host.h that may need the device's total memory, rule(total_mem, &ask): asked for only where the decision gets that far
+template <class Rule>
+auto isle_route_mem(isle_ctx* c, Rule rule) -> decltype(rule((uint64_t)0, (bool*)nullptr)) {
+  bool ask = false;
+  auto r = rule((uint64_t)c->total_mem, &ask);
+  if (ask && isle_total_mem(c)) r = rule((uint64_t)c->total_mem, &ask);
+  return r;
+}
 void isle_refresh_knobs(isle_ctx* c);
 int isle_enter(isle_ctx* c);  // entry of a C-ABI call: the context's device becomes current, the environment switches are read
 // ISLE_HOST_TRACE=1: host wall time since the previous mark, to stderr (marks that follow within 0.2 ms stay silent).  Finds GPU-idle
@@ -728,7 +718,6 @@ int k_randu(isle_ctx* c, float* F, uint64_t count, uint64_t seed);
 int k_gemm_nn(isle_ctx* c, const float* A, uint64_t M, int K, const float* B, int ldb, int N, float* C, int family = ISLE_T_ROTATE);  // col-major, lda = ldc = M
 // the same product for the D x k x k dot products of the assignment steps: bf16 matrix cores, operands split in three bf16 terms (gemm_bf16x3.h)
 int k_gemm_nn_assign(isle_ctx* c, const float* A, uint64_t M, int K, const float* B, int ldb, int N, float* C, int family);
-bool k_gemm_assign_fused_ok(isle_ctx* c, uint64_t M, int K, int N);
 int k_gemm_assign_yy(isle_ctx* c, const float* A, const float* Arm, int lda_rm, const float* an, uint64_t M, int K, const float* B, int ldb, int N, int G,
                      const float* cn, const float* dn, const float* cn_max, uint32_t* assign, float* ub, float* lb, int family, const void* A2 = nullptr,
                      const uint32_t* map2 = nullptr /*row of A2 -> document when A2 lies by position; A may be null then (made on demand)*/);

@@ -363,7 +363,7 @@ int k_update(isle_ctx* c, float* F, uint64_t n, int b, const float* Vb, int m, c
   if (n == 0) return 0;
   const int BT = bt_of(b);
   dim3 g(cdiv(n, 64)), blk(256);
-  if (b <= 16 && m >= 32 && (ld & 3) == 0 && (((uintptr_t)Vb | (uintptr_t)F) & 15) == 0 && !c->knob_zero(KN_UPDATE_MFMA)) {
+  if (route_update_mfma(b, m, ld, (((uintptr_t)Vb | (uintptr_t)F) & 15) == 0, c->route)) {
     // waves per workgroup: a workgroup is 64 rows, so a short panel (a rank's row slice) leaves CUs empty and every wave a long chain of
     // dependent trips (n = 12 500: 196 workgroups x 16 trips at m = 2010) — there the columns are dealt over 8 or 16 waves instead of 4
     const long wgs = cdiv(n, 64);
@@ -793,8 +793,7 @@ int k_gemm_nn(isle_ctx* c, const float* A, uint64_t M, int K, const float* B, in
 // against 123 TFLOP/s at 1.25 M x 1000 x 1000, 102 against 67 at 1 M x 200 x 200.  Small products and ISLE_GEMM_BF16X3=0: gemm_f32.h.
 using Gemm3Huge = isle_gemm3::Cfg<2, 2, 4, 4, 4>;  // 256 x 256 x 16, 1024 threads
 int k_gemm_nn_assign(isle_ctx* c, const float* A, uint64_t M, int K, const float* B, int ldb, int N, float* C, int family) {
-  if (c->knob_zero(KN_GEMM_BF16X3) || N < 64 || K < 32 || (M + 255) / 256 * (uint64_t)((N + 255) / 256) < 512)
-    return k_gemm_nn(c, A, M, K, B, ldb, N, C, family);
+  if (!route_gemm_bf16x3(M, K, N, c->route)) return k_gemm_nn(c, A, M, K, B, ldb, N, C, family);
   TimeScope ts(c, family);
   if (M >= (1ull << 32)) return isle_fail(c, ISLE_E_ARG, "gemm: operand too large for 32-bit row offsets");
   HIPCHK(c, c->gemm_b3.reserve((size_t)3 * isle_gemm3::kp8_of(K) * isle_gemm3::np_of<Gemm3Huge>(N)));
@@ -957,11 +956,6 @@ __global__ __launch_bounds__(256) void tiles_combine_k(const AssignRec* __restri
     if (open) redo[at] = map ? map[i] : i;
   }
 }
-// may the fused route be taken?  (the bf16 product with 256 x 256 tiles; small products keep the two-kernel route)
-bool k_gemm_assign_fused_ok(isle_ctx* c, uint64_t M, int K, int N) {
-  return !c->knob_zero(KN_GEMM_BF16X3) && !c->knob_zero(KN_GEMM_EPILOGUE) && N >= 64 && K >= 32 && (M + 255) / 256 * (uint64_t)((N + 255) / 256) >= 512 &&
-         M < (1ull << 32);
-}
 using Gemm2Huge = isle_gemm3::Cfg<2, 2, 4, 4, 4, 16, 2>;  // the same tile with two bf16 terms per operand
 // Both assignment steps: first pass (two terms unless ISLE_GEMM_TERMS=3) over all rows, then the rows it left open through the three-term
 // product.  make(map, eta) builds the epilogue, combine(part, n, map, eta, redo, nredo) launches the step's combine kernel.
@@ -986,8 +980,7 @@ static int gemm_assign_two_pass(isle_ctx* c, const float* A, const float* Arm, i
   };
   const int nslot = (N + 63) / 64;
   static_assert(sizeof(AssignRec) == 20, "");
-  const char* gt = c->knob(KN_GEMM_TERMS);
-  const bool two = !(gt && atoi(gt) == 3) && Arm != nullptr;
+  const bool two = route_gemm_two_terms(Arm != nullptr, c->route);
   HIPCHK(c, c->gemm_b3.reserve((size_t)3 * isle_gemm3::kp8_of(K) * isle_gemm3::np_of<Gemm3Huge>(N)));
   HIPCHK(c, c->assign_part.reserve((size_t)M * nslot * 5));
   AssignRec* part = reinterpret_cast<AssignRec*>(c->assign_part.p);
@@ -1002,7 +995,7 @@ static int gemm_assign_two_pass(isle_ctx* c, const float* A, const float* Arm, i
   HIPCHK(c, c->ga_redo.reserve(M + 1));
   uint32_t* nredo = c->ga_redo.p + M;
   HIPCHK(c, hipMemsetAsync(nredo, 0, sizeof(uint32_t), c->stream));
-  if (A2 && !c->knob_zero(KN_GEMM_DMA)) {
+  if (route_gemm_dma(A2 != nullptr, c->route)) {
     HIPCHK(c, isle_gemm3::launch_dma<Gemm2Dma>(c->stream, A2, M, K, B, ldb, N, c->gemm_b3.p, make(part, map2 ? map2 : map0, eta2)));
     combine(part, (uint32_t)M, map2 ? map2 : map0, eta2, c->ga_redo.p, nredo);
   } else {
@@ -1570,7 +1563,7 @@ int k_scale_centers(isle_ctx* c, float* Crm, uint64_t rows, int k, int ldk, cons
 // solver above is the fallback for sizes it does not take and for spectra whose eigenvectors fail its orthogonality check
 // (clusters far tighter than Ritz matrices show).  ISLE_EVD_JACOBI=1 forces the Jacobi solver.
 int k_eig_small(isle_ctx* c, const float* S_host, int n, float* evals_host, float* vecs_dev, int nvec) {
-  if (n >= 16 && !c->knob_on(KN_EVD_JACOBI)) {
+  if (route_evd_tridiag(n, c->route)) {
     int rc;
     {
       TimeScope ts(c, ISLE_T_EVD);

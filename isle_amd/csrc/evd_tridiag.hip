@@ -884,16 +884,9 @@ int k_tridiag_eig(isle_ctx* c, const float* S_host, int n, float* evals_host, fl
   ISLECHK(isle_max_lds(c, (const void*)td_back_k<4>, TD_NMAX_BACK * 4 * (int)sizeof(double)));
   ISLECHK(isle_max_lds(c, (const void*)td_back_wy_k<4, true, true>, 2 * TD_WY * TD_NMAX_BACK * (int)sizeof(double)));
   const bool small = n <= TD_ROWS * 4;
-  // persistent form: G workgroups, each with its columns (ncl of them) plus v and w in LDS
-  int pG = TD_P_GSMALL;
-  {
-    const int ncl_max = (int)(TD_P_LDS / sizeof(double) / (size_t)n) - 2;
-    if (ncl_max >= 1) pG = std::max(pG, (n + ncl_max - 1) / ncl_max);  // what the LDS needs
-    else pG = 1 << 30;
-  }
-  // one workgroup per CU at most: all must be resident.  A time-out at the grid barrier (the GPU is shared with other work) is
-  // remembered: later solves of this context go straight to the launch chain instead of paying the time-out again.
-  bool persist = pG <= c->num_cus && n <= TD_NMAX_BACK && !c->knob_on(KN_TD_CHAIN) && !c->td_persist_failed;
+  // persistent form: G workgroups, each with its columns (ncl of them) plus v and w in LDS, one workgroup per CU at most
+  const int pG = route_td_workgroups(n, TD_P_LDS, TD_P_GSMALL);
+  bool persist = route_td_persist(pG, n, TD_NMAX_BACK, c->num_cus, c->td_persist_failed, c->route);
   if (c->multi()) {  // every rank must take the same form (their roundings differ): the form is agreed, like the bail-out below
     unsigned int no = persist ? 0u : 1u;
     HIPCHK(c, hipMemcpyAsync(tickets + 1, &no, sizeof no, hipMemcpyHostToDevice, c->stream));
@@ -916,11 +909,10 @@ int k_tridiag_eig(isle_ctx* c, const float* S_host, int n, float* evals_host, fl
       GbHierArgs bar = {};
       bar.st = bar_state;
       HIPCHK(c, hipMemsetAsync(bar_state, 0, GBH_STATE_WORDS * sizeof(unsigned int), c->stream));
-      const char* bk = c->knob(KN_TD_BAR);
-      if (bk && !strcmp(bk, "flat")) {
+      if (c->route.td_bar == 0) {
         ISLECHK(isle_max_lds(c, (const void*)td_persist_k<0>, (int)TD_P_LDS));
         hipLaunchKernelGGL(td_persist_k<0>, dim3(pG), dim3(TD_P_T), p_lds, c->stream, A, n, d, e, tau, pv, bar, tickets + 1);
-      } else if (bk && !strcmp(bk, "hier")) {
+      } else if (c->route.td_bar == 1) {
         ISLECHK(isle_max_lds(c, (const void*)td_persist_k<1>, (int)TD_P_LDS));
         hipLaunchKernelGGL(td_persist_k<1>, dim3(pG), dim3(TD_P_T), p_lds, c->stream, A, n, d, e, tau, pv, bar, tickets + 1);
       } else {
@@ -973,24 +965,15 @@ int k_tridiag_eig(isle_ctx* c, const float* S_host, int n, float* evals_host, fl
   // n = 2010 to divide by the number of ranks; they do not: both kernels are chains of n dependent steps (a reflector / a row per step) whose
   // length does not depend on how many vectors a rank holds — 250 workgroups or 32, td_back_k takes its 4.2 ms — so the split buys an idle GPU and
   // costs an 8 MB all-gather per EVD that has never run over RCCL.  Default: every rank computes every vector.
-  int v0 = 0, v1 = nvec, kc = 0;
-  if (c->multi() && c->knob_on(KN_EVD_SPLIT) && !c->knob_zero(KN_EVD_SPLIT)) {
-    kc = ((nvec + c->world - 1) / c->world + 7) & ~7;
-    if ((size_t)kc * c->world <= (size_t)n) {  // the gathered block fits the caller's n x n array
-      v0 = std::min(nvec, c->rank * kc);
-      v1 = std::min(nvec, v0 + kc);
-    } else {
-      kc = 0;
-    }
-  }
-  const int nv = v1 - v0;
+  const TdSplit split = route_td_split(c->multi(), c->world, c->rank, nvec, n, c->route);
+  const int v0 = split.v0, v1 = split.v1, kc = split.kc, nv = v1 - v0;
   if (nv > 0) {
     hipLaunchKernelGGL(td_vectors_k, dim3((nv + 63) / 64), dim3(64), 0, c->stream, d, e, n, lam, nvec, Dp, Lf, Z, v0, v1);
     // back-transformation by blocks of four reflectors (compact WY): the T factors first (the buffer of the launch chain's partial sums is free by now);
     // ISLE_TD_BACK=seq: reflector by reflector (td_back_k)
-    const char* e_back = c->knob(KN_TD_BACK);
-    if (e_back && e_back[0] == 's') {
-      if ((nvec + 7) / 8 > c->num_cus / 2 && !kc)
+    const TdBack back = route_td_back(nvec, c->num_cus, kc, c->route);
+    if (back != TD_BACK_WY) {
+      if (back == TD_BACK_SEQ8)
         hipLaunchKernelGGL(td_back_k<8>, dim3((nv + 7) / 8), dim3(TD_B_T), (size_t)n * 8 * sizeof(double), c->stream, A, tau, n, Z, nvec, vecs_dev, v0, v1);
       else  // few eigenvectors: four per workgroup, twice the workgroups, half the rows per thread (two per workgroup measured no better)
         hipLaunchKernelGGL(td_back_k<4>, dim3((nv + 3) / 4), dim3(TD_B_T), (size_t)n * 4 * sizeof(double), c->stream, A, tau, n, Z, nvec, vecs_dev, v0, v1);

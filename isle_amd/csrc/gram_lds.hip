@@ -1283,7 +1283,7 @@ struct GlStream {
                                 c->gl_sbase.p, c->gl_scnt.p);
     HIPCHK(c, hipGetLastError());
     static_assert(GL_RB <= 4096, "the packed entries of the bucketed fill hold the document in 12 bits");
-    if (s.n_out <= (1u << 20) && c->nnz && !c->knob_zero(KN_GL_FILL_BUCKETS)) return fill2_bucketed(c, s);  // (word positions in 20 bits)
+    if (route_gl_fill_bucketed(s.n_out, c->nnz, c->route)) return fill2_bucketed(c, s);  // (word positions in 20 bits)
     return fill2_direct(c, s);
   }
 
@@ -1302,7 +1302,7 @@ struct GlStream {
   // bank-aware placement of the short slices (ISLE_GL_PLACE=0: none), and every id in the form gl_apply_k reads (8 * id)
   static int place_and_scale(isle_ctx* c, GlSide& s) {
     const size_t nsl = gl_nwb(s) * (size_t)s.G;
-    const bool place = !c->knob_zero(KN_GL_PLACE);
+    const bool place = c->route.gl_place;
     // at most 2^22 workgroups of 512 threads per launch (a launch of 2^32 threads or more does not run, and says nothing)
     for (size_t sid0 = 0; sid0 < nsl; sid0 += (size_t)8 << 22) {
       const dim3 grid((unsigned)cdiv((long)std::min<size_t>(nsl - sid0, (size_t)8 << 22), 8));
@@ -1374,9 +1374,8 @@ int launch_apply_any(isle_ctx* c, int LPE, bool half, const GlSide& s, const flo
 int k_gl_detect(isle_ctx* c) {
   if (c->gl_mode >= 0) return 0;  // decided for this B (reset by every upload / thresholding)
   c->gl_mode = 0;
-  const char* e = c->knob(KN_GRAM_LDS);
   // every rank takes part in the agreement below, whatever its own shard looks like
-  bool eligible = !(e && atoi(e) == 0) && c->nnz > 0 && c->D > 0 && c->V > 0 && c->D < 0xfffffff0ull && c->V < 0xfffffff0ull;
+  const bool eligible = route_gl_eligible(c->nnz, c->D, c->V, c->route);
   HIPCHK(c, c->gl_flag.reserve(4));
   HIPCHK(c, hipMemsetAsync(c->gl_flag.p, 0, sizeof(int), c->stream));
   if (eligible) {
@@ -1408,11 +1407,7 @@ int k_gl_detect(isle_ctx* c) {
 
 // every switch the plan depends on, read once
 static GlPlanOpts gl_options(const isle_ctx* c) {
-  GlPlanOpts o;
-  if (c->knob(KN_GL_G1)) o.g1 = gl_forced_g(atoi(c->knob(KN_GL_G1)));
-  if (c->knob(KN_GL_G2)) o.g2 = gl_forced_g(atoi(c->knob(KN_GL_G2)));
-  o.rounds = !c->knob_zero(KN_GL_ROUNDS);
-  o.columns = !c->knob_zero(KN_GL_COLUMNS);
+  GlPlanOpts o = route_gl_options(c->route);
   if (c->knob(KN_GL_TEST_CUS)) o.test_cus = (uint32_t)std::max(1, atoi(c->knob(KN_GL_TEST_CUS)));  // test hook
   return o;
 }
@@ -1690,17 +1685,8 @@ int k_centers_counts(isle_ctx* c, const uint32_t* assign, int k, int ld, float* 
   return 0;
 }
 
-// Columns per pass of the k-wide / thin products through the pass-1 stream: 10, the widest panel a planar band holds (40-byte rows); 8 at
-// 8 output items per lane (the 10-column form spills 8 registers there).  A pass costs what its slots cost, hardly more for more columns
-// (2.20 ms per 8-column pass against 2.29 per 10-column one at config 3 on one GPU): k = 1000 is walked in 100 passes.  Steps of 10 columns
-// leave the panels 8-byte aligned inside the output rows: they are stored as float2.  (Up to round 3's 48-byte row-major bands 12-column
-// passes were used up to 6 items per lane: 33.0 ms per C3-shard projection against 38.9 in 8-column passes.)  ISLE_GL_PANEL = 8 | 10.
-static int gl_panel_width(const isle_ctx* c) {
-  const char* e = c->knob(KN_GL_PANEL);
-  if (e && atoi(e) == 10) return 10;
-  if (e && atoi(e) == 8) return 8;
-  return c->gl1.G <= 7 ? 10 : 8;
-}
+// columns per pass of the k-wide / thin products through the pass-1 stream
+static int gl_panel_width(const isle_ctx* c) { return route_gl_panel_width(c->gl1.G, c->route); }
 
 // Columns a panel pass stores: its own, and behind the last panel the padding columns of the row (ld = 4 ceil(k / 4); the consumers read
 // whole float4 of a row and rely on zeros there — the packed panel is zero beyond its columns, so the accumulators are).
@@ -1876,13 +1862,10 @@ int k_gl_wide(isle_ctx* c, const float* Mrm, int k, int ld, float* Out, float* n
   const uint32_t V = (uint32_t)c->V;
   HIPCHK(c, c->gl_Xs.reserve(gl_packed_floats(V, 3, true)));
   const int PW = gl_panel_width(c);
-  // grouped form: asked for together with the norms (the projection), a wide operand on a large shard, 10-column panels (groups of 16 then
-  // start on multiples of 160 columns), and while the slabs fit (7.7 GB at 10 M documents)
   const uint64_t D = c->D;
   const int ngroups = (k + PW * GL_WG_PANELS - 1) / (PW * GL_WG_PANELS);
   const size_t slab = (size_t)D * 12;
-  if (norms && PW == 10 && k >= 160 && D >= 16384 && !c->knob_zero(KN_GL_WIDE_GROUPED) &&
-      isle_scratch_ok(c, 0, (double)(slab * GL_WG_PANELS + (size_t)ngroups * D) * sizeof(float))) {
+  if (isle_route_mem(c, [&](uint64_t total_mem, bool* ask) { return route_gl_wide_grouped(norms != nullptr, PW, k, D, GL_WG_PANELS, c->route, total_mem, ask); })) {
     HIPCHK(c, c->gl_pscratch.reserve(slab * GL_WG_PANELS + (size_t)ngroups * D));
     float* normpart = c->gl_pscratch.p + slab * GL_WG_PANELS;
     int gi = 0;

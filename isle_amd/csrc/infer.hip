@@ -581,10 +581,7 @@ int k_infer_docs(isle_ctx* c, const float* M, int k, uint64_t D, const float* co
   // CU at 160 KB) runs 3.1 M docs/s, re-reading the rows from L2 / Infinity Cache in every iteration with ~10 workgroups per
   // CU 5.3 M docs/s (6.9 TB/s of row gathers) — occupancy beats locality, so no rows are staged unless
   // ISLE_INFER_CAP_ROWS asks for it.
-  {
-    const char* e = c->knob(KN_INFER_CAP_ROWS);
-    cap_rows = std::min<uint32_t>(cap_rows, e ? (uint32_t)atoi(e) : 0u);
-  }
+  cap_rows = std::min<uint32_t>(cap_rows, c->route.infer_cap_rows);
   const size_t lds = (size_t)cap_rows * ld * sizeof(float) + fixed + (size_t)cap_rows * sizeof(float);
 #define INF(KERNEL)                                                                                                                  \
   do {                                                                                                                               \

@@ -311,13 +311,8 @@ int k_kmpp_update(isle_ctx* c, const float* P, const float* pn, uint64_t D, int 
   // measured rates: a pass of the pass-1 stream costs ~2.8 ps per nonzero (= 15.4 bytes of streaming at 5.5 TB/s), the materialised
   // projection streams at 5.5 TB/s for <= 16 new seeds (kmpp_min_pt_k) and 2.3x slower through the matrix-core tile beyond.
   {
-    const char* e = c->knob(KN_KMPP_SPARSE);
-    const int PW = k_gl_panel_width(c);
-    const int passes = (nc + PW - 1) / PW;  // columns per pass of the pass-1 stream (gram_lds.hip gl_panel_width)
     const bool can = c->gl_mode == 1 && c->band_ready && c->U_k == k;
-    bool sparse = can && 15.4 * (double)c->nnz * passes < 4.0 * (double)ldk * (double)D * (nc <= 16 ? 1.0 : 2.3);
-    if (e) sparse = atoi(e) != 0 && can;
-    if (sparse) {
+    if (route_kmpp_sparse(can, c->nnz, D, ldk, nc, k_gl_panel_width(c), c->route)) {
       // (Round 3 also built the pruned round of accelerated k-means++ seeding — only the documents a new seed can reach by the
       // triangle inequality, from the materialised projection.  On this corpus the documents of topics without a seed stay within
       // reach: 98 % at 20 seeds, 50 % at 570, 28 % at 906 of 1000, and a visited document costs a 4 kB row plus 2 k flops per new seed
@@ -1042,9 +1037,7 @@ int k_kmpp_to_tiles(isle_ctx* c, uint64_t D, int k, const float* pn, const float
 }
 
 bool k_proj_full_by_gemm(isle_ctx* c, uint64_t D, int k) {
-  const char* pf = c->knob(KN_PROJ_FULL);
-  return (c->Pt_ready || c->Pt2_ready) && D > 0 && k >= 64 && (k_gemm_assign_fused_ok(c, D, k, k) || isle_scratch_ok(c, c->dotsT.cap, (double)D * k * sizeof(float))) &&
-         ((2.0 * (double)D * k * k >= 2e10 && !(pf && !strcmp(pf, "fused"))) || (pf && !strcmp(pf, "gemm")));
+  return isle_route_mem(c, [&](uint64_t total_mem, bool* ask) { return route_proj_full_by_gemm(c->Pt_ready, c->Pt2_ready, D, k, c->route, total_mem, ask); });
 }
 int k_proj_assign_tiles(isle_ctx* c, const float* P, const float* pn, uint64_t D, int k, int ldk, const float* C, const float* cn, uint32_t* assign,
                         float* ub, float* tlb, int TL, const uint32_t* active, uint32_t n, const uint32_t* need, float* Pa, float* pna) {
@@ -1055,7 +1048,7 @@ int k_proj_assign_tiles(isle_ctx* c, const float* P, const float* pn, uint64_t D
     // 69 of the fused kernel's full pass, k_gemm_nn) on the coordinate-major copy of P, followed by the epilogue above over the D x k
     // dot products (5 GB at a C3 shard: 18 + 2 ms instead of 36).  ISLE_PROJ_FULL=gemm|fused forces a route.
     if (k_proj_full_by_gemm(c, D, k)) {
-      if (k_gemm_assign_fused_ok(c, D, k, k)) {  // distances, tile bounds and candidates formed inside the product: no D x k matrix in memory
+      if (route_gemm_assign_fused_ok(D, k, k, c->route)) {  // distances, tile bounds and candidates formed inside the product: no D x k matrix in memory
         HIPCHK(c, c->cmax_buf.reserve(4));
         ISLECHK(k_max_f32(c, cn, k, c->cmax_buf.p));
         const bool a2 = c->Pt2_ready && P == c->P.p;
@@ -1076,16 +1069,14 @@ int k_proj_assign_tiles(isle_ctx* c, const float* P, const float* pn, uint64_t D
       // All centres for the active documents through the assignment product on their gathered rows (two bf16 terms first): 5.9 us per
       // 1000 documents against 6 - 11 for the tiles they name through the register kernel — and EVERY tile bound of these documents is
       // refreshed, so fewer of them come back in the next iteration.
-      const char* pa = c->knob(KN_PROJ_ACTIVE);
-      const bool by_gemm = pa ? !strcmp(pa, "gemm") : true;
-      if (by_gemm && k_gemm_assign_fused_ok(c, n, k, k)) {
+      if (route_proj_active_by_gemm(n, k, c->route)) {
         ISLECHK(k_compact_rows(c, P, pn, ldk, active, n, Pa, pna));
         HIPCHK(c, c->cmax_buf.reserve(4));
         ISLECHK(k_max_f32(c, cn, k, c->cmax_buf.p));
         return k_gemm_assign_tiles(c, Pa, P, ldk, n, k, C, ldk, k, TL, cn, pn, c->cmax_buf.p, assign, ub, tlb, ISLE_T_LLOYD_PROJ, active);
       }
     }
-    if (need && n > 256 && !c->knob_zero(KN_PT_SORT)) {  // documents that ask for the same tiles next to each other (pt_need_keys_k)
+    if (route_pt_sort(need != nullptr, n, c->route)) {  // documents that ask for the same tiles next to each other (pt_need_keys_k)
       HIPCHK(c, c->gl_key_a.reserve(n));
       HIPCHK(c, c->gl_key_b.reserve(n));
       HIPCHK(c, c->gl_val_a.reserve(n));

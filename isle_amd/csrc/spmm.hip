@@ -530,28 +530,22 @@ static int launch_wide(isle_ctx* c, const float* Mrm, int k, int ldk, float* P, 
   const uint32_t D = (uint32_t)c->D;
   if (D == 0) return 0;
   const int nq = ldk / 4;
-  const int nit = cdiv(nq, 64);
   dim3 g(8 * cdiv(cdiv(D, 4), 8)), b(256);  // multiple of 8 so that the XCD slot map is a bijection
 #define LW(N)                                                                                                              \
   hipLaunchKernelGGL((spmm_wide_k<N, MODE>), g, b, 0, c->stream, c->vals.p, c->rows.p, c->offs.p, (const float4*)Mrm, nq, k, D, \
                      (float4*)P, norms, cn, dn, assign, perm, nslots, ub, lb, G)
-  if (nit <= 1) LW(1);
-  else if (nit <= 2) LW(2);
-  else if (nit <= 4) LW(4);
-  else if (nit <= 8) LW(8);
-  else return isle_fail(c, ISLE_E_ARG, "k = %d too large (max 2048)", k);
+  switch (route_wide_nit(ldk)) {
+    case 1: LW(1); break;
+    case 2: LW(2); break;
+    case 4: LW(4); break;
+    case 8: LW(8); break;
+    default: return isle_fail(c, ISLE_E_ARG, "k = %d too large (max 2048)", k);
+  }
 #undef LW
   HIPCHK(c, hipGetLastError());
   return 0;
 }
-// The k-wide products as ceil(k / 12) passes of the LDS-banded pass-1 stream pay one staging of every word band per pass: a
-// win while the vocabulary spans few bands (C2: 15 bands, 5.8 vs 7.0 ms), a loss at 30 bands (C3 shard: 68 vs 52 ms).
-// ISLE_WIDE_GATHER=1 / ISLE_WIDE_LDS=1 force either form.
-static bool wide_through_lds(const isle_ctx* c) {
-  if (c->knob_on(KN_WIDE_GATHER)) return false;
-  if (c->knob_on(KN_WIDE_LDS)) return true;
-  return c->V <= 32 * 3412;  // 8-column panels (gram_lds.hip gl_panel_width): measured 46.7 against 51.7 ms at 30 word bands (V = 100k, k = 1000)
-}
+static bool wide_through_lds(const isle_ctx* c) { return route_wide_through_lds(c->V, c->route); }
 
 // Assignment from stored dot products (dots = B^T C computed by the LDS-banded wide SpMM, gram_lds.hip): one wave per document.
 template <int NIT>
@@ -652,14 +646,16 @@ int k_dots_assign_cm(isle_ctx* c, const float* dotsT, int k, int G, const float*
 int k_dots_assign(isle_ctx* c, int k, int ldk, const float* cn, const float* dn, uint32_t* assign, float* ub, float* lb, int G) {
   const uint32_t D = (uint32_t)c->D;
   if (D == 0) return 0;
-  const int nq = ldk / 4, nit = cdiv(nq, 64);
+  const int nq = ldk / 4;
   const dim3 g(cdiv(D, 4)), b(256);
 #define DA(N) hipLaunchKernelGGL((dots_assign_k<N>), g, b, 0, c->stream, (const float4*)c->P.p, nq, k, D, cn, dn, assign, ub, lb, G)
-  if (nit <= 1) DA(1);
-  else if (nit <= 2) DA(2);
-  else if (nit <= 4) DA(4);
-  else if (nit <= 8) DA(8);
-  else return isle_fail(c, ISLE_E_ARG, "assignment: k = %d too large (max 2048)", k);
+  switch (route_wide_nit(ldk)) {
+    case 1: DA(1); break;
+    case 2: DA(2); break;
+    case 4: DA(4); break;
+    case 8: DA(8); break;
+    default: return isle_fail(c, ISLE_E_ARG, "assignment: k = %d too large (max 2048)", k);
+  }
 #undef DA
   HIPCHK(c, hipGetLastError());
   return 0;
@@ -743,7 +739,7 @@ __global__ __launch_bounds__(256) void centers_from_rows_k(const float* __restri
 int k_centers_from_rows(isle_ctx* c, const uint32_t* assign, int k, int ldk, float* Crm, bool first_of_run) {
   ISLECHK(k_gl_detect(c));
   if (c->gl_mode == 1)  // row-constant B: integer counting, no transposed copy
-    return k_centers_counts(c, assign, k, ldk, Crm, first_of_run || c->knob_on(KN_CENTERS_FRESH));
+    return k_centers_counts(c, assign, k, ldk, Crm, route_counts_fresh(first_of_run, c->route));
   ISLECHK(k_band_build(c));
   TimeScope ts(c, ISLE_T_SPARSE_UPDATE);
   const uint32_t V = (uint32_t)c->V;

@@ -22,10 +22,11 @@ The builders make the dyadic and non-dyadic inputs of the GPU sweep (test_gpu_gr
 (test_gram_certificate_cpu.py); GRAM_SWEEP is every switch value the GPU test runs, GRAM_EXCLUDED the switches it leaves out and why.
 """
 import os
-import re
 
 import numpy as np
 import scipy.sparse as sp
+
+import route_reads
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U_F32 = 2.0 ** -24
@@ -61,27 +62,12 @@ GRAM_EXCLUDED = {
 GRAM_SOURCES = ("gram_lds.hip", "spmm.hip")
 
 
-def knob_names_from_enum():
-    """{KN_...: index} from common.h's IsleKnob enum (the order of the switch table)."""
-    text = open(os.path.join(_ROOT, "isle_amd", "csrc", "common.h")).read()
-    body = re.search(r"enum IsleKnob \{(.*?)\};", text, flags=re.S).group(1)
-    ids = [t.strip() for t in body.replace("\n", " ").split(",") if t.strip()]
-    assert ids[-1] == "KN_COUNT"
-    return {k: i for i, k in enumerate(ids[:-1])}
-
-
 def gram_switches_read(table_names):
-    """Names of the switches the Gram apply reads: every KN_ read in GRAM_SOURCES, plus every knob api.cpp stores in band_rows."""
-    idx = knob_names_from_enum()
-    assert len(idx) == len(table_names), "common.h IsleKnob and isle_hip_switch_info disagree"
+    """Names of the switches the Gram apply reads: every switch GRAM_SOURCES read (route_reads.py), plus every one api.cpp stores in band_rows."""
     src = os.path.join(_ROOT, "isle_amd", "csrc")
-    used = set()
-    for f in GRAM_SOURCES:
-        used |= set(re.findall(r"\bknob(?:_on|_zero)?\((KN_[A-Z0-9_]+)\)", open(os.path.join(src, f)).read()))
-    for line in open(os.path.join(src, "api.cpp")):
-        if "band_rows" in line:
-            used |= set(re.findall(r"\bknob\((KN_[A-Z0-9_]+)\)", line))
-    return {table_names[idx[k]] for k in used}
+    text = "".join(open(os.path.join(src, f)).read() for f in GRAM_SOURCES)
+    text += "".join(line for line in open(os.path.join(src, "api.cpp")) if "band_rows" in line)
+    return route_reads.switches_read(text, table_names)
 
 
 def uncovered_gram_switches(table_names, sweep=GRAM_SWEEP, excluded=GRAM_EXCLUDED):

@@ -56,9 +56,10 @@ surely-finite guess exists among the ten and every earlier guess is surely overf
 exponent error the size condition allows (88.8 * 2^-13 ~ 0.011); the margins decide eligibility only, they are not tolerances.
 """
 import os
-import re
 
 import numpy as np
+
+import route_reads
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U_F32 = 2.0 ** -24
@@ -103,15 +104,10 @@ def lds_cap_rows(k):
 
 
 def infer_switches_read(table_names):
-    """Names of the switches infer.hip reads, through common.h's IsleKnob enum (the order of the switch table)."""
-    text = open(os.path.join(_ROOT, "isle_amd", "csrc", "common.h")).read()
-    body = re.search(r"enum IsleKnob \{(.*?)\};", text, flags=re.S).group(1)
-    ids = [t.strip() for t in body.replace("\n", " ").split(",") if t.strip()]
-    assert ids[-1] == "KN_COUNT" and len(ids) - 1 == len(table_names), "common.h IsleKnob and isle_hip_switch_info disagree"
+    """Names of the switches infer.hip reads (route_reads.py)."""
     src = open(os.path.join(_ROOT, "isle_amd", "csrc", "infer.hip")).read()
     assert "getenv" not in src
-    used = set(re.findall(r"\bknob(?:_on|_zero)?\((KN_[A-Z0-9_]+)\)", src))
-    return {table_names[ids.index(k)] for k in used}
+    return route_reads.switches_read(src, table_names)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -53,14 +53,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # The constants the cases were built from: name -> (file, line, pattern with one group per value, values).
 # test_ks_certificate_cpu.py reads the cited line and fails when the text or the line moved: update the cases, then this table.
 # ---------------------------------------------------------------------------------------------------------------------------------
-DENSE, KS_HOST = "isle_amd/csrc/dense.hip", "isle_amd/csrc/ks_host.h"
+DENSE, KS_HOST, ROUTE_HOST = "isle_amd/csrc/dense.hip", "isle_amd/csrc/ks_host.h", "isle_amd/csrc/route_host.h"
 SOURCE = {
     "VTF_CG": (DENSE, 25, r"constexpr int VTF_CG = (\d+);", (32,)),
     "vtf_rc": (DENSE, 27, r"constexpr int vtf_rc\(int BT\) \{ return BT <= (\d+) \? (\d+) : \(BT <= (\d+) \? (\d+) : (\d+)\); \}", (12, 1024, 16, 512, 256)),
     "VM_RC": (DENSE, 78, r"constexpr int VM_RC = (\d+);", (1024,)),
     "bt_of": (DENSE, 181, r"static int bt_of\(int b\) \{ return b <= (\d+) \? 4 : b <= (\d+) \? 8 : b <= (\d+) \? 12 : b <= (\d+) \? 16 : 32; \}", (4, 8, 12, 16)),
     "vtf_mfma": (DENSE, 211, r"if \(b <= (\d+) && m >= (\d+)\) \{", (16, 64)),
-    "update_mfma": (DENSE, 366, r"if \(b <= (\d+) && m >= (\d+) && \(ld & (\d+)\) == 0 && ", (16, 32, 3)),
+    "update_mfma": (ROUTE_HOST, 148, r"return b <= (\d+) && m >= (\d+) && \(ld & (\d+)\) == 0 && ", (16, 32, 3)),  # route_update_mfma
     "PQ_ROWS": (DENSE, 401, r"constexpr int PQ_ROWS = (\d+);", (256,)),
     "PQ_W": (DENSE, 402, r"constexpr int PQ_W = (\d+);", (32,)),
     "PQ_SUB": (DENSE, 403, r"constexpr int PQ_SUB = (\d+);", (2,)),
@@ -101,7 +101,7 @@ def route(n, b, m, num_cus=256, ld=None):
     """Which kernels one orthogonalisation pass of a b-wide panel against m basis vectors of n rows takes.  ld: the leading dimension of
     basis and panel — n in the dense entry and in the replicated step; the row count of the whole block when n is a rank's row slice
     (Ks::ortho: the slice starts at a multiple of four rows, ks_row_slice, so it is 16-byte aligned exactly when the block is).  Basis
-    and panel are separate allocations, so the 16-byte test of dense.hip:366 rests on ld alone.
+    and panel are separate allocations, so the 16-byte test of dense.hip:366 (route_update_mfma) rests on ld alone.
     -> dict(vtf: "mfma" | "valu" | "none", vtf_rows: rows per chunk, vtf_aligned: vtf_mfma_k's float4 path (dense.hip:97),
     update: "mfma" | "valu" | "none"); "none": a slice of zero rows launches nothing (dense.hip:207, :363)."""
     ld = n if ld is None else ld
@@ -345,10 +345,10 @@ def _case(name, edge, n, nev, blk, ncv, maxit):
 
 def _cases():
     out = []
-    # blk: bt_of (dense.hip:181) 4 | 12 | 16 | 32, vtf_rc (:27) 1024 | 512 | 256, update_mfma b <= 16 (:366), PQ_W (:402)
+    # blk: bt_of (dense.hip:181) 4 | 12 | 16 | 32, vtf_rc (:27) 1024 | 512 | 256, update_mfma b <= 16 (route_host.h route_update_mfma), PQ_W (:402)
     for blk, nev, ncv, maxit in ((1, 6, 24, 2), (12, 24, 60, 1), (13, 24, 60, 2), (16, 24, 64, 1), (17, 24, 68, 2), (32, 40, 104, 2)):
         out.append(_case("blk-%d" % blk, "blk", 400, nev, blk, ncv, maxit))
-    # n % 4: the (ld & 3) == 0 test of dense.hip:366 (and the aligned test of vtf_mfma_k, :97), b = 12 <= 16 and m up to 72 >= 64
+    # n % 4: the (ld & 3) == 0 test of route_update_mfma (and the aligned test of vtf_mfma_k, :97), b = 12 <= 16 and m up to 72 >= 64
     for n in (300, 301, 302, 303):
         out.append(_case("mod4-%d" % (n % 4), "mod4", n, 24, 12, 80, 2 if n % 2 else 1))
     # n at row-chunk edges: vtf_rc (:27) through blk = 20 (256 rows), 16 (512), 12 (1024); VM_RC (:78), PQ_ROWS (:401), and the

@@ -53,7 +53,8 @@ def _trim(B, D):
 
 def corpus(name):
     """small: V = 2003 (not a multiple of 4), D = 6001; big: V = 3001, D = 65601 (k = 257 on the bf16 route), its first 33001
-    documents for k = 1000.  D is never a multiple of 64."""
+    documents for k = 1000.  D is never a multiple of 64.  tiles511 / tiles512: V = 2003, D = 130 816 / 130 817 — at k <= 256 the
+    assignment products have 511 / 512 tiles of 256 x 256, the edge of their bf16 form (route_host.h route_gemm_assign_fused_ok)."""
     if name not in _CORPORA:
         from tools.synth import make_B
         if name == "small":
@@ -63,6 +64,10 @@ def corpus(name):
             B["vals"] = B["vals"] * (1.0 + 0.01 * np.random.default_rng(1).random(B["vals"].shape[0])).astype(np.float32)
         elif name == "big":
             B = _trim(make_B(3001, 66000, 50, 5), 65601)
+        elif name == "tiles512":
+            B = _trim(make_B(2003, 131000, 20, 7), 130817)
+        elif name == "tiles511":
+            B = _trim(corpus("tiles512"), 130816)
         else:
             B = _trim(corpus("big"), 33001)
         B["X"] = csc_points(B)
@@ -209,7 +214,9 @@ def certify_kmeanspp(c, g):
     kc.certify_kmeanspp(c, g, c.hp.get_min_dist())
 
 
-KS = [1, 7, 8, 9, 63, 64, 65, 224, 225, 255, 256, 257, 1000]
+# 224 / 225: Hamerly's single bound / tile bounds in span(U) (route_host.h route_proj_plan); 248 / 249: 31 / 32 Yinyang groups, by document / by
+# group on B (route_sparse_plan)
+KS = [1, 7, 8, 9, 63, 64, 65, 224, 225, 248, 249, 255, 256, 257, 1000]
 
 
 @pytest.mark.parametrize("k", KS)
@@ -246,13 +253,13 @@ def test_both_loops_iteration_by_iteration(hp, k, monkeypatch, capfd):
     assert hp.operator_form() == 1
 
 
-# Forms of Lloyd in span(U).  Tile bounds exist at k > 224 only (api_kmeans.cpp, proj_plan: tiles = hamerly && k > 224 && ...), and ISLE_PROJ_BOUNDS,
+# Forms of Lloyd in span(U).  Tile bounds exist at k > 224 only (route_host.h, route_proj_plan: tiles = hamerly && k > 224 && ...), and ISLE_PROJ_BOUNDS,
 # ISLE_PROJ_FULL and ISLE_PROJ_ACTIVE are read on that path alone (k_proj_full_by_gemm, k_proj_assign_tiles): at k = 9 and 65 they would
 # rerun the default form, so they run at k = 257 and 1000.
 PROJ_TILE_FORMS = [{"ISLE_PROJ_BOUNDS": "hamerly"}, {"ISLE_PROJ_FULL": "gemm"}, {"ISLE_PROJ_FULL": "fused"}, {"ISLE_PROJ_ACTIVE": "tiles"}]
 PROJ_FORMS = PROJ_TILE_FORMS + [{"ISLE_PROJ_SUMS": "fresh"}, {"ISLE_NO_HAMERLY": "1"}]
 # Forms of Lloyd on B.  Regrouping and the fused filter-and-tighten launch belong to the by-group Yinyang form, which the loop takes at
-# k >= 256 (api_kmeans.cpp, sparse_plan: yy_mode = ... G >= 32 ? 2 : 0; regroup = yinyang && yy_mode == 2 && ...): they run at k = 257 and 1000.
+# k >= 249 (route_host.h, route_sparse_plan: yy_mode = ... G >= 32 ? 2 : 0; regroup = yinyang && yy_mode == 2 && ...): they run at k = 257 and 1000.
 SPARSE_GROUP_FORMS = [{"ISLE_YY_FUSED": "0"}, {"ISLE_YY_REGROUP": "0"}]
 SPARSE_FORMS = [{"ISLE_KMEANS_BOUNDS": "hamerly"}, {"ISLE_KMEANS_BOUNDS": "none"}, {"ISLE_YY_MODE": "doc"}, {"ISLE_YY_MODE": "docg"},
                 {"ISLE_YY_MODE": "group"}, {"ISLE_YY_MOVERS": "0"}, {"ISLE_CENTERS_FRESH": "1"}, {"ISLE_FIRST_ASSIGN": "sparse"},
@@ -320,10 +327,10 @@ def test_every_form(hp, k, form, monkeypatch, capfd):
     assert hp.operator_form() == (0 if gather else 1)
 
 
-@pytest.mark.parametrize("k", [257, 1000])
+@pytest.mark.parametrize("k", [224, 225, 257, 1000])
 def test_first_assignment_taken_from_kmeanspp_rounds(hp, k, monkeypatch, capfd):
     """At k > 224 Lloyd in span(U) may start from the nearest seeds and tile minima the k-means++ rounds kept instead of computing its
-    first assignment (ISLE_KMPP_TRACK): certified like the computed one."""
+    first assignment (ISLE_KMPP_TRACK): certified like the computed one.  k = 224: the last k whose rounds keep nothing, computed."""
     c = Case(hp, corpus_for(k), k, seed=2)
     monkeypatch.setenv("ISLE_KMPP_SPARSE", "1")
     monkeypatch.setenv("ISLE_DEBUG_HAMERLY", "1")
@@ -338,7 +345,28 @@ def test_first_assignment_taken_from_kmeanspp_rounds(hp, k, monkeypatch, capfd):
     capfd.readouterr()
     projected_trajectory(c, C0, 3, before=before)
     err = capfd.readouterr().err
-    assert err.count("first assignment taken from the k-means++ rounds") == 3, err[-2000:]
+    assert err.count("first assignment taken from the k-means++ rounds") == (3 if k > 224 else 0), err[-2000:]
+    assert err.count("first assignment computed") == (0 if k > 224 else 3), err[-2000:]
+
+
+@pytest.mark.parametrize("D", [130816, 130817])
+def test_assignment_product_at_512_tiles(hp, D, monkeypatch, capfd):
+    """k = 64 on 511 / 512 tiles of 256 x 256: below, the first assignment of Lloyd on B through the projection is the f32 product and the
+    pass over its D x k scratch; from 512 tiles on the two-term bf16 product with the epilogue inside, which reads the split copy the
+    projection leaves.  k-means++, Lloyd in span(U) and Lloyd on B from the lifted centres on either side, and the route as the debug report
+    shows it."""
+    k = 64
+    c = Case(hp, corpus("tiles512" if D == 130817 else "tiles511"), k, seed=3)
+    assert c.B["D"] == D
+    monkeypatch.setenv("ISLE_DEBUG_HAMERLY", "1")
+    g = hp.kmeans_init_on_projected_space(k, inject_seeds=c.seeds)
+    certify_kmeanspp(c, g)
+    runs = projected_trajectory(c, g["C_lowd"], 2)
+    capfd.readouterr()
+    sparse_trajectory(c, 2, lift_from=runs[-1]["C_lowd"])
+    err = capfd.readouterr().err
+    assert bool(re.search(r"the two-term pass left \d+ of %d rows open" % D, err)) == (D == 130817), err[-2000:]
+    assert hp.operator_form() == 1
 
 
 def test_projected_loop_on_the_eigensolvers_U(hp):
