@@ -290,9 +290,26 @@ int isle_hip_lloyds_sparse(isle_ctx* ctx, int k, const float* centers_in, float*
                            uint32_t* assign, int max_reps, int* iters_run);
 
 /* ---- downstream stage: catchwords, topic model, edge topics ---
- * These operate on the count matrix A left in device memory by isle_hip_upload_counts_u32 (single
- * rank only for now) and on the partition of B's columns, mapped back to A's documents through
- * original_cols exactly as src/trainer.cpp:572-575 does.
+ * These operate on the count matrix A left in device memory by isle_hip_upload_counts_u32 and on the
+ * partition of B's columns, mapped back to A's documents through original_cols exactly as
+ * src/trainer.cpp:572-575 does.
+ *
+ * Several ranks (world > 1): rank r holds the documents [doc_offset, doc_offset + docs) of A, the columns of
+ * B that thresholding kept of them and the partition of those columns.  isle_hip_catchwords,
+ * isle_hip_topic_model and isle_hip_select_edge_pairs are then COLLECTIVE: every rank calls them, in the
+ * same order, with the same num_topics, r, rho, rank_threshold, max_edge_topics and min_docs; a rank
+ * without documents, or with documents but no column of B, calls them too.  What they state bit for bit
+ * on one rank they state bit for bit, and equal to the single-rank run on the concatenated corpus.
+ * REPLICATED (the whole corpus's, bit-identical on every rank): thresholds, catch_topic, num_catchwords,
+ * model, model_threshold, the selected edge pairs with their counts.  The SHARD'S (this rank's own
+ * documents, numbered from 0): top1 / top2, *doc_topic_sums and what isle_hip_get_doc_topic_sums returns.
+ * The model is summed over the ranks in fp32 (its entries differ from a single-rank run's in the last
+ * bits, as two single-rank runs do).  A rank that returns ISLE_E_ARG ahead of the first collective of a
+ * call leaves the others waiting: the conditions below are the caller's to hold on every rank alike.
+ * ISLE_E_COMM: the ranks disagree on a replicated count.  The readers of a model (isle_hip_edge_topics,
+ * isle_hip_model_top_words, isle_hip_edge_top_words, isle_hip_model_text, isle_hip_edge_topics_text,
+ * isle_hip_topic_diversity) involve no collective: each rank runs them for itself on the replicated catch
+ * model or on a host model.  Everything else downstream stays "single-rank only" (ISLE_E_ARG).
  *
  * isle_hip_catchwords = SparseMatrix::rth_highest_element for every topic (src/sparseMatrix.cpp:491-524,
  * called at src/trainer.cpp:586-590) + SparseMatrix::find_catchwords (:573-595).
@@ -302,7 +319,10 @@ int isle_hip_lloyds_sparse(isle_ctx* ctx, int k, const float* centers_in, float*
  *   thresholds (nullable): vocab x num_topics column-major, the reference's catchword_thresholds.
  *   catch_topic (nullable): vocab entries, the topic a word is a catchword of or -1 (the rule admits
  *           at most one topic per word); catchwords[t] of the reference = { w : catch_topic[w] == t }
- *           ascending. */
+ *           ascending.
+ * world > 1: collective; assign holds this rank's columns of B; all three outputs are replicated.
+ * ISLE_E_ARG: no count matrix, num_topics < 1, r < 1, an assign entry >= num_topics, no partition
+ * (assign null and none resident), a B uploaded separately whose columns are not A's documents. */
 int isle_hip_catchwords(isle_ctx* ctx, int num_topics, const uint32_t* assign, uint64_t r, double rho,
                         float* thresholds, int32_t* catch_topic, uint64_t* num_catchwords);
 
@@ -311,10 +331,14 @@ int isle_hip_catchwords(isle_ctx* ctx, int num_topics, const uint32_t* assign, u
  *   model (nullable): vocab x num_topics column-major, L1-normalised topic vectors (DenseMatrix Model).
  *   model_threshold (nullable): num_topics.  top1/top2 (nullable): per document of A, the two heaviest
  *   catchword topics (top_topic_pairs, :687-708) or -1/-1.  doc_topic_sums (nullable): number of
- *   non-zero (document, topic) catchword sums; fetch them with isle_hip_get_doc_topic_sums. */
+ *   non-zero (document, topic) catchword sums; fetch them with isle_hip_get_doc_topic_sums.
+ * world > 1: collective; model and model_threshold are replicated; top1 / top2 (docs(A) of this rank) and
+ * *doc_topic_sums are the shard's.  ISLE_E_ARG: no count matrix, no isle_hip_catchwords(num_topics)
+ * before, rank_threshold < 1. */
 int isle_hip_topic_model(isle_ctx* ctx, int num_topics, uint64_t rank_threshold, float* model,
                          float* model_threshold, int32_t* top1, int32_t* top2, uint64_t* doc_topic_sums);
-/* doc_offsets: docs(A) + 1 entries; topic / val: doc_topic_sums entries, (document, topic) ascending. */
+/* doc_offsets: docs(A) + 1 entries; topic / val: doc_topic_sums entries, (document, topic) ascending.  world > 1: the shard's own
+ * documents, numbered and offset from 0. */
 int isle_hip_get_doc_topic_sums(isle_ctx* ctx, int64_t* doc_offsets, uint32_t* topic, float* val);
 
 /* The FPaxpy pair of ISLETrainer::construct_edge_topics_v2 (src/trainer.cpp:1152-1159) on the
@@ -329,7 +353,10 @@ int isle_hip_edge_topics(isle_ctx* ctx, const int64_t* pairs, int n, float prima
  * each, uploaded for the call.  pairs: room for cap triples (primary, secondary, documents); selected > cap is ISLE_E_ARG with
  * *n_selected set.  n_selected / n_candidates / threshold are nullable; *threshold = the count of the first candidate cut off.
  * The pairs are counted in a table of num_topics^2 32-bit counters (integer atomics: the result does not depend on arrival order).
- * ISLE_E_ARG: world > 1, num_topics < 1 or > 8192 (the table's limit), max_edge_topics < 0, exactly one of top1 / top2 null, n_docs
+ * world > 1: collective.  The resident form counts this rank's documents (n_docs = its docs(A)), the other form takes the top topics of
+ * the rank's own documents; the table is summed over the ranks, the rest of the selection runs replicated: pairs, *n_selected,
+ * *n_candidates and *threshold are those of the whole corpus on every rank (cap bounds them, not this rank's n_docs).
+ * ISLE_E_ARG: num_topics < 1 or > 8192 (the table's limit), max_edge_topics < 0, exactly one of top1 / top2 null, n_docs
  * >= 2^32, a resident call before isle_hip_topic_model or with another size, a topic id >= num_topics or < -1 (the message names the
  * first such document; such an id is never used as an index). */
 #define ISLE_EDGE_TABLE_MAX_TOPICS 8192 /* 256 MB of counters */
@@ -376,7 +403,7 @@ int isle_hip_avg_topic_model(isle_ctx* ctx, int num_topics, float* model);
  * order): heaviest first, the lower word id first among equal weights (-0 == +0), NaN (and -inf) last.  Exact: a radix select on
  * the float bits per column, one read of the model.  ids: ncols x n row-major; weights (nullable): the model entries at those ids.
  * For CATCH and AVG, vocab and ncols must be the resident model's (V of A, num_topics), for LOADED the loaded model's; model_host is ignored.
- * ISLE_E_ARG: world > 1, n < 1 or n > min(vocab, 32), an unknown model, a resident model that does not exist (yet), a size mismatch,
+ * ISLE_E_ARG: world > 1 with AVG or LOADED (CATCH is replicated, HOST the caller's: each rank reads for itself), n < 1 or n > min(vocab, 32), an unknown model, a resident model that does not exist (yet), a size mismatch,
  * ids or (HOST) model_host null. */
 int isle_hip_model_top_words(isle_ctx* ctx, int which, const float* model_host, uint64_t vocab, int ncols, int n, uint32_t* ids, float* weights);
 
@@ -393,7 +420,7 @@ int isle_hip_edge_top_words(isle_ctx* ctx, int which, const float* model_host, u
  *   abar = (1/k') sum over finite t of m_t      dist[t] = sum_w (m_t[w] - abar[w])^2      avg = mean of dist over finite t
  * Non-finite topics get dist = NaN; no finite topic gives avg = NaN.  dist: num_topics doubles (nullable); avg (nullable).
  * Deviations from the reference: its cross term uses topic 1's vector for every topic (:769-771) and it accumulates in fp32.
- * ISLE_E_ARG: world > 1, an unknown or HOST model, a resident model that does not exist, num_topics not the model's. */
+ * ISLE_E_ARG: world > 1 with AVG or LOADED, an unknown or HOST model, a resident model that does not exist, num_topics not the model's. */
 int isle_hip_topic_diversity(isle_ctx* ctx, int which, int num_topics, double* dist, double* avg);
 
 /* The reference's model files, formatted on the device (isle_amd/csrc/model_text.hip): MMappedOutput (include/utils.h:383-478) under

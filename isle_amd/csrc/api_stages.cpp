@@ -451,18 +451,30 @@ extern "C" int isle_hip_get_B(isle_ctx* c, float* vals, uint32_t* rows, int64_t*
 // ------------------------------------------------------------------------------------------
 // downstream stage: catchwords, topic model, edge topics
 // ------------------------------------------------------------------------------------------
-static int post_prepare(isle_ctx* c, const char* who) {
+// the calls that are collective over document shards (catchwords, topic model) ...
+static int post_prepare_sharded(isle_ctx* c, const char* who) {
   if (!c->a_ready) return isle_fail(c, ISLE_E_ARG, "%s: no count matrix uploaded (isle_hip_upload_counts_u32)", who);
+  return 0;
+}
+// ... and the ones that read A on one rank only
+static int post_prepare(isle_ctx* c, const char* who) {
+  ISLECHK(post_prepare_sharded(c, who));
   if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "%s: single-rank only", who);
+  return 0;
+}
+// a reader of a model: with several ranks the catch model is replicated and a host model is the caller's; each rank reads for itself
+static int model_reader_ok(isle_ctx* c, int which, const char* who) {
+  if (c->world > 1 && which != ISLE_MODEL_CATCH && which != ISLE_MODEL_HOST) return isle_fail(c, ISLE_E_ARG, "%s: single-rank only", who);
   return 0;
 }
 
 // a_nv = avg_doc_sz * (count / doc_sum) over A (src/sparseMatrix.cpp:136-167), the values the catchword stage and the top-five
-// diagnostic read; avg_doc_sz from the thresholding when it ran, else computed here by the same rule (:92-99)
+// diagnostic read; avg_doc_sz from the thresholding when it ran, else computed here by the same rule (:92-99), over all ranks
 static int ensure_avg_doc_sz(isle_ctx* c) {
   if (!c->a_avg_valid) {  // B came from the host: the corpus statistics were never computed here
     HIPCHK(c, c->a_scan.reserve(isle_scan_scratch(c->a_D) + 4));
     ISLECHK(k_th_stats(c, (uint64_t*)c->a_scan.p));
+    ISLECHK(allreduce_sum<uint64_t>(c, (uint64_t*)c->a_scan.p, 2));
     uint64_t st[2];
     HIPCHK(c, hipMemcpyAsync(st, c->a_scan.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -476,11 +488,59 @@ static int post_normalize_A(isle_ctx* c) {
   return k_post_normalize(c, c->a_avg);
 }
 
+// The two order statistics of the stage with several ranks (route_post_select == POST_SELECT_HISTOGRAM): the device steps of post.hip and the
+// collectives between them.  Every count that shapes a collective comes from all-reduced data; the slot count still goes through agree_i32,
+// so that a rank that disagrees returns ISLE_E_COMM instead of issuing another sequence of collectives.
+struct PostShard {
+  isle_ctx* c;
+  const uint32_t k;
+
+  // four passes of eight bits over the slots' values, the slots in chunks of SELECT_CHUNK_SLOTS (stage_host.h); out[seg_id] = the value
+  int select(uint64_t nslots, float* out, const char* what) {
+    ISLECHK(agree_i32(c, (int)nslots, what));
+    const uint64_t nchunks = select_chunks(nslots, SELECT_CHUNK_SLOTS);
+    for (int shift = 24; shift >= 0; shift -= 8)
+      for (uint64_t i = 0; i < nchunks; ++i) {
+        const SlotChunk ch = select_chunk(nslots, SELECT_CHUNK_SLOTS, i);
+        ISLECHK(k_post_select_hist(c, ch.first, ch.count, shift));
+        ISLECHK(allreduce_sum<uint32_t>(c, c->p_sel_bins.p, (size_t)ch.count * 256));
+        ISLECHK(k_post_select_step(c, ch.first, ch.count, shift, out));
+      }
+    return 0;
+  }
+
+  // catchword thresholds (word-major V x k in p_thr) for rank r; sizes_dev: documents per topic over all ranks
+  int catch_thresholds(uint32_t r, const int* sizes_dev) {
+    const uint64_t np = c->a_V * k;
+    ISLECHK(k_post_pair_counts(c, k));
+    ISLECHK(allreduce_sum<uint32_t>(c, c->p_cnt_g.p, np));
+    {  // the minima as a maximum of complements: the transport has sum and max only
+      TimeScope ts(c, ISLE_T_COMM);
+      ISLECHK(isle_allreduce(c, c->p_min.p, np, ISLE_DT_U32, true));
+    }
+    ISLECHK(k_post_min_restore(c, c->p_min.p, np));
+    uint64_t nslots = 0;
+    ISLECHK(k_post_number_slots(c, c->p_cnt_g.p, c->p_cnt.p, np, r, r, nullptr, c->p_slot.p, c->p_slot.p, &nslots));
+    ISLECHK(k_post_scatter_segments(c, k, nslots));
+    ISLECHK(select(nslots, c->p_thr.p, "the number of catchword segments"));
+    return k_post_thr_final(c, k, r, sizes_dev);
+  }
+
+  // p_mthr: the rank-th largest document sum of a topic over all ranks, 0 where the topic has fewer
+  int model_thresholds(uint32_t rank) {
+    ISLECHK(k_post_topic_counts(c, k));
+    ISLECHK(allreduce_sum<uint32_t>(c, c->p_tcnt_g.p, k));
+    uint64_t nslots = 0;
+    ISLECHK(k_post_number_slots(c, c->p_tcnt_g.p, c->p_tcnt.p, k, rank - 1, rank, c->p_toff.p, c->p_tcnt_g.p + k, nullptr, &nslots));
+    return select(nslots, c->p_mthr.p, "the number of topics with a rank threshold");
+  }
+};
+
 extern "C" int isle_hip_catchwords(isle_ctx* c, int num_topics, const uint32_t* assign, uint64_t r, double rho, float* thresholds,
                                    int32_t* catch_topic, uint64_t* num_catchwords) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  ISLECHK(post_prepare(c, "catchwords"));
+  ISLECHK(post_prepare_sharded(c, "catchwords"));
   if (num_topics < 1) return isle_fail(c, ISLE_E_ARG, "catchwords: num_topics < 1");
   if (r < 1 || r > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "catchwords: rank r = %llu out of range (too few documents per topic?)",
                                                     (unsigned long long)r);
@@ -500,7 +560,13 @@ extern "C" int isle_hip_catchwords(isle_ctx* c, int num_topics, const uint32_t* 
   ISLECHK(k_post_cluster_of(c, c->assign.p, identity));
   HIPCHK(c, c->counts.reserve(num_topics));
   ISLECHK(k_count_sizes(c, c->assign.p, c->D, num_topics, c->counts.p));
-  ISLECHK(k_post_catch_thresholds(c, (uint32_t)num_topics, (uint32_t)r, c->counts.p));
+  ISLECHK(allreduce_sum<int>(c, c->counts.p, (size_t)num_topics));
+  if (route_post_select(c->world) == POST_SELECT_HISTOGRAM) {
+    PostShard ps = {c, (uint32_t)num_topics};
+    ISLECHK(ps.catch_thresholds((uint32_t)r, c->counts.p));
+  } else {
+    ISLECHK(k_post_catch_thresholds(c, (uint32_t)num_topics, (uint32_t)r, c->counts.p));
+  }
   uint64_t nc = 0;
   ISLECHK(k_post_find_catchwords(c, (uint32_t)num_topics, rho, &nc));
   if (num_catchwords) *num_catchwords = nc;
@@ -522,13 +588,20 @@ extern "C" int isle_hip_topic_model(isle_ctx* c, int num_topics, uint64_t rank_t
                                     int32_t* top2, uint64_t* doc_topic_sums) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  ISLECHK(post_prepare(c, "topic_model"));
+  ISLECHK(post_prepare_sharded(c, "topic_model"));
   if (!c->p_catch_ready || c->p_k != num_topics) return isle_fail(c, ISLE_E_ARG, "topic_model: run isle_hip_catchwords(num_topics = %d) first", num_topics);
   if (rank_threshold < 1 || rank_threshold > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "topic_model: rank_threshold out of range");  // :721
   uint64_t n = 0;
   ISLECHK(k_post_doc_topic_sums(c, (uint32_t)num_topics, &n));
-  ISLECHK(k_post_model_thresholds(c, (uint32_t)num_topics, (uint32_t)rank_threshold));
-  ISLECHK(k_post_model(c, (uint32_t)num_topics));
+  if (route_post_select(c->world) == POST_SELECT_HISTOGRAM) {
+    PostShard ps = {c, (uint32_t)num_topics};
+    ISLECHK(ps.model_thresholds((uint32_t)rank_threshold));
+  } else {
+    ISLECHK(k_post_model_thresholds(c, (uint32_t)num_topics, (uint32_t)rank_threshold));
+  }
+  ISLECHK(k_post_model_accumulate(c, (uint32_t)num_topics));  // this rank's documents ...
+  ISLECHK(allreduce_sum<float>(c, c->p_model.p, (size_t)c->a_V * num_topics));  // ... all documents: V x k floats
+  ISLECHK(k_post_model_normalize(c, (uint32_t)num_topics));
   c->p_model_ready = true;
   if (doc_topic_sums) *doc_topic_sums = n;
   if (model) HIPCHK(c, hipMemcpyAsync(model, c->p_model.p, (size_t)c->a_V * num_topics * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -585,7 +658,6 @@ extern "C" int isle_hip_select_edge_pairs(isle_ctx* c, const int32_t* top1, cons
   if (n_selected) *n_selected = 0;
   if (n_candidates) *n_candidates = 0;
   if (threshold) *threshold = 0;
-  if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: single-rank only");
   if (num_topics < 1) return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: num_topics < 1");
   if (num_topics > ISLE_EDGE_TABLE_MAX_TOPICS)
     return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: num_topics = %d, the pairs are counted in a table of num_topics^2 counters and %d is its limit",
@@ -707,7 +779,7 @@ extern "C" int isle_hip_model_top_words(isle_ctx* c, int which, const float* mod
                                         float* weights) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "model_top_words: single-rank only");
+  ISLECHK(model_reader_ok(c, which, "model_top_words"));
   if (ncols < 0 || vocab == 0 || vocab > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "model_top_words: vocab or ncols out of range");
   if (n < 1 || n > 32 || (uint64_t)n > vocab) return isle_fail(c, ISLE_E_ARG, "model_top_words: n = %d outside 1 .. min(vocab, 32)", n);
   if (!ids) return isle_fail(c, ISLE_E_ARG, "model_top_words: null ids");
@@ -732,7 +804,7 @@ extern "C" int isle_hip_edge_top_words(isle_ctx* c, int which, const float* mode
                                        float primary_ratio, int n, uint32_t* ids, float* weights) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "edge_top_words: single-rank only");
+  ISLECHK(model_reader_ok(c, which, "edge_top_words"));
   if (ncols < 0 || vocab == 0 || vocab > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "edge_top_words: vocab or ncols out of range");
   if (n < 1 || n > 32 || (uint64_t)n > vocab) return isle_fail(c, ISLE_E_ARG, "edge_top_words: n = %d outside 1 .. min(vocab, 32)", n);
   if (n_edge < 0 || (n_edge && (!pairs || !ids))) return isle_fail(c, ISLE_E_ARG, "edge_top_words: bad arguments");
@@ -766,7 +838,7 @@ extern "C" int isle_hip_model_text(isle_ctx* c, int which, const float* model_ho
   ISLECHK(isle_enter(c));
   if (nbytes) *nbytes = 0;
   if (nentries) *nentries = 0;
-  if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "model_text: single-rank only");
+  ISLECHK(model_reader_ok(c, which, "model_text"));
   if (format != ISLE_TEXT_SPARSE && format != ISLE_TEXT_DENSE) return isle_fail(c, ISLE_E_ARG, "model_text: unknown format %d", format);
   if (ncols < 0 || vocab == 0 || vocab > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "model_text: vocab or ncols out of range");
   const float* dev = nullptr;
@@ -844,7 +916,7 @@ extern "C" int isle_hip_edge_topics_text(isle_ctx* c, const int64_t* pairs, int 
 extern "C" int isle_hip_topic_diversity(isle_ctx* c, int which, int num_topics, double* dist, double* avg) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "topic_diversity: single-rank only");
+  ISLECHK(model_reader_ok(c, which, "topic_diversity"));
   uint64_t V = 0;
   int cols = 0;
   const float* dev = resident_model(c, which, "topic_diversity", &V, &cols);

@@ -257,7 +257,12 @@ struct isle_ctx {
   DevBuf<uint64_t> p_seg_id, p_seg_off, p_counters;
   DevBuf<uint32_t> p_seg_len, p_seg_rank, p_seg_cur;
   DevBuf<float> p_segvals;
-  DevBuf<int32_t> p_catch;         // V: topic the word is a catchword of, or -1
+  // several ranks (route_post_select): p_cnt / p_tcnt hold this rank's counts, these the counts summed over the ranks; the slots are
+  // numbered by a scan of the qualifying pairs in pair order; per slot the prefix found and the rank left; the bins of one chunk of slots
+  DevBuf<uint32_t> p_cnt_g, p_tcnt_g;  // V x k word-major; k counts, then k flags
+  DevBuf<int64_t> p_slot_scan;         // V x k + 1
+  DevBuf<uint32_t> p_sel_prefix, p_sel_rem, p_sel_bins;
+  DevBuf<int32_t> p_catch;        // V: topic the word is a catchword of, or -1
   DevBuf<uint32_t> p_nz;
   DevBuf<int64_t> p_dts_off;       // a_D + 1
   DevBuf<uint32_t> p_dts_topic;
@@ -647,7 +652,20 @@ int k_post_find_catchwords(isle_ctx* c, uint32_t k, double rho, uint64_t* ncatch
 int k_post_thr_colmajor(isle_ctx* c, uint32_t k, float* out_dev);
 int k_post_doc_topic_sums(isle_ctx* c, uint32_t k, uint64_t* n_out);
 int k_post_model_thresholds(isle_ctx* c, uint32_t k, uint32_t rank);
-int k_post_model(isle_ctx* c, uint32_t k);
+int k_post_model_accumulate(isle_ctx* c, uint32_t k);  // this rank's documents into a zeroed V x k
+int k_post_model_normalize(isle_ctx* c, uint32_t k);
+// ... the steps of the thresholds with several ranks (route_post_select == POST_SELECT_HISTOGRAM), between the collectives of api_stages.cpp
+int k_post_pair_counts(isle_ctx* c, uint32_t k);       // p_cnt, p_min of this rank's documents; p_cnt_g = p_cnt, p_min as complements (post_min_flip_k)
+int k_post_min_restore(isle_ctx* c, uint32_t* p, uint64_t n);  // the all-reduced complements back to value bits
+int k_post_topic_counts(isle_ctx* c, uint32_t k);      // p_tcnt, p_toff, the sums gathered per topic; p_tcnt_g = p_tcnt; p_mthr = 0
+// ids with cnt_g > above get a slot, numbered in id order: seg_id, seg_len = cnt_l, seg_off (off_l, or the scan of the lengths), prefix 0,
+// rank left `rank`; flag: n words of scratch; slot_of: n words or null
+int k_post_number_slots(isle_ctx* c, const uint32_t* cnt_g, const uint32_t* cnt_l, uint64_t n, uint32_t above, uint32_t rank, const int64_t* off_l,
+                        uint32_t* flag, uint32_t* slot_of, uint64_t* nslots);
+int k_post_scatter_segments(isle_ctx* c, uint32_t k, uint64_t nslots);
+int k_post_select_hist(isle_ctx* c, uint64_t first, uint64_t count, int shift);              // -> p_sel_bins, count x 256
+int k_post_select_step(isle_ctx* c, uint64_t first, uint64_t count, int shift, float* out);  // shift == 0: out[seg_id] = the value
+int k_post_thr_final(isle_ctx* c, uint32_t k, uint32_t r, const int* sizes_dev);
 int k_post_edge(isle_ctx* c, const int64_t* pairs_dev, int n, float a, float b, float* edge_dev);
 
 // model_text.hip: the reference's text of a V x ncols column-major device model (ISLE_TEXT_SPARSE / ISLE_TEXT_DENSE) handed to `sink` in

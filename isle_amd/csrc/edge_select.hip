@@ -7,6 +7,7 @@
 //   ep_count_k      grid-stride over documents, one integer atomicAdd on table[top1 * k + top2]: integer sums do not depend on the
 //                   order of arrival.  An id >= k or < -1 is never used as an index: the first such document is reported through
 //                   one 64-bit atomicMin (as feed_key_k reports its first bad entry)
+//   (all-reduce)    several ranks: every rank counted its own documents; the table is summed, everything below runs replicated
 //   ep_flag_k       flag[bin] = count >= min_docs, the largest count and the smallest candidate count
 //   (isle_scan)     exclusive scan of the flags: the candidates' positions in ascending bin order
 //   ep_compact_k    candidates -> (key = max_count - count, value = bin) in ascending bin order
@@ -121,6 +122,13 @@ int k_edge_select(isle_ctx* c, const int32_t* top1_dev, const int32_t* top2_dev,
       hipLaunchKernelGGL(ep_count_k, dim3(g), dim3(ET), 0, c->stream, top1_dev, top2_dev, D, (int32_t)k, table.p, (unsigned long long*)small.p);
       LAUNCH_CHECK(c);
     }
+  }
+  if (c->multi()) {  // the documents are this rank's: the counters summed over the ranks, the rest of the selection replicated on every rank
+    TimeScope ts(c, ISLE_T_COMM);
+    ISLECHK(isle_allreduce(c, table.p, nb, ISLE_DT_U32));
+  }
+  {
+    TimeScope ts(c, ISLE_T_POST);
     hipLaunchKernelGGL(ep_flag_k, dim3(cdiv((long)nb, ET)), dim3(ET), 0, c->stream, table.p, nb, md, flag.p, mm);
     LAUNCH_CHECK(c);
     HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, flag.p, nb, at.p, scratch.p)));

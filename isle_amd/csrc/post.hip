@@ -9,6 +9,10 @@
 //   post_select_k        r-th largest of a segment: 4-pass radix select on the   :514-516 (the reference sorts)
 //                        float bits (all values are positive)
 //   post_thr_final_k     the "else" arm: minimum or zero                         :517-523
+//   post_flag_k / post_slots_k / post_select_hist_k / post_select_step_k / post_min_flip_k
+//                        several ranks (route_post_select): the values of a segment lie on different ranks.  Slots numbered by a scan in
+//                        pair order, per pass the bins of a rank's part of every segment, summed over the ranks (api_stages.cpp), the
+//                        digit picked from the sum by select_digit (stage_host.h): the same r-th largest on every rank
 //   post_catch_k         catchword rule, one wave per word: only the arg-max     src/sparseMatrix.cpp:573-595
 //                        topic can pass  thr_t > rho * thr_o  for all o != t
 //   post_dts_k           document-topic catchword sums, entry order preserved    src/sparseMatrix.cpp:656-683
@@ -23,6 +27,7 @@
 // bit for bit.
 #include "common.h"
 #include "scan.h"
+#include "stage_host.h"
 
 namespace {
 
@@ -160,6 +165,74 @@ __global__ __launch_bounds__(PT) void post_select_k(const float* __restrict__ va
     __syncthreads();
   }
   if (threadIdx.x == 0) out[seg_id[sg]] = __uint_as_float(prefix);
+}
+
+// ---- several ranks: a segment's values lie on different ranks (route_host.h route_post_select, stage_host.h select_digit) ----
+// The minimum of the value bits over the ranks through a transport that has sum and max: the maximum of the complements.  The values
+// are positive floats (sign bit clear), so the complement is taken within the 31 value bits: the words stay below 2^31, and a transport
+// that reduces them as signed integers (gloo has no unsigned types) orders them as an unsigned one does.  No value (all ones) <-> 0, below
+// every value's complement.  back: the way back.
+__global__ __launch_bounds__(PT) void post_min_flip_k(uint32_t* __restrict__ p, uint64_t n, bool back) {
+  const uint64_t i = (uint64_t)blockIdx.x * PT + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t x = p[i];
+  p[i] = back ? (x == 0u ? NONE32 : 0x7fffffffu - x) : (x == NONE32 ? 0u : 0x7fffffffu - x);
+}
+__global__ __launch_bounds__(PT) void post_flag_k(const uint32_t* __restrict__ cnt_g, uint64_t n, uint32_t above, uint32_t* __restrict__ flag) {
+  const uint64_t i = (uint64_t)blockIdx.x * PT + threadIdx.x;
+  if (i < n) flag[i] = cnt_g[i] > above ? 1u : 0u;
+}
+// at[i]: the exclusive scan of the flags: slot ids in id order, the same on every rank.  The length of a segment is this rank's count.
+__global__ __launch_bounds__(PT) void post_slots_k(const uint32_t* __restrict__ cnt_g, const uint32_t* __restrict__ cnt_l, uint64_t n, uint32_t above,
+                                                    uint32_t rank, const int64_t* __restrict__ at, const int64_t* __restrict__ off_l,
+                                                    uint32_t* __restrict__ slot_of, uint64_t* __restrict__ seg_id, uint64_t* __restrict__ seg_off,
+                                                    uint32_t* __restrict__ seg_len, uint32_t* __restrict__ prefix, uint32_t* __restrict__ remaining) {
+  const uint64_t i = (uint64_t)blockIdx.x * PT + threadIdx.x;
+  if (i >= n) return;
+  uint32_t slot = NONE32;
+  if (cnt_g[i] > above) {
+    const int64_t s = at[i];  // < the number of flags set = the size of the slot arrays
+    slot = (uint32_t)s;
+    seg_id[s] = i;
+    seg_len[s] = cnt_l[i];
+    if (off_l) seg_off[s] = (uint64_t)off_l[i];
+    prefix[s] = 0u;
+    remaining[s] = rank;
+  }
+  if (slot_of) slot_of[i] = slot;
+}
+// One pass of the radix select on the float bits, one workgroup per slot: the values of this rank's part of the segment that carry the
+// prefix found so far, counted by their digit at `shift`.  bins: 256 counts per slot of the chunk; an empty part stores zeros.
+__global__ __launch_bounds__(PT) void post_select_hist_k(const float* __restrict__ vals, const uint64_t* __restrict__ seg_off, const uint32_t* __restrict__ seg_len,
+                                                          const uint32_t* __restrict__ prefix_of, uint64_t first, int shift, uint32_t* __restrict__ bins) {
+  __shared__ uint32_t hist[256];
+  const uint64_t sg = first + blockIdx.x;
+  const uint32_t n = seg_len[sg];
+  const uint32_t prefix = prefix_of[sg], mask = select_mask(shift);
+  hist[threadIdx.x] = 0;
+  __syncthreads();
+  if (n) {
+    const uint32_t* v = (const uint32_t*)(vals + seg_off[sg]);
+    for (uint32_t i = threadIdx.x; i < n; i += PT) {
+      const uint32_t key = v[i];
+      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+    }
+  }
+  __syncthreads();
+  bins[(size_t)blockIdx.x * 256 + threadIdx.x] = hist[threadIdx.x];
+}
+// ... and the digit picked from the bins summed over the ranks: identical integers on every rank, one thread per slot
+__global__ __launch_bounds__(PT) void post_select_step_k(const uint32_t* __restrict__ bins, uint64_t first, uint64_t count, int shift,
+                                                          uint32_t* __restrict__ prefix_of, uint32_t* __restrict__ remaining, const uint64_t* __restrict__ seg_id,
+                                                          float* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * PT + threadIdx.x;
+  if (i >= count) return;
+  const uint64_t sg = first + i;
+  const SelectPick p = select_digit(bins + (size_t)i * 256, remaining[sg]);
+  const uint32_t prefix = prefix_of[sg] | (p.digit << shift);
+  prefix_of[sg] = prefix;
+  remaining[sg] = p.remaining;
+  if (shift == 0) out[seg_id[sg]] = __uint_as_float(prefix);
 }
 
 // everything that did not get a segment (src/sparseMatrix.cpp:517-523, and :500-504 for empty clusters)
@@ -481,6 +554,108 @@ int k_post_catch_thresholds(isle_ctx* c, uint32_t k, uint32_t r, const int* size
   return 0;
 }
 
+// ---- the same thresholds with several ranks, cut at the collectives (api_stages.cpp PostShard) ----
+int k_post_pair_counts(isle_ctx* c, uint32_t k) {
+  TimeScope ts(c, ISLE_T_POST);
+  const uint64_t V = c->a_V, D = c->a_D, np = V * k;
+  HIPCHK(c, c->p_cnt.reserve(np));
+  HIPCHK(c, c->p_cnt_g.reserve(np));
+  HIPCHK(c, c->p_min.reserve(np));
+  HIPCHK(c, c->p_thr.reserve(np));
+  HIPCHK(c, c->p_slot.reserve(np));
+  HIPCHK(c, hipMemsetAsync(c->p_cnt.p, 0, np * sizeof(uint32_t), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->p_min.p, 0xff, np * sizeof(uint32_t), c->stream));
+  if (D) hipLaunchKernelGGL(post_pair_count_k, dim3(doc_grid(c, D)), dim3(PT), 0, c->stream, c->a_rows.p, c->a_offs.p, c->a_nv.p, c->p_cluster_of.p, D, k,
+                            c->p_cnt.p, c->p_min.p);
+  LAUNCH_CHECK(c);
+  HIPCHK(c, hipMemcpyAsync(c->p_cnt_g.p, c->p_cnt.p, np * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+  hipLaunchKernelGGL(post_min_flip_k, dim3(cdiv((long)np, PT)), dim3(PT), 0, c->stream, c->p_min.p, np, false);
+  LAUNCH_CHECK(c);
+  return 0;
+}
+
+int k_post_min_restore(isle_ctx* c, uint32_t* p, uint64_t n) {
+  TimeScope ts(c, ISLE_T_POST);
+  if (n) hipLaunchKernelGGL(post_min_flip_k, dim3(cdiv((long)n, PT)), dim3(PT), 0, c->stream, p, n, true);
+  LAUNCH_CHECK(c);
+  return 0;
+}
+
+int k_post_number_slots(isle_ctx* c, const uint32_t* cnt_g, const uint32_t* cnt_l, uint64_t n, uint32_t above, uint32_t rank, const int64_t* off_l,
+                        uint32_t* flag, uint32_t* slot_of, uint64_t* nslots_out) {
+  TimeScope ts(c, ISLE_T_POST);
+  HIPCHK(c, c->p_slot_scan.reserve(n + 1));
+  HIPCHK(c, c->a_scan.reserve(isle_scan_scratch(n) + 4));
+  hipLaunchKernelGGL(post_flag_k, dim3(cdiv((long)n, PT)), dim3(PT), 0, c->stream, cnt_g, n, above, flag);
+  LAUNCH_CHECK(c);
+  HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, flag, n, c->p_slot_scan.p, c->a_scan.p)));
+  int64_t ns = 0;
+  HIPCHK(c, hipMemcpyAsync(&ns, c->p_slot_scan.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t nslots = (uint64_t)ns;
+  *nslots_out = nslots;
+  if (nslots >= 0x7fffffffull)  // a slot id is 32 bits, the count goes through agree_i32
+    return isle_fail(c, ISLE_E_ARG, "thresholds: %llu segments to select from (at most 2^31 - 2)", (unsigned long long)nslots);
+  HIPCHK(c, c->p_seg_id.reserve(nslots + 1));
+  HIPCHK(c, c->p_seg_off.reserve(nslots + 1));
+  HIPCHK(c, c->p_seg_len.reserve(nslots + 1));
+  HIPCHK(c, c->p_seg_cur.reserve(nslots + 1));
+  HIPCHK(c, c->p_sel_prefix.reserve(nslots + 1));
+  HIPCHK(c, c->p_sel_rem.reserve(nslots + 1));
+  hipLaunchKernelGGL(post_slots_k, dim3(cdiv((long)n, PT)), dim3(PT), 0, c->stream, cnt_g, cnt_l, n, above, rank, c->p_slot_scan.p, off_l, slot_of,
+                     c->p_seg_id.p, c->p_seg_off.p, c->p_seg_len.p, c->p_sel_prefix.p, c->p_sel_rem.p);
+  LAUNCH_CHECK(c);
+  if (!off_l) {  // this rank's segments one behind the other, in slot order
+    HIPCHK(c, c->a_scan.reserve(isle_scan_scratch(nslots) + 4));
+    HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, c->p_seg_len.p, nslots, (int64_t*)c->p_seg_off.p, c->a_scan.p)));
+  }
+  return 0;
+}
+
+// this rank's values of the qualifying pairs into its segments (behind k_post_number_slots without off_l)
+int k_post_scatter_segments(isle_ctx* c, uint32_t k, uint64_t nslots) {
+  TimeScope ts(c, ISLE_T_POST);
+  const uint64_t D = c->a_D;
+  int64_t total = 0;
+  HIPCHK(c, hipMemcpyAsync(&total, c->p_seg_off.p + nslots, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if ((uint64_t)total > c->a_nnz) return isle_fail(c, ISLE_E_NUMERIC, "catch thresholds: %lld values in segments, %llu entries", (long long)total,
+                                                   (unsigned long long)c->a_nnz);
+  HIPCHK(c, c->p_segvals.reserve(total ? (size_t)total : 1));
+  if (nslots && D) {
+    HIPCHK(c, hipMemsetAsync(c->p_seg_cur.p, 0, nslots * sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(post_scatter_k, dim3(doc_grid(c, D)), dim3(PT), 0, c->stream, c->a_rows.p, c->a_offs.p, c->a_nv.p, c->p_cluster_of.p, D, k,
+                       c->p_slot.p, c->p_seg_off.p, c->p_seg_cur.p, c->p_segvals.p);
+    LAUNCH_CHECK(c);
+  }
+  return 0;
+}
+
+int k_post_select_hist(isle_ctx* c, uint64_t first, uint64_t count, int shift) {
+  TimeScope ts(c, ISLE_T_POST);
+  HIPCHK(c, c->p_sel_bins.reserve(count * 256));
+  hipLaunchKernelGGL(post_select_hist_k, dim3((unsigned)count), dim3(PT), 0, c->stream, c->p_segvals.p, c->p_seg_off.p, c->p_seg_len.p, c->p_sel_prefix.p,
+                     first, shift, c->p_sel_bins.p);
+  LAUNCH_CHECK(c);
+  return 0;
+}
+
+int k_post_select_step(isle_ctx* c, uint64_t first, uint64_t count, int shift, float* out) {
+  TimeScope ts(c, ISLE_T_POST);
+  hipLaunchKernelGGL(post_select_step_k, dim3(cdiv((long)count, PT)), dim3(PT), 0, c->stream, c->p_sel_bins.p, first, count, shift, c->p_sel_prefix.p,
+                     c->p_sel_rem.p, c->p_seg_id.p, out);
+  LAUNCH_CHECK(c);
+  return 0;
+}
+
+int k_post_thr_final(isle_ctx* c, uint32_t k, uint32_t r, const int* sizes_dev) {
+  TimeScope ts(c, ISLE_T_POST);
+  const uint64_t np = c->a_V * k;
+  hipLaunchKernelGGL(post_thr_final_k, dim3(cdiv((long)np, PT)), dim3(PT), 0, c->stream, c->p_cnt_g.p, c->p_min.p, sizes_dev, np, k, r, c->p_thr.p);
+  LAUNCH_CHECK(c);
+  return 0;
+}
+
 int k_post_find_catchwords(isle_ctx* c, uint32_t k, double rho, uint64_t* ncatch_host) {
   TimeScope ts(c, ISLE_T_POST);
   HIPCHK(c, c->p_catch.reserve(c->a_V));
@@ -532,9 +707,8 @@ int k_post_doc_topic_sums(isle_ctx* c, uint32_t k, uint64_t* n_out) {
   return 0;
 }
 
-// per-topic thresholds c->p_mthr (k floats) = rank-th largest document sum of the topic, 0 if it has fewer
-int k_post_model_thresholds(isle_ctx* c, uint32_t k, uint32_t rank) {
-  TimeScope ts(c, ISLE_T_POST);
+// this rank's sums counted per topic (p_tcnt), placed (p_toff) and gathered per topic (p_segvals)
+static int topic_segments(isle_ctx* c, uint32_t k) {
   const uint64_t n = c->p_dts_n;
   HIPCHK(c, c->p_tcnt.reserve(2 * (size_t)k));
   HIPCHK(c, c->p_toff.reserve(k + 1));
@@ -555,6 +729,14 @@ int k_post_model_thresholds(isle_ctx* c, uint32_t k, uint32_t rank) {
   if (n)
     hipLaunchKernelGGL(post_topic_scatter_k, dim3(g), dim3(PT), 2 * (size_t)k * sizeof(uint32_t), c->stream, c->p_dts_topic.p, c->p_dts_val.p, n, k,
                        c->p_toff.p, c->p_tcnt.p + k, c->p_segvals.p);
+  LAUNCH_CHECK(c);
+  return 0;
+}
+
+// per-topic thresholds c->p_mthr (k floats) = rank-th largest document sum of the topic, 0 if it has fewer
+int k_post_model_thresholds(isle_ctx* c, uint32_t k, uint32_t rank) {
+  TimeScope ts(c, ISLE_T_POST);
+  ISLECHK(topic_segments(c, k));
   hipLaunchKernelGGL(post_topic_segs_k, dim3(cdiv(k, PT)), dim3(PT), 0, c->stream, c->p_tcnt.p, c->p_toff.p, k, rank, (unsigned long long*)c->p_counters.p,
                      c->p_seg_id.p, c->p_seg_off.p, c->p_seg_len.p, c->p_seg_rank.p, c->p_mthr.p);
   LAUNCH_CHECK(c);
@@ -569,7 +751,18 @@ int k_post_model_thresholds(isle_ctx* c, uint32_t k, uint32_t rank) {
   return 0;
 }
 
-int k_post_model(isle_ctx* c, uint32_t k) {
+// ... with several ranks: up to the gathered sums, the counts copied for their all-reduce (k words of flags behind them), thresholds zeroed
+int k_post_topic_counts(isle_ctx* c, uint32_t k) {
+  TimeScope ts(c, ISLE_T_POST);
+  ISLECHK(topic_segments(c, k));
+  HIPCHK(c, c->p_tcnt_g.reserve(2 * (size_t)k));
+  HIPCHK(c, hipMemcpyAsync(c->p_tcnt_g.p, c->p_tcnt.p, k * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->p_mthr.p, 0, k * sizeof(float), c->stream));
+  return 0;
+}
+
+// The model in two steps: with several ranks the V x k sums of the ranks' documents are added up between them
+int k_post_model_accumulate(isle_ctx* c, uint32_t k) {
   TimeScope ts(c, ISLE_T_POST);
   const uint64_t V = c->a_V, D = c->a_D;
   HIPCHK(c, c->p_model.reserve(V * k));
@@ -577,7 +770,12 @@ int k_post_model(isle_ctx* c, uint32_t k) {
   if (D)
     hipLaunchKernelGGL(post_model_acc_k, dim3(doc_grid(c, D)), dim3(PT), 0, c->stream, c->a_rows.p, c->a_offs.p, c->a_nv.p, c->p_cluster_of.p, D, V,
                        c->p_dts_off.p, c->p_dts_topic.p, c->p_dts_val.p, c->p_mthr.p, c->p_model.p);
-  hipLaunchKernelGGL(post_model_norm_k, dim3(k), dim3(PT), 0, c->stream, c->p_model.p, V);
+  LAUNCH_CHECK(c);
+  return 0;
+}
+int k_post_model_normalize(isle_ctx* c, uint32_t k) {
+  TimeScope ts(c, ISLE_T_POST);
+  hipLaunchKernelGGL(post_model_norm_k, dim3(k), dim3(PT), 0, c->stream, c->p_model.p, c->a_V);
   LAUNCH_CHECK(c);
   return 0;
 }

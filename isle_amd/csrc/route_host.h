@@ -349,6 +349,14 @@ inline bool route_gl_wide_grouped(bool with_norms, int PW, int k, uint64_t D, in
          route_scratch_ok((double)(slab * wg_panels + (size_t)ngroups * D) * sizeof(float), total_mem, ask);
 }
 
+// ---- the stage downstream of the path (api_stages.cpp, post.hip) -------------------------------------------------------------------------
+// The r-th largest value of every segment (catchword thresholds, rank thresholds of the document-topic sums).  One rank holds every
+// segment whole: one workgroup per segment (post_select_k, behind post_qualify_k's slots).  Several ranks: a segment's values lie on
+// different ranks, the digits are picked from histograms summed over the ranks (post_select_hist_k / post_select_step_k, behind slots
+// numbered in pair order).  A communicator of one rank takes the first form: it issues the launches of a context without one.
+enum PostSelect { POST_SELECT_ONE_WORKGROUP = 0, POST_SELECT_HISTOGRAM = 1 };
+inline PostSelect route_post_select(int world) { return world > 1 ? POST_SELECT_HISTOGRAM : POST_SELECT_ONE_WORKGROUP; }
+
 // ---- small EVD by tridiagonalisation (evd_tridiag.hip) -------------------------------------------------------------------------------
 // workgroups of the persistent form: each holds its columns plus v and w in lds_bytes of LDS; at least gsmall (more only add barrier latency)
 inline int route_td_workgroups(int n, size_t lds_bytes, int gsmall) {

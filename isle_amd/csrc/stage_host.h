@@ -1,6 +1,6 @@
 // isle_amd/csrc/stage_host.h — what the stages either side of the hot path (api_stages.cpp) decide on the host: the corpus average and its
 // limit, the two thresholding counts, the sampling keys, their pivot over all ranks and the drop mask, a shard's place in B's columns, the
-// plan and the sums of the UMass coherence, the top-five count rule, the diversity average and the line of a byte.  Plain C++ (no HIP type,
+// plan and the sums of the UMass coherence, the digit pick and the chunk plan of the distributed select, the top-five count rule, the diversity average and the line of a byte.  Plain C++ (no HIP type,
 // no isle_ctx, nothing read from the environment), so that rules whose mistakes do not fault but keep other documents run without a device
 // and without a transport: ../host/stage_host_main.cpp applies them to a script, tests/test_stage_host_cpu.py checks the answers.  Operand
 // types, casts and the order of every float and double operation are the reference's, as cited: no build of it takes -ffast-math.
@@ -162,6 +162,48 @@ inline void coherence_sums(const CoherencePlan& pl, const uint32_t* cnt, double 
     if (doc_freq)
       for (size_t i = 0; i < m; ++i) doc_freq[t * m + i] = du[pl.loc[t * m + i]];
   }
+}
+
+// ---- the distributed radix select of the stage downstream (post.hip post_select_hist_k / post_select_step_k) ---------------------------------
+// With several ranks the values of a segment (the normalised counts of a word over the documents of a cluster; the sums of a topic) lie on
+// different ranks.  The r-th largest is found from the float bits, eight at a time from the top (all values are positive: unsigned order is
+// float order): every rank counts its own values under the prefix found so far into 256 bins, the bins are summed over the ranks, and every
+// rank picks the next digit from the same integers by the rule post_select_k's thread 0 applies within one workgroup.
+#if defined(__HIPCC__)
+#define ISLE_STAGE_HD __host__ __device__
+#else
+#define ISLE_STAGE_HD
+#endif
+struct SelectPick {
+  uint32_t digit, remaining;
+};
+// bins: the counts of the 256 values of a digit; remaining >= 1: the rank (1-based, from the largest) still to go among them.  The digit
+// is the largest d whose values together with all above reach the rank; what remains is the rank among the values of digit d.  A rank
+// past all the values (which no caller asks for) ends in digit 0.
+ISLE_STAGE_HD inline SelectPick select_digit(const uint32_t* bins, uint32_t remaining) {
+  uint32_t cum = 0;
+  int d = 255;
+  for (; d > 0; --d) {
+    if (cum + bins[d] >= remaining) break;
+    cum += bins[d];
+  }
+  SelectPick p = {(uint32_t)d, remaining - cum};
+  return p;
+}
+// the bits already fixed ahead of the pass that reads the digit at `shift` (24, 16, 8, 0)
+ISLE_STAGE_HD inline uint32_t select_mask(int shift) { return shift >= 24 ? 0u : 0xffffffffu << (shift + 8); }
+// The slots (segments) are walked in chunks, one all-reduce of chunk x 256 bins per chunk and pass, so that the table of bins stays bounded.
+// The size is a number nobody has measured: 64 MiB of bins per all-reduce, 65 536 slots, to begin with.
+constexpr uint64_t SELECT_BINS_BYTES = 64ull << 20;
+constexpr uint64_t SELECT_CHUNK_SLOTS = SELECT_BINS_BYTES / (256 * sizeof(uint32_t));
+struct SlotChunk {
+  uint64_t first, count;
+};
+inline uint64_t select_chunks(uint64_t nslots, uint64_t chunk_slots) { return (nslots + chunk_slots - 1) / chunk_slots; }
+inline SlotChunk select_chunk(uint64_t nslots, uint64_t chunk_slots, uint64_t i) {
+  const uint64_t first = std::min(nslots, i * chunk_slots);
+  SlotChunk s = {first, std::min(chunk_slots, nslots - first)};
+  return s;
 }
 
 // ---- corpus diagnostics and what reads a model ------------------------------------------------------------------------------------------------

@@ -196,6 +196,7 @@ class HotPath:
     def comm_init(self, world, rank, uid):
         uid = np.ascontiguousarray(uid, np.uint8)
         self._chk(self._lib.isle_hip_comm_init(self._h, world, rank, _p(uid)))
+        self._world = int(world)
 
     def comm_init_host(self, world, rank, exchange):
         """Rehearsal transport (tests only; include/isle_hip.h): every collective is staged through host memory and
@@ -217,6 +218,7 @@ class HotPath:
 
         self._xchg_cb = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_int)(tramp)
         self._chk(self._lib.isle_hip_comm_init_host(self._h, world, rank, C.cast(self._xchg_cb, C.c_void_p), None))
+        self._world = int(world)
 
     @staticmethod
     def gloo_exchange(dist, world, rank):
@@ -415,7 +417,10 @@ class HotPath:
     # ---- downstream stage: catchwords, topic model, edge topics ---------------------------
     def find_catchwords(self, num_topics, r, assign=None, rho=1.1, fetch_thresholds=True):
         """rth_highest_element per topic + find_catchwords (src/trainer.cpp:586-627).
-        -> dict(thresholds (V,k) F-order or None, catch_topic int32[V], num_catchwords)."""
+        -> dict(thresholds (V,k) F-order or None, catch_topic int32[V], num_catchwords).
+        Under comm_init / comm_init_host the call is collective: every rank holds its documents of A (upload_counts with doc_offset /
+        docs_global) and passes the same num_topics, r and rho; assign is the partition of the columns of B this rank kept (or the
+        resident one).  All three results are replicated: those of the whole corpus, bit-identical on every rank."""
         V = self.V
         thr = np.empty((V, num_topics), np.float32, order="F") if fetch_thresholds else None
         ct = np.empty(V, np.int32)
@@ -426,7 +431,10 @@ class HotPath:
         return dict(thresholds=thr, catch_topic=ct, num_catchwords=int(n.value))
 
     def construct_topic_model(self, num_topics, rank_threshold, num_docs_A, fetch_sums=True):
-        """SparseMatrix::construct_topic_model (src/sparseMatrix.cpp:597-838) on the device."""
+        """SparseMatrix::construct_topic_model (src/sparseMatrix.cpp:597-838) on the device.
+        Under comm_init / comm_init_host the call is collective (the same num_topics and rank_threshold on every rank) and num_docs_A is
+        the rank's own document count.  model and model_threshold are replicated: the whole corpus's, bit-identical on every rank.
+        top1 / top2, dts_off / dts_topic / dts_val and num_sums are the shard's: the rank's own documents, numbered from 0."""
         V = self.V
         M = np.empty((V, num_topics), np.float32, order="F")
         mt = np.empty(num_topics, np.float32)
@@ -455,7 +463,10 @@ class HotPath:
         """select_edge_pairs() on the device (isle_hip_select_edge_pairs), bit-equal to it: over the resident top-two topics of the last
         construct_topic_model (top1 and top2 None; nothing is fetched), or over the given int32 arrays with num_topics given (every id in
         -1 .. num_topics - 1).  -> (int64 (n, 3): primary, secondary, documents; dict(candidates, threshold)), threshold the count of
-        the first candidate cut off, None when nothing was cut."""
+        the first candidate cut off, None when nothing was cut.
+        Under comm_init / comm_init_host the call is collective: the resident form counts the documents of the rank's shard, the other
+        form takes the top topics of the rank's own documents; the pair counts are summed over the ranks and every rank returns the
+        same selection, that of the whole corpus (replicated)."""
         if top1 is None and top2 is None:
             docs = getattr(self, "_a_shape", (0, 0))[1]
             k = getattr(self, "_post_k", 0) if num_topics is None else int(num_topics)
@@ -469,7 +480,10 @@ class HotPath:
                 raise ValueError("top1 and top2 differ in length")
             docs = int((t1 if t1 is not None else t2).size)
             k = int(num_topics)
-        cap = max(min(int(max_edge_topics), k * k, docs), 0)
+        # (several ranks: the candidates are those of all ranks' documents, so this rank's count is no bound on them)
+        cap = max(min(int(max_edge_topics), k * k), 0)
+        if getattr(self, "_world", 1) <= 1:
+            cap = min(cap, docs)
         pairs = np.empty((cap, 3), np.int64)
         nsel, ncand, thr = C.c_uint64(), C.c_uint64(), C.c_uint64()
         # (an empty array still hands the library a non-null pointer: which of top1 / top2 was given is what it sees)
