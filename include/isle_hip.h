@@ -162,6 +162,33 @@ int isle_hip_tdf_acquire(isle_ctx* ctx, char** buf, uint64_t* cap);
 int isle_hip_tdf_commit(isle_ctx* ctx, uint64_t nbytes);
 int isle_hip_tdf_write(isle_ctx* ctx, const char* bytes, uint64_t nbytes);
 int isle_hip_tdf_finalize(isle_ctx* ctx, uint64_t max_entries, uint64_t* entries_read, uint64_t* nnz);
+/* One tdf file onto document shards, in two passes over the file, without any rank holding the corpus (the reference reads the file on one
+ * host, include/utils.h:158-228, and sorts it there, src/trainer.cpp:236-247; isle_hip_tdf_begin stays single-rank).  Pieces travel through
+ * tdf_acquire / tdf_commit / tdf_write as above.
+ * Pass 1, tdf_begin_counts ... tdf_finalize_counts: a stream that counts the valid lines of every document into a table of num_docs 32-bit
+ * counters on the device and holds no entry.  Each rank streams its own part of the file, whole lines only: rank r of N takes the lines
+ * whose first byte lies in [size * r / N, size * (r + 1) / N) (tdf_pump::file_range, isle_amd/host/tdf_pump.h).  The counting stream refuses
+ * nothing about the text: a bad line is not counted, since line numbers inside a byte range are not the file's; pass 2 names the first bad
+ * line of the whole file.  tdf_finalize_counts counts what stands behind the last '\n' as the last line and ends the stream.  With several
+ * ranks it is collective: agree_tag (the file's size) must be alike on all ranks, or all of them return ISLE_E_COMM; the table is summed
+ * over the ranks, and so is the line count.  More than 4294967295 lines in all are ISLE_E_ARG (a summed counter might have wrapped).
+ * bounds (parts + 1 values): bounds[p] .. bounds[p + 1] are the documents of shard p, by the rule of isle_hip_plan_shards applied to the line
+ * counts: bound p is the first document at or behind p / parts of the lines.  The balance is by lines, repeated (doc, word) pairs included,
+ * not by nnz after de-duplication.  parts need not be the number of ranks: one process may plan for N.  doc_lines (nullable, num_docs
+ * values): the table.  lines_local / lines_global (nullable): valid lines this rank streamed / all ranks streamed.
+ * Pass 2, tdf_begin_window ... tdf_finalize: a text stream over the WHOLE file that keeps the entries of documents doc_begin <= doc <
+ * doc_end (0-based) only.  Allowed with any number of ranks; no collective is inside it.  Every line is parsed and checked as by
+ * tdf_begin: the first bad line of the file, its number and its kind are what isle_hip_ingest_tdf reports.  tdf_finalize checks max_entries
+ * against the valid lines of the whole text and returns that number as entries_read.  The result is the columns [doc_begin, doc_end) of what
+ * isle_hip_ingest_tdf of the same bytes gives, offsets rebased, bit for bit: num_docs of the context's count matrix is doc_end - doc_begin,
+ * its doc_offset doc_begin, its docs_global num_docs (src/sparseMatrix.cpp:58-87 per shard).  doc_begin == doc_end gives a matrix of zero
+ * columns.  The sort runs over ceil(log2(doc_end - doc_begin)) document bits, and device memory follows the shard: 12 bytes per held entry.
+ * What is replicated: every rank reads and parses the whole file in pass 2. */
+int isle_hip_tdf_begin_counts(isle_ctx* ctx, uint64_t vocab_size, uint64_t num_docs, uint64_t piece_bytes);
+int isle_hip_tdf_finalize_counts(isle_ctx* ctx, int parts, uint64_t agree_tag, uint64_t* bounds, uint32_t* doc_lines, uint64_t* lines_local,
+                                 uint64_t* lines_global);
+int isle_hip_tdf_begin_window(isle_ctx* ctx, uint64_t vocab_size, uint64_t num_docs, uint64_t doc_begin, uint64_t doc_end,
+                              uint64_t reserve_entries, uint64_t piece_bytes);
 /* Copies the context's count matrix to the host (any pointer may be NULL); nnz via the call above
  * or offsets[num_docs]. */
 int isle_hip_get_A(isle_ctx* ctx, float* counts, uint32_t* rows, int64_t* offsets);

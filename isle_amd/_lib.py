@@ -29,6 +29,9 @@ SYMBOLS = {
     "isle_hip_tdf_commit": (_I, [_P, _U64]),
     "isle_hip_tdf_write": (_I, [_P, _P, _U64]),
     "isle_hip_tdf_finalize": (_I, [_P, _U64, _P, _P]),
+    "isle_hip_tdf_begin_counts": (_I, [_P, _U64, _U64, _U64]),
+    "isle_hip_tdf_finalize_counts": (_I, [_P, _I, _U64, _P, _P, _P, _P]),
+    "isle_hip_tdf_begin_window": (_I, [_P, _U64, _U64, _U64, _U64, _U64, _U64]),
     "isle_hip_get_A": (_I, [_P, _P, _P, _P]),
     "isle_hip_threshold": (_I, [_P, _U64, C.c_double, _U64, _P, _P, _P, _P]),
     "isle_hip_get_B": (_I, [_P, _P, _P, _P, _P, _P]),

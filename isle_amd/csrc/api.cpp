@@ -19,6 +19,7 @@
 #include <dlfcn.h>
 
 #include "api_internal.h"
+#include "stage_host.h"
 
 // ------------------------------------------------------------------------------------------
 // errors, timing
@@ -531,16 +532,8 @@ extern "C" int isle_hip_comm_init_host(isle_ctx* c, int world, int rank, isle_ho
 
 extern "C" int isle_hip_plan_shards(uint64_t num_docs, const int64_t* offs, int parts, uint64_t* bounds) {
   if (!offs || !bounds || parts < 1) return ISLE_E_ARG;
-  const int64_t nnz = offs[num_docs];
   bounds[0] = 0;
-  for (int p = 1; p < parts; ++p) {
-    const int64_t target = (int64_t)(((__int128)nnz * p) / parts);
-    const int64_t* it = std::lower_bound(offs, offs + num_docs + 1, target);
-    uint64_t d = (uint64_t)(it - offs);
-    if (d > num_docs) d = num_docs;
-    if (d < bounds[p - 1]) d = bounds[p - 1];
-    bounds[p] = d;
-  }
+  for (int p = 1; p < parts; ++p) bounds[p] = plan_bound(offs, num_docs, p, parts, bounds[p - 1]);  // stage_host.h
   bounds[parts] = num_docs;
   return 0;
 }

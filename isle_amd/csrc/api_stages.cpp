@@ -165,18 +165,16 @@ static int tdf_settle(isle_ctx* c, const char* who) {
   const int rc = k_tdf_wait(c);
   if (rc) return feed_discard(c, rc);
   const uint64_t bad = c->feed.known.err;
-  if (bad == ~0ull) return 0;
+  if (bad == ~0ull || c->feed.counting) return 0;  // (a counting stream refuses no line: the windowed pass names the first bad line of the file)
   c->feed.release();
   return isle_fail(c, ISLE_E_ARG, "%s: %s on line %llu", who, kTdfKind[(bad & 7ull) < 7 ? (bad & 7ull) : 0], (unsigned long long)((bad >> 3) + 1));
 }
 
-extern "C" int isle_hip_tdf_begin(isle_ctx* c, uint64_t V, uint64_t D, uint64_t reserve_entries, uint64_t piece_bytes) {
-  if (!c) return ISLE_E_ARG;
-  ISLECHK(isle_enter(c));
+// what the three ways to open a text stream share: the shape, the piece size, the store's reservation (none: a counting stream), the
+// page-locked buffers, the device state.  The stream is not yet open when this returns.
+static int tdf_open_stream(isle_ctx* c, const char* who, uint64_t V, uint64_t D, uint64_t reserve_entries, uint64_t piece_bytes) {
   IsleFeed& f = c->feed;
-  f.release();  // an open text stream, or an open feed, is discarded
-  if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "tdf_begin: single-rank only");
-  ISLECHK(shape_ok(c, "tdf_begin: ", V, D, false));
+  ISLECHK(shape_ok(c, who, V, D, false));
   f.V = V;
   f.D = D;
   f.piece = (piece_bytes && piece_bytes < ISLE_TDF_PIECE) ? piece_bytes : ISLE_TDF_PIECE;
@@ -191,9 +189,101 @@ extern "C" int isle_hip_tdf_begin(isle_ctx* c, uint64_t V, uint64_t D, uint64_t 
   if (e == hipSuccess) rc = k_tdf_open(c);
   if (e != hipSuccess || rc) f.release();
   HIPCHK(c, e);
-  ISLECHK(rc);
+  return rc;
+}
+
+extern "C" int isle_hip_tdf_begin(isle_ctx* c, uint64_t V, uint64_t D, uint64_t reserve_entries, uint64_t piece_bytes) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  IsleFeed& f = c->feed;
+  f.release();  // an open text stream, or an open feed, is discarded
+  if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "tdf_begin: single-rank only");
+  ISLECHK(tdf_open_stream(c, "tdf_begin: ", V, D, reserve_entries, piece_bytes));
   f.open = f.text = true;
   return 0;
+}
+
+// ---- one tdf file onto document shards: the counting stream and its plan (pass 1), the windowed stream (pass 2)
+extern "C" int isle_hip_tdf_begin_counts(isle_ctx* c, uint64_t V, uint64_t D, uint64_t piece_bytes) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  IsleFeed& f = c->feed;
+  f.release();
+  ISLECHK(tdf_open_stream(c, "tdf_begin_counts: ", V, D, 0, piece_bytes));
+  f.counting = true;
+  const int rc = k_tdf_open_counts(c);
+  if (rc) return feed_discard(c, rc);
+  f.open = f.text = true;
+  return 0;
+}
+
+extern "C" int isle_hip_tdf_begin_window(isle_ctx* c, uint64_t V, uint64_t D, uint64_t doc_begin, uint64_t doc_end, uint64_t reserve_entries,
+                                         uint64_t piece_bytes) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  IsleFeed& f = c->feed;
+  f.release();
+  if (doc_begin > doc_end || doc_end > D)
+    return isle_fail(c, ISLE_E_ARG, "tdf_begin_window: documents [%llu, %llu) of %llu", (unsigned long long)doc_begin, (unsigned long long)doc_end, (unsigned long long)D);
+  ISLECHK(tdf_open_stream(c, "tdf_begin_window: ", V, D, reserve_entries, piece_bytes));
+  f.windowed = true;
+  f.w_begin = doc_begin;
+  f.w_end = doc_end;
+  f.open = f.text = true;
+  return 0;
+}
+
+// The end of a counting stream.  Collective with several ranks: every collective below is issued by all ranks or by none (ranks that
+// disagree on agree_tag all leave behind the first).
+extern "C" int isle_hip_tdf_finalize_counts(isle_ctx* c, int parts, uint64_t agree_tag, uint64_t* bounds, uint32_t* doc_lines, uint64_t* lines_local,
+                                            uint64_t* lines_global) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  IsleFeed& f = c->feed;
+  if (!f.open || !f.text || !f.counting) return isle_fail(c, ISLE_E_ARG, "tdf_finalize_counts: no open counting stream (isle_hip_tdf_begin_counts)");
+  if (parts < 1 || !bounds) {
+    f.release();
+    return isle_fail(c, ISLE_E_ARG, "tdf_finalize_counts: parts < 1 or null bounds");
+  }
+  ISLECHK(tdf_settle(c, "tdf_finalize_counts"));
+  if (f.known.carry) {  // the bytes behind the last '\n': the last line
+    const int rc = k_tdf_piece(c, nullptr, 0, true);
+    if (rc) return feed_discard(c, rc);
+    ISLECHK(tdf_settle(c, "tdf_finalize_counts"));
+  }
+  const uint64_t local = f.known.seen;
+  uint64_t global = local;
+  k_tdf_release_text(c);
+  if (c->multi()) {
+    DevBuf<uint64_t> word;
+    StreamDrain drain(c);
+    hipError_t e = word.reserve(2);
+    if (e != hipSuccess) f.release();
+    HIPCHK(c, e);
+    uint64_t tag[2] = {agree_tag, ~agree_tag};  // max over (v, ~v): the largest and the complement of the smallest
+    int rc = allreduce_host<uint64_t>(c, tag, 2, word.p, true);
+    if (rc) return feed_discard(c, rc);
+    if (tag[0] != ~tag[1]) {
+      f.release();
+      return isle_fail(c, ISLE_E_COMM, "tdf_finalize_counts: ranks disagree on agree_tag (min %llu, max %llu): not the same file", (unsigned long long)~tag[1],
+                       (unsigned long long)tag[0]);
+    }
+    rc = allreduce_sum<uint32_t>(c, f.t_doc_cnt.p, (size_t)f.D);
+    if (rc == 0) rc = allreduce_host<uint64_t>(c, &global, 1, word.p);
+    if (rc) return feed_discard(c, rc);
+  }
+  if (lines_local) *lines_local = local;
+  if (lines_global) *lines_global = global;
+  if (global > 0xffffffffull) {  // a summed 32-bit counter may have wrapped
+    f.release();
+    return isle_fail(c, ISLE_E_ARG, "tdf_finalize_counts: %llu lines, more than 4294967295: the per-document counters are 32 bits wide", (unsigned long long)global);
+  }
+  int rc = k_tdf_plan(c, global, parts, bounds);
+  if (rc == 0 && doc_lines) {
+    const hipError_t e = hipMemcpy(doc_lines, f.t_doc_cnt.p, (size_t)f.D * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = isle_fail(c, ISLE_E_HIP, "tdf_finalize_counts: %s", hipGetErrorString(e));
+  }
+  return feed_discard(c, rc);
 }
 
 extern "C" int isle_hip_tdf_acquire(isle_ctx* c, char** buf, uint64_t* cap) {
@@ -236,23 +326,25 @@ extern "C" int isle_hip_tdf_write(isle_ctx* c, const char* bytes, uint64_t nbyte
 
 extern "C" int isle_hip_tdf_finalize(isle_ctx* c, uint64_t max_entries, uint64_t* entries_read, uint64_t* nnz) {
   FEED_OPEN("tdf_finalize", true);
+  if (f.counting) return isle_fail(c, ISLE_E_ARG, "tdf_finalize: the open stream counts lines (isle_hip_tdf_finalize_counts ends it)");
   ISLECHK(tdf_settle(c, "tdf_finalize"));
   if (f.known.carry) {  // the text does not end in '\n': what is left is its last line
     const int rc = k_tdf_piece(c, nullptr, 0, true);
     if (rc) return feed_discard(c, rc);
     ISLECHK(tdf_settle(c, "tdf_finalize"));
   }
-  const uint64_t nread = f.known.entries;
+  const uint64_t nread = f.known.seen;  // the valid lines of the whole text: on an ordinary stream also the entries held
+  const uint64_t doc_offset = f.windowed ? f.w_begin : 0, docs_global = f.windowed ? f.D : 0;
   const int refused = entries_ok(c, "tdf_finalize", nread, max_entries);
   if (refused) {
     f.release();
     return refused;
   }
   c->a_ready = false;  // a_cnt / a_rows / a_offs are rewritten from here
-  f.n = nread;
+  f.n = f.known.entries;
   k_tdf_release_text(c);
   ISLECHK(feed_discard(c, k_feed_finalize(c)));
-  return install_A(c, 0, 0, nread, entries_read, nnz);
+  return install_A(c, doc_offset, docs_global, nread, entries_read, nnz);
 }
 
 extern "C" int isle_hip_get_A(isle_ctx* c, float* counts, uint32_t* rows, int64_t* offs) {

@@ -151,9 +151,10 @@ constexpr uint64_t ISLE_FEED_CHUNK = 1ull << 26;  // entries per upload + launch
 constexpr uint64_t ISLE_TDF_PIECE = 16ull << 20;  // bytes of text per piece: of 1, 4, 16 and 64 MiB the best wall, level with 4 MiB, at less device time (profiles/tdf_stream_c2.jsonl)
 struct IsleTdfState {
   unsigned long long lines;    // '\n' seen since tdf_begin: the 0-based number of the line the carry begins
-  unsigned long long entries;  // entries in the store
+  unsigned long long entries;  // entries in the store: the held ones (a windowed stream holds those of its documents, a counting stream none)
   unsigned long long carry;    // bytes of the unfinished last line
   unsigned long long err;      // all ones, or (0-based line << 3) | kind of the first bad line (ing_parse_k)
+  unsigned long long seen;     // valid lines of the whole text so far; == entries on an ordinary stream
 };
 struct IsleFeed {
   bool open = false;
@@ -162,7 +163,10 @@ struct IsleFeed {
   uint64_t pieces = 0;         // non-empty pieces committed
   bool acquired = false;       // t_pin[pieces & 1] is with the caller
   bool in_flight = false;      // a piece is queued whose state has not been read back
-  IsleTdfState known = {0, 0, 0, ~0ull};  // t_state after the last piece that was waited for
+  bool counting = false;       // text stream of isle_hip_tdf_begin_counts: lines per document into t_doc_cnt, no entry store, no line refused
+  bool windowed = false;       // text stream of isle_hip_tdf_begin_window: every line checked, the entries of documents [w_begin, w_end) held
+  uint64_t w_begin = 0, w_end = 0;
+  IsleTdfState known = {0, 0, 0, ~0ull, 0};  // t_state after the last piece that was waited for
   PinBuf t_pin[2], t_back;
   hipEvent_t t_done = nullptr;
   DevBuf<unsigned char> t_text[2];
@@ -170,6 +174,8 @@ struct IsleFeed {
   DevBuf<uint32_t> t_tile_cnt;
   DevBuf<int64_t> t_tile_off;
   DevBuf<uint64_t> t_line_start;
+  DevBuf<uint32_t> t_doc_cnt;            // counting stream: valid lines per document, D counters
+  DevBuf<unsigned long long> t_seen;     // counting / windowed stream: valid lines of the piece in flight
   uint64_t V = 0, D = 0;
   uint64_t n = 0;        // entries held (zero counts are not)
   uint64_t offered = 0;  // entries offered since feed_begin, skipped ones included: the ordinal an error names
@@ -624,6 +630,8 @@ int k_feed_chunk(isle_ctx* c, const uint32_t* docs, const uint32_t* words, const
 int k_feed_finalize(isle_ctx* c);
 int k_tdf_open(isle_ctx* c);                                                      // the device state and the event of a text stream
 int k_tdf_piece(isle_ctx* c, const char* bytes, uint64_t n, bool last_line);      // queues [carry | n bytes from page-locked memory]; last_line: the carry alone
+int k_tdf_open_counts(isle_ctx* c);                                               // the zeroed table of a counting stream
+int k_tdf_plan(isle_ctx* c, uint64_t lines_global, int parts, uint64_t* bounds);  // the counting stream's table (summed over the ranks) -> parts + 1 bounds
 int k_tdf_wait(isle_ctx* c);                                                      // -> IsleFeed::known is the state after everything queued
 void k_tdf_release_text(isle_ctx* c);
 

@@ -10,6 +10,10 @@
 //   feed_key_k                       binary (doc, word, count) triples in batches (isle_hip_feed_*) instead of lines
 //   tdf_advance_k                    the same text in pieces cut anywhere (isle_hip_tdf_*): the same kernels over the complete lines of
 //                                    [carry | piece], the entries packed behind those held; the rest becomes the next carry
+//   tdf_window_k                     the windowed stream (isle_hip_tdf_begin_window): every line checked as above, then only the entries of
+//                                    documents [doc_begin, doc_end) stay valid, keyed by doc - doc_begin
+//   tdf_doc_count_k / tdf_plan_k     the counting stream (isle_hip_tdf_begin_counts): valid lines per document, one atomic add per run of
+//                                    equal documents within a wave; then the bounds of `parts` shards balanced by lines (stage_host.h plan_bound)
 //
 // Deviations from the reference parser, shared with the host parser of isle_amd/host/prestage.h: trailing blanks do not
 // leak into the next line (the reference keeps its was_whitespace flag across '\n'), blank lines are skipped, a bad
@@ -22,6 +26,7 @@
 
 #include "common.h"
 #include "scan.h"
+#include "stage_host.h"
 
 namespace {
 
@@ -466,13 +471,13 @@ hipError_t feed_stage(IsleFeed& f, uint64_t m, uint64_t scan_n) {
 }  // namespace
 
 void IsleFeed::release() {
-  open = text = acquired = in_flight = false;
-  n = offered = piece = pieces = 0;
-  known = {0, 0, 0, ~0ull};
+  open = text = acquired = in_flight = counting = windowed = false;
+  n = offered = piece = pieces = w_begin = w_end = 0;
+  known = {0, 0, 0, ~0ull, 0};
   if (t_done) (void)hipEventDestroy(t_done);
   t_done = nullptr;
   t_text[0].release(); t_text[1].release(); t_state.release(); t_tile_cnt.release(); t_tile_off.release(); t_line_start.release();
-  t_pin[0].release(); t_pin[1].release(); t_back.release();
+  t_pin[0].release(); t_pin[1].release(); t_back.release(); t_doc_cnt.release(); t_seen.release();
   key.release(); cnt.release(); in_docs.release(); in_words.release(); in_cnt.release(); t_key.release(); t_cnt.release(); t_valid.release();
   t_at.release(); t_scratch.release(); t_err.release();
 }
@@ -522,14 +527,15 @@ int k_feed_chunk(isle_ctx* c, const uint32_t* docs, const uint32_t* words, const
 int k_feed_finalize(isle_ctx* c) {
   IsleFeed& f = c->feed;
   TimeScope ts(c, ISLE_T_INGEST);
+  const uint64_t D = f.windowed ? f.w_end - f.w_begin : f.D;  // a windowed stream's keys are doc - w_begin: fewer document bits to sort
   int wbits, dbits;
-  ing_key_bits(f.V, f.D, &wbits, &dbits);
+  ing_key_bits(f.V, D, &wbits, &dbits);
   f.in_docs.release(); f.in_words.release(); f.in_cnt.release(); f.t_valid.release(); f.t_at.release(); f.t_scratch.release();
   HIPCHK(c, f.key.reserve(1));  // (a feed without entries: the kernels below still take pointers)
   HIPCHK(c, f.cnt.reserve(1));
   HIPCHK(c, f.t_key.reserve(f.n ? f.n : 1));
   HIPCHK(c, f.t_cnt.reserve(f.n ? f.n : 1));
-  return ing_sort_dedup_install(c, f.V, f.D, wbits, dbits, f.key.p, f.cnt.p, f.t_key.p, f.t_cnt.p, f.n);
+  return ing_sort_dedup_install(c, f.V, D, wbits, dbits, f.key.p, f.cnt.p, f.t_key.p, f.t_cnt.p, f.n);
 }
 
 // ---------------- tdf text in pieces cut anywhere (isle_hip_tdf_*) ----------------------------------------------------------------------
@@ -538,18 +544,77 @@ int k_feed_finalize(isle_ctx* c) {
 namespace {
 
 // What stands behind the last '\n' of text[0, L) goes to the front of the other text buffer, and the stream's state moves on: the last
-// kernel of a piece, the only one that writes the state's counts (no other thread of it reads them).
+// kernel of a piece, the only one that writes the state's counts (no other thread of it reads them).  nvalid: the entries the piece added to
+// the store (null: none); nseen: its valid lines where they are not the same number (the windowed and the counting stream), else null.
 __global__ __launch_bounds__(IT) void tdf_advance_k(const unsigned char* __restrict__ text, uint64_t L, const uint64_t* __restrict__ line_start,
-                                                     const int64_t* __restrict__ nnl, const int64_t* __restrict__ nvalid, int last_line,
-                                                     unsigned char* __restrict__ next, IsleTdfState* __restrict__ st) {
+                                                     const int64_t* __restrict__ nnl, const int64_t* __restrict__ nvalid,
+                                                     const unsigned long long* __restrict__ nseen, int last_line, unsigned char* __restrict__ next,
+                                                     IsleTdfState* __restrict__ st) {
   const uint64_t from = last_line ? L : line_start[*nnl];
   const uint64_t len = L - from;
   for (uint64_t i = (uint64_t)blockIdx.x * IT + threadIdx.x; i < len; i += (uint64_t)gridDim.x * IT) next[i] = text[from + i];
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     st->lines += last_line ? 1ull : (unsigned long long)*nnl;
-    st->entries += (unsigned long long)*nvalid;
+    const unsigned long long held = nvalid ? (unsigned long long)*nvalid : 0ull;  // (a counting stream holds nothing)
+    st->entries += held;
+    st->seen += nseen ? *nseen : held;  // an ordinary stream holds every valid line
     st->carry = len;
   }
+}
+
+// The windowed stream, between ing_parse_k and the scan: valid[l] is ok(l) on entry and ok(l) && doc in [doc_begin, doc_end) on exit, the
+// key of a line that stays rebased to doc - doc_begin.  *nseen (zeroed per piece) receives the number of ok lines, one add per workgroup.
+__global__ __launch_bounds__(IT) void tdf_window_k(uint64_t* __restrict__ key, uint32_t* __restrict__ valid, uint64_t nmax, int wbits, uint64_t doc_begin,
+                                                    uint64_t doc_end, unsigned long long* __restrict__ nseen) {
+  const uint64_t l = (uint64_t)blockIdx.x * IT + threadIdx.x;
+  const bool ok = l < nmax && valid[l] != 0u;
+  if (ok) {
+    const uint64_t k = key[l], doc = k >> wbits;
+    if (doc >= doc_begin && doc < doc_end) key[l] = ((doc - doc_begin) << wbits) | (k & ((1ull << wbits) - 1ull));
+    else valid[l] = 0u;
+  }
+  const int n = __syncthreads_count(ok ? 1 : 0);
+  if (threadIdx.x == 0 && n) atomicAdd(nseen, (unsigned long long)n);
+}
+
+// The counting stream, in place of the scan and ing_pack_k: one line per lane.  Among the valid lanes of a wave a run is a maximal sequence
+// of lanes, consecutive among the valid ones, that share a document; an invalid or blank line in between belongs to no run and ends none.
+// The head of a run (no valid lane before it in the wave, or another document there) adds the run's length to the document's counter: one
+// 32-bit atomic per run instead of one per line on the same address (document-major text puts about a hundred lines of a document in a
+// row).  The wave as the unit of aggregation is a choice no measurement stands behind.  *nseen as in tdf_window_k.
+__global__ __launch_bounds__(IT) void tdf_doc_count_k(const uint64_t* __restrict__ key, const uint32_t* __restrict__ valid, uint64_t nmax, int wbits,
+                                                       uint32_t* __restrict__ doc_cnt, unsigned long long* __restrict__ nseen) {
+  const uint64_t l = (uint64_t)blockIdx.x * IT + threadIdx.x;
+  const int lane = threadIdx.x & (ISLE_WAVE - 1);
+  const bool ok = l < nmax && valid[l] != 0u;
+  const uint32_t doc = ok ? (uint32_t)(key[l] >> wbits) : 0u;  // < D <= 0xfffffff0 (ing_parse_line)
+  const unsigned long long vmask = __ballot(ok);
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const unsigned long long before = vmask & below;
+  const int prev = before ? 63 - __clzll((long long)before) : lane;  // the valid lane before this one
+  const uint32_t prev_doc = (uint32_t)__shfl((int)doc, prev);
+  const bool head = ok && (!before || prev_doc != doc);
+  const unsigned long long hmask = __ballot(head);
+  if (head) {
+    const unsigned long long above = hmask & ~((2ull << lane) - 1ull);  // (lane 63: 2 << 63 wraps to 0, no lane is above)
+    const unsigned long long upto = above ? (1ull << (__ffsll((long long)above) - 1)) - 1ull : ~0ull;  // the lanes below the next head
+    atomicAdd(&doc_cnt[doc], (uint32_t)__popcll(vmask & upto & ~below));
+  }
+  const int n = __syncthreads_count(ok ? 1 : 0);
+  if (threadIdx.x == 0 && n) atomicAdd(nseen, (unsigned long long)n);
+}
+
+// bounds[p], 0 < p < parts: one thread per inner bound (stage_host.h plan_bound on the offsets of the line counts); bounds[0] = 0,
+// bounds[parts] = D.  offs[D] is the number of lines of the whole text.
+__global__ __launch_bounds__(IT) void tdf_plan_k(const int64_t* __restrict__ offs, uint64_t D, int parts, unsigned long long* __restrict__ bounds) {
+  const int p = (int)(blockIdx.x * IT + threadIdx.x);
+  if (p > parts) return;
+  if (p == 0 || p == parts) {
+    bounds[p] = p ? D : 0ull;
+    return;
+  }
+  const uint64_t before = p > 1 ? plan_bound(offs, D, p - 1, parts, 0) : 0;
+  bounds[p] = plan_bound(offs, D, p, parts, before);
 }
 
 }  // namespace
@@ -558,8 +623,9 @@ int k_tdf_open(isle_ctx* c) {
   IsleFeed& f = c->feed;
   HIPCHK(c, f.t_state.reserve(1));
   HIPCHK(c, f.t_back.reserve(sizeof(IsleTdfState)));
+  HIPCHK(c, f.t_seen.reserve(1));
   HIPCHK(c, hipEventCreateWithFlags(&f.t_done, hipEventDisableTiming));
-  f.known = {0, 0, 0, ~0ull};
+  f.known = {0, 0, 0, ~0ull, 0};
   HIPCHK(c, hipMemcpyAsync(f.t_state.p, &f.known, sizeof(IsleTdfState), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
@@ -591,7 +657,7 @@ int k_tdf_piece(isle_ctx* c, const char* bytes, uint64_t n, bool last_line) {
   const uint64_t nmax = last_line ? 1 : n, ntiles = (L + TILE_BYTES - 1) / TILE_BYTES;
   HIPCHK(c, grow_keeping(c->stream, f.t_text[s], carry, L + 16));  // (fits unless a line outgrows its pieces)
   HIPCHK(c, grow_keeping(c->stream, f.t_text[s ^ 1], 0, L + 16));  // the next carry: at most all of this text
-  HIPCHK(c, feed_room(c->stream, f, f.known.entries, n / 6 + 1));
+  if (!f.counting) HIPCHK(c, feed_room(c->stream, f, f.known.entries, n / 6 + 1));
   HIPCHK(c, f.t_tile_cnt.reserve(ntiles));
   HIPCHK(c, f.t_tile_off.reserve(ntiles + 1));
   HIPCHK(c, f.t_line_start.reserve(n + 2));
@@ -605,18 +671,63 @@ int k_tdf_piece(isle_ctx* c, const char* bytes, uint64_t n, bool last_line) {
     hipLaunchKernelGGL(ing_parse_k, dim3(cdiv((long)nmax, IT)), dim3(IT), 0, c->stream, text, L, f.t_line_start.p, last_line ? nullptr : nnl, (uint64_t)0, nmax,
                        (int)last_line, f.V, f.D, wbits, f.t_key.p, f.t_cnt.p, f.t_valid.p, &f.t_state.p->err, &f.t_state.p->lines);
     LAUNCH_CHECK(c);
-    HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, f.t_valid.p, nmax, f.t_at.p, f.t_scratch.p)));
-    hipLaunchKernelGGL(ing_pack_k, dim3(cdiv((long)nmax, IT)), dim3(IT), 0, c->stream, f.t_key.p, f.t_cnt.p, f.t_valid.p, f.t_at.p, nmax, f.key.p, f.cnt.p,
-                       &f.t_state.p->entries);
-    LAUNCH_CHECK(c);
+    const bool own_seen = f.counting || f.windowed;  // the piece's valid lines are not the entries it adds to the store
+    if (own_seen) HIPCHK(c, hipMemsetAsync(f.t_seen.p, 0, sizeof(unsigned long long), c->stream));
+    if (f.counting) {
+      hipLaunchKernelGGL(tdf_doc_count_k, dim3(cdiv((long)nmax, IT)), dim3(IT), 0, c->stream, f.t_key.p, f.t_valid.p, nmax, wbits, f.t_doc_cnt.p, f.t_seen.p);
+      LAUNCH_CHECK(c);
+    } else {
+      if (f.windowed) {
+        hipLaunchKernelGGL(tdf_window_k, dim3(cdiv((long)nmax, IT)), dim3(IT), 0, c->stream, f.t_key.p, f.t_valid.p, nmax, wbits, f.w_begin, f.w_end, f.t_seen.p);
+        LAUNCH_CHECK(c);
+      }
+      HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, f.t_valid.p, nmax, f.t_at.p, f.t_scratch.p)));
+      hipLaunchKernelGGL(ing_pack_k, dim3(cdiv((long)nmax, IT)), dim3(IT), 0, c->stream, f.t_key.p, f.t_cnt.p, f.t_valid.p, f.t_at.p, nmax, f.key.p, f.cnt.p,
+                         &f.t_state.p->entries);
+      LAUNCH_CHECK(c);
+    }
     const unsigned nb = (unsigned)std::min<uint64_t>((L + IT - 1) / IT, 1024);
-    hipLaunchKernelGGL(tdf_advance_k, dim3(nb), dim3(IT), 0, c->stream, text, L, f.t_line_start.p, nnl, f.t_at.p + nmax, (int)last_line, f.t_text[s ^ 1].p,
-                       f.t_state.p);
+    hipLaunchKernelGGL(tdf_advance_k, dim3(nb), dim3(IT), 0, c->stream, text, L, f.t_line_start.p, nnl, f.counting ? nullptr : f.t_at.p + nmax,
+                       own_seen ? f.t_seen.p : nullptr, (int)last_line, f.t_text[s ^ 1].p, f.t_state.p);
     LAUNCH_CHECK(c);
   }
   HIPCHK(c, hipMemcpyAsync(f.t_back.p, f.t_state.p, sizeof(IsleTdfState), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipEventRecord(f.t_done, c->stream));
   f.in_flight = true;
   ++f.pieces;
+  return 0;
+}
+
+// ---------------- the counting stream's table and the plan from it ------------------------------------------------------------------------
+int k_tdf_open_counts(isle_ctx* c) {
+  IsleFeed& f = c->feed;
+  HIPCHK(c, f.t_doc_cnt.reserve(f.D));
+  HIPCHK(c, hipMemsetAsync(f.t_doc_cnt.p, 0, f.D * sizeof(uint32_t), c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// t_doc_cnt holds the lines per document of the whole text (summed over the ranks).  Their exclusive scan and tdf_plan_k on the device;
+// parts + 1 bounds travel to the host.  offs[D], the scan's total, is lines_global: the caller has checked that it fits 32 bits, so no
+// counter of the table has wrapped.
+int k_tdf_plan(isle_ctx* c, uint64_t lines_global, int parts, uint64_t* bounds) {
+  IsleFeed& f = c->feed;
+  TimeScope ts(c, ISLE_T_INGEST);
+  DevBuf<int64_t> offs, scratch;
+  DevBuf<unsigned long long> bd;
+  HIPCHK(c, offs.reserve(f.D + 1));
+  HIPCHK(c, scratch.reserve(isle_scan_scratch(f.D + 16) + 8));
+  HIPCHK(c, bd.reserve((size_t)parts + 1));
+  HIPCHK(c, (isle_scan::exclusive_scan<uint32_t, int64_t>(c->stream, f.t_doc_cnt.p, f.D, offs.p, scratch.p)));
+  hipLaunchKernelGGL(tdf_plan_k, dim3(cdiv((long)parts + 1, IT)), dim3(IT), 0, c->stream, offs.p, f.D, parts, bd.p);
+  LAUNCH_CHECK(c);
+  int64_t total = 0;
+  std::vector<unsigned long long> h((size_t)parts + 1);
+  HIPCHK(c, hipMemcpyAsync(h.data(), bd.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&total, offs.p + f.D, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if ((uint64_t)total != lines_global)
+    return isle_fail(c, ISLE_E_NUMERIC, "tdf_finalize_counts: the table sums to %lld lines, the streams counted %llu", (long long)total, (unsigned long long)lines_global);
+  for (int p = 0; p <= parts; ++p) bounds[p] = (uint64_t)h[p];
   return 0;
 }

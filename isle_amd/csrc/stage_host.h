@@ -206,6 +206,28 @@ inline SlotChunk select_chunk(uint64_t nslots, uint64_t chunk_slots, uint64_t i)
   return s;
 }
 
+// ---- document bounds of `parts` shards balanced by weight (isle_hip_plan_shards: entries; the tdf counting stream, tdf_plan_k: lines) ----------
+// offs: num_docs + 1 ascending offsets of the weights, offs[0] = 0, offs[num_docs] = total.  Bound p (0 < p < parts) is the first document d
+// with offs[d] >= floor(total * p / parts), never above num_docs and never below `before`, the bound p - 1.  The target is formed without
+// 128-bit arithmetic: total = q * parts + r gives q * p + floor(r * p / parts), and r * p < parts * p < 2^62.  Targets ascend with p, so the
+// chain of `before` equals max(bound p - 1 found alone, bound p found alone): a thread per bound computes both.
+ISLE_STAGE_HD inline int64_t plan_target(int64_t total, int p, int parts) {
+  const int64_t q = total / parts, r = total % parts;
+  return q * p + (r * p) / parts;
+}
+ISLE_STAGE_HD inline uint64_t plan_bound(const int64_t* offs, uint64_t num_docs, int p, int parts, uint64_t before) {
+  const int64_t target = plan_target(offs[num_docs], p, parts);
+  uint64_t lo = 0, hi = num_docs + 1;  // the first d in [0, num_docs] with offs[d] >= target, num_docs + 1 if none
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (offs[mid] < target) lo = mid + 1;
+    else hi = mid;
+  }
+  uint64_t d = lo > num_docs ? num_docs : lo;
+  if (d < before) d = before;
+  return d;
+}
+
 // ---- corpus diagnostics and what reads a model ------------------------------------------------------------------------------------------------
 // The loop of src/sparseMatrix.cpp:198-208 moves its mark from p to p + max(rem(p), m), rem(p) = distance from p to the end of
 // its run, and counts every move that lands before n.  r: the run holding p, rb: the run's first position.  Runs are not empty, m >= 2.

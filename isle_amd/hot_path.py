@@ -5,6 +5,7 @@ Method names follow the reference methods they replace (ISLE::FPSparseMatrix<flo
 numpy arrays in, numpy arrays out; all device work happens inside libisle_hip.so.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -196,7 +197,7 @@ class HotPath:
     def comm_init(self, world, rank, uid):
         uid = np.ascontiguousarray(uid, np.uint8)
         self._chk(self._lib.isle_hip_comm_init(self._h, world, rank, _p(uid)))
-        self._world = int(world)
+        self._world, self._rank = int(world), int(rank)
 
     def comm_init_host(self, world, rank, exchange):
         """Rehearsal transport (tests only; include/isle_hip.h): every collective is staged through host memory and
@@ -218,7 +219,7 @@ class HotPath:
 
         self._xchg_cb = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_int)(tramp)
         self._chk(self._lib.isle_hip_comm_init_host(self._h, world, rank, C.cast(self._xchg_cb, C.c_void_p), None))
-        self._world = int(world)
+        self._world, self._rank = int(world), int(rank)
 
     @staticmethod
     def gloo_exchange(dist, world, rank):
@@ -334,32 +335,123 @@ class HotPath:
         self._a_shape = self._feed_shape + (int(nz.value),)
         return dict(entries_read=int(nr.value), nnz=int(nz.value))
 
+    def _pump(self, f, b=0, e=None):
+        """The open file f (unbuffered) into the open text stream, read straight into the stream's page-locked buffers (readinto, no copy in
+        between).  With e: the lines of the byte range [b, e) only, those whose first byte s has b <= s < e (the rule of tdf_pump::file_range,
+        isle_amd/host/tdf_pump.h): with b > 0 the bytes through the first newline at or after b - 1 are another range's, and the last line ends
+        with the first newline at a position >= e - 1 or with the file.  -> bytes committed."""
+        if e is not None and b >= e:
+            return 0
+        left, at = b"", b
+        if e is not None and b > 0:
+            f.seek(b - 1)
+            pos = b - 1
+            while True:
+                chunk = f.read(4096)
+                if not chunk:
+                    return 0                    # the file ends inside the line that began before b
+                i = chunk.find(b"\n")
+                if i >= 0:
+                    at, left = pos + i + 1, chunk[i + 1:]
+                    break
+                pos += len(chunk)
+            if at >= e:
+                return 0
+        buf, cap = C.c_void_p(), C.c_uint64()
+        total, done = 0, False
+        while not done:
+            self._chk(self._lib.isle_hip_tdf_acquire(self._h, C.byref(buf), C.byref(cap)))
+            got = 0
+            try:
+                view = memoryview((C.c_char * cap.value).from_address(buf.value)).cast("B")
+                while got < cap.value and not done:      # a read may return fewer bytes than asked for; only 0 is the end of the file
+                    if left:
+                        r = min(len(left), cap.value - got)
+                        view[got:got + r] = left[:r]
+                        left = left[r:]
+                    else:
+                        r = f.readinto(view[got:])
+                        if not r:
+                            done = True
+                            break
+                    if e is not None:
+                        start = got + max(e - 1 - at, 0)  # of these r bytes, the first that may be the closing newline
+                        nl = bytes(view[start:got + r]).find(b"\n") if start < got + r else -1
+                        if nl >= 0:
+                            r, done = start + nl + 1 - got, True
+                    got += r
+                    at += r
+                del view
+            except BaseException:           # a read error: the buffer goes back; the stream stays open until the next begin discards it
+                self._lib.isle_hip_tdf_commit(self._h, 0)
+                raise
+            self._chk(self._lib.isle_hip_tdf_commit(self._h, got))
+            total += got
+        return total
+
     def ingest_tdf_file(self, path, vocab_size, num_docs, max_entries=0, _piece_bytes=0):
         """ingest_tdf of a file's bytes without holding them: the file is read straight into the stream's page-locked buffers (readinto,
         no copy in between), piece by piece, each piece parsed on the device while the next is read.  -> dict(entries_read, nnz).
         A file that cannot be opened opens no stream; after a read error the stream stays open, holding what was read, until the next
         tdf_begin or feed_begin discards it."""
-        buf, cap = C.c_void_p(), C.c_uint64()
         with open(path, "rb", buffering=0) as f:      # before tdf_begin: a file that is not there opens no stream and discards no feed
             self.tdf_begin(vocab_size, num_docs, _piece_bytes=_piece_bytes)
-            eof = False
-            while not eof:
-                self._chk(self._lib.isle_hip_tdf_acquire(self._h, C.byref(buf), C.byref(cap)))
-                got = 0
-                try:
-                    view = memoryview((C.c_char * cap.value).from_address(buf.value)).cast("B")
-                    while got < cap.value:      # a read may return fewer bytes than asked for; only 0 is the end of the file
-                        r = f.readinto(view[got:])
-                        if not r:
-                            eof = True
-                            break
-                        got += r
-                    del view
-                except BaseException:           # a read error: the buffer goes back; the stream stays open until the next begin discards it
-                    self._lib.isle_hip_tdf_commit(self._h, 0)
-                    raise
-                self._chk(self._lib.isle_hip_tdf_commit(self._h, got))
+            self._pump(f)
         return self.tdf_finalize(max_entries)
+
+    # ---- one tdf file onto document shards: counting stream and plan (pass 1), windowed stream (pass 2) --------------------------------
+    def tdf_begin_counts(self, vocab_size, num_docs, _piece_bytes=0):
+        """Opens a text stream that counts the valid lines per document and holds no entry (isle_hip_tdf_begin_counts); tdf_write feeds it."""
+        self._chk(self._lib.isle_hip_tdf_begin_counts(self._h, int(vocab_size), int(num_docs), int(_piece_bytes)))
+        self._feed_shape = (int(vocab_size), int(num_docs))
+
+    def tdf_finalize_counts(self, parts, agree_tag=0, fetch_doc_lines=False):
+        """Ends the counting stream; collective under a communicator (agree_tag, the file's size, must be alike on all ranks).
+        -> dict(bounds (parts + 1, int64: shard p holds documents bounds[p] .. bounds[p + 1], balanced by lines), lines_local, lines_global,
+        doc_lines (uint32 per document over all ranks, or None))."""
+        bounds = np.zeros(int(parts) + 1, np.uint64)
+        doc_lines = np.zeros(self._feed_shape[1], np.uint32) if fetch_doc_lines else None
+        ll, lg = C.c_uint64(), C.c_uint64()
+        self._chk(self._lib.isle_hip_tdf_finalize_counts(self._h, int(parts), int(agree_tag), _p(bounds), _p(doc_lines) if fetch_doc_lines else None,
+                                                         C.byref(ll), C.byref(lg)))
+        return dict(bounds=bounds.astype(np.int64), lines_local=int(ll.value), lines_global=int(lg.value), doc_lines=doc_lines)
+
+    def tdf_begin_window(self, vocab_size, num_docs, doc_begin, doc_end, reserve_entries=0, _piece_bytes=0):
+        """Opens a text stream over the whole text that keeps the entries of documents doc_begin <= doc < doc_end (0-based) only
+        (isle_hip_tdf_begin_window); tdf_write feeds it, tdf_finalize ends it: A becomes those columns of what ingest_tdf gives."""
+        self._chk(self._lib.isle_hip_tdf_begin_window(self._h, int(vocab_size), int(num_docs), int(doc_begin), int(doc_end), int(reserve_entries),
+                                                      int(_piece_bytes)))
+        self._feed_shape = (int(vocab_size), int(doc_end) - int(doc_begin))
+
+    def ingest_tdf_file_sharded(self, path, vocab_size, num_docs, max_entries=0, parts=None, part=None, _piece_bytes=0):
+        """One tdf file onto document shards in two passes, no rank holding the corpus.  Under a communicator parts = world and part =
+        rank: pass 1 counts the lines per document over this rank's byte range of the file (collective), pass 2 streams the whole file and
+        keeps the documents bounds[part] .. bounds[part + 1].  Without a communicator parts and part are given and pass 1 reads the whole
+        file.  A becomes the shard, with its doc_offset and docs_global.  -> dict(bounds, entries_read, nnz, lines_local, lines_global)."""
+        world = getattr(self, "_world", 1)
+        rank = getattr(self, "_rank", 0)
+        if world > 1:
+            if parts not in (None, world) or part not in (None, rank):
+                raise ValueError("under a communicator parts and part are the world size and the rank")
+            parts, part = world, rank
+        elif parts is None or part is None:
+            raise ValueError("without a communicator parts and part must be given")
+        if not 0 <= int(part) < int(parts):
+            raise ValueError("part %r of %r" % (part, parts))
+        with open(path, "rb", buffering=0) as f:
+            size = os.fstat(f.fileno()).st_size
+            self.tdf_begin_counts(vocab_size, num_docs, _piece_bytes=_piece_bytes)
+            if world > 1:
+                self._pump(f, size * rank // world, size * (rank + 1) // world)
+            else:
+                self._pump(f)
+            plan = self.tdf_finalize_counts(parts, agree_tag=size)
+            b = plan["bounds"]
+            f.seek(0)
+            self.tdf_begin_window(vocab_size, num_docs, b[part], b[part + 1], _piece_bytes=_piece_bytes)
+            self._pump(f)
+        res = self.tdf_finalize(max_entries)
+        return dict(res, bounds=b, lines_local=plan["lines_local"], lines_global=plan["lines_global"])
 
     def upload_coo(self, V, D, docs, words, counts, batch=None):
         """feed_begin + feed + feed_finalize for triples held in arrays, fed in slices of `batch` entries (None: one call).
