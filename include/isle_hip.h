@@ -336,7 +336,10 @@ int isle_hip_lloyds_sparse(isle_ctx* ctx, int k, const float* centers_in, float*
  * ISLE_E_COMM: the ranks disagree on a replicated count.  The readers of a model (isle_hip_edge_topics,
  * isle_hip_model_top_words, isle_hip_edge_top_words, isle_hip_model_text, isle_hip_edge_topics_text,
  * isle_hip_topic_diversity) involve no collective: each rank runs them for itself on the replicated catch
- * model or on a host model.  Everything else downstream stays "single-rank only" (ISLE_E_ARG).
+ * model, on a host model or on the model the rank loaded itself (isle_hip_load_model_text; ISLE_MODEL_AVG stays refused: nothing
+ * builds the average model there).  Inference and the document reports run on the shards too, see "Document shards" at
+ * isle_hip_infer_resident and isle_hip_doc_report_text.  isle_hip_avg_topic_model, isle_hip_topic_coherence,
+ * isle_hip_log_combinatorial and isle_hip_distinct_top_five stay "single-rank only" (ISLE_E_ARG).
  *
  * isle_hip_catchwords = SparseMatrix::rth_highest_element for every topic (src/sparseMatrix.cpp:491-524,
  * called at src/trainer.cpp:586-590) + SparseMatrix::find_catchwords (:573-595).
@@ -511,11 +514,12 @@ int isle_hip_entry_text(float w, int format, char* out16);
  * limits beside the token's keep every walk of the parser short on a corrupt text, both refused as "bad character": a SPARSE line of
  * more than 4096 bytes (its '\n' excluded), more than 64 consecutive '\r' in a DENSE text.  The line named is the rule; where one line
  * holds several violations the kind named is one of them.
- * ISLE_E_ARG: world > 1, an unknown format, base > 1, vocab 0 or above 0xfffffff0, ncols < 1, text null with nbytes > 0, and the parse
+ * ISLE_E_ARG: an unknown format, base > 1, vocab 0 or above 0xfffffff0, ncols < 1, text null with nbytes > 0, and the parse
  * errors: the FIRST offending line of the file (whatever the launch order) is named, 1-based, with its kind, as
  * "load_model_text: line <n>: <kind>" in isle_hip_last_error; the kinds are "bad character", "too many fields", "too few fields",
  * "id zero or out of range", "token too long", "wrong token count", "wrong line count" (named at the last line).  Where the host
- * parser of model_read.h throws, this call fails.  Device time is booked under ISLE_T_INGEST.  Single rank.
+ * parser of model_read.h throws, this call fails.  Device time is booked under ISLE_T_INGEST.  world > 1: no collective, each rank
+ * loads for itself (the same text on every rank, if the ranks are to agree).
  * isle_hip_get_loaded_model: the loaded model (vocab x ncols column-major) and its size, each nullable; ISLE_E_ARG when nothing is loaded.
  * isle_hip_parse_weight (host only, no context): the n bytes of one <weight> token under `format` into *out; 0, or -1 for a token
  * outside the grammar ("nan" under SPARSE, the empty token, '\r' included) or an unknown format.  The library's one copy of the weight
@@ -591,7 +595,12 @@ int isle_hip_infer(isle_ctx* ctx, uint64_t vocab_size, int num_topics, const flo
  *     count can reach docs x ncols), topic / weight nentries entries, (document, topic) ascending; each nullable.
  *   chunk_docs: documents per pass; the device holds the dense weights of one pass only (chunk_docs x ncols floats), never docs x ncols.
  *     0 = as many as keep them within 1 GiB (at most 2^22).  No result depends on it, bit for bit.
- * ISLE_E_ARG: world > 1, no count matrix, doc_begin > doc_end, doc_end > docs(A), iters < 1, Lf_guess <= 0, the model conditions above.
+ * Document shards (world > 1): doc_begin / doc_end and every output are the rank's own documents', rows numbered from the call's doc_begin.
+ * avg_doc_sz is the CORPUS value over all ranks' documents.  Where the thresholding has not left it behind (B came from the host) the call
+ * all-reduces two 64-bit totals to form it, once per count matrix: isle_hip_infer_resident and isle_hip_avg_doc_sz are then COLLECTIVE,
+ * called by every rank in the same order, a rank without documents included.  A document is computed from its own words, the model and
+ * avg_doc_sz alone: the shards' entries side by side are the single-rank run's, bit for bit.  ISLE_MODEL_AVG is refused.
+ * ISLE_E_ARG: no count matrix, doc_begin > doc_end, doc_end > docs(A), iters < 1, Lf_guess <= 0, the model conditions above.
  * doc_begin == doc_end is valid: no entries, nconverged = 0.  Every argument is checked before any work: after a refusal the context is
  * usable and the entries of the previous call are intact; a call that fails later (ISLE_E_HIP) leaves none (isle_hip_get_infer_entries
  * then returns ISLE_E_ARG, as it does before the first call and after a new A).  top_topic / top_weight of the call stay resident with the
@@ -618,7 +627,9 @@ int isle_hip_get_infer_entries(isle_ctx* ctx, int64_t* doc_offsets, uint32_t* to
  * calling thread while the device formats the next.  sink == NULL: the size query.  A non-zero return of the sink ends the call with
  * ISLE_E_ARG and the context stays usable.  nbytes / nlines (nullable): the size of the text and its lines.  No lines: no sink call, 0.
  * ISLE_E_ARG also for: an unknown `what`, row_begin > row_end, row_end beyond the rows of the last isle_hip_infer_resident, no valid
- * resident result (before the first call, after a new count matrix, after a call that failed), world > 1.
+ * resident result (before the first call, after a new count matrix, after a call that failed).
+ * Document shards (world > 1): no collective.  number_base stays the caller's: a rank whose isle_hip_infer_resident covered documents
+ * [b, e) of its shard passes base + doc_offset(A) + b (isle_hip_counts_shape), and the ranks' texts in rank order are the corpus's file.
  * The call changes nothing resident: a second call gives the same bytes and isle_hip_get_infer_entries returns what it returned before.
  * Device time is booked under ISLE_T_INFER.
  * isle_hip_doc_line_text (host only, no context): one line for the printed numbers doc_number, topic_number (the + base and + 1 already
@@ -648,7 +659,17 @@ int isle_hip_doc_line_text(uint64_t doc_number, uint64_t topic_number, float w, 
  * Domain, delivery, the size query (sink == NULL), a non-zero sink return and "no lines: no sink call" are isle_hip_infer_text's: a
  * printed number >= 0x7fffffff, or a printed weight that is negative, NaN, infinite or >= 2^31, fails the call with ISLE_E_ARG naming the
  * first such line before any byte is delivered; pieces of at most 16 MiB, each non-empty and ending at a line end.
- * ISLE_E_ARG also for: an unknown `what`, doc_begin > doc_end, doc_end > docs(A), world > 1, no count matrix, a call before
+ * Document shards (world > 1): doc_begin / doc_end are the rank's own documents; the document printed is doc_offset(A) + doc + 1, the
+ * number in the corpus, and the domain check applies to it (the refusal names the local and the corpus's document).  With world == 1 the
+ * offset is not applied, whatever the upload said.  CATCHWORDS, TOPIC_SUMS_BY_DOC and TOP_TWO involve no collective: the ranks' texts in
+ * rank order are the corpus's file.  TOPIC_SUMS is one order over all ranks' sums and COLLECTIVE: ALL RANKS MUST ASK FOR TOPIC_SUMS
+ * TOGETHER, in the same order among their collective calls, the size query (sink == NULL) and a rank without documents or sums included.
+ * The keys of every rank's range are all-gathered with their corpus documents, sorted on every rank, and rank q's sink receives lines
+ * [slice(q), slice(q + 1)) of the corpus's L lines, slice(q) = q floor(L / W) + min(q, L mod W): the ranks' texts in rank order are the
+ * single-rank file, equal pairs by document ascending.  nbytes / nlines are the slice's.  L >= 2^32 is ISLE_E_ARG on every rank.  Every
+ * collective of the call precedes its first sink call: a sink that refuses, or a line outside the domain, on one rank leaves the others
+ * to complete.  Device memory of this form: about (W + 1) nmax 12 bytes and the sort's twin, nmax the largest count of a rank; NOT measured.
+ * ISLE_E_ARG also for: an unknown `what`, doc_begin > doc_end, doc_end > docs(A), no count matrix, a call before
  * isle_hip_catchwords (CATCHWORDS) or before isle_hip_topic_model (the other kinds), a call after a new count matrix.
  * The call changes nothing resident: a second call gives the same bytes.  Device time is booked under ISLE_T_POST.
  * isle_hip_top_two_line_text (host only, no context): one TOP_TWO line for the numbers as printed into out40 (NUL-terminated); returns its
@@ -661,9 +682,13 @@ int isle_hip_doc_line_text(uint64_t doc_number, uint64_t topic_number, float w, 
 int isle_hip_doc_report_text(isle_ctx* ctx, int what, uint64_t doc_begin, uint64_t doc_end, isle_text_sink_fn sink, void* user,
                              uint64_t* nbytes, uint64_t* nlines);
 int isle_hip_top_two_line_text(uint64_t doc_number, uint64_t t1_number, uint64_t t2_number, char* out40);
-/* The avg_doc_sz of the resident count matrix as the context holds it (see above; computed on first use).  ISLE_E_ARG: no count matrix,
- * world > 1, out null. */
+/* The avg_doc_sz of the resident count matrix as the context holds it (see above; computed on first use).  world > 1: the corpus value
+ * over all ranks' documents, collective where it has to be computed (see isle_hip_infer_resident).  ISLE_E_ARG: no count matrix, out null. */
 int isle_hip_avg_doc_sz(isle_ctx* ctx, float* out);
+/* The shape of the resident count matrix A and its place in the corpus as the upload, the feed or the windowed tdf stream gave them
+ * (each nullable); separate from isle_hip_shape, which describes B.  ISLE_E_ARG: no count matrix. */
+int isle_hip_counts_shape(isle_ctx* ctx, uint64_t* vocab_size, uint64_t* num_docs, uint64_t* nnz, uint64_t* doc_offset,
+                          uint64_t* docs_global);
 
 /* ---- measurement ----------------------------------------------------------------------- */
 /* Per-kernel-family device time accumulated with HIP events on the context's stream since the

@@ -515,6 +515,17 @@ extern "C" int isle_hip_threshold(isle_ctx* c, uint64_t num_topics, double sampl
   return th.emit(docs_kept, nnz_kept);
 }
 
+extern "C" int isle_hip_counts_shape(isle_ctx* c, uint64_t* V, uint64_t* D, uint64_t* nnz, uint64_t* doc_offset, uint64_t* docs_global) {
+  if (!c) return ISLE_E_ARG;
+  if (!c->a_ready) return isle_fail(c, ISLE_E_ARG, "counts_shape: no count matrix");
+  if (V) *V = c->a_V;
+  if (D) *D = c->a_D;
+  if (nnz) *nnz = c->a_nnz;
+  if (doc_offset) *doc_offset = c->a_doc_offset;
+  if (docs_global) *docs_global = c->a_D_global;
+  return 0;
+}
+
 extern "C" int isle_hip_shape(isle_ctx* c, uint64_t* V, uint64_t* D, uint64_t* nnz, uint64_t* doc_offset, uint64_t* docs_global) {
   if (!c) return ISLE_E_ARG;
   if (V) *V = c->V;
@@ -554,9 +565,11 @@ static int post_prepare(isle_ctx* c, const char* who) {
   if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "%s: single-rank only", who);
   return 0;
 }
-// a reader of a model: with several ranks the catch model is replicated and a host model is the caller's; each rank reads for itself
+// a reader of a model: with several ranks the catch model is replicated, a host model is the caller's and a loaded model is what each rank
+// loaded for itself; each rank reads for itself.  Nothing builds the average model there.
 static int model_reader_ok(isle_ctx* c, int which, const char* who) {
-  if (c->world > 1 && which != ISLE_MODEL_CATCH && which != ISLE_MODEL_HOST) return isle_fail(c, ISLE_E_ARG, "%s: single-rank only", who);
+  if (c->world > 1 && which != ISLE_MODEL_CATCH && which != ISLE_MODEL_HOST && which != ISLE_MODEL_LOADED)
+    return isle_fail(c, ISLE_E_ARG, "%s: single-rank only", who);
   return 0;
 }
 
@@ -946,7 +959,6 @@ extern "C" int isle_hip_load_model_text(isle_ctx* c, const char* text, uint64_t 
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
   if (nentries) *nentries = 0;
-  if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "load_model_text: single-rank only");
   if (format != ISLE_TEXT_SPARSE && format != ISLE_TEXT_DENSE) return isle_fail(c, ISLE_E_ARG, "load_model_text: unknown format %d", format);
   if (base > 1) return isle_fail(c, ISLE_E_ARG, "load_model_text: base = %u (0 or 1)", base);
   if (vocab == 0 || vocab > 0xfffffff0ull || ncols < 1) return isle_fail(c, ISLE_E_ARG, "load_model_text: vocab or ncols out of range");
@@ -1086,7 +1098,8 @@ extern "C" int isle_hip_infer_resident(isle_ctx* c, int which, const float* mode
                                        float* top_weight, float* llh, uint64_t* nconverged, uint64_t* nentries) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  ISLECHK(post_prepare(c, "infer_resident"));
+  ISLECHK(post_prepare_sharded(c, "infer_resident"));
+  ISLECHK(model_reader_ok(c, which, "infer_resident"));
   if (doc_begin > doc_end || doc_end > c->a_D)
     return isle_fail(c, ISLE_E_ARG, "infer_resident: documents [%llu, %llu) of %llu", (unsigned long long)doc_begin, (unsigned long long)doc_end,
                      (unsigned long long)c->a_D);
@@ -1121,7 +1134,6 @@ extern "C" int isle_hip_infer_text(isle_ctx* c, int what, uint64_t row_begin, ui
   ISLECHK(isle_enter(c));
   if (nbytes) *nbytes = 0;
   if (nlines) *nlines = 0;
-  if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "infer_text: single-rank only");
   if (what != ISLE_DOCTEXT_ENTRIES && what != ISLE_DOCTEXT_TOP) return isle_fail(c, ISLE_E_ARG, "infer_text: unknown kind %d", what);
   if (!c->inf_valid) return isle_fail(c, ISLE_E_ARG, "infer_text: no resident result (run isle_hip_infer_resident; a new count matrix voids it)");
   if (row_begin > row_end || row_end > c->inf_docs)
@@ -1130,15 +1142,61 @@ extern "C" int isle_hip_infer_text(isle_ctx* c, int what, uint64_t row_begin, ui
   return k_infer_text(c, what, row_begin, row_end, number_base, sink, user, nbytes, nlines);
 }
 
+// DocTopicCatchwordSums.tsv over document shards (route_topic_sums == TOPIC_SUMS_GATHERED): the device steps of doc_report.hip and the three
+// collectives between them (the counts, the keys, the documents).  Every rank takes every step up to its own slice, a rank without documents
+// or without sums included; every count that shapes a collective comes from the gathered counts; no collective follows the first sink call.
+static int topic_sums_gathered(isle_ctx* c, uint64_t doc_begin, uint64_t doc_end, isle_text_sink_fn sink, void* user, uint64_t* nbytes, uint64_t* nlines) {
+  const size_t W = (size_t)c->world;
+  uint64_t first = 0, n_own = 0;
+  ISLECHK(k_dr_sums_range(c, doc_begin, doc_end, &first, &n_own));
+  DevBuf<uint64_t> cnt_dev, gkey, key_a, key_b;
+  DevBuf<uint32_t> gdoc, doc_a, doc_b;
+  StreamDrain drain(c);
+  std::vector<uint64_t> n_of(W);
+  HIPCHK(c, cnt_dev.reserve(W + 1));
+  ISLECHK(allgather_host<uint64_t>(c, &n_own, 1, cnt_dev.p, n_of.data()));
+  uint64_t L = 0, nmax = 0;
+  for (size_t q = 0; q < W; ++q) {
+    if (n_of[q] >= (1ull << 32) || (L += n_of[q]) >= (1ull << 32))  // on every rank alike
+      return isle_fail(c, ISLE_E_ARG, "doc_report_text(topic_sums): 2^32 sums or more over the ranks' ranges; the order's payload is 32 bits wide — write the ranges in parts");
+    nmax = std::max(nmax, n_of[q]);
+  }
+  if (L == 0) return 0;
+  HIPCHK(c, gkey.reserve(W * nmax));
+  HIPCHK(c, gdoc.reserve(W * nmax));
+  HIPCHK(c, key_a.reserve(L));
+  HIPCHK(c, key_b.reserve(L));
+  HIPCHK(c, doc_a.reserve(L));
+  HIPCHK(c, doc_b.reserve(L));
+  uint64_t* const my_key = gkey.p + (size_t)c->rank * nmax;
+  uint32_t* const my_doc = gdoc.p + (size_t)c->rank * nmax;
+  ISLECHK(k_dr_sums_keys(c, doc_begin, doc_end, first, n_own, nmax, my_key, my_doc));
+  {
+    TimeScope ts(c, ISLE_T_COMM);
+    ISLECHK(isle_allgather(c, my_key, gkey.p, nmax, ISLE_DT_U64));
+    ISLECHK(isle_allgather(c, my_doc, gdoc.p, nmax, ISLE_DT_U32));
+  }
+  uint64_t at = 0;
+  for (size_t q = 0; q < W; ++q) {  // the blocks without their padding, in rank order: document order
+    if (n_of[q]) {
+      HIPCHK(c, hipMemcpyAsync(key_a.p + at, gkey.p + q * nmax, n_of[q] * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(doc_a.p + at, gdoc.p + q * nmax, n_of[q] * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    }
+    at += n_of[q];
+  }
+  return k_dr_sums_gathered_text(c, key_a.p, doc_a.p, key_b.p, doc_b.p, L, topic_sums_slice(L, W, (uint64_t)c->rank),
+                                 topic_sums_slice(L, W, (uint64_t)c->rank + 1), sink, user, nbytes, nlines);
+}
+
 // The trainer's per-document report files formatted on the device (doc_report.hip) from what the catchword and topic-model stages left
-// resident
+// resident.  Several ranks: TOPIC_SUMS is collective, the other kinds are each rank's own business.
 extern "C" int isle_hip_doc_report_text(isle_ctx* c, int what, uint64_t doc_begin, uint64_t doc_end, isle_text_sink_fn sink, void* user,
                                         uint64_t* nbytes, uint64_t* nlines) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
   if (nbytes) *nbytes = 0;
   if (nlines) *nlines = 0;
-  ISLECHK(post_prepare(c, "doc_report_text"));
+  ISLECHK(post_prepare_sharded(c, "doc_report_text"));
   if (what != ISLE_DOCREPORT_CATCHWORDS && what != ISLE_DOCREPORT_TOPIC_SUMS && what != ISLE_DOCREPORT_TOPIC_SUMS_BY_DOC && what != ISLE_DOCREPORT_TOP_TWO)
     return isle_fail(c, ISLE_E_ARG, "doc_report_text: unknown kind %d", what);
   if (what == ISLE_DOCREPORT_CATCHWORDS ? !c->p_catch_ready : !c->p_model_ready)
@@ -1147,13 +1205,15 @@ extern "C" int isle_hip_doc_report_text(isle_ctx* c, int what, uint64_t doc_begi
   if (doc_begin > doc_end || doc_end > c->a_D)
     return isle_fail(c, ISLE_E_ARG, "doc_report_text: documents [%llu, %llu) of %llu", (unsigned long long)doc_begin, (unsigned long long)doc_end,
                      (unsigned long long)c->a_D);
+  if (what == ISLE_DOCREPORT_TOPIC_SUMS && route_topic_sums(c->world) == TOPIC_SUMS_GATHERED)
+    return topic_sums_gathered(c, doc_begin, doc_end, sink, user, nbytes, nlines);
   return k_doc_report_text(c, what, doc_begin, doc_end, sink, user, nbytes, nlines);
 }
 
 extern "C" int isle_hip_avg_doc_sz(isle_ctx* c, float* out) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  ISLECHK(post_prepare(c, "avg_doc_sz"));
+  ISLECHK(post_prepare_sharded(c, "avg_doc_sz"));
   if (!out) return isle_fail(c, ISLE_E_ARG, "avg_doc_sz: null out");
   ISLECHK(ensure_avg_doc_sz(c));
   *out = c->a_avg;

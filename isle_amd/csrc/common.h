@@ -699,6 +699,13 @@ int k_infer_text(isle_ctx* c, int what, uint64_t row_begin, uint64_t row_end, ui
 // that the stage that made the source has run.
 int k_doc_report_text(isle_ctx* c, int what, uint64_t doc_begin, uint64_t doc_end, isle_text_sink_fn sink, void* user, uint64_t* nbytes,
                       uint64_t* nlines);
+// ... and the steps of ISLE_DOCREPORT_TOPIC_SUMS over document shards (route_topic_sums == TOPIC_SUMS_GATHERED), between the collectives of
+// api_stages.cpp: the range's sums; this rank's block of (key, global document) pairs padded to nmax; the replicated sort of the L gathered
+// pairs and the lines [L0, L1) of the corpus's file
+int k_dr_sums_range(isle_ctx* c, uint64_t doc_begin, uint64_t doc_end, uint64_t* first, uint64_t* n);
+int k_dr_sums_keys(isle_ctx* c, uint64_t doc_begin, uint64_t doc_end, uint64_t first, uint64_t n, uint64_t nmax, uint64_t* key, uint32_t* doc);
+int k_dr_sums_gathered_text(isle_ctx* c, uint64_t* key_a, uint32_t* doc_a, uint64_t* key_b, uint32_t* doc_b, uint64_t L, uint64_t L0, uint64_t L1,
+                            isle_text_sink_fn sink, void* user, uint64_t* nbytes, uint64_t* nlines);
 
 // model_load.hip: the text of a model file (n bytes on the device, ISLE_TEXT_SPARSE / ISLE_TEXT_DENSE) parsed into model_dev (V x ncols
 // column-major).  *err_key: ~0 = none, else (byte position << 3) | kind of the first offending byte (isle_hip_load_model_text names them);

@@ -357,6 +357,12 @@ inline bool route_gl_wide_grouped(bool with_norms, int PW, int k, uint64_t D, in
 enum PostSelect { POST_SELECT_ONE_WORKGROUP = 0, POST_SELECT_HISTOGRAM = 1 };
 inline PostSelect route_post_select(int world) { return world > 1 ? POST_SELECT_HISTOGRAM : POST_SELECT_ONE_WORKGROUP; }
 
+// DocTopicCatchwordSums.tsv (isle_hip_doc_report_text, ISLE_DOCREPORT_TOPIC_SUMS) is one order over all documents' sums.  One rank sorts its
+// range's entries and finds a line's document by a search (doc_report.hip DrSrc).  Several ranks: the keys travel with their global document,
+// every rank sorts all of them and formats its slice (DrGatherSrc; stage_host.h topic_sums_slice).  A communicator of one rank takes the first.
+enum TopicSums { TOPIC_SUMS_LOCAL = 0, TOPIC_SUMS_GATHERED = 1 };
+inline TopicSums route_topic_sums(int world) { return world > 1 ? TOPIC_SUMS_GATHERED : TOPIC_SUMS_LOCAL; }
+
 // ---- small EVD by tridiagonalisation (evd_tridiag.hip) -------------------------------------------------------------------------------
 // workgroups of the persistent form: each holds its columns plus v and w in lds_bytes of LDS; at least gsmall (more only add barrier latency)
 inline int route_td_workgroups(int n, size_t lds_bytes, int gsmall) {

@@ -1,6 +1,6 @@
 // isle_amd/csrc/stage_host.h — what the stages either side of the hot path (api_stages.cpp) decide on the host: the corpus average and its
 // limit, the two thresholding counts, the sampling keys, their pivot over all ranks and the drop mask, a shard's place in B's columns, the
-// plan and the sums of the UMass coherence, the digit pick and the chunk plan of the distributed select, the top-five count rule, the diversity average and the line of a byte.  Plain C++ (no HIP type,
+// plan and the sums of the UMass coherence, the digit pick and the chunk plan of the distributed select, the slices of the gathered topic sums, the top-five count rule, the diversity average and the line of a byte.  Plain C++ (no HIP type,
 // no isle_ctx, nothing read from the environment), so that rules whose mistakes do not fault but keep other documents run without a device
 // and without a transport: ../host/stage_host_main.cpp applies them to a script, tests/test_stage_host_cpu.py checks the answers.  Operand
 // types, casts and the order of every float and double operation are the reference's, as cited: no build of it takes -ffast-math.
@@ -227,6 +227,11 @@ ISLE_STAGE_HD inline uint64_t plan_bound(const int64_t* offs, uint64_t num_docs,
   if (d < before) d = before;
   return d;
 }
+
+// ---- DocTopicCatchwordSums.tsv over document shards: the first line of rank q's part of the corpus's L lines, W ranks (q <= W) ---------------
+// slice(q) = q floor(L / W) + min(q, L mod W): slice(0) = 0, slice(W) = L, the first L mod W ranks take one line more.  No product wraps:
+// q floor(L / W) <= L.
+ISLE_STAGE_HD inline uint64_t topic_sums_slice(uint64_t L, uint64_t W, uint64_t q) { return q * (L / W) + std::min(q, L % W); }
 
 // ---- corpus diagnostics and what reads a model ------------------------------------------------------------------------------------------------
 // The loop of src/sparseMatrix.cpp:198-208 moves its mark from p to p + max(rem(p), m), rem(p) = distance from p to the end of

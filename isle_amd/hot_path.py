@@ -276,6 +276,14 @@ class HotPath:
                                                        doc_offset, docs_global))
         self._a_shape = (int(V), D, int(offs[-1]))
 
+    @property
+    def a_doc_offset(self):
+        """The number in the corpus of the first document of the resident count matrix A (upload_counts / feed_finalize / the sharded
+        tdf ingest); read from the context.  Separate from doc_offset, which is B's first column."""
+        off = C.c_uint64()
+        self._chk(self._lib.isle_hip_counts_shape(self._h, None, None, None, C.byref(off), None))
+        return int(off.value)
+
     def ingest_tdf(self, text, vocab_size, num_docs, max_entries=0):
         """tdf text (bytes) -> the context's count matrix A, on the device (include/utils.h:158-228,
         src/trainer.cpp:236-247, src/sparseMatrix.cpp:58-87).  -> dict(entries_read, nnz)."""
@@ -646,7 +654,8 @@ class HotPath:
         column) parsed on the device into the resident model "loaded", which model_top_words, topic_diversity, model_text /
         write_model / model_text_size and infer_resident take as model="loaded".  It is independent of A and of the other resident
         models and lives until the next successful load.  A refused text (IsleHipError naming the first offending line and the kind
-        of error) leaves the previous model in place.  -> entries read (sparse: lines, dense: vocab x cols)."""
+        of error) leaves the previous model in place.  Under comm_init / comm_init_host: no collective, each rank loads for itself.
+        -> entries read (sparse: lines, dense: vocab x cols)."""
         buf = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else text
         fmt = TEXT_FORMATS[format] if isinstance(format, str) else int(format)
         n = C.c_uint64()
@@ -918,6 +927,10 @@ class HotPath:
         The weights come back sparse: for every converged document the topics with weight > min_weight (None: 1 / cols), ascending,
         as CSR (offs int64 (n + 1,), topic uint32, weight float32); the dense (n, cols) matrix never exists.  chunk_docs: documents
         per pass on the device (0: a 1 GiB budget of dense weights); no result depends on it.
+        Under comm_init / comm_init_host: docs and every output are this rank's own documents', rows numbered from docs[0]; avg_doc_sz
+        is the corpus value over all ranks.  Where threshold() has not left it behind (B uploaded from the host) the call is COLLECTIVE
+        (one all-reduce of two totals): every rank calls, in the same order, a rank without documents included.  The shards' entries
+        side by side are the single-rank run's, bit for bit.  model="avg" is refused there.
         -> dict(top_topic, top_weight, llh, nconverged, nentries, avg_doc_sz[, offs, topic, weight])."""
         if isinstance(model, str):
             which, host = self._MODELS[model], None
@@ -951,7 +964,9 @@ class HotPath:
     def infer_text(self, what="entries", rows=None, base=1):
         """The lines "<row + base>\\t<topic + 1>\\t<weight>\\n" of rows (None: all; or (begin, end), row 0 = the first document) of the
         last infer_resident, formatted on the device from the resident result: "entries" (every entry, DocTopicWeights.tsv) or "top"
-        (the at most five heaviest topics of a document, ISLEInfer's top_topics_* files).  -> bytes."""
+        (the at most five heaviest topics of a document, ISLEInfer's top_topics_* files).  Under comm_init / comm_init_host: no
+        collective; base stays the caller's: after infer_resident(docs=(b, e)) pass base + a_doc_offset + b, and the ranks' texts in
+        rank order are the corpus's file.  -> bytes."""
         parts = []
         self._infer_text_call(what, rows, base, lambda mv: parts.append(bytes(mv)))
         return b"".join(parts)
@@ -979,6 +994,11 @@ class HotPath:
                                document ascending (the reference's order up to its unstable ties)
           "topic_sums_by_doc"  the same lines, (document, topic) ascending
           "top_two"            TopTwoTopicsPerDoc.txt: "<doc>\\t<top1>\\t<top2>\\n" for every document that has both
+        Under comm_init / comm_init_host: docs are this rank's own documents and <doc> is a_doc_offset + doc + 1, the number in the
+        corpus.  "catchwords", "topic_sums_by_doc" and "top_two" involve no collective: the ranks' texts in rank order are the corpus's
+        file.  "topic_sums" is COLLECTIVE (write_doc_report and doc_report_size too): all ranks ask for it together, a rank without
+        documents included; the sums of all ranks are ordered as one and rank q receives lines [slice(q), slice(q + 1)) of the L lines
+        of the corpus's file, slice(q) = q * (L // W) + min(q, L % W): the ranks' texts in rank order are the single-rank file.
         -> bytes."""
         parts = []
         self._doc_report_call(what, docs, lambda mv: parts.append(bytes(mv)))
@@ -994,7 +1014,9 @@ class HotPath:
         return self._doc_report_call(what, docs, None)
 
     def avg_doc_sz(self):
-        """avg_doc_sz of the resident count matrix (populate_CSC, src/sparseMatrix.cpp:87-98: floor(tokens / non-empty documents))."""
+        """avg_doc_sz of the resident count matrix (populate_CSC, src/sparseMatrix.cpp:87-98: floor(tokens / non-empty documents)).
+        Under comm_init / comm_init_host: the corpus value over all ranks' documents; COLLECTIVE where threshold() has not left it
+        behind (every rank calls, a rank without documents included)."""
         v = C.c_float()
         self._chk(self._lib.isle_hip_avg_doc_sz(self._h, C.byref(v)))
         return float(v.value)
