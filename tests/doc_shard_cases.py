@@ -1,6 +1,6 @@
 """Inference and the per-document reports on document shards (N > 1 ranks), held against the single-rank run on the whole corpus: the
-corpus, the layouts, what every rank must deliver, the per-rank worker, its launcher and the certificate (no GPU needed to import this
-module; the worker alone opens the device).
+corpus, the layouts, what every rank must deliver, the per-rank worker and the certificate (no GPU needed to import this module; the
+worker alone opens the device; tests/rank_launch.py starts the ranks).
 
 The rule: the ranks' outputs side by side in rank order are what one rank gives on the whole corpus, byte for byte and bit for bit.
 The expected bytes of the four report kinds come from the host statements of tests/test_doc_report_cpu.py (catchwords_text,
@@ -22,22 +22,16 @@ Layouts (rank q holds the documents [bounds[q], bounds[q + 1])):
                                     999 -> 1000 printed digits; the cut at 998 lies inside the identical documents
   W1  1 rank   a communicator of one rank: the launches of a context without one; the single-rank inference result comes from here
 layout_facts() states from the reference alone what the cuts must hit; tests/test_doc_shard_cases_cpu.py asserts it."""
-import os
-import subprocess
-import sys
-import time
-
 import numpy as np
 
+import rank_launch
 import shard_cases as sc
 import stages_certificate as stc
 from test_doc_report_cpu import catchwords_text, top_two_text, topic_sums_order, topic_sums_text
 from test_doc_text_cpu import doc_lines_text
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 RHO = 1.1
-LAUNCH_TIMEOUT_S = 60  # the slowest clean launch seen took 3.9 s (four ranks), four times that is 16 s; 60 leaves room for four cold Python starts on a shared machine (profiles/doc_shard_certificate.md)
 MT_TILE, IT_WIN = 1024, 1024  # text_format.h, doc_text.h
 V, TOPICS, D = 200, 7, 2301
 TIES, EMPTY_RUN, LONG = (700, 1100), (1150, 2200), (2200, 2301)
@@ -441,28 +435,8 @@ def infer_ranks(layout, single, prefix, inner=False, local_numbers=False):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the worker: one process per rank
 # ---------------------------------------------------------------------------------------------------------------------------------
-WORKER = r'''
-import sys
-sys.path.insert(0, %r); sys.path.insert(0, %r + "/tests")
-import doc_shard_cases
-doc_shard_cases.worker_main(*sys.argv[1:])
-''' % (ROOT, ROOT)
-
-
-def worker_main(layout, rank, port, out):
-    rank, port, world = int(rank), int(port), WORLD[layout]
-    os.environ["OMP_NUM_THREADS"] = "2"
-    import torch.distributed as dist
-    from isle_amd import HotPath
-    hp = HotPath(0)
-    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
-    hp.comm_init_host(world, rank, HotPath.gloo_exchange(dist, world, rank))
-    res = {}
-    _worker(hp, layout, rank, world, res)
-    np.savez(out, **res)
-    dist.barrier()
-    dist.destroy_process_group()
-    hp.close()
+def worker_main(rank, port, out, layout):
+    rank_launch.run_rank(WORLD[layout], int(rank), int(port), out, lambda hp, rank, world, res: _worker(hp, layout, rank, world, res))
 
 
 def _report(hp, res, name, what, docs):
@@ -576,50 +550,6 @@ def certify_domain(ranks):
     assert "outside the writers' domain" in msg and ranks[1]["dom_all"].size == 0
 
 
-# ---------------------------------------------------------------------------------------------------------------------------------
-# the launcher: one fresh process per rank, all under one time limit; a rank that fails ends the others; nothing is repeated
-# ---------------------------------------------------------------------------------------------------------------------------------
-def launch(layout, tmp, timeout=LAUNCH_TIMEOUT_S):
-    """-> dict(ranks (the loaded .npz per rank), outputs (stdout + stderr per rank), wall (seconds)); shard_cases.LaunchFailed otherwise."""
-    world, port = WORLD[layout], sc._free_port()
-    assert world <= 4
-    procs, logs, outs = [], [], []
-    t0 = time.monotonic()
-    for r in range(world):
-        out = os.path.join(tmp, "docs_%s_r%d.npz" % (layout, r))
-        outs.append(out)
-        logs.append(open(os.path.join(tmp, "docs_%s_r%d.log" % (layout, r)), "w+"))
-        procs.append(subprocess.Popen([sys.executable, "-c", WORKER, layout, str(r), str(port), out], stdout=logs[-1], stderr=subprocess.STDOUT))
-    why = None
-    try:
-        live = list(range(world))
-        while live and why is None:
-            left = timeout - (time.monotonic() - t0)
-            if left <= 0:
-                why = "time limit of %d s" % timeout
-                break
-            try:
-                procs[live[0]].wait(timeout=min(left, 0.2))
-            except subprocess.TimeoutExpired:
-                pass
-            for r in list(live):
-                rc = procs[r].poll()
-                if rc is not None:
-                    live.remove(r)
-                    if rc != 0:
-                        why = "rank %d ended with status %d" % (r, rc)
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-        for p in procs:
-            p.wait()
-    wall = time.monotonic() - t0
-    texts = []
-    for f in logs:
-        f.seek(0)
-        texts.append(f.read())
-        f.close()
-    if why is not None:
-        raise sc.LaunchFailed("docs %s: %s\n%s" % (layout, why, "\n".join("--- rank %d\n%s" % (r, t[-2500:]) for r, t in enumerate(texts))))
-    return dict(ranks=[dict(np.load(o)) for o in outs], outputs=texts, wall=wall)
+def launch(layout, tmp, timeout=rank_launch.LAUNCH_TIMEOUT_S):
+    """rank_launch.launch of the layout's ranks"""
+    return rank_launch.launch("docs %s" % layout, "docs_%s" % layout, WORLD[layout], tmp, rank_launch.module_command("doc_shard_cases", layout), timeout=timeout)

@@ -1,6 +1,6 @@
 """Catchwords, the topic model and the edge pairs on column-sharded documents (N > 1 ranks), held against the plain reference of the
-single-rank stage: layouts, the per-rank worker, its launcher and the certificate (no GPU needed to import this module; the worker alone
-opens the device).
+single-rank stage: layouts, the per-rank worker and the certificate (no GPU needed to import this module; the worker alone opens the
+device; tests/rank_launch.py starts the ranks).
 
 The cases are the downstream cases of stages_certificate (p_arms_case, p_select_case, p_dts_case(k) for k in DTS_K) and their reference
 is post_reference(case): what one rank computes on the whole corpus.  Layouts give the document bounds (rank r holds the documents
@@ -26,20 +26,14 @@ per rank.  certify_post takes those per-rank arrays; tests/test_post_shard_cases
 The model's bound is certify_model's, unchanged: (m + max m + V + C) u' |ref| holds for any tree of the m additions of an entry, and
 partial sums per rank followed by N - 1 additions of partials is such a tree (a rank that contributes nothing adds an exact zero): no
 margin for N."""
-import os
-import subprocess
-import sys
-import time
-
 import numpy as np
 
+import rank_launch
 import shard_cases as sc
 import stages_certificate as stc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 RHO = 1.1
-LAUNCH_TIMEOUT_S = 60  # the figure shard_cases.LAUNCH_TIMEOUT_S justifies for four cold Python starts on a shared machine (profiles/post_shard_certificate.md)
 TOP_WORDS = 5
 EDGE_MAX, EDGE_MIN_DOCS = 10, 1
 
@@ -314,38 +308,20 @@ def reference_ranks(case, name, r, rank, bnd, thr=None, rebase=True, leave_out=N
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the worker: one process per rank
 # ---------------------------------------------------------------------------------------------------------------------------------
-WORKER = r'''
-import sys
-sys.path.insert(0, %r); sys.path.insert(0, %r + "/tests")
-import post_shard_cases
-post_shard_cases.worker_main(*sys.argv[1:])
-''' % (ROOT, ROOT)
-
-
-def worker_main(layout, rank, port, out):
-    rank, port, world = int(rank), int(port), WORLD[layout]
-    os.environ["OMP_NUM_THREADS"] = "2"
-    import torch.distributed as dist
-    from isle_amd import HotPath
-    hp = HotPath(0)
-    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
-    hp.comm_init_host(world, rank, HotPath.gloo_exchange(dist, world, rank))
-    res = {}
-    for name in cases_of(layout):
-        if name == "chunk":
-            _worker_chunk(hp, rank, res)
-        else:
-            _worker_case(hp, name, bounds(layout, case_of(name)), rank, res)
-    if world > 1:  # what this stage does not build stays refused, with its message
-        try:
-            hp.avg_topic_model(2)
-            res["avg_refused"] = np.array("")
-        except Exception as e:
-            res["avg_refused"] = np.array(str(e))
-    np.savez(out, **res)
-    dist.barrier()
-    dist.destroy_process_group()
-    hp.close()
+def worker_main(rank, port, out, layout):
+    def body(hp, rank, world, res):
+        for name in cases_of(layout):
+            if name == "chunk":
+                _worker_chunk(hp, rank, res)
+            else:
+                _worker_case(hp, name, bounds(layout, case_of(name)), rank, res)
+        if world > 1:  # what this stage does not build stays refused, with its message
+            try:
+                hp.avg_topic_model(2)
+                res["avg_refused"] = np.array("")
+            except Exception as e:
+                res["avg_refused"] = np.array(str(e))
+    rank_launch.run_rank(WORLD[layout], int(rank), int(port), out, body)
 
 
 def _worker_chunk(hp, rank, res):
@@ -379,50 +355,6 @@ def _worker_case(hp, name, bnd, rank, res):
             res[key(name, r, what)] = v
 
 
-# ---------------------------------------------------------------------------------------------------------------------------------
-# the launcher: one fresh process per rank, all under one time limit; a rank that fails ends the others; nothing is repeated
-# ---------------------------------------------------------------------------------------------------------------------------------
-def launch(layout, tmp, timeout=LAUNCH_TIMEOUT_S):
-    """-> dict(ranks (the loaded .npz per rank), outputs (stdout + stderr per rank), wall (seconds)); shard_cases.LaunchFailed otherwise."""
-    world, port = WORLD[layout], sc._free_port()
-    assert world <= 4
-    procs, logs, outs = [], [], []
-    t0 = time.monotonic()
-    for r in range(world):
-        out = os.path.join(tmp, "post_%s_r%d.npz" % (layout, r))
-        outs.append(out)
-        logs.append(open(os.path.join(tmp, "post_%s_r%d.log" % (layout, r)), "w+"))
-        procs.append(subprocess.Popen([sys.executable, "-c", WORKER, layout, str(r), str(port), out], stdout=logs[-1], stderr=subprocess.STDOUT))
-    why = None
-    try:
-        live = list(range(world))
-        while live and why is None:
-            left = timeout - (time.monotonic() - t0)
-            if left <= 0:
-                why = "time limit of %d s" % timeout
-                break
-            try:
-                procs[live[0]].wait(timeout=min(left, 0.2))
-            except subprocess.TimeoutExpired:
-                pass
-            for r in list(live):
-                rc = procs[r].poll()
-                if rc is not None:
-                    live.remove(r)
-                    if rc != 0:
-                        why = "rank %d ended with status %d" % (r, rc)
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-        for p in procs:
-            p.wait()
-    wall = time.monotonic() - t0
-    texts = []
-    for f in logs:
-        f.seek(0)
-        texts.append(f.read())
-        f.close()
-    if why is not None:
-        raise sc.LaunchFailed("post %s: %s\n%s" % (layout, why, "\n".join("--- rank %d\n%s" % (r, t[-2500:]) for r, t in enumerate(texts))))
-    return dict(ranks=[dict(np.load(o)) for o in outs], outputs=texts, wall=wall)
+def launch(layout, tmp, timeout=rank_launch.LAUNCH_TIMEOUT_S):
+    """rank_launch.launch of the layout's ranks"""
+    return rank_launch.launch("post %s" % layout, "post_%s" % layout, WORLD[layout], tmp, rank_launch.module_command("post_shard_cases", layout), timeout=timeout)

@@ -1,5 +1,6 @@
-"""The sharded (N > 1) path held against fp64 at shard edges: layouts, inputs, the per-rank worker, its launcher and the certificates
-(no GPU needed to import this module; the worker alone opens the device).
+"""The sharded (N > 1) path held against fp64 at shard edges: layouts, inputs, the per-rank worker and the certificates
+(no GPU needed to import this module; the worker alone opens the device).  tests/rank_launch.py starts the ranks and gives each its
+context and communicator.
 
 Layouts give the document bounds explicitly (rank r holds documents [bounds[r], bounds[r + 1])):
 
@@ -22,22 +23,18 @@ Bounds: gram_certificate / kmeans_certificate / ks_certificate / stages_certific
 - the centroid bound (n_c + m_c + 2) u holds for any tree of the n_c additions, so it does not depend on how the sums were split.
 """
 import os
-import socket
-import subprocess
-import sys
-import time
 
 import numpy as np
 
 import gram_certificate as gc
 import kmeans_certificate as kc
 import ks_certificate as ksc
+import rank_launch
 import stages_certificate as stc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 WORLD = {"L2": 2, "L3": 3, "L4": 4, "LP": 4, "slice-empty": 4, "ld-odd": 4, "ld-even": 3}  # layouts, then the Krylov-Schur cases
-LAUNCH_TIMEOUT_S = 60  # slowest clean launch 4.3 s, four times that is 17 s; 60 leaves room for four cold Python starts on a shared machine (profiles/shard_certificate.md)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -550,37 +547,18 @@ def certify_ks(c, ranks, tag):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the worker: one process per rank
 # ---------------------------------------------------------------------------------------------------------------------------------
-WORKER = r'''
-import sys
-sys.path.insert(0, %r); sys.path.insert(0, %r + "/tests")
-import shard_cases
-shard_cases.worker_main(*sys.argv[1:])
-''' % (ROOT, ROOT)
-
-
-def worker_main(job, rank, port, out):
+def worker_main(rank, port, out, job):
     """job: a layout (Gram apply, thresholding, k-means on its shards) or a Krylov-Schur case."""
-    layout = job
-    rank, port, world = int(rank), int(port), WORLD[job]
-    os.environ["OMP_NUM_THREADS"] = "2"
-    import torch.distributed as dist
-    from isle_amd import HotPath
-    hp = HotPath(0)
-    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
-    hp.comm_init_host(world, rank, HotPath.gloo_exchange(dist, world, rank))
-    res = {}
-    if job in KS_CASES:
-        _worker_ks(hp, job, rank, res)
-    else:
-        _worker_gram(hp, layout, rank, res)
-        if layout in TH_LAYOUTS:
-            _worker_threshold(hp, layout, rank, res)
-        if layout in KM_LAYOUTS:
-            _worker_kmeans(hp, layout, rank, res)
-    np.savez(out, **res)
-    dist.barrier()
-    dist.destroy_process_group()
-    hp.close()
+    def body(hp, rank, world, res):
+        if job in KS_CASES:
+            _worker_ks(hp, job, rank, res)
+        else:
+            _worker_gram(hp, job, rank, res)
+            if job in TH_LAYOUTS:
+                _worker_threshold(hp, job, rank, res)
+            if job in KM_LAYOUTS:
+                _worker_kmeans(hp, job, rank, res)
+    rank_launch.run_rank(WORLD[job], int(rank), int(port), out, body)
 
 
 def _worker_gram(hp, layout, rank, res):
@@ -669,61 +647,6 @@ def _worker_kmeans(hp, layout, rank, res):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the launcher
 # ---------------------------------------------------------------------------------------------------------------------------------
-class LaunchFailed(Exception):
-    pass
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def launch(layout, tmp, env=None, timeout=LAUNCH_TIMEOUT_S, tag=""):
-    """One fresh process per rank, all under one time limit; a rank that fails ends the others (they would wait in a collective); nothing
-    is repeated.  -> dict(ranks (the loaded .npz per rank), outputs (stdout + stderr per rank), wall (seconds)); LaunchFailed otherwise."""
-    world, port = WORLD[layout], _free_port()
-    assert world <= 4
-    procs, logs, outs = [], [], []
-    t0 = time.monotonic()
-    for r in range(world):
-        out = os.path.join(tmp, "%s%s_r%d.npz" % (layout, tag, r))
-        outs.append(out)
-        logs.append(open(os.path.join(tmp, "%s%s_r%d.log" % (layout, tag, r)), "w+"))
-        procs.append(subprocess.Popen([sys.executable, "-c", WORKER, layout, str(r), str(port), out], stdout=logs[-1], stderr=subprocess.STDOUT,
-                                      env=dict(os.environ, **(env or {}))))
-    why = None
-    try:
-        live = list(range(world))
-        while live and why is None:
-            left = timeout - (time.monotonic() - t0)
-            if left <= 0:
-                why = "time limit of %d s" % timeout
-                break
-            try:
-                procs[live[0]].wait(timeout=min(left, 0.2))
-            except subprocess.TimeoutExpired:
-                pass
-            for r in list(live):
-                rc = procs[r].poll()
-                if rc is not None:
-                    live.remove(r)
-                    if rc != 0:
-                        why = "rank %d ended with status %d" % (r, rc)
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-        for p in procs:
-            p.wait()
-    wall = time.monotonic() - t0
-    texts = []
-    for f in logs:
-        f.seek(0)
-        texts.append(f.read())
-        f.close()
-    if why is not None:
-        raise LaunchFailed("%s%s: %s\n%s" % (layout, tag, why, "\n".join("--- rank %d\n%s" % (r, t[-2500:]) for r, t in enumerate(texts))))
-    return dict(ranks=[dict(np.load(o)) for o in outs], outputs=texts, wall=wall)
+def launch(layout, tmp, env=None, timeout=rank_launch.LAUNCH_TIMEOUT_S, tag=""):
+    """rank_launch.launch of the layout's (or the Krylov-Schur case's) ranks"""
+    return rank_launch.launch(layout + tag, layout + tag, WORLD[layout], tmp, rank_launch.module_command("shard_cases", layout), env=env, timeout=timeout)

@@ -2,21 +2,14 @@
 thresholding, and the sharded form of the Gram apply  Z = sum_g B_g (B_g^T X)  that the RCCL all-reduce in
 libisle_hip.so implements (checked here with the oracle as the per-shard operator and gloo as the all-reduce)."""
 import os
-import socket
 import sys
 
 import numpy as np
 import pytest
 
+from rank_launch import free_port
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, out_dir):
@@ -51,7 +44,7 @@ def test_two_shards_equal_one(tmp_path):
     import torch.multiprocessing as mp
     from tools.synth import Corpus
     from oracle.oracle import OracleCsc
-    port = _free_port()
+    port = free_port()
     mp.spawn(_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
     r0, r1 = np.load(tmp_path / "r0.npz"), np.load(tmp_path / "r1.npz")
     V, D, k, seed = 800, 3000, 8, 21

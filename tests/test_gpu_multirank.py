@@ -7,12 +7,12 @@ application, replicated eigensolver, k-means++ over per-shard D^2 prefix sums, c
 ranks must reproduce the single-rank run (same U and seeds injected), and the replicated results must be bit-identical on
 all ranks (that is what keeps the ranks' control flow — restarts, rank decisions, stop rules — in step)."""
 import os
-import socket
-import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+import rank_launch
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,40 +100,19 @@ hp.close()
 ''' % (ROOT, ROOT)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _run(world, tmp, env=None, tag=""):
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        out = os.path.join(tmp, "w%d%s_r%d.npz" % (world, tag, r))
-        procs.append(subprocess.Popen([sys.executable, "-c", WORKER, str(r), str(world), str(port), out],
-                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=dict(os.environ, **(env or {}))))
-    outs = []
-    try:
-        for p in procs:
-            o, _ = p.communicate(timeout=420)
-            outs.append(o)
-    finally:
-        for p in procs:  # a rank that failed leaves the others waiting in a collective: end exactly those processes
-            if p.poll() is None:
-                p.kill()
-    for r, p in enumerate(procs):
-        assert p.returncode == 0, "world %d rank %d failed:\n%s" % (world, r, (outs[r] if r < len(outs) else "")[-3000:])
-    _run.last_outputs = outs
-    return [np.load(os.path.join(tmp, "w%d%s_r%d.npz" % (world, tag, r))) for r in range(world)]
+    """-> the launch (ranks, outputs, wall) of `world` ranks of WORKER under one time limit of 420 s; its wall time is printed."""
+    stem = "w%d%s" % (world, tag)
+    l = rank_launch.launch("world %d%s" % (world, tag), stem, world, tmp,
+                           lambda rank, port, out: [sys.executable, "-c", WORKER, str(rank), str(world), str(port), out], env=env, timeout=420)
+    print("multirank launch %s (%d ranks): %.1f s" % (stem, world, l["wall"]))
+    return l
 
 
 @pytest.fixture(scope="module")
 def single(tmp_path_factory):
     tmp = str(tmp_path_factory.mktemp("multirank"))
-    return tmp, _run(1, tmp)[0]
+    return tmp, _run(1, tmp)["ranks"][0]
 
 
 def _rel(a, b):
@@ -149,7 +128,7 @@ def test_n_ranks_reproduce_one_rank(single, world, rowshard):
     tmp, one = single
     # "split": the opt-in column split of the small EVD's eigenvector stage (ISLE_EVD_SPLIT=1) on top of the defaults
     env = {"ISLE_EVD_SPLIT": "1"} if rowshard == "split" else {"ISLE_KS_ROWSHARD": rowshard} if rowshard else None
-    rs = _run(world, tmp, env=env, tag="rs" + str(rowshard))
+    rs = _run(world, tmp, env=env, tag="rs" + str(rowshard))["ranks"]
     _compare_with_one_rank(rs, one, world)
 
 
@@ -202,7 +181,7 @@ def test_one_rank_bailing_out_of_the_persistent_evd_takes_all_ranks_along(single
     every small EVD: the flag is all-reduced, so rank 0 follows it to the chain, the replicated Ritz data stay bit-identical,
     the ranks' restart decisions and collective sequences stay in step, and the run completes with the single-rank results."""
     tmp, one = single
-    rs = _run(2, tmp, env={"ISLE_TD_FORCE_BAIL_RANK": "1"}, tag="bail")
+    rs = _run(2, tmp, env={"ISLE_TD_FORCE_BAIL_RANK": "1"}, tag="bail")["ranks"]
     for name in ("evals", "restarts", "U", "Z", "lp_C", "ls_cen", "ls_it"):
         assert np.array_equal(rs[1][name], rs[0][name]), "%s differs between ranks" % name
     assert np.max(np.abs(rs[0]["evals"] - one["evals"]) / one["evals"]) <= 1e-5
@@ -216,8 +195,9 @@ def test_comm_selftest_through_the_host_transport(single):
     more than one rank).  Here through the host-staged transport at two ranks: the same call sites, the same checks, and the run behind it
     still reproduces the single-rank one."""
     tmp, one = single
-    rs = _run(2, tmp, env={"ISLE_COMM_SELFTEST": "1"}, tag="selftest")
-    for r, o in enumerate(_run.last_outputs):
+    l = _run(2, tmp, env={"ISLE_COMM_SELFTEST": "1"}, tag="selftest")
+    rs = l["ranks"]
+    for r, o in enumerate(l["outputs"]):
         assert "rank %d of 2" % r in o and "communicator self-test: 72 collectives" in o and "correct in" in o, o[-1500:]
         assert "host-staged test transport" in o
     assert np.array_equal(rs[0]["U"], rs[1]["U"])
@@ -237,6 +217,6 @@ def test_two_ranks_over_rccl(single, rowshard):
     env = {"ISLE_TEST_RCCL": "1", "ISLE_COMM_TIMEOUT_S": "60"}
     if rowshard:
         env["ISLE_KS_ROWSHARD"] = rowshard
-    rs = _run(2, tmp, env=env, tag="rccl" + str(rowshard))
-    _compare_with_one_rank(rs, one, 2)
-    assert all("communicator self-test: 72 collectives" in o for o in _run.last_outputs)
+    l = _run(2, tmp, env=env, tag="rccl" + str(rowshard))
+    _compare_with_one_rank(l["ranks"], one, 2)
+    assert all("communicator self-test: 72 collectives" in o for o in l["outputs"])

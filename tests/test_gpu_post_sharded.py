@@ -4,13 +4,13 @@ for bit and bit-identical on every rank, the per-document results of the shards 
 within the single-rank certificate's bound of fp64.  Each layout's worker runs once per module; the tests certify the arrays it stored,
 on the host.  A launch that fails fails that layout's tests and ends the launches: nothing more is started on the GPU behind a fault, an
 abort or a time limit."""
-import os
+from functools import partial
 
 import numpy as np
 import pytest
 
 import post_shard_cases as ps
-import shard_cases as sc
+from rank_launch import launch_each, ranks_of, write_report
 
 pytestmark = pytest.mark.gpu
 
@@ -22,17 +22,8 @@ _FAILED = []  # the first launch of this module that failed: nothing is started 
 @pytest.fixture(scope="module")
 def launches(tmp_path_factory):
     """layout -> its launch (every case of the layout, every run of the case), one launch after another"""
-    tmp, out = str(tmp_path_factory.mktemp("post_shards")), {}
-    for layout in LAYOUTS:
-        if _FAILED:
-            out[layout] = sc.LaunchFailed("not started: the launch %s failed" % _FAILED[0])
-            continue
-        try:
-            out[layout] = ps.launch(layout, tmp)
-        except sc.LaunchFailed as e:
-            out[layout] = e
-            _FAILED.append(layout)
-    return out
+    tmp = str(tmp_path_factory.mktemp("post_shards"))
+    return launch_each([(layout, layout, partial(ps.launch, layout, tmp)) for layout in LAYOUTS], _FAILED)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -42,18 +33,7 @@ def report(launches):
     yield
     lines = ["post shard certificate, launch %s (%d ranks): %.1f s" % (name, ps.WORLD[name], l["wall"]) for name, l in launches.items() if isinstance(l, dict)]
     lines += ["post shard certificate, %s on %s: model max error / bound %.3g" % r for r in REPORT]
-    path = os.environ.get("ISLE_POST_SHARD_REPORT")
-    if path:
-        with open(path, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
-
-
-def ranks_of(launches, layout):
-    l = launches[layout]
-    if isinstance(l, Exception):
-        pytest.fail(str(l), pytrace=False)
-    return l["ranks"]
+    write_report(lines, "ISLE_POST_SHARD_REPORT")
 
 
 def _certify(launches, name, layout):

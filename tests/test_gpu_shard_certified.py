@@ -2,48 +2,35 @@
 one-document shard, empty first / middle / last shards, the planner's own empty shards (tests/shard_cases.py).  Each layout's worker
 runs once per module; the tests certify the arrays it stored, on the host.  A launch that fails fails that layout's tests and ends the
 launches: nothing more is started on the GPU behind a fault, an abort or a time limit."""
-import os
+from functools import partial
 
 import numpy as np
 import pytest
 
 import kmeans_certificate as kc
 import shard_cases as sc
+from rank_launch import launch_each, ranks_of, write_report
 
 pytestmark = pytest.mark.gpu
 
 LAYOUTS = ("L2", "L3", "L4", "LP")
 REPORT = []  # (case, quantity, error / bound)
 
-
 _FAILED = []  # the first launch of this module that failed: nothing is started behind it, by either fixture
-
-
-def _launch_all(tmp, jobs):
-    """jobs: (key, job, tag, env) -> {key: dict(ranks, outputs, wall) or the LaunchFailed}; one launch after another."""
-    out = {}
-    for key, job, tag, env in jobs:
-        if _FAILED:
-            out[key] = sc.LaunchFailed("not started: the launch %s failed" % _FAILED[0])
-            continue
-        try:
-            out[key] = sc.launch(job, tmp, env=env, tag=tag)
-        except sc.LaunchFailed as e:
-            out[key] = e
-            _FAILED.append("%s%s" % (job, tag))
-    return out
 
 
 @pytest.fixture(scope="module")
 def launches(tmp_path_factory):
     """layout -> its launch: Gram apply, thresholding and k-means on the layout's shards."""
-    return _launch_all(str(tmp_path_factory.mktemp("shards")), [(layout, layout, "", None) for layout in LAYOUTS])
+    tmp = str(tmp_path_factory.mktemp("shards"))
+    return launch_each([(layout, layout, partial(sc.launch, layout, tmp)) for layout in LAYOUTS], _FAILED)
 
 
 @pytest.fixture(scope="module")
 def ks_launches(tmp_path_factory):
     """(case, tag) -> its launch: the sparse entry of the eigensolver on an even split of the documents."""
-    return _launch_all(str(tmp_path_factory.mktemp("shards_ks")), [((name, tag), name, "-" + tag, env) for name, tag, env in sc.KS_RUNS])
+    tmp = str(tmp_path_factory.mktemp("shards_ks"))
+    return launch_each([((name, tag), "%s-%s" % (name, tag), partial(sc.launch, name, tmp, env=env, tag="-" + tag)) for name, tag, env in sc.KS_RUNS], _FAILED)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -54,18 +41,7 @@ def report(launches, ks_launches):
     lines = ["shard certificate, launch %s: %.1f s" % ("-".join(name) if isinstance(name, tuple) else name, l["wall"])
              for name, l in list(launches.items()) + list(ks_launches.items()) if isinstance(l, dict)]
     lines += ["shard certificate, %s: %s %.3g" % r for r in REPORT]
-    path = os.environ.get("ISLE_SHARD_REPORT")
-    if path:
-        with open(path, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
-
-
-def ranks_of(launches, layout):
-    l = launches[layout]
-    if isinstance(l, Exception):
-        pytest.fail(str(l), pytrace=False)
-    return l["ranks"]
+    write_report(lines, "ISLE_SHARD_REPORT")
 
 
 @pytest.mark.parametrize("kind", sc.GRAM_KINDS)

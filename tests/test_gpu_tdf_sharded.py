@@ -4,7 +4,7 @@ bit, entries_read is the whole file's on every rank, ranks that pass different a
 the collective threshold and is held to shard_cases.certify_threshold against the single-rank run.  Each world's worker runs once per
 module; a launch that fails fails its tests and ends the launches: nothing more is started on the GPU behind a fault, an abort or a time
 limit."""
-import os
+from functools import partial
 
 import numpy as np
 import pytest
@@ -12,25 +12,18 @@ import pytest
 import shard_cases as sc
 import tdf_shard_cases as tc
 import tdf_shard_rule as tr
+from rank_launch import launch_each, ranks_of, write_report
 
 pytestmark = pytest.mark.gpu
 
-_FAILED = []
+_FAILED = []  # the first launch of this module that failed: nothing is started behind it
 
 
 @pytest.fixture(scope="module")
 def launches(tmp_path_factory):
-    tmp, out = str(tmp_path_factory.mktemp("tdf_shards")), {}
-    for world in tc.WORLDS:
-        if _FAILED:
-            out[world] = sc.LaunchFailed("not started: the launch of %d ranks failed" % _FAILED[0])
-            continue
-        try:
-            out[world] = tc.launch(world, tmp)
-        except sc.LaunchFailed as e:
-            out[world] = e
-            _FAILED.append(world)
-    return out
+    """world -> its launch, one launch after another"""
+    tmp = str(tmp_path_factory.mktemp("tdf_shards"))
+    return launch_each([(world, "of %d ranks" % world, partial(tc.launch, world, tmp)) for world in tc.WORLDS], _FAILED)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -39,18 +32,7 @@ def report(launches):
     yield
     lines = ["tdf shard certificate, launch of %d rank%s (%s): %.1f s" % (w, "" if w == 1 else "s", ", ".join(tc.cases_of(w)), l["wall"])
              for w, l in launches.items() if isinstance(l, dict)]
-    path = os.environ.get("ISLE_TDF_SHARD_REPORT")
-    if path:
-        with open(path, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
-
-
-def ranks_of(launches, world):
-    l = launches[world]
-    if isinstance(l, Exception):
-        pytest.fail(str(l), pytrace=False)
-    return l["ranks"]
+    write_report(lines, "ISLE_TDF_SHARD_REPORT")
 
 
 @pytest.mark.parametrize("case", list(tr.SHARDED))

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import post_shard_cases as ps
+import rank_launch
 import shard_cases as sc
 import stages_certificate as stc
 
@@ -171,4 +172,8 @@ def test_the_chunk_case_needs_a_second_chunk_of_bins():
 
 def test_the_worker_covers_what_the_certificate_reads():
     assert set(ps.WORLD) == set(ps.GENERAL_LAYOUTS) | set(ps.SELECT_LAYOUTS) | {"W1", "C2"} and max(ps.WORLD.values()) <= 4
-    assert ps.LAUNCH_TIMEOUT_S == sc.LAUNCH_TIMEOUT_S == 60
+    # one limit for every launch, rank_launch's: no case module has one of its own
+    import doc_shard_cases
+    import tdf_shard_cases
+    assert rank_launch.LAUNCH_TIMEOUT_S == 60
+    assert not any(hasattr(m, "LAUNCH_TIMEOUT_S") for m in (sc, ps, tdf_shard_cases, doc_shard_cases))
