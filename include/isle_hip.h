@@ -316,6 +316,45 @@ int isle_hip_lift_centers(isle_ctx* ctx, const float* in, int ld_in, int ncols, 
 int isle_hip_lloyds_sparse(isle_ctx* ctx, int k, const float* centers_in, float* centers_out,
                            uint32_t* assign, int max_reps, int* iters_run);
 
+/* The k-means objective of a partition, per cluster and in total, in word space or in span(U): what the reference's
+ * lloyds_iter(..., compute_residual) returns (src/sparseMatrix.cpp:1649-1663, printed at :1714) and its projected twin leaves
+ * unwritten (:1995-1998).
+ *   doc_dist[d]     = max(0, |x_d - c_assign[d]|^2), evaluated in fp64 on the fp32 values the device holds; x_d = column d of B
+ *                     (WORD) or row d of P = B^T U (PROJECTED).  local docs, nullable; the SHARD'S.
+ *   cluster_sums[t] = the sum of doc_dist over the documents of cluster t on all ranks; 0 for an empty cluster.  k, nullable.
+ *   cluster_sizes[t]: k, nullable.   total (nullable): the sum of cluster_sums, t ascending, formed on the host.
+ * The sums are exact sums of the distances rounded to multiples of q = 2^(ex - 53), ex the binary exponent of the largest distance of
+ * the corpus: they do not depend on the order the documents are visited in, nor on how the documents are spread over ranks, so two
+ * runs can be compared bit for bit.
+ *   assign:  local docs -> centre, uploaded into scratch; NULL: the partition resident from the last loop, which must have been the loop
+ *            of `space` with this k (isle_hip_lloyds_sparse for WORD, isle_hip_lloyds_projected for PROJECTED).
+ *   centers: WORD: vocab x k column-major; PROJECTED: k x k, centre c at c*k (C_lowd); uploaded into scratch.  NULL: the resident
+ *            centres: of the last isle_hip_lloyds_sparse (or isle_hip_lift_centers) with this k, or of the last isle_hip_lloyds_projected.
+ * A call leaves every resident buffer as it was (partition, centres, member lists): isle_hip_catchwords afterwards reads what it read
+ * before.  PROJECTED forms P where it is not resident.
+ * world > 1: COLLECTIVE, like isle_hip_catchwords: every rank calls it with the same space and k and with replicated centers, a rank
+ * without documents too; cluster_sums, cluster_sizes and total are REPLICATED, bit-identical on every rank and equal to the single-rank
+ * run on the concatenated corpus.
+ * ISLE_E_ARG, before any work or collective: an unknown space, k < 1, no matrix, no resident partition or centres for that space and k,
+ * an assign entry >= k, PROJECTED without U of k columns or with the projection the resident partition was computed on released (a new
+ * U since).  Device time is booked under ISLE_T_SPARSE_ASSIGN (WORD) / ISLE_T_LLOYD_PROJ (PROJECTED). */
+#define ISLE_SPACE_WORD      0   /* documents = columns of B, centres V x k            */
+#define ISLE_SPACE_PROJECTED 1   /* documents = rows of P = B^T U, centres k x k (C_lowd) */
+int isle_hip_kmeans_objective(isle_ctx* ctx, int space, int k, const uint32_t* assign, const float* centers,
+                              double* cluster_sums, uint64_t* cluster_sizes, double* total, double* doc_dist);
+
+/* Optional test hook: the rows of P = B^T U the device holds for this shard (local docs x k, row-major), formed where they are
+ * not resident: the documents of ISLE_SPACE_PROJECTED.  ISLE_E_ARG without U of k columns. */
+int isle_hip_get_projection(isle_ctx* ctx, int k, float* P);
+
+/* Trace of the two Lloyd loops (default off: both loops run exactly as without it, no launch, allocation or synchronisation added).
+ * on: each loop evaluates the total objective after every centre update — the new centres with the partition they were averaged from,
+ * the reference's `residual` — and keeps one double per iteration run; the trace of a space is cleared when its loop is entered.  With
+ * world > 1 every rank switches it alike (the evaluation is collective); the trace is replicated.
+ * isle_hip_lloyds_trace_get: *n (nullable) = the entries of the last loop in `space`; objective (nullable) receives min(cap, *n). */
+int isle_hip_lloyds_trace(isle_ctx* ctx, int on);
+int isle_hip_lloyds_trace_get(isle_ctx* ctx, int space, double* objective, int cap, int* n);
+
 /* ---- downstream stage: catchwords, topic model, edge topics ---
  * These operate on the count matrix A left in device memory by isle_hip_upload_counts_u32 and on the
  * partition of B's columns, mapped back to A's documents through original_cols exactly as

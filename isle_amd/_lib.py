@@ -78,6 +78,10 @@ SYMBOLS = {
     "isle_hip_lloyds_projected": (_I, [_P, _I, _P, _I, _P, _P]),
     "isle_hip_lift_centers": (_I, [_P, _P, _I, _I, _P]),
     "isle_hip_lloyds_sparse": (_I, [_P, _I, _P, _P, _P, _I, _P]),
+    "isle_hip_kmeans_objective": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "isle_hip_get_projection": (_I, [_P, _I, _P]),
+    "isle_hip_lloyds_trace": (_I, [_P, _I]),
+    "isle_hip_lloyds_trace_get": (_I, [_P, _I, _P, _I, _P]),
     "isle_hip_timing_enable": (_I, [_P, _I]),
     "isle_hip_timing_reset": (_I, [_P]),
     "isle_hip_timing_get": (_I, [_P, _P, _P]),

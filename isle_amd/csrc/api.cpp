@@ -579,6 +579,8 @@ void isle_void_derived_from_B(isle_ctx* c) {
   c->centers_ready = false;
   c->assign_valid = false;
   c->kmpp_track_k = 0;
+  c->km_last_space = -1;
+  c->km_proj_k = 0;
   void_downstream(c);
 }
 

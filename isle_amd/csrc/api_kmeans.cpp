@@ -45,6 +45,8 @@ static void choose_movers(const std::vector<float>& delta, int k, int group, int
   }
 }
 
+static int trace_objective(isle_ctx* c, int space, int k);  // isle_hip_lloyds_trace: below, with the objective
+
 static int ensure_P(isle_ctx* c, int k) {
   if (c->U_k != k) return isle_fail(c, ISLE_E_ARG, "U has %d columns, k = %d (run isle_hip_block_ks / set_U first)", c->U_k, k);
   if (c->P_ready) return 0;
@@ -205,6 +207,7 @@ extern "C" int isle_hip_kmeanspp_projected(isle_ctx* c, int k, const uint64_t* i
   std::vector<uint64_t> centers;
   const uint64_t first = inject ? inject[0] : (uint64_t)(((size_t)rng.next31() * (size_t)84619573) % (size_t)Dg);  // :2150
   centers.push_back(first);
+  c->km_proj_k = 0;  // Cdev holds seeds from here on
   ISLECHK(fetch_rows(c, &first, 1, c->Cdev.p));
   int new_added = 1, rounds = 0;
   double grand = 0.0, last_md = 0.0;
@@ -524,6 +527,9 @@ extern "C" int isle_hip_lloyds_projected(isle_ctx* c, int k, float* C_lowd, int 
   if (!c || !C_lowd || k < 1) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
   isle_host_mark("lloyds_projected: entry");
+  c->lloyd_trace_v[ISLE_SPACE_PROJECTED].clear();
+  c->km_proj_k = 0;
+  c->km_last_space = -1;
   ISLECHK(ensure_P(c, k));  // compute_projected_docs_l2sq :2032
   const ProjPlan plan = proj_plan(c, k, C_lowd);
   const uint64_t D = c->D;
@@ -557,6 +563,7 @@ extern "C" int isle_hip_lloyds_projected(isle_ctx* c, int k, float* C_lowd, int 
     ISLECHK(k_count_sizes(c, c->assign.p, D, k, c->counts.p));
     std::vector<long long> sizes;
     ISLECHK(proj_update_centres(c, plan, k, it, sizes));
+    if (c->lloyd_trace) ISLECHK(trace_objective(c, ISLE_SPACE_PROJECTED, k));
     if (plan.hamerly && it + 1 < max_reps) ISLECHK(proj_movements(c, plan, sc, k, pdelta_host));
     bool conv = false;
     ISLECHK(stop.converged(sizes, c->assign.p, &conv));
@@ -571,6 +578,12 @@ extern "C" int isle_hip_lloyds_projected(isle_ctx* c, int k, float* C_lowd, int 
   HIPCHK(c, hipStreamSynchronize(c->stream));
   centres_unpack(C_lowd, Ch, k, ldk);
   if (iters_run) *iters_run = it;
+  if (max_reps > 0) {  // what isle_hip_kmeans_objective reads as the resident state of this space
+    c->km_last_space = ISLE_SPACE_PROJECTED;
+    c->km_last_k = k;
+    c->km_proj_k = k;
+    c->km_proj_P_gen = c->P_gen;
+  }
   isle_host_mark("lloyds_projected: exit");
   return 0;
 }
@@ -861,6 +874,8 @@ extern "C" int isle_hip_lloyds_sparse(isle_ctx* c, int k, const float* centers_i
   if (c->V == 0) return isle_fail(c, ISLE_E_ARG, "no matrix uploaded");
   ISLECHK(isle_enter(c));
   isle_host_mark("lloyds_sparse: entry");
+  c->lloyd_trace_v[ISLE_SPACE_WORD].clear();
+  c->km_last_space = -1;
   const uint64_t D = c->D, V = c->V;
   const int ld = round4(k), G = (k + 7) / 8;
   if (centers_in) {
@@ -877,7 +892,10 @@ extern "C" int isle_hip_lloyds_sparse(isle_ctx* c, int k, const float* centers_i
   HIPCHK(c, c->counts.reserve(k));
   HIPCHK(c, c->assign.reserve(D ? D : 1));
   c->assign_valid = false;
-  ISLECHK(k_doc_norms(c, c->dnorm.p));  // :1680-1687
+  {
+    TimeScope ts(c, ISLE_T_SPARSE_ASSIGN);  // the plain pass over B: the floor of every other pass over it (tools/objective_probe.py)
+    ISLECHK(k_doc_norms(c, c->dnorm.p));  // :1680-1687
+  }
   if (plan.yinyang) HIPCHK(c, c->yglb.reserve((size_t)(D ? D : 1) * G + 64));
   HIPCHK(c, c->hub.reserve(D ? D : 1));
   HIPCHK(c, c->hlb.reserve(D ? D : 1));
@@ -916,6 +934,7 @@ extern "C" int isle_hip_lloyds_sparse(isle_ctx* c, int k, const float* centers_i
     ISLECHK(k_count_sizes(c, c->assign.p, D, k, c->counts.p));
     std::vector<long long> sizes;
     ISLECHK(sparse_update_centres(c, plan, k, ld, it, sizes));
+    if (c->lloyd_trace) ISLECHK(trace_objective(c, ISLE_SPACE_WORD, k));
     if (plan.hamerly && it + 1 < max_reps) ISLECHK(sparse_movements(c, plan, sc, k, ld, groups.ymap, delta_host));
     bool conv = false;
     ISLECHK(stop.converged(sizes, c->assign.p, &conv));
@@ -926,6 +945,10 @@ extern "C" int isle_hip_lloyds_sparse(isle_ctx* c, int k, const float* centers_i
   }
   isle_host_mark("lloyds_sparse: loop done");
   c->assign_valid = true;  // the partition stays resident for isle_hip_catchwords
+  if (max_reps > 0) {
+    c->km_last_space = ISLE_SPACE_WORD;
+    c->km_last_k = k;
+  }
   if (assign && D) HIPCHK(c, hipMemcpyAsync(assign, c->assign.p, D * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   if (centers_out) {
     HIPCHK(c, c->centers_cm.reserve((size_t)V * k));
@@ -936,5 +959,142 @@ extern "C" int isle_hip_lloyds_sparse(isle_ctx* c, int k, const float* centers_i
   HIPCHK(c, hipStreamSynchronize(c->stream));
   isle_host_mark("lloyds_sparse: exit");
   if (iters_run) *iters_run = it;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// the k-means objective (objective.hip)
+// ------------------------------------------------------------------------------------------
+// The visiting order of the word-space pass: the resident member lists where they stand, lists of the given partition otherwise.  The
+// lists reach the speed alone, never the result; where they were not valid they are left marked so (c->members is then nobody's).
+static int objective_order(isle_ctx* c, int k, const uint32_t* assign_dev, const uint32_t** order) {
+  *order = nullptr;
+  if (c->D == 0) return 0;
+  if (!c->members_valid) {
+    TimeScope ts(c, ISLE_T_SPARSE_ASSIGN);
+    HIPCHK(c, c->ob_cnt.reserve(k));
+    ISLECHK(k_count_sizes(c, assign_dev, c->D, k, c->ob_cnt.p));
+    ISLECHK(k_member_lists_dev(c, assign_dev, c->D, k, c->ob_cnt.p));
+    c->members_valid = false;
+  }
+  *order = c->members.p;
+  return 0;
+}
+
+// the objective of the resident state of a loop in `space`: c->assign with centers_rm / Cdev
+static int objective_resident(isle_ctx* c, int space, int k) {
+  if (space == ISLE_SPACE_WORD) {
+    const uint32_t* order = nullptr;
+    ISLECHK(objective_order(c, k, c->assign.p, &order));
+    return k_objective(c, space, k, c->assign.p, c->centers_rm.p, round4(k), order, ISLE_T_SPARSE_ASSIGN);
+  }
+  return k_objective(c, space, k, c->assign.p, c->Cdev.p, c->ldk, nullptr, ISLE_T_LLOYD_PROJ);
+}
+
+// c->ob_sums on the host and their sum, t ascending
+static int objective_fetch_sums(isle_ctx* c, int k, std::vector<double>& sums, double* total) {
+  sums.resize(k);
+  HIPCHK(c, hipMemcpyAsync(sums.data(), c->ob_sums.p, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  double s = 0.0;
+  for (int t = 0; t < k; ++t) s += sums[t];
+  *total = s;
+  return 0;
+}
+
+// isle_hip_lloyds_trace: the total objective of the centres just updated with the partition they were averaged from (the reference's
+// `residual`, src/sparseMatrix.cpp:1649-1663)
+static int trace_objective(isle_ctx* c, int space, int k) {
+  ISLECHK(objective_resident(c, space, k));
+  std::vector<double> sums;
+  double total = 0.0;
+  ISLECHK(objective_fetch_sums(c, k, sums, &total));
+  c->lloyd_trace_v[space].push_back(total);
+  return 0;
+}
+
+extern "C" int isle_hip_kmeans_objective(isle_ctx* c, int space, int k, const uint32_t* assign, const float* centers, double* cluster_sums,
+                                         uint64_t* cluster_sizes, double* total, double* doc_dist) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  if (space != ISLE_SPACE_WORD && space != ISLE_SPACE_PROJECTED) return isle_fail(c, ISLE_E_ARG, "kmeans_objective: unknown space %d", space);
+  if (k < 1) return isle_fail(c, ISLE_E_ARG, "kmeans_objective: k < 1");
+  if (c->V == 0) return isle_fail(c, ISLE_E_ARG, "kmeans_objective: no matrix uploaded");
+  const bool word = space == ISLE_SPACE_WORD;
+  const char* sname = word ? "word" : "projected";
+  const uint64_t D = c->D, V = c->V;
+  if (!word && c->U_k != k)
+    return isle_fail(c, ISLE_E_ARG, "kmeans_objective: projected space needs U of k = %d columns, U has %d (run isle_hip_block_ks / set_U first)", k, c->U_k);
+  if (!assign) {
+    if (c->km_last_space != space || c->km_last_k != k || (word && !c->assign_valid))
+      return isle_fail(c, ISLE_E_ARG, "kmeans_objective: no resident partition for the %s space and k = %d (run the loop of that space or pass assign)", sname, k);
+    if (!word && (!c->P_ready || c->P_gen != c->km_proj_P_gen))
+      return isle_fail(c, ISLE_E_ARG, "kmeans_objective: the projection P of the resident partition was released (run isle_hip_lloyds_projected again or pass assign)");
+  } else {
+    for (uint64_t j = 0; j < D; ++j)
+      if (assign[j] >= (uint32_t)k) return isle_fail(c, ISLE_E_ARG, "kmeans_objective: assign[%llu] = %u out of range (k = %d)", (unsigned long long)j, assign[j], k);
+  }
+  if (!centers && (word ? !c->centers_ready || c->centers_k != k : c->km_proj_k != k))
+    return isle_fail(c, ISLE_E_ARG, "kmeans_objective: no resident centres for the %s space and k = %d (run the loop of that space or pass centers)", sname, k);
+  ISLECHK(agree_i32(c, 2 * k + space, "the space and k of kmeans_objective"));
+  if (!word) ISLECHK(ensure_P(c, k));  // local to the shard: no collective
+  const int ld = word ? round4(k) : c->ldk;
+  const uint32_t* assign_dev = c->assign.p;
+  if (assign) {
+    HIPCHK(c, c->ob_assign.reserve(D ? D : 1));
+    if (D) HIPCHK(c, hipMemcpyAsync(c->ob_assign.p, assign, D * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    assign_dev = c->ob_assign.p;
+  }
+  const float* centres_dev = word ? c->centers_rm.p : c->Cdev.p;
+  std::vector<float> packed;  // outlives the stream work: every path below synchronises
+  if (centers && word) {
+    HIPCHK(c, c->ob_cm.reserve((size_t)V * k));
+    HIPCHK(c, c->ob_centres.reserve((size_t)V * ld));
+    HIPCHK(c, hipMemcpyAsync(c->ob_cm.p, centers, (size_t)V * k * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->ob_centres.p, 0, (size_t)V * ld * sizeof(float), c->stream));
+    ISLECHK(k_transpose(c, c->ob_cm.p, V, k, V, c->ob_centres.p, ld));
+    centres_dev = c->ob_centres.p;
+  } else if (centers) {
+    packed.resize((size_t)k * ld);
+    centres_pack(packed.data(), centers, k, ld);
+    HIPCHK(c, c->ob_centres.reserve((size_t)k * ld));
+    HIPCHK(c, hipMemcpyAsync(c->ob_centres.p, packed.data(), (size_t)k * ld * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    centres_dev = c->ob_centres.p;
+  }
+  const uint32_t* order = nullptr;
+  if (word) ISLECHK(objective_order(c, k, assign_dev, &order));
+  ISLECHK(k_objective(c, space, k, assign_dev, centres_dev, ld, order, word ? ISLE_T_SPARSE_ASSIGN : ISLE_T_LLOYD_PROJ));
+  std::vector<double> sums;
+  double tot = 0.0;
+  ISLECHK(objective_fetch_sums(c, k, sums, &tot));
+  if (cluster_sums) std::copy(sums.begin(), sums.end(), cluster_sums);
+  if (total) *total = tot;
+  if (cluster_sizes) HIPCHK(c, hipMemcpy(cluster_sizes, c->ob_acc.p + 2 * (size_t)k, (size_t)k * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if (doc_dist && D) HIPCHK(c, hipMemcpy(doc_dist, c->ob_dd.p, D * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+extern "C" int isle_hip_get_projection(isle_ctx* c, int k, float* P) {
+  if (!c || !P || k < 1) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(ensure_P(c, k));
+  if (c->D)
+    HIPCHK(c, hipMemcpy2DAsync(P, (size_t)k * sizeof(float), c->P.p, (size_t)c->ldk * sizeof(float), (size_t)k * sizeof(float), c->D, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+extern "C" int isle_hip_lloyds_trace(isle_ctx* c, int on) {
+  if (!c) return ISLE_E_ARG;
+  c->lloyd_trace = on != 0;
+  return 0;
+}
+
+extern "C" int isle_hip_lloyds_trace_get(isle_ctx* c, int space, double* objective, int cap, int* n) {
+  if (!c) return ISLE_E_ARG;
+  if (space != ISLE_SPACE_WORD && space != ISLE_SPACE_PROJECTED) return isle_fail(c, ISLE_E_ARG, "lloyds_trace_get: unknown space %d", space);
+  const std::vector<double>& v = c->lloyd_trace_v[space];
+  if (n) *n = (int)v.size();
+  if (objective && cap > 0) std::copy(v.begin(), v.begin() + std::min<size_t>(v.size(), (size_t)cap), objective);
   return 0;
 }

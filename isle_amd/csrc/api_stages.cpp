@@ -658,6 +658,7 @@ extern "C" int isle_hip_catchwords(isle_ctx* c, int num_topics, const uint32_t* 
     if (c->D) HIPCHK(c, hipMemcpy(c->assign.p, assign, c->D * sizeof(uint32_t), hipMemcpyHostToDevice));
     c->assign_valid = true;
     c->members_valid = false;
+    c->km_last_space = -1;  // the caller's partition, no loop's
   } else if (!c->assign_valid) {
     return isle_fail(c, ISLE_E_ARG, "catchwords: no partition resident (run isle_hip_lloyds_sparse or pass assign)");
   }

@@ -441,6 +441,17 @@ struct isle_ctx {
   DevBuf<uint8_t> yy_pgrp;             // group of every pair (slot-major order)
   DevBuf<float> centers_old;  // V x ldk
   DevBuf<float> Pa, pna, Cold; // compacted active rows (ldk x n), their norms, previous projected centres
+  // the k-means objective (objective.hip, isle_hip_kmeans_objective): scratch of its own, so that a call leaves every resident buffer as it was
+  DevBuf<double> ob_dd, ob_cn, ob_sums;  // D distances, k centre norms, k cluster sums
+  DevBuf<unsigned long long> ob_acc;     // k (lo, hi) pairs, k sizes, the largest distance's high word
+  DevBuf<uint32_t> ob_assign;            // an explicit partition
+  DevBuf<float> ob_centres, ob_cm;       // explicit centres as the kernels read them; their column-major upload
+  DevBuf<int> ob_cnt;                    // k local sizes for the member lists
+  int km_last_space = -1, km_last_k = 0;  // the loop that wrote c->assign last (ISLE_SPACE_*), and its k
+  int km_proj_k = 0;                      // Cdev holds the centres of a finished projected loop with this k ...
+  uint64_t km_proj_P_gen = 0;             // ... computed on this generation of the projection
+  bool lloyd_trace = false;               // isle_hip_lloyds_trace
+  std::vector<double> lloyd_trace_v[2];   // the total objective after every centre update of the last loop, per space
 
   // block Krylov-Schur, pipelined expand loop: device mailbox [rank, status, pivots | R | coefficients] of a step, fetched by
   // one copy; the events that mark its arrival
@@ -800,5 +811,9 @@ int k_proj_accumulate_delta(isle_ctx* c, const float* P, uint64_t D, int k, int 
                             const int* counts, bool* done);
 int k_proj_finalize(isle_ctx* c, const float* Csum, const int* counts, int k, int ldk, float* C);
 int k_count_sizes(isle_ctx* c, const uint32_t* assign, uint64_t D, int k, int* counts);
+// objective.hip: c->ob_dd[d] = max(0, |x_d - c_assign[d]|^2) in fp64 for the local documents, c->ob_sums / c->ob_acc[2k, 3k) the clusters'
+// sums and sizes over all ranks (collective).  space WORD: centres V x ld row-major, order (nullable) a permutation of the local documents
+// that only shapes the visiting order; PROJECTED: centres k x ld, documents = rows of c->P.  fam: the timing family of the kernels.
+int k_objective(isle_ctx* c, int space, int k, const uint32_t* assign, const float* centres, int ld, const uint32_t* order, int fam);
 int k_compare_u32(isle_ctx* c, const uint32_t* a, const uint32_t* b, uint64_t n, int* flag_dev);
 int k_fill_f32(isle_ctx* c, float* p, uint64_t n, float v);

@@ -357,6 +357,13 @@ inline bool route_gl_wide_grouped(bool with_norms, int PW, int k, uint64_t D, in
 enum PostSelect { POST_SELECT_ONE_WORKGROUP = 0, POST_SELECT_HISTOGRAM = 1 };
 inline PostSelect route_post_select(int world) { return world > 1 ? POST_SELECT_HISTOGRAM : POST_SELECT_ONE_WORKGROUP; }
 
+// The k-means objective's exact accumulation (objective.hip ob_acc_k): 2 k accumulator words and k sizes, 64-bit each, privatised per
+// workgroup in LDS while they fit in 24 KB, global atomics beyond.  The sums are integer sums: the form cannot reach the result.
+enum ObjAcc { OBJ_ACC_LDS = 0, OBJ_ACC_GLOBAL = 1 };
+constexpr int ROUTE_OBJ_LDS_MAX_K = 1024;
+inline ObjAcc route_objective_acc(int k) { return k <= ROUTE_OBJ_LDS_MAX_K ? OBJ_ACC_LDS : OBJ_ACC_GLOBAL; }
+inline size_t route_objective_lds_bytes(int k) { return route_objective_acc(k) == OBJ_ACC_LDS ? 3 * (size_t)k * 8 : 0; }
+
 // DocTopicCatchwordSums.tsv (isle_hip_doc_report_text, ISLE_DOCREPORT_TOPIC_SUMS) is one order over all documents' sums.  One rank sorts its
 // range's entries and finds a line's document by a search (doc_report.hip DrSrc).  Several ranks: the keys travel with their global document,
 // every rank sorts all of them and formats its slice (DrGatherSrc; stage_host.h topic_sums_slice).  A communicator of one rank takes the first.

@@ -9,6 +9,7 @@
 #include <sys/stat.h>
 
 #include <cassert>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -87,6 +88,7 @@ class FPSparseMatrixHip {
   isle_ctx* ctx_ = nullptr;
   bool uploaded_ = false;
   doc_id_t U_cols_ = 0;
+  bool compute_residual_ = false;  // set_compute_residual: the loops print and return the reference's residual
   int last_nconv_ = 0;  // Ritz pairs that really passed the residual test in the last compute_block_ks
   doc_id_t a_docs_ = 0;  // documents of the count matrix A (from_counts / from_tdf)
   std::vector<uint64_t> top5_runs_;  // count_distint_top_five_words: run lengths of the sorted tuples, from the first call
@@ -287,6 +289,16 @@ class FPSparseMatrixHip {
     for (doc_id_t i = 0; i < num_topics; ++i) evalues.push_back(ev[i]);
     U_cols_ = num_topics;
   }
+  // the trace of the last loop in `space` as the reference prints its residuals; -> the last residual (0 with the flag clear)
+  FPTYPE print_residuals(const int space) {
+    if (!compute_residual_) return 0.0f;
+    int n = 0;
+    check(isle_hip_lloyds_trace_get(ctx_, space, nullptr, 0, &n), "lloyds_trace_get");
+    std::vector<double> tr(n);
+    check(isle_hip_lloyds_trace_get(ctx_, space, tr.data(), n, nullptr), "lloyds_trace_get");
+    for (int i = 0; i < n; ++i) std::cout << "Lloyd's iter " << i << "  dist_sq residual: " << std::sqrt((FPTYPE)tr[i]) << "\n";
+    return n ? (FPTYPE)tr[n - 1] : 0.0f;
+  }
   void cleanup_after_eigensolver() {}  // :1264-1275 (U stays device-resident until the context dies)
 
   FPTYPE kmeans_init_on_projected_space(const int num_centers, const int max_reps, std::vector<doc_id_t>& best_seed,
@@ -316,9 +328,10 @@ class FPSparseMatrixHip {
     int iters = 0;
     check(isle_hip_lloyds_projected(ctx_, (int)num_centers, projected_centers, max_reps, &iters, assign.data()),
           "run_lloyds_on_projected_space");
+    const FPTYPE residual = print_residuals(ISLE_SPACE_PROJECTED);  // the reference's loop prints none and returns 0 (:1995-1998)
     if (iters < max_reps) std::cout << "Lloyds converged\n";
     fill_partition(assign.data(), closest_docs, num_centers);
-    return 0.0f;  // the reference returns the (disabled) residual: always 0 (:1995-1998)
+    return residual;
   }
   // out == NULL: the product stays on the device as the start point of run_lloyds(k, NULL, ...)
   void left_multiply_by_U_Spectra(FPTYPE* const out, const FPTYPE* in, const doc_id_t ld_in, const doc_id_t ncols) {  // :1438-1450
@@ -334,10 +347,26 @@ class FPSparseMatrixHip {
     std::vector<uint32_t> assign(num_docs_);
     int iters = 0;
     check(isle_hip_lloyds_sparse(ctx_, (int)num_centers, centers, centers, assign.data(), max_reps, &iters), "run_lloyds");
-    for (int i = 0; i < iters; ++i) std::cout << "Lloyd's iter " << i << "  dist_sq residual: " << 0 << "\n";  // :1714 (residual disabled)
+    FPTYPE residual = 0.0f;
+    if (compute_residual_) residual = print_residuals(ISLE_SPACE_WORD);  // :1714, sqrt of lloyds_iter's residual (:1649-1663)
+    else
+      for (int i = 0; i < iters; ++i) std::cout << "Lloyd's iter " << i << "  dist_sq residual: " << 0 << "\n";  // :1714 (residual disabled)
     if (iters < max_reps) std::cout << "Lloyds converged\n";
     fill_partition(assign.data(), closest_docs, num_centers);
-    return 0.0f;
+    return residual;
+  }
+
+  // lloyds_iter(..., compute_residual) of the reference (:1649-1663): with the flag set both loops evaluate sum_d |b_d - c_a(d)|^2
+  // after every centre update on the device (isle_hip_lloyds_trace), print the reference's residual lines and return the last residual;
+  // with the flag clear (the default) they print and return what they always did.
+  void set_compute_residual(const bool on) {
+    compute_residual_ = on;
+    check(isle_hip_lloyds_trace(ctx_, on ? 1 : 0), "set_compute_residual");
+  }
+  // The objective of the partition and centres the last loop in `space` (ISLE_SPACE_*) left on the device: sums[t] (num_centers
+  // doubles, nullable) per cluster, *total their sum.
+  void kmeans_objective(const int space, const doc_id_t num_centers, double* sums, double* total, uint64_t* sizes = nullptr) {
+    check(isle_hip_kmeans_objective(ctx_, space, (int)num_centers, nullptr, nullptr, sums, sizes, total, nullptr), "kmeans_objective");
   }
 
   // ---- the stage after the hot path, on the count matrix this object was built from (from_counts) --------------------

@@ -2,7 +2,10 @@
 // standalone C++ program over ISLE::FPSparseMatrixHip, with the reference's own log lines
 // (the "Eigvals:" block in the format of include/logUtils.h:101-122; trainer.cpp:490 "Frob(B_fl_CSC):").
 //
-//   hot_path_main <B.bin> <num_topics> <out.bin>
+//   hot_path_main <B.bin> <num_topics> <out.bin> [residual]
+// residual: set_compute_residual(true) before the two Lloyd loops, which then print the reference's residual lines, and behind the slice
+// one line per space, "k-means objective (<space>): <last residual as returned> <total %.17g> <sum of the cluster sums %.17g>"
+// (tests/test_gpu_objective_host_cpp.py).  Without it stdout is what it always was.
 // B.bin  : u64 V, u64 D, u64 nnz, f32 vals[nnz], u64 rows[nnz], i64 offs[D+1]   (the reference's 8-byte types)
 // out.bin: u64 k, f32 evalues[k], u64 seeds[k], f32 centers[V*k] (col-major), u64 sizes[k], then the partition
 //          as k lists (u64 ids, ascending), in topic order
@@ -40,8 +43,9 @@ static void log_spectrum(const std::vector<FPTYPE>& lambda, doc_id_t k) {
 }
 
 int main(int argc, char** argv) {
-  if (argc != 4) {
-    std::cerr << "usage: hot_path_main <B.bin> <num_topics> <out.bin>\n";
+  const bool residual = argc == 5 && std::string(argv[4]) == "residual";
+  if (argc != 4 && !residual) {
+    std::cerr << "usage: hot_path_main <B.bin> <num_topics> <out.bin> [residual]\n";
     return 2;
   }
   try {
@@ -76,14 +80,29 @@ int main(int argc, char** argv) {
     FPTYPE best_residual = B_fl->kmeans_init_on_projected_space(num_centers_lowd, 1 /*KMEANS_INIT_REPS*/, best_kmeans_seeds, centers_lowd);
     std::cout << "Best k-means init residual: " << std::to_string(best_residual) << "\n";
 
-    B_fl->run_lloyds_on_projected_space(num_centers_lowd, centers_lowd, NULL, 10 /*MAX_KMEANS_LOWD_REPS*/);
+    if (residual) B_fl->set_compute_residual(true);
+    const FPTYPE res_lowd = B_fl->run_lloyds_on_projected_space(num_centers_lowd, centers_lowd, NULL, 10 /*MAX_KMEANS_LOWD_REPS*/);
+    double obj_lowd = 0.0, obj_lowd_sum = 0.0;
+    if (residual) {
+      std::vector<double> sums(num_topics);
+      B_fl->kmeans_objective(ISLE_SPACE_PROJECTED, num_topics, sums.data(), &obj_lowd);
+      for (double s : sums) obj_lowd_sum += s;
+    }
     FPTYPE* centers = new FPTYPE[(size_t)vocab_size * num_topics];
     B_fl->left_multiply_by_U_Spectra(centers, centers_lowd, num_topics, num_topics);
     delete[] centers_lowd;
     B_fl->cleanup_after_eigensolver();
 
     std::vector<doc_id_t>* closest_docs = new std::vector<doc_id_t>[num_topics];
-    B_fl->run_lloyds(num_topics, centers, closest_docs, 10 /*MAX_KMEANS_REPS*/);
+    const FPTYPE res_word = B_fl->run_lloyds(num_topics, centers, closest_docs, 10 /*MAX_KMEANS_REPS*/);
+    if (residual) {
+      std::vector<double> sums(num_topics);
+      double obj = 0.0, obj_sum = 0.0;
+      B_fl->kmeans_objective(ISLE_SPACE_WORD, num_topics, sums.data(), &obj);
+      for (double s : sums) obj_sum += s;
+      std::printf("k-means objective (projected): %.9g %.17g %.17g\n", (double)res_lowd, obj_lowd, obj_lowd_sum);
+      std::printf("k-means objective (word): %.9g %.17g %.17g\n", (double)res_word, obj, obj_sum);
+    }
     uint64_t closest_docs_sizes_sum = 0;
     for (doc_id_t t = 0; t < num_topics; ++t) closest_docs_sizes_sum += closest_docs[t].size();
     assert(closest_docs_sizes_sum == B_fl->num_docs());  // :567-570

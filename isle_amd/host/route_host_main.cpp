@@ -25,6 +25,7 @@
 //   td n lds_bytes gsmall nmax_back num_cus failed             route_td_workgroups, route_td_persist
 //   td_split multi world rank nvec n      route_td_split
 //   td_back nvec num_cus kc               route_td_back
+//   objective k                           route_objective_acc, route_objective_lds_bytes
 #include <cstdio>
 #include <iostream>
 #include <string>
@@ -212,6 +213,9 @@ int main() {
       const int nvec = take<int>(), cus = take<int>(), kc = take<int>();
       const TdBack b = route_td_back(nvec, cus, kc, e);
       put("back", b == TD_BACK_WY ? 0 : b == TD_BACK_SEQ8 ? 8 : 4);
+    } else if (cmd == "objective") {
+      const int k = take<int>();
+      put("lds", route_objective_acc(k) == OBJ_ACC_LDS), put_u("lds_bytes", route_objective_lds_bytes(k));
     } else {
       std::fprintf(stderr, "route_host_main: unknown command %s\n", cmd.c_str());
       return 2;

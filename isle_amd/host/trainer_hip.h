@@ -853,6 +853,25 @@ class ISLETrainer {
     B_fl_CSC->write_infer_text(log_dir + "/DocTopicWeights.tsv", ISLE_DOCTEXT_ENTRIES, 0, docs, 1);
     log->next_time_secs("Writing document topic weights to file");
   }
+  // The k-means objective of the partition train() ended with, on the thresholded matrix B: sum over the documents of a cluster of
+  // |b_d - c_t|^2 with the centres run_lloyds left on the device (what the reference's lloyds_iter returns as its residual,
+  // src/sparseMatrix.cpp:1649-1663, and never writes anywhere).  ClusterObjective.tsv: "<topic>\t<size>\t<distsq_sum>\n", topics 1-based,
+  // the sum as %.9g; the log gets the total.  Not part of what ISLETrain writes by default.
+  void output_kmeans_objective() {
+    if (!is_training_complete) throw std::runtime_error("output_kmeans_objective() before train()");
+    std::vector<double> sums(num_topics);
+    std::vector<uint64_t> sizes(num_topics);
+    double total = 0.0;
+    B_fl_CSC->kmeans_objective(ISLE_SPACE_WORD, num_topics, sums.data(), &total, sizes.data());
+    FILE* f = std::fopen((log_dir + "/ClusterObjective.tsv").c_str(), "w");
+    if (!f) throw std::runtime_error("cannot write " + log_dir + "/ClusterObjective.tsv");
+    for (doc_id_t t = 0; t < num_topics; ++t) std::fprintf(f, "%llu\t%llu\t%.9g\n", (unsigned long long)(t + 1), (unsigned long long)sizes[t], sums[t]);
+    std::fclose(f);
+    char buf[64];
+    std::snprintf(buf, sizeof buf, "%.9g", total);
+    log->print(std::string("k-means objective on B: ") + buf + "\n");
+    log->next_time_secs("Computing the k-means objective");
+  }
   void finish_log() { log->total("TVSD"); }  // the "Total time for TVSD" line the reference's train() ends with (:652)
 
   // src/trainer.cpp:993-996: vocab_size x num_topics floats, column-major (element (word, topic) at word + topic * vocab_size)

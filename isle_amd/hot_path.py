@@ -879,7 +879,7 @@ class HotPath:
         it = C.c_int()
         assign = np.empty(self.D, np.uint32)
         self._chk(self._lib.isle_hip_lloyds_projected(self._h, k, _p(Cl), max_reps, C.byref(it), _p(assign)))
-        return dict(C_lowd=Cl, iters=it.value, assign=assign)
+        return self._with_trace(dict(C_lowd=Cl, iters=it.value, assign=assign), "projected")
 
     def left_multiply_by_U(self, C_lowd, fetch=True):
         """centers (V x n, F-order) = U * C_lowd^T, centre c = row c of C_lowd (ld_in = k)."""
@@ -895,7 +895,61 @@ class HotPath:
         assign = np.empty(self.D, np.uint32)
         it = C.c_int()
         self._chk(self._lib.isle_hip_lloyds_sparse(self._h, k, _p(cin), _p(cout), _p(assign), max_reps, C.byref(it)))
-        return dict(centers=cout, assign=assign, iters=it.value)
+        return self._with_trace(dict(centers=cout, assign=assign, iters=it.value), "word")
+
+    # ---- the k-means objective ------------------------------------------------------------------
+    SPACES = {"word": 0, "projected": 1}
+
+    def _space(self, space):
+        if space not in self.SPACES:
+            raise ValueError("space must be 'word' or 'projected', not %r" % (space,))
+        return self.SPACES[space]
+
+    def kmeans_objective(self, k, space="word", assign=None, centers=None, fetch_docs=False):
+        """Per-cluster and total k-means objective of a partition (include/isle_hip.h, isle_hip_kmeans_objective).
+        assign / centers None: the resident ones of the last loop in `space`.  centers: vocab x k (word), k x k rows = centres
+        (projected).  Returns dict(sums, sizes, total[, doc_dist]); collective over document shards."""
+        sp = self._space(space)
+        a = c = None
+        if assign is not None:
+            a = _as_u32(assign, "assign")
+            if a.shape[0] != self.D:
+                raise ValueError("assign has %d entries, the shard %d documents" % (a.shape[0], self.D))
+            if self.D == 0:
+                a = np.zeros(1, np.uint32)  # a rank without documents still passes an explicit (empty) partition
+        if centers is not None:
+            c = np.asfortranarray(centers, dtype=np.float32) if sp == 0 else np.ascontiguousarray(centers, dtype=np.float32)
+            if c.shape != ((self.V, k) if sp == 0 else (k, k)):
+                raise ValueError("centers have shape %r" % (c.shape,))
+        sums = np.empty(k, np.float64)
+        sizes = np.empty(k, np.uint64)
+        total = C.c_double()
+        dd = np.empty(self.D, np.float64) if fetch_docs else None
+        self._chk(self._lib.isle_hip_kmeans_objective(self._h, sp, k, _p(a), _p(c), _p(sums), _p(sizes), C.byref(total), _p(dd)))
+        out = dict(sums=sums, sizes=sizes, total=total.value)
+        if fetch_docs:
+            out["doc_dist"] = dd
+        return out
+
+    def get_projection(self, k):
+        """The shard's rows of P = B^T U as the device holds them (D x k): the documents of space="projected"."""
+        P = np.empty((self.D, k), np.float32)
+        self._chk(self._lib.isle_hip_get_projection(self._h, k, _p(P)))
+        return P
+
+    def lloyds_trace(self, on=True):
+        """While on, run_lloyds / run_lloyds_on_projected_space also return "objective": the total objective after every centre update."""
+        self._chk(self._lib.isle_hip_lloyds_trace(self._h, 1 if on else 0))
+        self._trace = bool(on)
+
+    def _with_trace(self, out, space):
+        if getattr(self, "_trace", False):
+            n = C.c_int()
+            self._chk(self._lib.isle_hip_lloyds_trace_get(self._h, self.SPACES[space], None, 0, C.byref(n)))
+            tr = np.empty(n.value, np.float64)
+            self._chk(self._lib.isle_hip_lloyds_trace_get(self._h, self.SPACES[space], _p(tr), n.value, None))
+            out["objective"] = tr
+        return out
 
     # ---- measurement ------------------------------------------------------------------------
     # ---- inference (SURVEY.md 8f next-4) -------------------------------------------------------
