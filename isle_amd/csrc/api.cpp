@@ -555,35 +555,6 @@ void isle_trim_derived(isle_ctx* c, uint64_t D, uint64_t nnz) {
   if (c->gl_fb_tmp.cap > 2 * z) c->gl_fb_tmp.release();
 }
 
-// What a new count matrix A voids, and what a new B voids: the one statement of each, for every call that replaces a matrix (upload,
-// ingest, thresholding).  b_from_threshold is the caller's to set.
-static void void_downstream(isle_ctx* c) {  // catchwords and models are read off both matrices
-  c->p_catch_ready = false;
-  c->p_model_ready = false;
-  c->p_avg_ready = false;
-}
-void isle_void_derived_from_A(isle_ctx* c) {
-  c->a_avg_valid = false;
-  c->inf_valid = false;  // the entries of isle_hip_infer_resident are about A's documents
-  void_downstream(c);
-}
-void isle_void_derived_from_B(isle_ctx* c) {
-  c->band_ready = false;
-  c->gl_mode = -1;
-  c->P_ready = false;
-  c->Pt_ready = false;
-  c->Pt2_ready = false;
-  c->lift_valid = false;
-  c->members_valid = false;
-  c->U_k = 0;
-  c->centers_ready = false;
-  c->assign_valid = false;
-  c->kmpp_track_k = 0;
-  c->km_last_space = -1;
-  c->km_proj_k = 0;
-  void_downstream(c);
-}
-
 static int upload_common(isle_ctx* c, uint64_t V, uint64_t D, uint64_t nnz, const float* vals, const uint32_t* rows32,
                          const int64_t* offs, uint64_t doc_offset, uint64_t docs_global) {
   if (!c) return ISLE_E_ARG;
@@ -595,8 +566,7 @@ static int upload_common(isle_ctx* c, uint64_t V, uint64_t D, uint64_t nnz, cons
   for (uint64_t d = 0; d < D; ++d)
     if (offs[d + 1] < offs[d] || (uint64_t)offs[d + 1] > nnz) return isle_fail(c, ISLE_E_ARG, "offsets not monotone at column %llu", (unsigned long long)d);
   // everything derived from the previous matrix is void from here on, whether or not the new one is accepted
-  isle_void_derived_from_B(c);
-  c->b_from_threshold = false;
+  c->res.B_replaced(false);
   isle_trim_derived(c, D, nnz);
   c->V = V;
   c->D = D;
@@ -663,7 +633,7 @@ extern "C" int isle_hip_frobenius(isle_ctx* c, float* out) {
 int gram_apply_dev(isle_ctx* c, const float* Xcm, int b, float* Zcm) {
   if (b < 1 || b > 32) return isle_fail(c, ISLE_E_ARG, "gram_apply: b = %d not in [1, 32]", b);
   ISLECHK(k_band_build(c));  // first application of a solve: operator build (and the choice of the form)
-  if (c->gl_mode == 1) {
+  if (c->res.gl_mode == 1) {
     // LDS-banded form (gram_lds.hip), panels of at most 10 columns (40-byte rows of a planar band); column groups of a col-major block
     // are contiguous
     for (int j0 = 0; j0 < b; j0 += 10) {
@@ -704,7 +674,7 @@ extern "C" int isle_hip_gram_apply(isle_ctx* c, const float* X, int b, float* Z)
 
 extern "C" int isle_hip_operator_form(isle_ctx* c, int* form) {
   if (!c || !form) return ISLE_E_ARG;
-  *form = c->band_ready ? c->gl_mode : -1;
+  *form = c->res.band_ready ? c->res.gl_mode : -1;
   return 0;
 }
 

@@ -68,8 +68,6 @@ struct StreamDrain {
 };
 
 // what a new count matrix A / a new B voids in the context (api.cpp)
-void isle_void_derived_from_A(isle_ctx* c);
-void isle_void_derived_from_B(isle_ctx* c);
 int agree_i32(isle_ctx* c, int v, const char* what);  // all ranks hold the same control value, or all return ISLE_E_COMM (api.cpp)
 int drain_events(isle_ctx* c);
 inline int round4(int k) { return (k + 3) & ~3; }

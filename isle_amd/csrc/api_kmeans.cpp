@@ -48,14 +48,12 @@ static void choose_movers(const std::vector<float>& delta, int k, int group, int
 static int trace_objective(isle_ctx* c, int space, int k);  // isle_hip_lloyds_trace: below, with the objective
 
 static int ensure_P(isle_ctx* c, int k) {
-  if (c->U_k != k) return isle_fail(c, ISLE_E_ARG, "U has %d columns, k = %d (run isle_hip_block_ks / set_U first)", c->U_k, k);
-  if (c->P_ready) return 0;
+  if (c->res.U_k != k) return isle_fail(c, ISLE_E_ARG, "U has %d columns, k = %d (run isle_hip_block_ks / set_U first)", c->res.U_k, k);
+  if (c->res.P_ready) return 0;
   const size_t D = c->D ? c->D : 1;
   HIPCHK(c, c->P.reserve(D * c->ldk));
   HIPCHK(c, c->pnorm.reserve(D));
-  c->Pt_ready = false;
-  c->Pt2_ready = false;
-  c->Pt2_pos = false;
+  c->res.projection_begins();
   // Where the assignment products run with their epilogues inside (a large shard) they read the projection's two bf16 terms in the layout
   // the LDS-DMA product stages (gemm_bf16x2_dma_k).  The grouped projection writes that copy on its way, by POSITION (the products map their
   // rows to documents through dperm): no transposition and no split pass behind the projection (round 5: 15 + 15 ms at config 3).
@@ -63,17 +61,13 @@ static int ensure_P(isle_ctx* c, int k) {
   bool a2_done = false;
   if (want_a2) HIPCHK(c, c->Pt2.reserve(k_gemm_split_a_bytes(c->D, k) / sizeof(uint4)));
   ISLECHK(k_spmm_wide_project(c, c->Urm.p, k, c->ldk, c->P.p, c->pnorm.p, want_a2 ? c->Pt2.p : nullptr, &a2_done));
-  c->P_ready = true;
-  c->P_gen++;
-  if (a2_done) {
-    c->Pt2_ready = true;
-    c->Pt2_pos = true;  // the f32 coordinate-major copy is made when a route asks for it (k_ensure_pt)
-  } else if (c->D) {
+  c->res.projection_made(a2_done);
+  if (!a2_done && c->D) {  // (with the split copy by position, the f32 coordinate-major copy is made when a route asks for it: k_ensure_pt)
     TimeScope ts(c, ISLE_T_PROJECT);
     ISLECHK(k_ensure_pt(c));
     if (want_a2) {  // the projection took another route than the grouped one: split the transposed copy
       ISLECHK(k_gemm_split_a(c, c->Pt.p, c->D, k, c->Pt2.p));
-      c->Pt2_ready = true;
+      c->res.split_copy_made();
     }
   }
   return 0;
@@ -207,11 +201,10 @@ extern "C" int isle_hip_kmeanspp_projected(isle_ctx* c, int k, const uint64_t* i
   std::vector<uint64_t> centers;
   const uint64_t first = inject ? inject[0] : (uint64_t)(((size_t)rng.next31() * (size_t)84619573) % (size_t)Dg);  // :2150
   centers.push_back(first);
-  c->km_proj_k = 0;  // Cdev holds seeds from here on
+  c->res.kmpp_begins();  // Cdev holds seeds from here on
   ISLECHK(fetch_rows(c, &first, 1, c->Cdev.p));
   int new_added = 1, rounds = 0;
   double grand = 0.0, last_md = 0.0;
-  c->kmpp_track_k = 0;
   std::vector<double> dice(plan.maxdraw);
   IslePinSmall* pin = c->pin_small();
   if ((size_t)(2 + 2 * c->world + 2 * plan.maxdraw + 42) * 8 > sizeof(pin->kmpp_stage)) return isle_fail(c, ISLE_E_ARG, "k-means++: staging area too small");
@@ -265,8 +258,7 @@ extern "C" int isle_hip_kmeanspp_projected(isle_ctx* c, int k, const uint64_t* i
   if (rounds_out) *rounds_out = rounds;
   if (plan.track && c->kmpp_track && c->kmpp_track_seeds == k) {  // complete: Lloyd may start from it if it is handed exactly these centres
     c->kmpp_C_host.assign(C_lowd, C_lowd + (size_t)k * k);
-    c->kmpp_P_gen = c->P_gen;
-    c->kmpp_track_k = k;
+    c->res.kmpp_kept_first_assignment(k);
   }
   isle_host_mark("kmeanspp: exit");
   return 0;
@@ -372,7 +364,7 @@ struct ProjScalars {
 // the route decisions of one call (route_host.h ProjPlan), taken once behind ensure_P: the switches are read at isle_enter only
 static ProjPlan proj_plan(isle_ctx* c, int k, const float* C_lowd) {
   const bool seeds_kept = c->kmpp_C_host.size() == (size_t)k * k && memcmp(c->kmpp_C_host.data(), C_lowd, (size_t)k * k * sizeof(float)) == 0;
-  const ProjFacts f = {c->D, c->Pt_ready, c->Pt2_ready, c->P_ready, c->kmpp_track_k, c->kmpp_P_gen == c->P_gen, seeds_kept};
+  const ProjFacts f = {c->D, c->res.Pt_ready, c->res.Pt2_ready(), c->res.P_ready, c->res.kmpp_track_k, c->res.kmpp_same_P(), seeds_kept};
   return route_proj_plan(f, k, c->route);
 }
 
@@ -451,7 +443,7 @@ static int proj_reassign_tiles(isle_ctx* c, const ProjPlan& p, const ProjScalars
   // (the k-means++ rounds' route), one pass of the pass-1 stream
   YyMovers mv;
   const float* tmove_use = sc.tmove;
-  if (p.movers && c->gl_mode == 1 && c->band_ready && c->U_k == k) {
+  if (p.movers && c->res.thin_product_possible(k)) {
     std::vector<float> tm;
     ISLECHK(prepare_movers(c, pdelta_host, k, 32, T, nullptr, &mv, &tm));
     if (mv.n) {
@@ -469,7 +461,7 @@ static int proj_reassign_tiles(isle_ctx* c, const ProjPlan& p, const ProjScalars
       tmove_use = c->yy_gmax2.p;
     }
   }
-  ISLECHK(k_pt_filter(c, p.pt_sorted ? nullptr : (c->members_valid ? c->members.p : nullptr), c->assign.p, c->hub.p, c->ptlb.p, T, TL, sc.delta, tmove_use,
+  ISLECHK(k_pt_filter(c, p.pt_sorted ? nullptr : (c->res.members_valid ? c->members.p : nullptr), c->assign.p, c->hub.p, c->ptlb.p, T, TL, sc.delta, tmove_use,
                       c->pneed.p, c->pcand.p, ncand, mv, c->yy_mdots.p, c->cnorm.p, c->pnorm.p));
   ISLECHK(k_pt_tighten(c, c->P.p, c->pnorm.p, ldk, c->Cdev.p, c->cnorm.p, c->assign.p, c->pcand.p, ncand, c->hub.p, c->ptlb.p, T, TL, c->pneed.p,
                        c->active.p, nact));
@@ -506,7 +498,7 @@ static int proj_update_centres(isle_ctx* c, const ProjPlan& p, int k, int it, st
     ISLECHK(k_proj_accumulate(c, c->P.p, D, k, ldk, c->assign.p, sums, c->counts.p));
     if (p.delta_sums && D) HIPCHK(c, hipMemcpyAsync(c->proj_counted.p, c->assign.p, D * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
   } else {
-    c->members_valid = false;  // the lists are those of an earlier assignment
+    c->res.member_lists_stale();
   }
   if (c->multi()) HIPCHK(c, hipMemcpyAsync(c->Csum.p, sums, (size_t)k * ldk * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
   ISLECHK(allreduce_sum<float>(c, c->Csum.p, (size_t)k * ldk));
@@ -528,8 +520,7 @@ extern "C" int isle_hip_lloyds_projected(isle_ctx* c, int k, float* C_lowd, int 
   ISLECHK(isle_enter(c));
   isle_host_mark("lloyds_projected: entry");
   c->lloyd_trace_v[ISLE_SPACE_PROJECTED].clear();
-  c->km_proj_k = 0;
-  c->km_last_space = -1;
+  c->res.lloyd_projected_begins();
   ISLECHK(ensure_P(c, k));  // compute_projected_docs_l2sq :2032
   const ProjPlan plan = proj_plan(c, k, C_lowd);
   const uint64_t D = c->D;
@@ -539,7 +530,7 @@ extern "C" int isle_hip_lloyds_projected(isle_ctx* c, int k, float* C_lowd, int 
   HIPCHK(c, c->cnorm.reserve(k));
   HIPCHK(c, c->counts.reserve(k));
   HIPCHK(c, c->assign.reserve(D ? D : 1));
-  c->assign_valid = false;
+  c->res.partition_rewrite_begins();
   const size_t ch_bytes = (size_t)k * ldk * sizeof(float);
   HIPCHK(c, c->pin_stage.reserve(ch_bytes));
   float* Ch = reinterpret_cast<float*>(c->pin_stage.p);
@@ -549,7 +540,7 @@ extern "C" int isle_hip_lloyds_projected(isle_ctx* c, int k, float* C_lowd, int 
   isle_host_mark("lloyds_projected: centres uploaded");
   ProjScalars sc;
   ISLECHK(proj_reserve(c, plan, k, &sc));
-  c->kmpp_track_k = 0;  // used (the tile minima become bounds in place) or stale
+  c->res.kmpp_first_assignment_taken();
   if (c->knob_on(KN_DEBUG_HAMERLY)) fprintf(stderr, "[projected Lloyd] first assignment %s\n", plan.from_kmpp ? "taken from the k-means++ rounds" : "computed");
   StopRule stop(c, k);
   int it = 0;
@@ -579,10 +570,7 @@ extern "C" int isle_hip_lloyds_projected(isle_ctx* c, int k, float* C_lowd, int 
   centres_unpack(C_lowd, Ch, k, ldk);
   if (iters_run) *iters_run = it;
   if (max_reps > 0) {  // what isle_hip_kmeans_objective reads as the resident state of this space
-    c->km_last_space = ISLE_SPACE_PROJECTED;
-    c->km_last_k = k;
-    c->km_proj_k = k;
-    c->km_proj_P_gen = c->P_gen;
+    c->res.lloyd_projected_done(ISLE_SPACE_PROJECTED, k);
   }
   isle_host_mark("lloyds_projected: exit");
   return 0;
@@ -596,15 +584,14 @@ static int install_centers(isle_ctx* c, int ncols) {  // centers_cm (V x ncols) 
   HIPCHK(c, c->centers_rm.reserve((size_t)c->V * ld));
   HIPCHK(c, hipMemsetAsync(c->centers_rm.p, 0, (size_t)c->V * ld * sizeof(float), c->stream));
   ISLECHK(k_transpose(c, c->centers_cm.p, c->V, ncols, c->V, c->centers_rm.p, ld));
-  c->centers_ready = true;
-  c->centers_k = ncols;
+  c->res.centres_installed(ncols);
   return 0;
 }
 
 extern "C" int isle_hip_lift_centers(isle_ctx* c, const float* in, int ld_in, int ncols, float* centers) {
   if (!c || !in || ncols < 1) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  if (c->U_k == 0 || ld_in < c->U_k) return isle_fail(c, ISLE_E_ARG, "lift: need U and ld_in >= k");
+  if (c->res.U_k == 0 || ld_in < c->res.U_k) return isle_fail(c, ISLE_E_ARG, "lift: need U and ld_in >= k");
   isle_host_mark("lift: entry");
   HIPCHK(c, c->Csum.reserve((size_t)ld_in * ncols));
   {
@@ -614,14 +601,12 @@ extern "C" int isle_hip_lift_centers(isle_ctx* c, const float* in, int ld_in, in
     HIPCHK(c, hipMemcpyAsync(c->Csum.p, c->pin_stage.p, in_bytes, hipMemcpyHostToDevice, c->stream));  // the call synchronises before it returns
   }
   HIPCHK(c, c->centers_cm.reserve((size_t)c->V * ncols));
-  ISLECHK(k_gemm_nn(c, c->Ucm.p, c->V, c->U_k, c->Csum.p, ld_in, ncols, c->centers_cm.p, ISLE_T_LIFT));
+  ISLECHK(k_gemm_nn(c, c->Ucm.p, c->V, c->res.U_k, c->Csum.p, ld_in, ncols, c->centers_cm.p, ISLE_T_LIFT));
   ISLECHK(install_centers(c, ncols));
   // the centres lie in span(U): Lloyd on B can take its first assignment from the projection (isle_hip_lloyds_sparse)
   HIPCHK(c, c->lift_C.reserve((size_t)ld_in * ncols));
   HIPCHK(c, hipMemcpyAsync(c->lift_C.p, c->Csum.p, (size_t)ld_in * ncols * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-  c->lift_ld = ld_in;
-  c->lift_k = ncols;
-  c->lift_valid = true;
+  c->res.centres_lifted(ld_in, ncols);
   if (centers) HIPCHK(c, hipMemcpyAsync(centers, c->centers_cm.p, (size_t)c->V * ncols * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   isle_host_mark("lift: exit");
@@ -659,7 +644,7 @@ static bool first_scratch_had(isle_ctx* c, int k) {
 
 // the route decisions of one call (route_host.h SparsePlan)
 static SparsePlan sparse_plan(isle_ctx* c, int k, int ld) {
-  const SparseFacts f = {c->D, c->nnz, c->lift_valid, c->lift_k, c->U_k, c->ldk, c->P_ready, c->Pt_ready, c->Pt2_ready};
+  const SparseFacts f = {c->D, c->nnz, c->res.lift_valid, c->res.lift_k, c->res.U_k, c->ldk, c->res.P_ready, c->res.Pt_ready, c->res.Pt2_ready()};
   return isle_route_mem(c, [&](uint64_t total_mem, bool* ask) { return route_sparse_plan(f, k, ld, c->route, total_mem, ask); });
 }
 
@@ -690,26 +675,24 @@ static int sparse_assign_first_via_projection(isle_ctx* c, const SparsePlan& p, 
     ISLECHK(k_max_f32(c, c->cnorm.p, k, sc.cn_max));
     const float* liftC = c->lift_C.p;
     if (p.regroup) {  // the product's columns in slot order: its groups of eight columns are the regrouped groups
-      HIPCHK(c, c->yy_liftC.reserve((size_t)k * c->lift_ld));
-      ISLECHK(k_yy_rows_by_slot(c, ymap, k, c->lift_C.p, c->lift_ld, c->yy_liftC.p));
+      HIPCHK(c, c->yy_liftC.reserve((size_t)k * c->res.lift_ld));
+      ISLECHK(k_yy_rows_by_slot(c, ymap, k, c->lift_C.p, c->res.lift_ld, c->yy_liftC.p));
       liftC = c->yy_liftC.p;
     }
-    ISLECHK(k_gemm_assign_yy(c, c->Pt_ready ? c->Pt.p : nullptr, c->P.p, c->ldk, c->pnorm.p, D, k, liftC, c->lift_ld, k, p.G, cn_grp, c->dnorm.p, sc.cn_max,
-                             c->assign.p, c->hub.p, c->yglb.p, ISLE_T_SPARSE_ASSIGN, c->Pt2_ready ? c->Pt2.p : nullptr,
-                             c->Pt2_ready && c->Pt2_pos ? c->dperm.p : nullptr));
+    ISLECHK(k_gemm_assign_yy(c, c->res.Pt_ready ? c->Pt.p : nullptr, c->P.p, c->ldk, c->pnorm.p, D, k, liftC, c->res.lift_ld, k, p.G, cn_grp, c->dnorm.p, sc.cn_max,
+                             c->assign.p, c->hub.p, c->yglb.p, ISLE_T_SPARSE_ASSIGN, c->res.Pt2_ready() ? c->Pt2.p : nullptr,
+                             c->res.Pt2_ready() && c->res.Pt2_by_position() ? c->dperm.p : nullptr));
     if (p.regroup) ISLECHK(k_yy_labels_to_ids(c, ymap, c->assign.p, D));  // columns (slots) -> centres
     return 0;
   }
   HIPCHK(c, c->dotsT.reserve((size_t)D * k));
   ISLECHK(k_ensure_pt(c));
-  ISLECHK(k_gemm_nn_assign(c, c->Pt.p, D, k, c->lift_C.p, c->lift_ld, k, c->dotsT.p, ISLE_T_SPARSE_ASSIGN));
+  ISLECHK(k_gemm_nn_assign(c, c->Pt.p, D, k, c->lift_C.p, c->res.lift_ld, k, c->dotsT.p, ISLE_T_SPARSE_ASSIGN));
   if (p.yinyang) {  // assignment and group bounds straight from the column-major product (the projection stays valid)
     ISLECHK(k_max_f32(c, c->cnorm.p, k, sc.cn_max));
     return k_dots_assign_cm(c, c->dotsT.p, k, p.G, c->cnorm.p, c->dnorm.p, sc.cn_max, c->assign.p, c->hub.p, c->yglb.p);
   }
-  c->P_ready = false;  // P now holds the dot products (as with the LDS-banded wide product)
-  c->Pt_ready = false;
-  c->Pt2_ready = false;
+  c->res.P_overwritten();  // P now holds the dot products (as with the LDS-banded wide product)
   if (ld != k) HIPCHK(c, hipMemsetAsync(c->P.p, 0, (size_t)D * ld * sizeof(float), c->stream));
   ISLECHK(k_transpose(c, c->dotsT.p, D, (uint64_t)k, D, c->P.p, (uint64_t)ld));
   return k_dots_assign(c, k, ld, c->cnorm.p, c->dnorm.p, c->assign.p, c->hub.p, c->hlb.p, 0);
@@ -784,7 +767,7 @@ static int sparse_reassign_yinyang(isle_ctx* c, const SparsePlan& p, const Spars
   // (the member lists), so that waves running together gather from one table in L2; ISLE_YY_MODE = doc | docg | group picks the form
   // (measured, Lloyd on B per step: C3 shard 176 ms by document -> 112 ms by group, all of config 3 on one GPU 825 -> 588 ms; at C2,
   // G = 25 and a 40 MB table, the three forms are within 10 % of each other and the plain one stays)
-  const uint32_t* order = p.yy_mode && c->members_valid && p.by_members ? c->members.p : nullptr;
+  const uint32_t* order = p.yy_mode && c->res.members_valid && p.by_members ? c->members.p : nullptr;
   if (p.yy_mode) ISLECHK(k_yy_pack_groups(c, c->centers_rm.p, ld, G, ymap));
   // Movers.  A group's bound falls by the LARGEST movement among its eight centres, for every document: one centre that jumped (a
   // cluster of a handful of documents that gained or lost one) takes a whole group's bound away and makes nearly every document
@@ -797,7 +780,7 @@ static int sparse_reassign_yinyang(isle_ctx* c, const SparsePlan& p, const Spars
   // (the movers' distances are a thin product through the pass-1 stream: LDS-banded form only — the gather form, ISLE_GRAM_LDS=0 or a
   // matrix whose rows are not single-valued, keeps every centre inside its group's movement)
   if (p.movers) ISLECHK(k_band_build(c));
-  if (p.movers && c->gl_mode == 1) {
+  if (p.movers && c->res.gl_mode == 1) {
     std::vector<float> gm;
     ISLECHK(prepare_movers(c, delta_host, k, 8, G, p.regroup ? &g.slot_of_id_host : nullptr, &mv, &gm));
     if (mv.n) {
@@ -831,7 +814,7 @@ static int sparse_reassign_yinyang(isle_ctx* c, const SparsePlan& p, const Spars
 
 static int sparse_reassign_hamerly(isle_ctx* c, const SparseScalars& sc, int k, int ld, int it) {
   uint32_t* nact = c->active.p + c->D;
-  ISLECHK(k_hamerly_filter(c, c->members_valid ? c->members.p : nullptr, c->assign.p, c->hub.p, c->hlb.p, sc.delta, sc.top, c->active.p, nact));
+  ISLECHK(k_hamerly_filter(c, c->res.members_valid ? c->members.p : nullptr, c->assign.p, c->hub.p, c->hlb.p, sc.delta, sc.top, c->active.p, nact));
   ISLECHK(k_spmm_wide_assign(c, c->centers_rm.p, k, ld, c->cnorm.p, c->dnorm.p, c->assign.p, c->active.p, nact, c->hub.p, c->hlb.p));
   if (c->knob_on(KN_DEBUG_HAMERLY)) {
     uint32_t na = 0;
@@ -846,11 +829,11 @@ static int sparse_update_centres(isle_ctx* c, const SparsePlan& p, int k, int ld
   const uint64_t D = c->D, V = c->V;
   // documents grouped by centre: visiting order of the next assignment (SparsePlan::by_members), and what the FRESH counting centroid
   // update walks (the first of a run; later ones go by the documents that changed centre)
-  if (route_member_lists(it, p.by_members, c->gl_mode, c->route)) {
+  if (route_member_lists(it, p.by_members, c->res.gl_mode, c->route)) {
     TimeScope ts(c, ISLE_T_SPARSE_ASSIGN);
     ISLECHK(k_member_lists_dev(c, c->assign.p, D, k, c->counts.p));
   } else {
-    c->members_valid = false;  // the lists are those of an earlier assignment
+    c->res.member_lists_stale();
   }
   if (p.hamerly) HIPCHK(c, hipMemcpyAsync(c->centers_old.p, c->centers_rm.p, (size_t)V * ld * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
   ISLECHK(k_centers_from_rows(c, c->assign.p, k, ld, c->centers_rm.p, it == 0));  // :1613-1638
@@ -875,15 +858,15 @@ extern "C" int isle_hip_lloyds_sparse(isle_ctx* c, int k, const float* centers_i
   ISLECHK(isle_enter(c));
   isle_host_mark("lloyds_sparse: entry");
   c->lloyd_trace_v[ISLE_SPACE_WORD].clear();
-  c->km_last_space = -1;
+  c->res.lloyd_word_begins();
   const uint64_t D = c->D, V = c->V;
   const int ld = round4(k), G = (k + 7) / 8;
   if (centers_in) {
     HIPCHK(c, c->centers_cm.reserve((size_t)V * k));
     HIPCHK(c, hipMemcpy(c->centers_cm.p, centers_in, (size_t)V * k * sizeof(float), hipMemcpyHostToDevice));
     ISLECHK(install_centers(c, k));
-    c->lift_valid = false;
-  } else if (!c->centers_ready || c->centers_k != k) {
+    c->res.centres_not_lifted();
+  } else if (!c->res.centers_ready || c->res.centers_k != k) {
     return isle_fail(c, ISLE_E_ARG, "lloyds_sparse: no device-resident centres for k = %d (call isle_hip_lift_centers)", k);
   }
   const SparsePlan plan = sparse_plan(c, k, ld);
@@ -891,7 +874,7 @@ extern "C" int isle_hip_lloyds_sparse(isle_ctx* c, int k, const float* centers_i
   HIPCHK(c, c->cnorm.reserve(k));
   HIPCHK(c, c->counts.reserve(k));
   HIPCHK(c, c->assign.reserve(D ? D : 1));
-  c->assign_valid = false;
+  c->res.partition_rewrite_begins();
   {
     TimeScope ts(c, ISLE_T_SPARSE_ASSIGN);  // the plain pass over B: the floor of every other pass over it (tools/objective_probe.py)
     ISLECHK(k_doc_norms(c, c->dnorm.p));  // :1680-1687
@@ -905,7 +888,7 @@ extern "C" int isle_hip_lloyds_sparse(isle_ctx* c, int k, const float* centers_i
   const SparseScalars sc = sparse_scalars(c, k);
   StopRule stop(c, k);
   const bool dense_first = plan.via_projection && (plan.fused_first || first_scratch_had(c, k));
-  c->lift_valid = false;  // the centres move below
+  c->res.centres_not_lifted();  // the centres move below
   int it = 0;
   SparseGroups groups;
   std::vector<float> delta_host;  // the k centre movements of the last update (Yinyang: choice of the movers)
@@ -925,7 +908,7 @@ extern "C" int isle_hip_lloyds_sparse(isle_ctx* c, int k, const float* centers_i
       ISLECHK(sparse_assign_first_via_projection(c, plan, sc, k, ld, groups.ymap, cn_grp));
     else if (it == 0 || !plan.hamerly)
       // documents are visited grouped by their previous centre (cache locality of the centre rows); results are order-independent
-      ISLECHK(k_spmm_wide_assign(c, c->centers_rm.p, k, ld, c->cnorm.p, c->dnorm.p, c->assign.p, c->members_valid ? c->members.p : nullptr, nullptr, c->hub.p,
+      ISLECHK(k_spmm_wide_assign(c, c->centers_rm.p, k, ld, c->cnorm.p, c->dnorm.p, c->assign.p, c->res.members_valid ? c->members.p : nullptr, nullptr, c->hub.p,
                                  plan.yinyang ? c->yglb.p : c->hlb.p, plan.yinyang ? G : 0));  // :1606
     else if (plan.yinyang)
       ISLECHK(sparse_reassign_yinyang(c, plan, sc, k, ld, it, groups, cn_grp, delta_host));
@@ -944,11 +927,7 @@ extern "C" int isle_hip_lloyds_sparse(isle_ctx* c, int k, const float* centers_i
     }
   }
   isle_host_mark("lloyds_sparse: loop done");
-  c->assign_valid = true;  // the partition stays resident for isle_hip_catchwords
-  if (max_reps > 0) {
-    c->km_last_space = ISLE_SPACE_WORD;
-    c->km_last_k = k;
-  }
+  c->res.lloyd_word_done(ISLE_SPACE_WORD, k, max_reps > 0);  // the partition stays resident for isle_hip_catchwords
   if (assign && D) HIPCHK(c, hipMemcpyAsync(assign, c->assign.p, D * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   if (centers_out) {
     HIPCHK(c, c->centers_cm.reserve((size_t)V * k));
@@ -970,12 +949,12 @@ extern "C" int isle_hip_lloyds_sparse(isle_ctx* c, int k, const float* centers_i
 static int objective_order(isle_ctx* c, int k, const uint32_t* assign_dev, const uint32_t** order) {
   *order = nullptr;
   if (c->D == 0) return 0;
-  if (!c->members_valid) {
+  if (!c->res.members_valid) {
     TimeScope ts(c, ISLE_T_SPARSE_ASSIGN);
     HIPCHK(c, c->ob_cnt.reserve(k));
     ISLECHK(k_count_sizes(c, assign_dev, c->D, k, c->ob_cnt.p));
     ISLECHK(k_member_lists_dev(c, assign_dev, c->D, k, c->ob_cnt.p));
-    c->members_valid = false;
+    c->res.member_lists_stale();
   }
   *order = c->members.p;
   return 0;
@@ -1023,18 +1002,18 @@ extern "C" int isle_hip_kmeans_objective(isle_ctx* c, int space, int k, const ui
   const bool word = space == ISLE_SPACE_WORD;
   const char* sname = word ? "word" : "projected";
   const uint64_t D = c->D, V = c->V;
-  if (!word && c->U_k != k)
-    return isle_fail(c, ISLE_E_ARG, "kmeans_objective: projected space needs U of k = %d columns, U has %d (run isle_hip_block_ks / set_U first)", k, c->U_k);
+  if (!word && c->res.U_k != k)
+    return isle_fail(c, ISLE_E_ARG, "kmeans_objective: projected space needs U of k = %d columns, U has %d (run isle_hip_block_ks / set_U first)", k, c->res.U_k);
   if (!assign) {
-    if (c->km_last_space != space || c->km_last_k != k || (word && !c->assign_valid))
+    if (!c->res.loop_partition_resident(space, k, word))
       return isle_fail(c, ISLE_E_ARG, "kmeans_objective: no resident partition for the %s space and k = %d (run the loop of that space or pass assign)", sname, k);
-    if (!word && (!c->P_ready || c->P_gen != c->km_proj_P_gen))
+    if (!word && !c->res.loop_projection_resident())
       return isle_fail(c, ISLE_E_ARG, "kmeans_objective: the projection P of the resident partition was released (run isle_hip_lloyds_projected again or pass assign)");
   } else {
     for (uint64_t j = 0; j < D; ++j)
       if (assign[j] >= (uint32_t)k) return isle_fail(c, ISLE_E_ARG, "kmeans_objective: assign[%llu] = %u out of range (k = %d)", (unsigned long long)j, assign[j], k);
   }
-  if (!centers && (word ? !c->centers_ready || c->centers_k != k : c->km_proj_k != k))
+  if (!centers && !c->res.loop_centres_resident(word, k))
     return isle_fail(c, ISLE_E_ARG, "kmeans_objective: no resident centres for the %s space and k = %d (run the loop of that space or pass centers)", sname, k);
   ISLECHK(agree_i32(c, 2 * k + space, "the space and k of kmeans_objective"));
   if (!word) ISLECHK(ensure_P(c, k));  // local to the shard: no collective

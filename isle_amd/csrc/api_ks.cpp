@@ -365,12 +365,7 @@ int install_U(isle_ctx* c, const float* Ucm_dev, int k) {
     HIPCHK(c, hipMemcpyAsync(c->Ucm.p, Ucm_dev, (size_t)c->V * k * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(c->Urm.p, 0, (size_t)c->V * c->ldk * sizeof(float), c->stream));
   ISLECHK(k_transpose(c, c->Ucm.p, c->V, k, c->V, c->Urm.p, c->ldk));  // compute_U_rowmajor :1223-1231
-  c->U_k = k;
-  c->P_ready = false;
-  c->Pt_ready = false;
-  c->Pt2_ready = false;
-  c->lift_valid = false;
-  c->centers_ready = false;
+  c->res.U_installed(k);
   return 0;
 }
 
@@ -417,7 +412,7 @@ extern "C" int isle_hip_block_ks(isle_ctx* c, int nev, int ncv, int maxit, int b
   ISLECHK(isle_enter(c));
   Ks ks;
   ks.dim = c->V;
-  c->band_ready = false;  // the operator (CSR copy) is rebuilt per solve, as in src/sparseMatrix.cpp:1199
+  c->res.operator_must_be_rebuilt();  // the operator (CSR copy) is rebuilt per solve, as in src/sparseMatrix.cpp:1199
   int nc = 0;
   const int rc = ks_solve(c, ks, nev, ncv, maxit, blk, tol, seed, evals, &nc, restarts, napplies, nullptr);
   if (nconv) *nconv = nc;
@@ -459,9 +454,9 @@ extern "C" int isle_hip_block_ks_dense(isle_ctx* c, const float* A, uint64_t n, 
 }
 
 extern "C" int isle_hip_get_U(isle_ctx* c, float* U) {
-  if (!c || !U || c->U_k == 0) return isle_fail(c, ISLE_E_ARG, "no U available");
+  if (!c || !U || c->res.U_k == 0) return isle_fail(c, ISLE_E_ARG, "no U available");
   ISLECHK(isle_enter(c));
-  HIPCHK(c, hipMemcpyAsync(U, c->Ucm.p, (size_t)c->V * c->U_k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(U, c->Ucm.p, (size_t)c->V * c->res.U_k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }

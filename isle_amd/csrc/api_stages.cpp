@@ -31,8 +31,7 @@ static int entries_ok(isle_ctx* c, const char* who, uint64_t nread, uint64_t max
 static int install_A(isle_ctx* c, uint64_t doc_offset, uint64_t docs_global, uint64_t entries, uint64_t* entries_out, uint64_t* nnz_out) {
   c->a_doc_offset = doc_offset;
   c->a_D_global = docs_global ? docs_global : c->a_D;
-  c->a_ready = true;
-  isle_void_derived_from_A(c);
+  c->res.A_installed();
   if (entries_out) *entries_out = entries;
   if (nnz_out) *nnz_out = c->a_nnz;
   return 0;
@@ -69,6 +68,7 @@ extern "C" int isle_hip_upload_counts_u32(isle_ctx* c, uint64_t V, uint64_t D, u
       if (!(counts[i] > 0.f)) return isle_fail(c, ISLE_E_ARG, "count not positive at %lld", (long long)i);
     }
   }
+  c->res.A_rewrite_begins();  // a_V / a_D / a_nnz and the buffers are rewritten from here: a failed allocation leaves no A
   c->a_V = V;
   c->a_D = D;
   c->a_nnz = nnz;
@@ -94,7 +94,7 @@ extern "C" int isle_hip_ingest_tdf(isle_ctx* c, const char* text, uint64_t nbyte
   if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "ingest_tdf: single-rank only");
   ISLECHK(shape_ok(c, "ingest_tdf: ", V, D, false));
   if (nbytes && !text) return isle_fail(c, ISLE_E_ARG, "ingest_tdf: null text");
-  c->a_ready = false;
+  c->res.A_rewrite_begins();
   DevBuf<unsigned char> td;
   StreamDrain drain(c);
   HIPCHK(c, td.reserve(nbytes + 16));
@@ -153,7 +153,7 @@ extern "C" int isle_hip_feed_entries_pieces(isle_ctx* c, uint64_t n, const uint3
 
 extern "C" int isle_hip_feed_finalize(isle_ctx* c, uint64_t doc_offset, uint64_t docs_global, uint64_t* entries_fed, uint64_t* nnz) {
   FEED_OPEN("feed_finalize", false);
-  c->a_ready = false;  // a_cnt / a_rows / a_offs are rewritten from here
+  c->res.A_rewrite_begins();  // a_cnt / a_rows / a_offs are rewritten from here
   const uint64_t fed = f.n;
   ISLECHK(feed_discard(c, k_feed_finalize(c)));
   return install_A(c, doc_offset, docs_global, fed, entries_fed, nnz);
@@ -340,7 +340,7 @@ extern "C" int isle_hip_tdf_finalize(isle_ctx* c, uint64_t max_entries, uint64_t
     f.release();
     return refused;
   }
-  c->a_ready = false;  // a_cnt / a_rows / a_offs are rewritten from here
+  c->res.A_rewrite_begins();  // a_cnt / a_rows / a_offs are rewritten from here
   f.n = f.known.entries;
   k_tdf_release_text(c);
   ISLECHK(feed_discard(c, k_feed_finalize(c)));
@@ -350,7 +350,7 @@ extern "C" int isle_hip_tdf_finalize(isle_ctx* c, uint64_t max_entries, uint64_t
 extern "C" int isle_hip_get_A(isle_ctx* c, float* counts, uint32_t* rows, int64_t* offs) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  if (!c->a_ready) return isle_fail(c, ISLE_E_ARG, "get_A: no count matrix");
+  if (!c->res.a_ready) return isle_fail(c, ISLE_E_ARG, "get_A: no count matrix");
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (counts && c->a_nnz) HIPCHK(c, hipMemcpy(counts, c->a_cnt.p, c->a_nnz * sizeof(float), hipMemcpyDeviceToHost));
   if (rows && c->a_nnz) HIPCHK(c, hipMemcpy(rows, c->a_rows.p, c->a_nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -387,7 +387,7 @@ struct Th {
     avg = corpus_avg(st[0], nz_docs);
     if (avg_out) *avg_out = avg;
     c->a_avg = avg;
-    c->a_avg_valid = true;
+    c->res.corpus_average_known();
     if (!hist_maxv(avg, &maxv)) return isle_fail(c, ISLE_E_ARG, "threshold: average document size %g too large", (double)avg);
     return 0;
   }
@@ -491,8 +491,7 @@ struct Th {
     if (D == 0) HIPCHK(c, hipMemsetAsync(c->offs.p, 0, sizeof(int64_t), c->stream));
     ISLECHK(k_th_emit(c, c->a_doc_offset));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    isle_void_derived_from_B(c);
-    c->b_from_threshold = true;
+    c->res.B_replaced(true);
     if (docs_kept) *docs_kept = Db;
     if (nnz_kept) *nnz_kept = bnnz;
     return 0;
@@ -503,7 +502,7 @@ extern "C" int isle_hip_threshold(isle_ctx* c, uint64_t num_topics, double sampl
                                   uint64_t* nnz_kept, uint64_t* entries_above, float* avg_out) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  if (!c->a_ready) return isle_fail(c, ISLE_E_ARG, "threshold: no count matrix uploaded");
+  if (!c->res.a_ready) return isle_fail(c, ISLE_E_ARG, "threshold: no count matrix uploaded");
   if (num_topics == 0) return isle_fail(c, ISLE_E_ARG, "threshold: num_topics == 0");
   Th th(c, num_topics, sample_rate, sample_seed);
   ISLECHK(th.stats(avg_out));
@@ -517,7 +516,7 @@ extern "C" int isle_hip_threshold(isle_ctx* c, uint64_t num_topics, double sampl
 
 extern "C" int isle_hip_counts_shape(isle_ctx* c, uint64_t* V, uint64_t* D, uint64_t* nnz, uint64_t* doc_offset, uint64_t* docs_global) {
   if (!c) return ISLE_E_ARG;
-  if (!c->a_ready) return isle_fail(c, ISLE_E_ARG, "counts_shape: no count matrix");
+  if (!c->res.a_ready) return isle_fail(c, ISLE_E_ARG, "counts_shape: no count matrix");
   if (V) *V = c->a_V;
   if (D) *D = c->a_D;
   if (nnz) *nnz = c->a_nnz;
@@ -540,7 +539,7 @@ extern "C" int isle_hip_get_B(isle_ctx* c, float* vals, uint32_t* rows, int64_t*
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
   if (c->V == 0) return isle_fail(c, ISLE_E_ARG, "get_B: no matrix");
-  if ((original_cols || zetas) && !c->b_from_threshold)
+  if ((original_cols || zetas) && !c->res.b_from_threshold)
     return isle_fail(c, ISLE_E_ARG, "get_B: original_cols / zetas exist only after isle_hip_threshold");
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (vals && c->nnz) HIPCHK(c, hipMemcpy(vals, c->vals.p, c->nnz * sizeof(float), hipMemcpyDeviceToHost));
@@ -556,7 +555,7 @@ extern "C" int isle_hip_get_B(isle_ctx* c, float* vals, uint32_t* rows, int64_t*
 // ------------------------------------------------------------------------------------------
 // the calls that are collective over document shards (catchwords, topic model) ...
 static int post_prepare_sharded(isle_ctx* c, const char* who) {
-  if (!c->a_ready) return isle_fail(c, ISLE_E_ARG, "%s: no count matrix uploaded (isle_hip_upload_counts_u32)", who);
+  if (!c->res.a_ready) return isle_fail(c, ISLE_E_ARG, "%s: no count matrix uploaded (isle_hip_upload_counts_u32)", who);
   return 0;
 }
 // ... and the ones that read A on one rank only
@@ -576,7 +575,7 @@ static int model_reader_ok(isle_ctx* c, int which, const char* who) {
 // a_nv = avg_doc_sz * (count / doc_sum) over A (src/sparseMatrix.cpp:136-167), the values the catchword stage and the top-five
 // diagnostic read; avg_doc_sz from the thresholding when it ran, else computed here by the same rule (:92-99), over all ranks
 static int ensure_avg_doc_sz(isle_ctx* c) {
-  if (!c->a_avg_valid) {  // B came from the host: the corpus statistics were never computed here
+  if (!c->res.a_avg_valid) {  // B came from the host: the corpus statistics were never computed here
     HIPCHK(c, c->a_scan.reserve(isle_scan_scratch(c->a_D) + 4));
     ISLECHK(k_th_stats(c, (uint64_t*)c->a_scan.p));
     ISLECHK(allreduce_sum<uint64_t>(c, (uint64_t*)c->a_scan.p, 2));
@@ -584,7 +583,7 @@ static int ensure_avg_doc_sz(isle_ctx* c) {
     HIPCHK(c, hipMemcpyAsync(st, c->a_scan.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->a_avg = corpus_avg(st[0], st[1]);
-    c->a_avg_valid = true;
+    c->res.corpus_average_known();
   }
   return 0;
 }
@@ -649,17 +648,15 @@ extern "C" int isle_hip_catchwords(isle_ctx* c, int num_topics, const uint32_t* 
   if (num_topics < 1) return isle_fail(c, ISLE_E_ARG, "catchwords: num_topics < 1");
   if (r < 1 || r > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "catchwords: rank r = %llu out of range (too few documents per topic?)",
                                                     (unsigned long long)r);
-  const bool identity = !c->b_from_threshold;
+  const bool identity = !c->res.b_from_threshold;
   if (identity && c->D != c->a_D) return isle_fail(c, ISLE_E_ARG, "catchwords: B was uploaded separately and its columns do not match A's");
   if (assign) {
     for (uint64_t j = 0; j < c->D; ++j)
       if (assign[j] >= (uint32_t)num_topics) return isle_fail(c, ISLE_E_ARG, "catchwords: assign[%llu] out of range", (unsigned long long)j);
     HIPCHK(c, c->assign.reserve(c->D ? c->D : 1));
     if (c->D) HIPCHK(c, hipMemcpy(c->assign.p, assign, c->D * sizeof(uint32_t), hipMemcpyHostToDevice));
-    c->assign_valid = true;
-    c->members_valid = false;
-    c->km_last_space = -1;  // the caller's partition, no loop's
-  } else if (!c->assign_valid) {
+    c->res.partition_given();
+  } else if (!c->res.assign_valid) {
     return isle_fail(c, ISLE_E_ARG, "catchwords: no partition resident (run isle_hip_lloyds_sparse or pass assign)");
   }
   ISLECHK(post_normalize_A(c));
@@ -676,10 +673,7 @@ extern "C" int isle_hip_catchwords(isle_ctx* c, int num_topics, const uint32_t* 
   uint64_t nc = 0;
   ISLECHK(k_post_find_catchwords(c, (uint32_t)num_topics, rho, &nc));
   if (num_catchwords) *num_catchwords = nc;
-  c->p_k = num_topics;
-  c->p_catch_ready = true;
-  c->p_model_ready = false;
-  c->p_avg_ready = false;
+  c->res.catchwords_done(num_topics);
   if (thresholds) {
     HIPCHK(c, c->p_segvals.reserve((size_t)c->a_V * num_topics));
     ISLECHK(k_post_thr_colmajor(c, (uint32_t)num_topics, c->p_segvals.p));
@@ -695,7 +689,7 @@ extern "C" int isle_hip_topic_model(isle_ctx* c, int num_topics, uint64_t rank_t
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
   ISLECHK(post_prepare_sharded(c, "topic_model"));
-  if (!c->p_catch_ready || c->p_k != num_topics) return isle_fail(c, ISLE_E_ARG, "topic_model: run isle_hip_catchwords(num_topics = %d) first", num_topics);
+  if (!c->res.p_catch_ready || c->res.p_k != num_topics) return isle_fail(c, ISLE_E_ARG, "topic_model: run isle_hip_catchwords(num_topics = %d) first", num_topics);
   if (rank_threshold < 1 || rank_threshold > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "topic_model: rank_threshold out of range");  // :721
   uint64_t n = 0;
   ISLECHK(k_post_doc_topic_sums(c, (uint32_t)num_topics, &n));
@@ -708,7 +702,7 @@ extern "C" int isle_hip_topic_model(isle_ctx* c, int num_topics, uint64_t rank_t
   ISLECHK(k_post_model_accumulate(c, (uint32_t)num_topics));  // this rank's documents ...
   ISLECHK(allreduce_sum<float>(c, c->p_model.p, (size_t)c->a_V * num_topics));  // ... all documents: V x k floats
   ISLECHK(k_post_model_normalize(c, (uint32_t)num_topics));
-  c->p_model_ready = true;
+  c->res.topic_model_done();
   if (doc_topic_sums) *doc_topic_sums = n;
   if (model) HIPCHK(c, hipMemcpyAsync(model, c->p_model.p, (size_t)c->a_V * num_topics * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   if (model_threshold) HIPCHK(c, hipMemcpyAsync(model_threshold, c->p_mthr.p, num_topics * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -721,7 +715,7 @@ extern "C" int isle_hip_topic_model(isle_ctx* c, int num_topics, uint64_t rank_t
 extern "C" int isle_hip_get_doc_topic_sums(isle_ctx* c, int64_t* doc_offsets, uint32_t* topic, float* val) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  if (!c->p_model_ready) return isle_fail(c, ISLE_E_ARG, "get_doc_topic_sums: run isle_hip_topic_model first");
+  if (!c->res.p_model_ready) return isle_fail(c, ISLE_E_ARG, "get_doc_topic_sums: run isle_hip_topic_model first");
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (doc_offsets) HIPCHK(c, hipMemcpy(doc_offsets, c->p_dts_off.p, (c->a_D + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
   if (topic && c->p_dts_n) HIPCHK(c, hipMemcpy(topic, c->p_dts_topic.p, c->p_dts_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -731,14 +725,14 @@ extern "C" int isle_hip_get_doc_topic_sums(isle_ctx* c, int64_t* doc_offsets, ui
 
 static int check_topic_pairs(isle_ctx* c, const int64_t* pairs, int n, const char* who) {
   for (int e = 0; e < 2 * n; ++e)
-    if (pairs[e] < 0 || pairs[e] >= c->p_k) return isle_fail(c, ISLE_E_ARG, "%s: topic id %lld out of range", who, (long long)pairs[e]);
+    if (pairs[e] < 0 || pairs[e] >= c->res.p_k) return isle_fail(c, ISLE_E_ARG, "%s: topic id %lld out of range", who, (long long)pairs[e]);
   return 0;
 }
 
 extern "C" int isle_hip_edge_topics(isle_ctx* c, const int64_t* pairs, int n, float primary_ratio, float* edge) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  if (!c->p_model_ready) return isle_fail(c, ISLE_E_ARG, "edge_topics: run isle_hip_topic_model first");
+  if (!c->res.p_model_ready) return isle_fail(c, ISLE_E_ARG, "edge_topics: run isle_hip_topic_model first");
   if (n < 0 || (n && (!pairs || !edge))) return isle_fail(c, ISLE_E_ARG, "edge_topics: bad arguments");
   if (n == 0) return 0;
   ISLECHK(check_topic_pairs(c, pairs, n, "edge_topics"));
@@ -777,10 +771,10 @@ extern "C" int isle_hip_select_edge_pairs(isle_ctx* c, const int32_t* top1, cons
   DevBuf<int32_t> u1, u2;
   StreamDrain drain(c);
   if (resident) {
-    if (!c->p_model_ready) return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: no resident top topics (run isle_hip_topic_model, or pass top1 / top2)");
-    if (n_docs != c->a_D || num_topics != c->p_k)
+    if (!c->res.p_model_ready) return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: no resident top topics (run isle_hip_topic_model, or pass top1 / top2)");
+    if (n_docs != c->a_D || num_topics != c->res.p_k)
       return isle_fail(c, ISLE_E_ARG, "select_edge_pairs: n_docs x num_topics = %llu x %d, the resident topic model has %llu x %d", (unsigned long long)n_docs,
-                       num_topics, (unsigned long long)c->a_D, c->p_k);
+                       num_topics, (unsigned long long)c->a_D, c->res.p_k);
     t1 = c->p_top1.p;
     t2 = c->p_top2.p;
   } else {
@@ -829,11 +823,11 @@ extern "C" int isle_hip_avg_topic_model(isle_ctx* c, int num_topics, float* mode
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
   ISLECHK(post_prepare(c, "avg_topic_model"));
-  if (num_topics < 1 || !c->p_catch_ready || c->p_k != num_topics)
+  if (num_topics < 1 || !c->res.p_catch_ready || c->res.p_k != num_topics)
     return isle_fail(c, ISLE_E_ARG, "avg_topic_model: run isle_hip_catchwords(num_topics = %d) first", num_topics);
-  c->p_avg_ready = false;
+  c->res.avg_model_begins();
   ISLECHK(k_avg_model(c, (uint32_t)num_topics));
-  c->p_avg_ready = true;
+  c->res.avg_model_done();
   if (model) HIPCHK(c, hipMemcpyAsync(model, c->p_avg_model.p, (size_t)c->a_V * num_topics * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
@@ -842,17 +836,17 @@ extern "C" int isle_hip_avg_topic_model(isle_ctx* c, int num_topics, float* mode
 // the resident model `which` names and its size, or null with the reason in the context
 static const float* resident_model(isle_ctx* c, int which, const char* who, uint64_t* V, int* cols) {
   *V = c->a_V;
-  *cols = c->p_k;
+  *cols = c->res.p_k;
   if (which == ISLE_MODEL_CATCH) {
-    if (c->p_model_ready) return c->p_model.p;
+    if (c->res.p_model_ready) return c->p_model.p;
     isle_fail(c, ISLE_E_ARG, "%s: no catch model (run isle_hip_topic_model)", who);
   } else if (which == ISLE_MODEL_AVG) {
-    if (c->p_avg_ready) return c->p_avg_model.p;
+    if (c->res.p_avg_ready) return c->p_avg_model.p;
     isle_fail(c, ISLE_E_ARG, "%s: no average model (run isle_hip_avg_topic_model)", who);
   } else if (which == ISLE_MODEL_LOADED) {
     *V = c->ml_V;
     *cols = c->ml_cols;
-    if (c->ml_ready) return c->ml_model.p;
+    if (c->res.ml_ready) return c->ml_model.p;
     isle_fail(c, ISLE_E_ARG, "%s: no loaded model (run isle_hip_load_model_text)", who);
   } else {
     isle_fail(c, ISLE_E_ARG, "%s: unknown model %d", who, which);
@@ -983,7 +977,7 @@ extern "C" int isle_hip_load_model_text(isle_ctx* c, const char* text, uint64_t 
   std::swap(c->ml_model.cap, next.cap);
   c->ml_V = vocab;
   c->ml_cols = ncols;
-  c->ml_ready = true;
+  c->res.model_loaded();
   if (nentries) *nentries = n;
   return 0;
 }
@@ -991,7 +985,7 @@ extern "C" int isle_hip_load_model_text(isle_ctx* c, const char* text, uint64_t 
 extern "C" int isle_hip_get_loaded_model(isle_ctx* c, float* model, uint64_t* vocab, int* ncols) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  if (!c->ml_ready) return isle_fail(c, ISLE_E_ARG, "get_loaded_model: no loaded model (run isle_hip_load_model_text)");
+  if (!c->res.ml_ready) return isle_fail(c, ISLE_E_ARG, "get_loaded_model: no loaded model (run isle_hip_load_model_text)");
   if (vocab) *vocab = c->ml_V;
   if (ncols) *ncols = c->ml_cols;
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1005,7 +999,7 @@ extern "C" int isle_hip_edge_topics_text(isle_ctx* c, const int64_t* pairs, int 
   ISLECHK(isle_enter(c));
   if (nbytes) *nbytes = 0;
   if (nentries) *nentries = 0;
-  if (!c->p_model_ready) return isle_fail(c, ISLE_E_ARG, "edge_topics_text: run isle_hip_topic_model first");
+  if (!c->res.p_model_ready) return isle_fail(c, ISLE_E_ARG, "edge_topics_text: run isle_hip_topic_model first");
   if (format != ISLE_TEXT_SPARSE && format != ISLE_TEXT_DENSE) return isle_fail(c, ISLE_E_ARG, "edge_topics_text: unknown format %d", format);
   if (n < 0 || (n && !pairs)) return isle_fail(c, ISLE_E_ARG, "edge_topics_text: bad arguments");
   if (n == 0) return 0;
@@ -1120,7 +1114,7 @@ extern "C" int isle_hip_infer_resident(isle_ctx* c, int which, const float* mode
 extern "C" int isle_hip_get_infer_entries(isle_ctx* c, int64_t* doc_offsets, uint32_t* topic, float* weight) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  if (!c->inf_valid) return isle_fail(c, ISLE_E_ARG, "get_infer_entries: no entries (run isle_hip_infer_resident; a new count matrix voids them)");
+  if (!c->res.inf_valid) return isle_fail(c, ISLE_E_ARG, "get_infer_entries: no entries (run isle_hip_infer_resident; a new count matrix voids them)");
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (doc_offsets) HIPCHK(c, hipMemcpy(doc_offsets, c->inf_off.p, (c->inf_docs + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
   if (topic && c->inf_n) HIPCHK(c, hipMemcpy(topic, c->inf_topic.p, c->inf_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -1136,7 +1130,7 @@ extern "C" int isle_hip_infer_text(isle_ctx* c, int what, uint64_t row_begin, ui
   if (nbytes) *nbytes = 0;
   if (nlines) *nlines = 0;
   if (what != ISLE_DOCTEXT_ENTRIES && what != ISLE_DOCTEXT_TOP) return isle_fail(c, ISLE_E_ARG, "infer_text: unknown kind %d", what);
-  if (!c->inf_valid) return isle_fail(c, ISLE_E_ARG, "infer_text: no resident result (run isle_hip_infer_resident; a new count matrix voids it)");
+  if (!c->res.inf_valid) return isle_fail(c, ISLE_E_ARG, "infer_text: no resident result (run isle_hip_infer_resident; a new count matrix voids it)");
   if (row_begin > row_end || row_end > c->inf_docs)
     return isle_fail(c, ISLE_E_ARG, "infer_text: rows [%llu, %llu) of %llu", (unsigned long long)row_begin, (unsigned long long)row_end,
                      (unsigned long long)c->inf_docs);
@@ -1200,7 +1194,7 @@ extern "C" int isle_hip_doc_report_text(isle_ctx* c, int what, uint64_t doc_begi
   ISLECHK(post_prepare_sharded(c, "doc_report_text"));
   if (what != ISLE_DOCREPORT_CATCHWORDS && what != ISLE_DOCREPORT_TOPIC_SUMS && what != ISLE_DOCREPORT_TOPIC_SUMS_BY_DOC && what != ISLE_DOCREPORT_TOP_TWO)
     return isle_fail(c, ISLE_E_ARG, "doc_report_text: unknown kind %d", what);
-  if (what == ISLE_DOCREPORT_CATCHWORDS ? !c->p_catch_ready : !c->p_model_ready)
+  if (what == ISLE_DOCREPORT_CATCHWORDS ? !c->res.p_catch_ready : !c->res.p_model_ready)
     return isle_fail(c, ISLE_E_ARG, "doc_report_text: run %s first (a new count matrix voids its result)",
                      what == ISLE_DOCREPORT_CATCHWORDS ? "isle_hip_catchwords" : "isle_hip_topic_model");
   if (doc_begin > doc_end || doc_end > c->a_D)

@@ -13,6 +13,7 @@
 
 #include "gl_plan.h"
 #include "knobs.h"
+#include "resident_host.h"
 #include "route_host.h"
 
 // ------------------------------------------------------------------------------------------
@@ -201,6 +202,7 @@ struct isle_ctx {
   hipStream_t stream = nullptr;
   std::string err;
   int num_cus = 256;
+  IsleResident res;  // which of the products below still describe the current inputs (resident_host.h: read anywhere, written by its events only)
 
   // --- page-locked host memory for the small per-iteration copies of the control loops (mailboxes, scalars, flags): a
   // hipMemcpyAsync to or from pageable memory blocks the host until the copy has run, which serialises the enqueue-ahead
@@ -239,7 +241,6 @@ struct isle_ctx {
 
   // --- A (word-document counts, this rank's column shard) and the thresholding workspaces (threshold.hip)
   uint64_t a_V = 0, a_D = 0, a_nnz = 0, a_doc_offset = 0, a_D_global = 0;
-  bool a_ready = false;
   IsleFeed feed;
   DevBuf<float> a_cnt;
   DevBuf<uint32_t> a_rows;
@@ -251,9 +252,7 @@ struct isle_ctx {
   DevBuf<int64_t> a_off_all, a_col_of, a_scan;
   DevBuf<float> zetas;             // V
   DevBuf<uint64_t> original_cols;  // D (B column -> global document id of A)
-  bool b_from_threshold = false;
   float a_avg = 0.f;               // avg_doc_sz of the whole corpus (src/sparseMatrix.cpp:98)
-  bool a_avg_valid = false;
 
   // --- downstream stage (post.hip): catchwords, topic model, edge topics
   DevBuf<float> a_nv;              // normalised values of A
@@ -292,17 +291,12 @@ struct isle_ctx {
   DevBuf<int32_t> inf_top_topic;   // docs x 5, < 0 = no further topic: what isle_hip_infer_text(ISLE_DOCTEXT_TOP) prints
   DevBuf<float> inf_top_weight;
   uint64_t inf_docs = 0, inf_n = 0;
-  bool inf_valid = false;
-  int p_k = 0;                     // num_topics of the last catchword pass
   // the model of the last successful isle_hip_load_model_text (model_load.hip): independent of A, B, the partition and the catchwords
   DevBuf<float> ml_model;          // ml_V x ml_cols col-major
   uint64_t ml_V = 0;
   int ml_cols = 0;
-  bool ml_ready = false;
-  bool p_catch_ready = false, p_model_ready = false, p_avg_ready = false, assign_valid = false;
 
   // --- chunked-CSR copy of B for Z = B*Y (built per eigensolve, like the reference's operator ctor)
-  bool band_ready = false;
   uint32_t band_rows = 0;  // requested columns per chunk (0 = default), env ISLE_CHUNK_COLS
   uint32_t nbands = 0;     // number of column chunks (multiple of 8)
   uint32_t chunk_cols = 0;
@@ -313,7 +307,6 @@ struct isle_ctx {
 
   // --- LDS-banded Gram apply (gram_lds.hip): used when every row of B holds a single value (B = diag(s) * pattern, which is
   // what threshold_and_copy produces, src/sparseMatrix.cpp:1285-1321); otherwise the gather kernels of spmm.hip run.
-  int gl_mode = -1;          // -1 not decided for the current B, 0 gather path, 1 LDS path
   GlSide gl1, gl2;           // pass 1 (outputs = documents, sources = words), pass 2 (outputs = words, sources = documents)
   DevBuf<float> rowval;      // V: the value of row w
   DevBuf<int> gl_flag;
@@ -361,7 +354,6 @@ struct isle_ctx {
   DevBuf<double> jacS;        // per-pair Gram / rotation scratch
   DevBuf<float> Wf;        // n x n float eigenvectors
   DevBuf<float> evd_in;    // n x n: the fp32 matrix handed to the small EVD
-  int U_k = 0;             // number of columns of U available
   DevBuf<float> Ucm;       // V x k col-major  (copy of basis[:, :k])
   DevBuf<float> Urm;       // V x ldk row-major
   int ldk = 0;
@@ -369,7 +361,6 @@ struct isle_ctx {
   // --- k-means state
   DevBuf<float> P;         // D x ldk
   DevBuf<float> pnorm;     // D
-  bool P_ready = false;
   DevBuf<float> Pt;        // ldk x D coordinate-major copy (projected assignment), only for ldk <= 256
   DevBuf<float> dotsT;     // D x k centre-major dot products (first assignment of Lloyd on B through the projection)
   DevBuf<uint4> gemm_b3;   // the small operand of k_gemm_nn_assign split into three bf16 terms (gemm_bf16x3.h)
@@ -384,12 +375,8 @@ struct isle_ctx {
   uint32_t ga_last_redo = 0;  // their number in the last product (diagnostic: isle_hip_measure)
   DevBuf<float> assign_part;  // per document and 64-column slot the best centre of the slot (16 bytes: k_gemm_assign_yy / _tiles, dense.hip)
   DevBuf<float> lift_C;    // the k x k coefficients the device-resident centres were lifted from (centres = U lift_C^T)
-  int lift_ld = 0, lift_k = 0;
-  bool lift_valid = false;
-  bool Pt_ready = false;
   DevBuf<uint4> Pt2;       // the coordinate-major copy split in two bf16 terms, as the LDS image of every (row block, slab): the A operand of the
-  bool Pt2_ready = false;  // LDS-DMA assignment products (gemm_bf16x3.h, gemm_bf16x2_dma_k)
-  bool Pt2_pos = false;    // its rows are POSITIONS of the length order (row m = document dperm[m]): made by the grouped projection on its way
+                           // LDS-DMA assignment products (gemm_bf16x3.h, gemm_bf16x2_dma_k); by document or by position: res.Pt2
   DevBuf<float> min_dist;  // D
   DevBuf<double> cum;      // D + 1
   DevBuf<double> scan_blk;
@@ -400,12 +387,9 @@ struct isle_ctx {
   DevBuf<int> counts;
   DevBuf<uint32_t> members;  // documents grouped by centre
   DevBuf<int> moff;          // k+1 offsets, k cursors
-  bool members_valid = false; // members = a permutation of the local docs grouped by centre
   DevBuf<int> flags;
   DevBuf<float> centers_rm;   // V x ldk  (word-space centres, row-major)
   DevBuf<float> centers_cm;   // V x k col-major staging
-  bool centers_ready = false;
-  int centers_k = 0;
   DevBuf<float> dnorm;     // D   |b_d|^2
   DevBuf<float> hub, hlb;  // D   Hamerly bounds (sparse Lloyd)
   DevBuf<float> yglb;      // D x G Yinyang group bounds (sparse Lloyd)
@@ -427,8 +411,6 @@ struct isle_ctx {
   DevBuf<float> kmpp_best;     // distances to the nearest of ALL k seeds (min_dist does not include the last batch)
   bool kmpp_track = false;     // every round so far went through the tracking kernel
   int kmpp_track_seeds = 0;    // seeds folded in
-  int kmpp_track_k = 0;        // 0: nothing to start from; k: state complete for the k seeds in kmpp_C_host, projection generation kmpp_P_gen
-  uint64_t P_gen = 0, kmpp_P_gen = 0;
   std::vector<float> kmpp_C_host;  // the seeds' coordinates as handed to the caller (k x k)
   // Yinyang iteration ordered by group (spmm.hip, k_yy2_assign)
   DevBuf<float> yy_cg;                 // centres group-major: G tables of V x 8 floats
@@ -447,9 +429,6 @@ struct isle_ctx {
   DevBuf<uint32_t> ob_assign;            // an explicit partition
   DevBuf<float> ob_centres, ob_cm;       // explicit centres as the kernels read them; their column-major upload
   DevBuf<int> ob_cnt;                    // k local sizes for the member lists
-  int km_last_space = -1, km_last_k = 0;  // the loop that wrote c->assign last (ISLE_SPACE_*), and its k
-  int km_proj_k = 0;                      // Cdev holds the centres of a finished projected loop with this k ...
-  uint64_t km_proj_P_gen = 0;             // ... computed on this generation of the projection
   bool lloyd_trace = false;               // isle_hip_lloyds_trace
   std::vector<double> lloyd_trace_v[2];   // the total objective after every centre update of the last loop, per space
 
@@ -616,7 +595,7 @@ int k_pt_filter(isle_ctx* c, const uint32_t* order, const uint32_t* assign, floa
 int k_pt_tighten(isle_ctx* c, const float* P, const float* pn, int ldk, const float* C, const float* cn, const uint32_t* assign, const uint32_t* cand,
                  const uint32_t* ncand, float* ub, const float* tlb, int T, int TL, uint32_t* need, uint32_t* active, uint32_t* nactive);
 // gram_lds.hip
-int k_gl_detect(isle_ctx* c);            // sets c->gl_mode for the current B (no-op once decided)
+int k_gl_detect(isle_ctx* c);            // sets c->res.gl_mode for the current B (no-op once decided)
 int k_centers_counts(isle_ctx* c, const uint32_t* assign, int k, int ldk, float* Crm, bool fresh);  // fresh: needs c->members grouped by `assign`
 int k_gl_build(isle_ctx* c);
 int k_gl_wide(isle_ctx* c, const float* Mrm, int k, int ld, float* Out, float* norms = nullptr /*also the rows' squared norms (selects the grouped form)*/,
@@ -701,7 +680,7 @@ int k_text_pump(isle_ctx* c, const char* who, const uint64_t* offs_dev, uint64_t
 
 // infer_text.hip: the lines "<row + base>\t<topic + 1>\t<weight>\n" of rows [row_begin, row_end) of the resident inference result
 // (ISLE_DOCTEXT_ENTRIES: c->inf_off / inf_topic / inf_weight; ISLE_DOCTEXT_TOP: c->inf_top_topic / inf_top_weight), delivered as k_model_text
-// delivers.  The caller has checked the range and c->inf_valid.
+// delivers.  The caller has checked the range and c->res.inf_valid.
 int k_infer_text(isle_ctx* c, int what, uint64_t row_begin, uint64_t row_end, uint64_t base, isle_text_sink_fn sink, void* user, uint64_t* nbytes,
                  uint64_t* nlines);
 

@@ -1099,11 +1099,11 @@ int k_transpose(isle_ctx* c, const float* in, uint64_t rows, uint64_t cols, uint
 // routes that still want f32 columns — the register kernels, the three-term whole-product fallbacks, the non-fused products, the small-shape
 // k-means++ pass — ask for it here.
 int k_ensure_pt(isle_ctx* c) {
-  if (c->Pt_ready) return 0;
-  if (!c->P_ready || !c->D) return isle_fail(c, ISLE_E_ARG, "no projection to transpose");
+  if (c->res.Pt_ready) return 0;
+  if (!c->res.P_ready || !c->D) return isle_fail(c, ISLE_E_ARG, "no projection to transpose");
   HIPCHK(c, c->Pt.reserve((size_t)c->D * c->ldk));
   ISLECHK(k_transpose(c, c->P.p, c->ldk, c->D, c->ldk, c->Pt.p, c->D));
-  c->Pt_ready = true;
+  c->res.transposed_copy_made();
   return 0;
 }
 

@@ -222,7 +222,7 @@ int k_dr_sums_gathered_text(isle_ctx* c, uint64_t* key_a, uint32_t* doc_a, uint6
   bool in_a = true;
   {
     TimeScope ts(c, ISLE_T_POST);
-    ISLECHK(k_sort_pairs_u64(c, key_a, doc_a, key_b, doc_b, L, key_bits_of(c->p_k), &in_a));
+    ISLECHK(k_sort_pairs_u64(c, key_a, doc_a, key_b, doc_b, L, key_bits_of(c->res.p_k), &in_a));
   }
   if (L1 == L0) return 0;
   const DrGatherSrc src{in_a ? key_a : key_b, in_a ? doc_a : doc_b, L0, L1 - L0};
@@ -284,7 +284,7 @@ int k_doc_report_text(isle_ctx* c, int what, uint64_t doc_begin, uint64_t doc_en
     if (src.ncand >= (1ull << 32))
       return isle_fail(c, ISLE_E_ARG, "doc_report_text(topic_sums): %llu sums in one range; the order's payload is 32 bits wide — write the range in parts",
                        (unsigned long long)src.ncand);
-    const int key_bits = key_bits_of(c->p_k);
+    const int key_bits = key_bits_of(c->res.p_k);
     HIPCHK(c, key_a.reserve(src.ncand));
     HIPCHK(c, key_b.reserve(src.ncand));
     HIPCHK(c, idx_a.reserve(src.ncand));

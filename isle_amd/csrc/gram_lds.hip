@@ -1372,8 +1372,8 @@ int launch_apply_any(isle_ctx* c, int LPE, bool half, const GlSide& s, const flo
 // host side
 // ---------------------------------------------------------------------------------------------------------------
 int k_gl_detect(isle_ctx* c) {
-  if (c->gl_mode >= 0) return 0;  // decided for this B (reset by every upload / thresholding)
-  c->gl_mode = 0;
+  if (c->res.gl_mode >= 0) return 0;  // decided for this B (reset by every upload / thresholding)
+  c->res.operator_form_decided(false);  // until the answer is in: a failure below leaves the form every kernel can run
   // every rank takes part in the agreement below, whatever its own shard looks like
   const bool eligible = route_gl_eligible(c->nnz, c->D, c->V, c->route);
   HIPCHK(c, c->gl_flag.reserve(4));
@@ -1398,7 +1398,7 @@ int k_gl_detect(isle_ctx* c) {
   int flag = 0;
   HIPCHK(c, hipMemcpyAsync(&flag, c->gl_flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->gl_mode = flag ? 0 : 1;
+  c->res.operator_form_decided(flag == 0);
   return 0;
 }
 
@@ -1728,7 +1728,7 @@ int k_gl_panel_width(const isle_ctx* c) { return gl_panel_width(c); }
 // no partial-sector writes (round 5: k-means++ 264 -> 246 ms at config 3 in the timing-only build).
 int k_gl_thin(isle_ctx* c, const float* Wcm, int nc, int ld, float* Out, bool by_position) {
   ISLECHK(k_band_build(c));
-  if (c->gl_mode != 1) return isle_fail(c, ISLE_E_ARG, "k_gl_thin needs the LDS-banded form");
+  if (c->res.gl_mode != 1) return isle_fail(c, ISLE_E_ARG, "k_gl_thin needs the LDS-banded form");
   if (ld % 4 || nc > ld) return isle_fail(c, ISLE_E_ARG, "k_gl_thin: bad leading dimension");
   const uint32_t V = (uint32_t)c->V;
   HIPCHK(c, c->gl_Xs.reserve(gl_packed_floats(V, 3, true)));
@@ -1857,7 +1857,7 @@ __global__ __launch_bounds__(256) void gl_wide_norms_k(const float* __restrict__
 int k_gl_wide(isle_ctx* c, const float* Mrm, int k, int ld, float* Out, float* norms, void* A2pos, bool* a2_done) {
   if (a2_done) *a2_done = false;
   ISLECHK(k_band_build(c));
-  if (c->gl_mode != 1) return isle_fail(c, ISLE_E_ARG, "k_gl_wide needs the LDS-banded form");
+  if (c->res.gl_mode != 1) return isle_fail(c, ISLE_E_ARG, "k_gl_wide needs the LDS-banded form");
   if (ld % 4) return isle_fail(c, ISLE_E_ARG, "k_gl_wide: leading dimension %d not a multiple of 4", ld);
   const uint32_t V = (uint32_t)c->V;
   HIPCHK(c, c->gl_Xs.reserve(gl_packed_floats(V, 3, true)));

@@ -157,7 +157,7 @@ int k_infer_resident(isle_ctx* c, const float* model_cm_dev, int k, uint64_t doc
   chunk = std::min(chunk, ISLE_INFER_CHUNK_MAX_DOCS);
   chunk = std::max<uint64_t>(1, std::min(chunk, R));
   const uint64_t nch = (R + chunk - 1) / chunk;
-  c->inf_valid = false;
+  c->res.inference_begins();
 
   DevBuf<float> dM, dfa, dW, dllh;
   DevBuf<uint32_t> dfw, dnk, dcnt;
@@ -235,7 +235,7 @@ int k_infer_resident(isle_ctx* c, const float* model_cm_dev, int k, uint64_t doc
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->inf_docs = R;
   c->inf_n = (uint64_t)running;
-  c->inf_valid = true;
+  c->res.inference_done();
   if (nconverged) *nconverged = nc;
   if (nentries) *nentries = (uint64_t)running;
   return 0;

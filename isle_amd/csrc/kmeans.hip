@@ -311,8 +311,7 @@ int k_kmpp_update(isle_ctx* c, const float* P, const float* pn, uint64_t D, int 
   // measured rates: a pass of the pass-1 stream costs ~2.8 ps per nonzero (= 15.4 bytes of streaming at 5.5 TB/s), the materialised
   // projection streams at 5.5 TB/s for <= 16 new seeds (kmpp_min_pt_k) and 2.3x slower through the matrix-core tile beyond.
   {
-    const bool can = c->gl_mode == 1 && c->band_ready && c->U_k == k;
-    if (route_kmpp_sparse(can, c->nnz, D, ldk, nc, k_gl_panel_width(c), c->route)) {
+    if (route_kmpp_sparse(c->res.thin_product_possible(k), c->nnz, D, ldk, nc, k_gl_panel_width(c), c->route)) {
       // (Round 3 also built the pruned round of accelerated k-means++ seeding — only the documents a new seed can reach by the
       // triangle inequality, from the materialised projection.  On this corpus the documents of topics without a seed stay within
       // reach: 98 % at 20 seeds, 50 % at 570, 28 % at 906 of 1000, and a visited document costs a 4 kB row plus 2 k flops per new seed
@@ -347,7 +346,7 @@ int k_kmpp_update(isle_ctx* c, const float* P, const float* pn, uint64_t D, int 
     }
   }
   c->kmpp_track = false;  // the routes below do not keep the nearest seed and the tile minima
-  if (nc <= 16 && (c->Pt_ready || c->Pt2_ready) && (size_t)k * ((nc + 3) / 4) * sizeof(float4) <= 64 * 1024) {
+  if (nc <= 16 && (c->res.Pt_ready || c->res.Pt2_ready()) && (size_t)k * ((nc + 3) / 4) * sizeof(float4) <= 64 * 1024) {
     ISLECHK(k_ensure_pt(c));
     // streaming pass over the coordinate-major copy (the centres fit the default 64 KB of dynamic LDS)
     const int nq = (nc + 3) / 4;
@@ -829,7 +828,7 @@ static int launch_proj_reg(isle_ctx* c, uint64_t D, int k, int ldk, const float*
   *done = false;
   if (!D) return 0;
   if (!Pt) {  // the context's projection, coordinate-major: made from P if the default routes have not needed it yet
-    if (!(c->Pt_ready || c->Pt2_ready)) return 0;
+    if (!(c->res.Pt_ready || c->res.Pt2_ready())) return 0;
     ISLECHK(k_ensure_pt(c));
     Pt = c->Pt.p;
   }
@@ -1037,7 +1036,7 @@ int k_kmpp_to_tiles(isle_ctx* c, uint64_t D, int k, const float* pn, const float
 }
 
 bool k_proj_full_by_gemm(isle_ctx* c, uint64_t D, int k) {
-  return isle_route_mem(c, [&](uint64_t total_mem, bool* ask) { return route_proj_full_by_gemm(c->Pt_ready, c->Pt2_ready, D, k, c->route, total_mem, ask); });
+  return isle_route_mem(c, [&](uint64_t total_mem, bool* ask) { return route_proj_full_by_gemm(c->res.Pt_ready, c->res.Pt2_ready(), D, k, c->route, total_mem, ask); });
 }
 int k_proj_assign_tiles(isle_ctx* c, const float* P, const float* pn, uint64_t D, int k, int ldk, const float* C, const float* cn, uint32_t* assign,
                         float* ub, float* tlb, int TL, const uint32_t* active, uint32_t n, const uint32_t* need, float* Pa, float* pna) {
@@ -1051,9 +1050,9 @@ int k_proj_assign_tiles(isle_ctx* c, const float* P, const float* pn, uint64_t D
       if (route_gemm_assign_fused_ok(D, k, k, c->route)) {  // distances, tile bounds and candidates formed inside the product: no D x k matrix in memory
         HIPCHK(c, c->cmax_buf.reserve(4));
         ISLECHK(k_max_f32(c, cn, k, c->cmax_buf.p));
-        const bool a2 = c->Pt2_ready && P == c->P.p;
-        return k_gemm_assign_tiles(c, c->Pt_ready ? c->Pt.p : nullptr, P, ldk, D, k, C, ldk, k, TL, cn, pn, c->cmax_buf.p, assign, ub, tlb, ISLE_T_LLOYD_PROJ, nullptr,
-                                   a2 ? c->Pt2.p : nullptr, a2 && c->Pt2_pos ? c->dperm.p : nullptr);
+        const bool a2 = c->res.Pt2_ready() && P == c->P.p;
+        return k_gemm_assign_tiles(c, c->res.Pt_ready ? c->Pt.p : nullptr, P, ldk, D, k, C, ldk, k, TL, cn, pn, c->cmax_buf.p, assign, ub, tlb, ISLE_T_LLOYD_PROJ, nullptr,
+                                   a2 ? c->Pt2.p : nullptr, a2 && c->res.Pt2_by_position() ? c->dperm.p : nullptr);
       }
       HIPCHK(c, c->dotsT.reserve((size_t)D * k));
       ISLECHK(k_ensure_pt(c));
@@ -1254,7 +1253,7 @@ int k_member_lists_dev(isle_ctx* c, const uint32_t* assign, uint64_t D, int k, c
     hipLaunchKernelGGL(member_fill_k, dim3(cdiv(D, 256 * CS_ITEMS)), dim3(256), 2 * (size_t)k * sizeof(int), c->stream, assign, (uint32_t)D, k,
                        offd, cur, c->members.p);
   HIPCHK(c, hipGetLastError());
-  c->members_valid = true;
+  c->res.member_lists_built();
   return 0;
 }
 
@@ -1324,7 +1323,7 @@ int k_member_lists(isle_ctx* c, const uint32_t* assign, uint64_t D, int k, const
     ISLECHK(k_sort_pairs_u64(c, c->gl_key_a.p, va, c->gl_key_b.p, vb, D, bits, &in_a));
     if ((in_a ? va : vb) != c->members.p) return isle_fail(c, ISLE_E_NUMERIC, "member lists: unexpected number of sort passes");
   }
-  c->members_valid = true;
+  c->res.member_lists_built();
   return 0;
 }
 

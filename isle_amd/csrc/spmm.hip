@@ -200,12 +200,12 @@ __global__ __launch_bounds__(256) void csr_fill_k(const float* __restrict__ vals
 // The operator build of a solve: decides between the LDS-banded form (gram_lds.hip; every row of B holds one value) and the
 // gather form below, and builds the transposed copy of B that form needs.
 int k_band_build(isle_ctx* c) {
-  if (c->band_ready) return 0;
+  if (c->res.band_ready) return 0;
   TimeScope ts(c, ISLE_T_BAND_BUILD);
   ISLECHK(k_gl_detect(c));
-  if (c->gl_mode == 1) ISLECHK(k_gl_build(c));
+  if (c->res.gl_mode == 1) ISLECHK(k_gl_build(c));
   else ISLECHK(k_band_build_chunked(c));
-  c->band_ready = true;
+  c->res.operator_built();
   return 0;
 }
 
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(256) void reduce_chunks_k(const float4* __restrict_
 
 int k_gram_pass2(isle_ctx* c, int BP) {
   ISLECHK(k_band_build(c));
-  if (c->gl_mode == 1) return isle_fail(c, ISLE_E_ARG, "gather pass 2 called on the LDS-banded form");
+  if (c->res.gl_mode == 1) return isle_fail(c, ISLE_E_ARG, "gather pass 2 called on the LDS-banded form");
   TimeScope ts(c, ISLE_T_GRAM_PASS2);
   const uint32_t V = (uint32_t)c->V;
   const uint32_t nch = c->nbands;
@@ -665,7 +665,7 @@ int k_spmm_wide_project(isle_ctx* c, const float* Mrm, int k, int ldk, float* P,
   TimeScope ts(c, ISLE_T_PROJECT);
   if (a2_done) *a2_done = false;
   ISLECHK(k_gl_detect(c));
-  if (c->gl_mode == 1 && wide_through_lds(c)) {  // row-constant B: panels of M through LDS (gram_lds.hip)
+  if (c->res.gl_mode == 1 && wide_through_lds(c)) {  // row-constant B: panels of M through LDS (gram_lds.hip)
     return k_gl_wide(c, Mrm, k, ldk, P, norms, A2pos, a2_done);  // (the grouped form forms the norms — and the split copy — on its way; the plain one calls k_rownorms)
   }
   return launch_wide<WIDE_PROJECT>(c, Mrm, k, ldk, P, norms, nullptr, nullptr, nullptr, nullptr);
@@ -674,14 +674,12 @@ int k_spmm_wide_assign(isle_ctx* c, const float* Mrm, int k, int ldk, const floa
                        const uint32_t* perm, const uint32_t* nslots, float* ub, float* lb, int G) {
   TimeScope ts(c, ISLE_T_SPARSE_ASSIGN);
   ISLECHK(k_gl_detect(c));
-  if (c->gl_mode == 1 && !nslots && c->D && wide_through_lds(c)) {
+  if (c->res.gl_mode == 1 && !nslots && c->D && wide_through_lds(c)) {
     // full assignment on a row-constant B: dots = B^T C by the LDS-banded wide SpMM into the projection buffer (P is
     // recomputed if it is needed again), then the same epilogue from memory.  `perm` is only a visiting order: ignored.
     const uint32_t D = (uint32_t)c->D;
     HIPCHK(c, c->P.reserve((size_t)D * ldk));
-    c->P_ready = false;
-    c->Pt_ready = false;
-    c->Pt2_ready = false;
+    c->res.P_overwritten();
     ISLECHK(k_gl_wide(c, Mrm, k, ldk, c->P.p));
     return k_dots_assign(c, k, ldk, cn, dn, assign, ub, lb, G);
   }
@@ -738,7 +736,7 @@ __global__ __launch_bounds__(256) void centers_from_rows_k(const float* __restri
 // documents that changed centre)
 int k_centers_from_rows(isle_ctx* c, const uint32_t* assign, int k, int ldk, float* Crm, bool first_of_run) {
   ISLECHK(k_gl_detect(c));
-  if (c->gl_mode == 1)  // row-constant B: integer counting, no transposed copy
+  if (c->res.gl_mode == 1)  // row-constant B: integer counting, no transposed copy
     return k_centers_counts(c, assign, k, ldk, Crm, route_counts_fresh(first_of_run, c->route));
   ISLECHK(k_band_build(c));
   TimeScope ts(c, ISLE_T_SPARSE_UPDATE);
@@ -1795,7 +1793,7 @@ int k_yy_pack_groups(isle_ctx* c, const float* Crm, int ld, int G, const YyMap& 
   if ((ld & 3) != 0 || ((uintptr_t)Crm & 15) != 0) return isle_fail(c, ISLE_E_ARG, "yy_pack_groups: leading dimension %d not a multiple of 4", ld);
   const size_t lds = (size_t)YYP_W * ld * sizeof(float);
   ISLECHK(isle_max_lds(c, (const void*)yy2_pack_k, (int)lds));
-  hipLaunchKernelGGL(yy2_pack_k, dim3(cdiv(V, YYP_W)), dim3(256), lds, c->stream, Crm, V, ld, G, (float4*)c->yy_cg.p, c->centers_k, map.id_of_slot);
+  hipLaunchKernelGGL(yy2_pack_k, dim3(cdiv(V, YYP_W)), dim3(256), lds, c->stream, Crm, V, ld, G, (float4*)c->yy_cg.p, c->res.centers_k, map.id_of_slot);
   HIPCHK(c, hipGetLastError());
   return 0;
 }
