@@ -721,6 +721,43 @@ int isle_hip_doc_line_text(uint64_t doc_number, uint64_t topic_number, float w, 
 int isle_hip_doc_report_text(isle_ctx* ctx, int what, uint64_t doc_begin, uint64_t doc_end, isle_text_sink_fn sink, void* user,
                              uint64_t* nbytes, uint64_t* nlines);
 int isle_hip_top_two_line_text(uint64_t doc_number, uint64_t t1_number, uint64_t t2_number, char* out40);
+/* The n heaviest documents of every topic, selected on the device (isle_amd/csrc/topic_docs.hip) from entries that are stored by document,
+ * where they lie: nothing is sorted and nothing is gathered per topic.  The rule is stated once, in isle_amd/csrc/topdocs_host.h:
+ *   an entry is (row, topic, value); value is fp32 with bits b; the row's document is doc = doc_base + row, a 32-bit number in the corpus
+ *   ord(b) = b ^ (b >> 31 ? 0xffffffff : 0x80000000)           (for positive finite values, as both resident sources hold, the numeric order)
+ *   key    = (uint64)ord(b) << 32 | (uint32)~doc                the larger key wins: the heavier value, the smaller document among bit-equal
+ *                                                               values (the tie rule of ISLE_DOCREPORT_TOPIC_SUMS)
+ * For topic t the result is its min(n, cnt_t) largest keys in descending order, cnt_t the topic's entries over all ranks:
+ * docs[t n + i] / values[t n + i] for i < counts[t] = min(n, cnt_t), the unused slots 0xffffffff / 0.0f; topic_entries[t] = cnt_t (nullable).
+ * Values that are not positive finite go by ord as well (-0.0 below +0.0, negatives below, +inf above the finite values, NaN patterns by
+ * their bits): no value is refused.  docs / values are num_topics x n, topic-major.
+ *   ISLE_TOPDOCS_INFER  the resident entries of the last isle_hip_infer_resident; row 0 is that call's doc_begin
+ *   ISLE_TOPDOCS_SUMS   the document-topic catchword sums of the last isle_hip_topic_model; a row is a document of A; num_topics is that call's
+ *   ISLE_TOPDOCS_HOST   the caller's CSR: doc_offsets (num_rows + 1, ascending from 0), topic and value per entry, uploaded for the call; the
+ *                       topics of a row ascend strictly.  For the other sources num_rows is ignored and the three arrays may be NULL.
+ * doc_base is the caller's, as number_base is for isle_hip_infer_text: with document shards a rank passes doc_offset(A) (+ doc_begin for INFER).
+ * Document shards (world > 1): COLLECTIVE.  ALL RANKS CALL TOGETHER, with the same source, num_topics and n (checked: ISLE_E_COMM otherwise), in
+ * the same order among their collective calls, a rank without rows or with rows and no entries included.  The counts go through one u64
+ * all-reduce, the select's bins (num_topics x 256 u32) through eight, the ranks' tables of winners (num_topics x n u64 each) through one
+ * all-gather; the sort runs replicated.  Every rank returns the corpus's lists, bit-identical, and they are the lists one rank holding all
+ * the entries returns.  The refusals below that depend on a rank's own arguments alone precede every collective: the ranks must agree on them.
+ * A bad entry on one rank, or a topic with 2^31 entries or more (one rank: 2^32), is ISLE_E_ARG on every rank.
+ * ISLE_E_ARG: an unknown source, num_topics < 1, n outside 1 .. ISLE_TOPDOCS_MAX_N, world x n > 8192 (the keys of a topic are sorted in
+ * 64 KiB of LDS), doc_base + rows > 0xfffffff1, null docs / values / counts, HOST arrays null where there are rows / entries, doc_offsets
+ * that do not ascend from 0, INFER without a valid resident result, SUMS before isle_hip_topic_model or with another num_topics; and, found on
+ * the device, a topic >= num_topics or topics that do not ascend strictly within a row: the message names the first such entry and its row.
+ * The call changes nothing resident and keeps nothing: a second call returns the same arrays, and isle_hip_infer_text,
+ * isle_hip_get_infer_entries, isle_hip_get_doc_topic_sums and isle_hip_doc_report_text return what they returned before.
+ * Device memory of the call: 4 bytes per entry (the entry's document), num_topics KiB of bins, (world + 1) num_topics n 8 bytes of tables
+ * (HOST: and the uploaded arrays).  Device time is booked under ISLE_T_INFER for ISLE_TOPDOCS_INFER and under ISLE_T_POST otherwise.  Measured
+ * on one rank at configuration 2 only (tools/top_docs_probe.py, profiles/top_docs_c2.jsonl); NO TIME IS MEASURED on several ranks, and the
+ * bins' two homes were never timed at one num_topics. */
+#define ISLE_TOPDOCS_INFER 0 /* the resident entries of the last isle_hip_infer_resident (row 0 = that call's doc_begin) */
+#define ISLE_TOPDOCS_SUMS 1  /* the document-topic catchword sums of the last isle_hip_topic_model (row = document of A) */
+#define ISLE_TOPDOCS_HOST 2  /* the caller's CSR: doc_offsets (num_rows + 1), topic, value, uploaded for the call */
+#define ISLE_TOPDOCS_MAX_N 256
+int isle_hip_topic_top_docs(isle_ctx* ctx, int source, int num_topics, int n, uint64_t doc_base, uint64_t num_rows, const int64_t* doc_offsets,
+                            const uint32_t* topic, const float* value, uint32_t* docs, float* values, uint32_t* counts, uint64_t* topic_entries);
 /* The avg_doc_sz of the resident count matrix as the context holds it (see above; computed on first use).  world > 1: the corpus value
  * over all ranks' documents, collective where it has to be computed (see isle_hip_infer_resident).  ISLE_E_ARG: no count matrix, out null. */
 int isle_hip_avg_doc_sz(isle_ctx* ctx, float* out);

@@ -10,6 +10,7 @@
 
 #include "api_internal.h"
 #include "stage_host.h"
+#include "topdocs_host.h"
 
 // ------------------------------------------------------------------------------------------
 // upstream stage: A -> B on the device
@@ -1203,6 +1204,114 @@ extern "C" int isle_hip_doc_report_text(isle_ctx* c, int what, uint64_t doc_begi
   if (what == ISLE_DOCREPORT_TOPIC_SUMS && route_topic_sums(c->world) == TOPIC_SUMS_GATHERED)
     return topic_sums_gathered(c, doc_begin, doc_end, sink, user, nbytes, nlines);
   return k_doc_report_text(c, what, doc_begin, doc_end, sink, user, nbytes, nlines);
+}
+
+// The n heaviest documents of every topic (topic_docs.hip; the rule: topdocs_host.h), selected on entries that lie by document.  Several
+// ranks: collective — the control values are agreed, the counts (with a word that says whether any rank found a bad entry) and the bins of
+// every round are all-reduced, the ranks' tables of winners all-gathered and sorted replicated.  Every rank takes every step, a rank
+// without rows or without entries included.  Nothing resident is written.
+extern "C" int isle_hip_topic_top_docs(isle_ctx* c, int source, int num_topics, int n, uint64_t doc_base, uint64_t num_rows, const int64_t* doc_offsets,
+                                       const uint32_t* topic, const float* value, uint32_t* docs, float* values, uint32_t* counts, uint64_t* topic_entries) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  const bool infer = source == ISLE_TOPDOCS_INFER, sums = source == ISLE_TOPDOCS_SUMS;
+  if (infer && !c->res.inf_valid)
+    return isle_fail(c, ISLE_E_ARG, "topic_top_docs: no resident result (run isle_hip_infer_resident; a new count matrix voids it)");
+  if (sums && !c->res.p_model_ready) return isle_fail(c, ISLE_E_ARG, "topic_top_docs: run isle_hip_topic_model first (a new count matrix voids its result)");
+  const uint64_t rows = infer ? c->inf_docs : (sums ? c->a_D : num_rows);
+  const std::string why = topdocs_check_args(source, num_topics, n, c->world, doc_base, rows);
+  if (!why.empty()) return isle_fail(c, ISLE_E_ARG, "%s", why.c_str());
+  if (sums && num_topics != c->res.p_k)
+    return isle_fail(c, ISLE_E_ARG, "topic_top_docs: num_topics = %d, the resident topic model has %d topics", num_topics, c->res.p_k);
+  if (!docs || !values || !counts) return isle_fail(c, ISLE_E_ARG, "topic_top_docs: null docs / values / counts");
+  uint64_t nnz = infer ? c->inf_n : (sums ? c->p_dts_n : 0);
+  if (source == ISLE_TOPDOCS_HOST && rows) {
+    if (!doc_offsets) return isle_fail(c, ISLE_E_ARG, "topic_top_docs: null doc_offsets with %llu rows", (unsigned long long)rows);
+    const std::string bad_off = topdocs_check_offsets(doc_offsets, rows);
+    if (!bad_off.empty()) return isle_fail(c, ISLE_E_ARG, "%s", bad_off.c_str());
+    nnz = (uint64_t)doc_offsets[rows];
+    if (nnz && (!topic || !value)) return isle_fail(c, ISLE_E_ARG, "topic_top_docs: null topic / value with %llu entries", (unsigned long long)nnz);
+  }
+  const size_t T = (size_t)num_topics, W = (size_t)c->world;
+  DevBuf<int64_t> up_off;
+  DevBuf<uint32_t> up_topic, doc, rem, fill, bins, out_docs, out_counts;
+  DevBuf<float> up_value, out_values;
+  DevBuf<uint64_t> cnt, prefix, tables, err;
+  StreamDrain drain(c);
+  if (c->multi()) {  // (every local refusal lies before this line)
+    ISLECHK(agree_i32(c, source, "topic_top_docs: source"));
+    ISLECHK(agree_i32(c, num_topics, "topic_top_docs: num_topics"));
+    ISLECHK(agree_i32(c, n, "topic_top_docs: n"));
+  }
+  TdView v = {infer ? c->inf_off.p : c->p_dts_off.p, infer ? c->inf_topic.p : c->p_dts_topic.p, infer ? c->inf_weight.p : c->p_dts_val.p,
+              rows,  nnz, doc_base, (uint32_t)num_topics, (uint32_t)n, infer ? ISLE_T_INFER : ISLE_T_POST};
+  if (source == ISLE_TOPDOCS_HOST) {
+    const int64_t zero = 0;
+    HIPCHK(c, up_off.reserve(rows + 1));
+    HIPCHK(c, up_topic.reserve(nnz ? nnz : 1));
+    HIPCHK(c, up_value.reserve(nnz ? nnz : 1));
+    HIPCHK(c, hipMemcpy(up_off.p, rows ? doc_offsets : &zero, (rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (nnz) HIPCHK(c, hipMemcpy(up_topic.p, topic, nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (nnz) HIPCHK(c, hipMemcpy(up_value.p, value, nnz * sizeof(float), hipMemcpyHostToDevice));
+    v.off = up_off.p;
+    v.topic = up_topic.p;
+    v.value = up_value.p;
+  }
+  HIPCHK(c, doc.reserve(nnz ? nnz : 1));
+  HIPCHK(c, cnt.reserve(T + 1));
+  HIPCHK(c, err.reserve(1));
+  HIPCHK(c, prefix.reserve(T));
+  HIPCHK(c, rem.reserve(T));
+  HIPCHK(c, fill.reserve(T));
+  HIPCHK(c, bins.reserve(T * 256));
+  HIPCHK(c, tables.reserve((W + 1) * T * (size_t)n));
+  HIPCHK(c, out_docs.reserve(T * (size_t)n));
+  HIPCHK(c, out_values.reserve(T * (size_t)n));
+  HIPCHK(c, out_counts.reserve(T));
+  // the documents, this rank's counts, the form of the rows; the counts of the corpus travel with the number of ranks that refuse
+  uint64_t bad = ~0ull;
+  ISLECHK(k_td_docs(c, v, doc.p, cnt.p, err.p, &bad));
+  const uint64_t refuses = bad != ~0ull;
+  HIPCHK(c, hipMemcpy(cnt.p + T, &refuses, sizeof(uint64_t), hipMemcpyHostToDevice));
+  ISLECHK(allreduce_sum<uint64_t>(c, cnt.p, T + 1));
+  std::vector<uint64_t> cnt_host(T + 1);
+  HIPCHK(c, hipMemcpyAsync(cnt_host.data(), cnt.p, (T + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (refuses) {
+    const uint64_t e = bad >> 2;
+    std::vector<int64_t> off(rows + 1);
+    uint32_t tp = 0;
+    HIPCHK(c, hipMemcpy(off.data(), v.off, (rows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&tp, v.topic + e, sizeof(tp), hipMemcpyDeviceToHost));
+    const uint64_t row = (uint64_t)(std::upper_bound(off.begin(), off.end(), (int64_t)e) - off.begin()) - 1;
+    return isle_fail(c, ISLE_E_ARG, "%s", topdocs_fault_text((unsigned)(bad & 3), e, row, tp, (uint32_t)num_topics).c_str());
+  }
+  if (cnt_host[T]) return isle_fail(c, ISLE_E_ARG, "topic_top_docs: another rank refused its entries (a topic >= num_topics, or topics that do not ascend in a row)");
+  const uint64_t cnt_end = c->multi() ? (1ull << 31) : (1ull << 32);  // the bins are u32; the host-staged transport sums signed words
+  for (size_t t = 0; t < T; ++t)
+    if (cnt_host[t] >= cnt_end)
+      return isle_fail(c, ISLE_E_ARG, "topic_top_docs: topic %zu has %llu entries, 2^%d or more", t, (unsigned long long)cnt_host[t], c->multi() ? 31 : 32);
+  // eight rounds, most significant byte first: every rank steps to the same smallest selected key from the same integers
+  ISLECHK(k_td_init(c, v, cnt.p, prefix.p, rem.p));
+  for (int shift = 56; shift >= 0; shift -= 8) {
+    ISLECHK(k_td_hist(c, v, doc.p, prefix.p, shift, bins.p));
+    ISLECHK(allreduce_sum<uint32_t>(c, bins.p, T * 256));
+    ISLECHK(k_td_step(c, v, bins.p, cnt.p, shift, prefix.p, rem.p));
+  }
+  // each rank's winners, the tables side by side, the sort replicated
+  uint64_t* const mine = c->multi() ? tables.p + W * T * (size_t)n : tables.p;
+  ISLECHK(k_td_collect(c, v, doc.p, prefix.p, fill.p, mine));
+  if (c->multi()) {
+    TimeScope ts(c, ISLE_T_COMM);
+    ISLECHK(isle_allgather(c, mine, tables.p, T * (size_t)n, ISLE_DT_U64));
+  }
+  ISLECHK(k_td_sort(c, v, tables.p, c->multi() ? (uint32_t)W : 1u, cnt.p, out_docs.p, out_values.p, out_counts.p));
+  HIPCHK(c, hipMemcpyAsync(docs, out_docs.p, T * (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(values, out_values.p, T * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(counts, out_counts.p, T * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (topic_entries) std::copy(cnt_host.begin(), cnt_host.begin() + T, topic_entries);
+  return 0;
 }
 
 extern "C" int isle_hip_avg_doc_sz(isle_ctx* c, float* out) {

@@ -697,6 +697,23 @@ int k_dr_sums_keys(isle_ctx* c, uint64_t doc_begin, uint64_t doc_end, uint64_t f
 int k_dr_sums_gathered_text(isle_ctx* c, uint64_t* key_a, uint32_t* doc_a, uint64_t* key_b, uint32_t* doc_b, uint64_t L, uint64_t L0, uint64_t L1,
                             isle_text_sink_fn sink, void* user, uint64_t* nbytes, uint64_t* nlines);
 
+// topic_docs.hip: the device steps of isle_hip_topic_top_docs (the rule: topdocs_host.h) on a CSR of (topic, value) over `rows` rows, between
+// the collectives of api_stages.cpp.  Every buffer is the call's; device time goes to `fam`.
+struct TdView {
+  const int64_t* off;  // rows + 1, off[0] = 0
+  const uint32_t* topic;
+  const float* value;
+  uint64_t rows, nnz, doc_base;
+  uint32_t num_topics, n;
+  int fam;
+};
+int k_td_docs(isle_ctx* c, const TdView& v, uint32_t* doc, uint64_t* cnt, uint64_t* err_dev, uint64_t* bad);
+int k_td_init(isle_ctx* c, const TdView& v, const uint64_t* cnt, uint64_t* prefix, uint32_t* rem);
+int k_td_hist(isle_ctx* c, const TdView& v, const uint32_t* doc, const uint64_t* prefix, int shift, uint32_t* bins);
+int k_td_step(isle_ctx* c, const TdView& v, const uint32_t* bins, const uint64_t* cnt, int shift, uint64_t* prefix, uint32_t* rem);
+int k_td_collect(isle_ctx* c, const TdView& v, const uint32_t* doc, const uint64_t* tau, uint32_t* fill, uint64_t* table);
+int k_td_sort(isle_ctx* c, const TdView& v, const uint64_t* tables, uint32_t world, const uint64_t* cnt, uint32_t* docs, float* values, uint32_t* counts);
+
 // model_load.hip: the text of a model file (n bytes on the device, ISLE_TEXT_SPARSE / ISLE_TEXT_DENSE) parsed into model_dev (V x ncols
 // column-major).  *err_key: ~0 = none, else (byte position << 3) | kind of the first offending byte (isle_hip_load_model_text names them);
 // *nentries: lines parsed (SPARSE), tokens (DENSE)

@@ -515,6 +515,19 @@ class FPSparseMatrixHip {
     val.assign((size_t)offs[a_docs_], 0.0f);
     check(isle_hip_get_doc_topic_sums(ctx_, nullptr, topic.data(), val.data()), "get_doc_topic_sums");
   }
+  // The n heaviest documents of every topic, selected on the device (isle_hip_topic_top_docs; the rule: isle_amd/csrc/topdocs_host.h) from
+  // a resident source, ISLE_TOPDOCS_SUMS (the catchword sums of the last construct_topic_model) or ISLE_TOPDOCS_INFER (the entries of the
+  // last infer_documents_resident; doc_base = its doc_begin): docs / values num_topics x n topic-major, the unused slots 0xffffffff / 0.0f;
+  // counts[t] = min(n, the topic's entries); entries (nullable): the topics' entry counts.
+  void topic_top_docs(const int source, const doc_id_t num_topics, const int n, const uint64_t doc_base, std::vector<uint32_t>& docs,
+                      std::vector<FPTYPE>& values, std::vector<uint32_t>& counts, std::vector<uint64_t>* entries = nullptr) {
+    docs.assign((size_t)num_topics * n, 0);
+    values.assign((size_t)num_topics * n, 0.0f);
+    counts.assign((size_t)num_topics, 0);
+    if (entries) entries->assign((size_t)num_topics, 0);
+    check(isle_hip_topic_top_docs(ctx_, source, (int)num_topics, n, doc_base, 0, nullptr, nullptr, nullptr, docs.data(), values.data(), counts.data(),
+                                  entries ? entries->data() : nullptr), "topic_top_docs");
+  }
   doc_id_t count_docs() const { return a_docs_; }  // documents of the count matrix A (B may hold fewer after sampling)
   // DenseMatrix::write_to_file_as_sparse (format = ISLE_TEXT_SPARSE) / write_to_file (ISLE_TEXT_DENSE), src/denseMatrix.cpp:124-186, of a
   // resident model (ISLE_MODEL_CATCH / ISLE_MODEL_AVG), or with ISLE_MODEL_HOST of model_host (vocab x ncols column-major): the text is

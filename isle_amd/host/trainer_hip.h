@@ -872,6 +872,25 @@ class ISLETrainer {
     log->print(std::string("k-means objective on B: ") + buf + "\n");
     log->next_time_secs("Computing the k-means objective");
   }
+  // "Which documents show topic t best": the n heaviest documents of every topic by their catchword sums (ISLE_TOPDOCS_SUMS) or, after
+  // output_doc_topic_weights(), by their inferred weights (ISLE_TOPDOCS_INFER), selected on the device (FPSparseMatrixHip::topic_top_docs ->
+  // isle_hip_topic_top_docs).  TopDocsPerTopic.tsv: topics ascending, within a topic the selected documents in order (the heavier value
+  // first, the smaller document among bit-equal values), one line "<doc + 1>\t<topic + 1>\t<value>\n" per document as doc_line_text prints
+  // it: a host loop over at most num_topics x n lines.  The reference has no such file; not part of what ISLETrain writes by default.
+  void output_topic_top_docs(const int n = 10, const int source = ISLE_TOPDOCS_SUMS) {
+    if (!is_training_complete) throw std::runtime_error("output_topic_top_docs() before train()");
+    std::vector<uint32_t> docs, counts;
+    std::vector<FPTYPE> values;
+    B_fl_CSC->topic_top_docs(source, num_topics, n, 0, docs, values, counts);
+    FILE* f = std::fopen((log_dir + "/TopDocsPerTopic.tsv").c_str(), "wb");
+    if (!f) throw std::runtime_error("cannot write " + log_dir + "/TopDocsPerTopic.tsv");
+    char text[40];
+    for (doc_id_t t = 0; t < num_topics; ++t)
+      for (uint32_t i = 0; i < counts[t]; ++i)
+        std::fwrite(text, 1, trainer_detail::doc_line_text((uint64_t)docs[(size_t)t * n + i] + 1, (uint64_t)t + 1, values[(size_t)t * n + i], text), f);
+    std::fclose(f);
+    log->next_time_secs("Writing the heaviest documents of every topic");
+  }
   void finish_log() { log->total("TVSD"); }  // the "Total time for TVSD" line the reference's train() ends with (:652)
 
   // src/trainer.cpp:993-996: vocab_size x num_topics floats, column-major (element (word, topic) at word + topic * vocab_size)

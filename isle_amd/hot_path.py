@@ -1004,6 +1004,7 @@ class HotPath:
                                                     -1.0 if min_weight is None else float(min_weight), int(chunk_docs), _p(tt), _p(tw),
                                                     _p(llh), C.byref(nc), C.byref(ne)))
         self._inf_rows = n
+        self._inf_cols = int(cols)
         out = dict(top_topic=tt, top_weight=tw, llh=llh, nconverged=int(nc.value), nentries=int(ne.value), avg_doc_sz=self.avg_doc_sz())
         if fetch_entries:
             out.update(zip(("offs", "topic", "weight"), self.infer_entries(n, out["nentries"])))
@@ -1082,6 +1083,48 @@ class HotPath:
         wt = np.empty(nentries, np.float32)
         self._chk(self._lib.isle_hip_get_infer_entries(self._h, _p(off), _p(tp), _p(wt)))
         return off, tp, wt
+
+    # ---- the heaviest documents of every topic, selected on the device (include/isle_hip.h, isle_hip_topic_top_docs) ---------------
+    _TOPDOCS = {"infer": 0, "sums": 1}
+
+    def topic_top_docs(self, n, source="infer", num_topics=None, doc_base=0):
+        """The n (1 .. 256) heaviest documents of every topic, by an exact selection on the device over entries stored by document:
+        source "infer" (the entries of the last infer_resident; row 0 is its first document), "sums" (the document-topic catchword sums
+        of the last construct_topic_model) or a CSR (doc_offsets (rows + 1,), topic, value) uploaded for the call, topics ascending
+        strictly within a row.  The document of a row is doc_base + row.  The heavier value comes first, in the order of the fp32 bits
+        (ord(b) = b ^ (0xffffffff if b >> 31 else 0x80000000): for positive finite values the numeric order), the smaller document among
+        bit-equal values.  num_topics: None = that of the source ("sums": the topic model's; "infer": the model's columns; a CSR: its
+        largest topic + 1).  Nothing resident changes and nothing is kept.
+        Under comm_init / comm_init_host the call is COLLECTIVE: every rank calls with the same source kind, num_topics and n, a rank
+        without rows or entries included, and passes its own doc_base (a_doc_offset, plus docs[0] of infer_resident for "infer"); every
+        rank gets the corpus's lists, bit-identical, the lists one rank holding all entries gets.
+        -> dict(docs uint32 (num_topics, n), values float32 (num_topics, n), counts uint32 (num_topics,) = min(n, entries of the topic),
+        topic_entries uint64 (num_topics,)); the unused slots hold 0xffffffff / 0.0."""
+        off = tp = va = None
+        rows = 0
+        if isinstance(source, str):
+            kind = self._TOPDOCS[source]
+            if num_topics is None:
+                num_topics = getattr(self, "_post_k", 0) if source == "sums" else getattr(self, "_inf_cols", 0)
+        else:
+            kind = 2
+            off = np.ascontiguousarray(source[0], np.int64)
+            tp = _as_u32(source[1], "topic")
+            va = np.ascontiguousarray(source[2], np.float32)
+            if off.ndim != 1 or off.size < 1 or va.ndim != 1 or tp.size != va.size or (off.size > 1 and int(off[-1]) != tp.size):
+                raise ValueError("source: (doc_offsets (rows + 1,), topic, value) with doc_offsets[-1] entries")
+            rows = off.size - 1
+            if num_topics is None:
+                num_topics = int(tp.max()) + 1 if tp.size else 1
+        k, n = int(num_topics), int(n)
+        shape = (max(k, 0), max(n, 0))
+        docs = np.empty(shape, np.uint32)
+        values = np.empty(shape, np.float32)
+        counts = np.empty(shape[0], np.uint32)
+        entries = np.empty(shape[0], np.uint64)
+        self._chk(self._lib.isle_hip_topic_top_docs(self._h, kind, k, n, int(doc_base), rows, _p(off), _p(tp), _p(va), _p(docs), _p(values), _p(counts),
+                                                    _p(entries)))
+        return dict(docs=docs, values=values, counts=counts, topic_entries=entries)
 
     def timing_enable(self, on=True):
         """0 / False: off; 1 / True: events around every launch; 2: around the Gram-apply launches only."""
