@@ -281,6 +281,32 @@ int isle_hip_set_U(isle_ctx* ctx, const float* U_colmajor, int k);
  * vecs col-major.  Exposed for parity tests. */
 int isle_hip_eig_sym(isle_ctx* ctx, const float* S_colmajor, int n, float* evals_desc, float* vecs_colmajor);
 
+/* The same with only the nvec leading eigenvectors (1 <= nvec <= n), as truncate() calls the solver (nvec = keep):
+ * vecs n x nvec col-major.  evals_desc has n entries.  evals_desc[0 .. nvec) are the nvec largest eigenvalues; evals_desc[nvec .. n) is
+ * as the solver that answered leaves it: the tridiagonal solver locates only the leading nvec eigenvalues and leaves ZEROS there, the
+ * Jacobi solver returns all n eigenvalues (isle_hip_eig_info says which of the two answered).  The upper triangle of S defines the
+ * matrix (LAPACK 'U'); the strict lower triangle is not read.  A non-finite entry in the upper triangle is refused with ISLE_E_NUMERIC
+ * before anything is launched (both entries). */
+int isle_hip_eig_sym_leading(isle_ctx* ctx, const float* S_colmajor, int n, int nvec, float* evals_desc, float* vecs_colmajor);
+
+/* What the most recent small symmetric EVD of this context did (isle_hip_eig_sym, isle_hip_eig_sym_leading, every truncate() of the
+ * block Krylov-Schur solver).  info: ISLE_EIG_INFO_COUNT ints, indexed by the enumeration below; defect (nullable): the largest
+ * orthogonality defect the tridiagonal solver's own check measured on its eigenvectors (0 where it did not get that far).
+ * Host words only: nothing is launched or copied.  No reference counterpart (LAPACK's ssyevd does not say). */
+enum {
+  ISLE_EIG_SOLVER = 0,    /* who produced the returned pairs: 0 nobody yet (or the solve failed), 1 tridiagonal solver, 2 Jacobi solver */
+  ISLE_EIG_TD_TRIED,      /* 1 if the tridiagonal solver was run */
+  ISLE_EIG_TD_FORM,       /* the tridiagonalisation that produced its T: 0 none, 1 persistent (one launch), 2 launch chain */
+  ISLE_EIG_TD_BAILED,     /* 1 if the persistent form gave up at a grid barrier in THIS solve (the chain then ran) */
+  ISLE_EIG_TD_BACK,       /* back-transformation: 0 none, 1 compact WY, 2 reflector by reflector x 8 vectors, 3 x 4 vectors */
+  ISLE_EIG_TD_REJECTED,   /* 1 if the tridiagonal solver's result failed its orthogonality check (the Jacobi solver then answered) */
+  ISLE_EIG_JACOBI_SWEEPS, /* sweeps of the Jacobi solver (0 if it did not run) */
+  ISLE_EIG_N,
+  ISLE_EIG_NVEC,
+  ISLE_EIG_INFO_COUNT
+};
+int isle_hip_eig_info(isle_ctx* ctx, int* info, float* defect);
+
 /* ---- k-means --------------------------------------------------------------------------- */
 /* FPSparseMatrix::kmeans_init_on_projected_space(k, reps = 1, seeds, centers_coords)
  * src/sparseMatrix.cpp:2212-2238 -> kmeanspp_on_projected_space :2133-2209.

@@ -470,12 +470,27 @@ extern "C" int isle_hip_set_U(isle_ctx* c, const float* U, int k) {
   return 0;
 }
 
-extern "C" int isle_hip_eig_sym(isle_ctx* c, const float* S, int n, float* evals, float* vecs) {
-  if (!c || !S || !evals || !vecs || n < 1) return ISLE_E_ARG;
+// LAPACK 'U' semantics: the upper triangle is the matrix.  A non-finite entry there would come back as rc 0 with NaN pairs from the
+// tridiagonal solver (its Sturm counts and its check compare with NaN): refused here, before any launch.  The strict lower triangle is not read.
+static int eig_sym_entry(isle_ctx* c, const float* S, int n, int nvec, float* evals, float* vecs) {
+  if (!c || !S || !evals || !vecs || n < 1 || nvec < 1 || nvec > n) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));
-  HIPCHK(c, c->Wf.reserve((size_t)n * n));
-  ISLECHK(k_eig_small(c, S, n, evals, c->Wf.p, n));
-  HIPCHK(c, hipMemcpy(vecs, c->Wf.p, (size_t)n * n * sizeof(float), hipMemcpyDeviceToHost));
+  for (int j = 0; j < n; ++j)
+    for (int i = 0; i <= j; ++i)
+      if (!std::isfinite(S[(size_t)j * n + i])) return isle_fail(c, ISLE_E_NUMERIC, "eig_sym: entry (%d, %d) of the upper triangle is not finite", i, j);
+  HIPCHK(c, c->Wf.reserve((size_t)n * n));  // n x n whatever nvec: the Jacobi solver returns every vector
+  ISLECHK(k_eig_small(c, S, n, evals, c->Wf.p, nvec));
+  HIPCHK(c, hipMemcpy(vecs, c->Wf.p, (size_t)n * nvec * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+extern "C" int isle_hip_eig_sym(isle_ctx* c, const float* S, int n, float* evals, float* vecs) { return eig_sym_entry(c, S, n, n, evals, vecs); }
+extern "C" int isle_hip_eig_sym_leading(isle_ctx* c, const float* S, int n, int nvec, float* evals, float* vecs) {
+  return eig_sym_entry(c, S, n, nvec, evals, vecs);
+}
+extern "C" int isle_hip_eig_info(isle_ctx* c, int* info, float* defect) {
+  if (!c || !info) return ISLE_E_ARG;
+  for (int i = 0; i < ISLE_EIG_INFO_COUNT; ++i) info[i] = c->eig_info[i];
+  if (defect) *defect = c->eig_defect;
   return 0;
 }
 

@@ -445,6 +445,9 @@ struct isle_ctx {
   // process-wide flag would leave the kernels of a second GPU at the 64 KB default)
   std::vector<std::pair<const void*, int>> lds_attr;
   bool td_persist_failed = false;  // the persistent tridiagonalisation hit its barrier time-out once (GPU shared): launch chain from now on
+  // what the most recent small EVD of this context did (isle_hip_eig_info): host words written where the host decides anyway
+  int eig_info[ISLE_EIG_INFO_COUNT] = {0};
+  float eig_defect = 0.f;  // the orthogonality defect td_check_k measured (0 where the tridiagonal solver did not get that far)
 
   // --- timing
   bool timing = false;

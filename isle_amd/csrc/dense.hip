@@ -1440,6 +1440,7 @@ int k_jacobi_eig(isle_ctx* c, const float* S_host, int n, float* evals_host, flo
     HIPCHK(c, hipMemcpyAsync(&nrot, rot, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->knob_on(KN_DEBUG_EVD)) fprintf(stderr, "[evd n=%d] sweep %d rotations %u\n", n, sweep, nrot);
+    c->eig_info[ISLE_EIG_JACOBI_SWEEPS] = sweep + 1;
     if (nrot == 0) converged = true;
   }
   if (!converged) return isle_fail(c, ISLE_E_NUMERIC, "Jacobi EVD (n=%d) did not converge in 60 sweeps", n);
@@ -1563,13 +1564,21 @@ int k_scale_centers(isle_ctx* c, float* Crm, uint64_t rows, int k, int ldk, cons
 // solver above is the fallback for sizes it does not take and for spectra whose eigenvectors fail its orthogonality check
 // (clusters far tighter than Ritz matrices show).  ISLE_EVD_JACOBI=1 forces the Jacobi solver.
 int k_eig_small(isle_ctx* c, const float* S_host, int n, float* evals_host, float* vecs_dev, int nvec) {
+  // the record of this solve (isle_hip_eig_info): host words, written where the host decides anyway
+  for (int i = 0; i < ISLE_EIG_INFO_COUNT; ++i) c->eig_info[i] = 0;
+  c->eig_defect = 0.f;
+  c->eig_info[ISLE_EIG_N] = n;
+  c->eig_info[ISLE_EIG_NVEC] = nvec;
   if (route_evd_tridiag(n, c->route)) {
     int rc;
     {
       TimeScope ts(c, ISLE_T_EVD);
       rc = k_tridiag_eig(c, S_host, n, evals_host, vecs_dev, nvec);
     }
+    if (rc == 0) c->eig_info[ISLE_EIG_SOLVER] = 1;
     if (rc <= 0) return rc;
   }
-  return k_jacobi_eig(c, S_host, n, evals_host, vecs_dev);
+  const int rc = k_jacobi_eig(c, S_host, n, evals_host, vecs_dev);
+  if (rc == 0) c->eig_info[ISLE_EIG_SOLVER] = 2;
+  return rc;
 }

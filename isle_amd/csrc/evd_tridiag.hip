@@ -815,7 +815,7 @@ __global__ __launch_bounds__(TD_B_T) void td_back_wy_k(const double* __restrict_
   }
 }
 
-// max over vectors of | <z_c, z_{c+q}> | (q = 1..4) and | |z_c|^2 - 1 |, as the bits of a non-negative float
+// max over vectors of | <z_c, z_{c+q}> | (q = 1..4) and | |z_c|^2 - 1 |, as the bits of a non-negative float; NaN if any sum is NaN
 __global__ __launch_bounds__(256) void td_check_k(const float* __restrict__ Zc, int n, int nvec, unsigned int* __restrict__ worst) {
   __shared__ double sh[16];
   const int c = blockIdx.x;
@@ -830,10 +830,14 @@ __global__ __launch_bounds__(256) void td_check_k(const float* __restrict__ Zc, 
 #pragma unroll
   for (int q = 0; q < 5; ++q) {
     const double s = td_block_sum(acc[q], sh);
-    if (c + q < nvec) dev = fmax(dev, fabs(q == 0 ? s - 1.0 : s));
+    if (c + q < nvec) {
+      const double x = fabs(q == 0 ? s - 1.0 : s);
+      dev = (x != x || dev != dev) ? x + dev : fmax(dev, x);  // fmax drops a NaN operand: keep it, a NaN sum must fail the check
+    }
     __syncthreads();
   }
-  if (threadIdx.x == 0) atomicMax(worst, __float_as_uint((float)dev));
+  // as bits, a quiet NaN (sign clear) is above every finite non-negative float and infinity: the maximum keeps it
+  if (threadIdx.x == 0) atomicMax(worst, __float_as_uint(fabsf((float)dev)));
 }
 
 // A (fp64, column-major) = the symmetric matrix whose upper triangle is S's
@@ -850,6 +854,7 @@ __global__ __launch_bounds__(256) void td_sym_k(const float* __restrict__ S, int
 int k_tridiag_eig(isle_ctx* c, const float* S_host, int n, float* evals_host, float* vecs_dev, int nvec) {
   if (n < 3 || n > TD_NMAX_BACK || n > TD_ROWS * 16) return 1;
   nvec = std::max(1, std::min(nvec, n));
+  c->eig_info[ISLE_EIG_TD_TRIED] = 1;
   const size_t nn = (size_t)n * n;
   // the fp32 matrix goes up once; td_sym_k makes the fp64 working copy from its upper triangle (LAPACK 'U' semantics) on the
   // device — at n = 2000 the host loop and the 32 MB pageable copy it replaced cost ~10 ms per solve
@@ -937,6 +942,7 @@ int k_tridiag_eig(isle_ctx* c, const float* S_host, int n, float* evals_host, fl
       if (!c->td_persist_failed)
         fprintf(stderr, "[isle_hip] persistent tridiagonalisation gave up at a grid barrier (n = %d): using the launch chain from now on\n", n);
       c->td_persist_failed = true;
+      c->eig_info[ISLE_EIG_TD_BAILED] = 1;
       persist = false;
       continue;
     }
@@ -957,6 +963,7 @@ int k_tridiag_eig(isle_ctx* c, const float* S_host, int n, float* evals_host, fl
     HIPCHK(c, hipGetLastError());
     break;
   }
+  c->eig_info[ISLE_EIG_TD_FORM] = persist ? 1 : 2;
   // ---- 2. eigenvalues, 3. eigenvectors of T, 4. back-transformation, 5. check
   hipLaunchKernelGGL(td_bisect_k, dim3((nvec + 3) / 4), dim3(256), 2 * (size_t)n * sizeof(double), c->stream, d, e, n, nvec, lam);
   // Several ranks, ISLE_EVD_SPLIT=1 (round 5; opt-in since round 6): the eigenvectors are independent of each other from here on — a thread per
@@ -972,6 +979,7 @@ int k_tridiag_eig(isle_ctx* c, const float* S_host, int n, float* evals_host, fl
     // back-transformation by blocks of four reflectors (compact WY): the T factors first (the buffer of the launch chain's partial sums is free by now);
     // ISLE_TD_BACK=seq: reflector by reflector (td_back_k)
     const TdBack back = route_td_back(nvec, c->num_cus, kc, c->route);
+    c->eig_info[ISLE_EIG_TD_BACK] = back == TD_BACK_WY ? 1 : back == TD_BACK_SEQ8 ? 2 : 3;
     if (back != TD_BACK_WY) {
       if (back == TD_BACK_SEQ8)
         hipLaunchKernelGGL(td_back_k<8>, dim3((nv + 7) / 8), dim3(TD_B_T), (size_t)n * 8 * sizeof(double), c->stream, A, tau, n, Z, nvec, vecs_dev, v0, v1);
@@ -1012,7 +1020,13 @@ int k_tridiag_eig(isle_ctx* c, const float* S_host, int n, float* evals_host, fl
   }
 #endif
   if (c->knob_on(KN_DEBUG_EVD)) fprintf(stderr, "[evd n=%d] tridiagonal solver: nvec %d, worst orthogonality defect %.3g\n", n, nvec, (double)dev);
-  if (!(dev <= 1e-6f)) return 1;
+  c->eig_defect = dev;
+  // a NaN sum (td_check_k reports it as NaN) is no clustered spectrum for the Jacobi solver to resolve: the input or the solve is broken
+  if (dev != dev) return isle_fail(c, ISLE_E_NUMERIC, "tridiagonal EVD (n=%d): an eigenvector is not a number", n);
+  if (!(dev <= 1e-6f)) {
+    c->eig_info[ISLE_EIG_TD_REJECTED] = 1;
+    return 1;
+  }
   for (int i = 0; i < n; ++i) evals_host[i] = (float)ev[i];
   return 0;
 }

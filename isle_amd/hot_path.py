@@ -851,13 +851,37 @@ class HotPath:
         U = np.asfortranarray(U, dtype=np.float32)
         self._chk(self._lib.isle_hip_set_U(self._h, _p(U), U.shape[1]))
 
-    def eig_sym(self, S):
+    def eig_sym(self, S, nvec=None):
+        """Small symmetric EVD of the matrix the UPPER triangle of S defines: (evals descending, vecs).  nvec=None: all n eigenvectors
+        (isle_hip_eig_sym).  nvec < n: only the leading ones, as truncate() asks for them (isle_hip_eig_sym_leading): vecs is n x nvec, and
+        evals[nvec:] is zero where the tridiagonal solver answered, all eigenvalues where the Jacobi solver did (eig_info says which)."""
         S = np.asfortranarray(S, dtype=np.float32)
         n = S.shape[0]
+        assert S.shape == (n, n)
         e = np.empty(n, np.float32)
-        v = np.empty((n, n), np.float32, order="F")
-        self._chk(self._lib.isle_hip_eig_sym(self._h, _p(S), n, _p(e), _p(v)))
+        if nvec is None:
+            v = np.empty((n, n), np.float32, order="F")
+            self._chk(self._lib.isle_hip_eig_sym(self._h, _p(S), n, _p(e), _p(v)))
+        else:
+            v = np.empty((n, int(nvec)), np.float32, order="F")
+            self._chk(self._lib.isle_hip_eig_sym_leading(self._h, _p(S), n, int(nvec), _p(e), _p(v)))
         return e, v
+
+    EIG_INFO = ("solver", "td_tried", "td_form", "td_bailed", "td_back", "td_rejected", "jacobi_sweeps", "n", "nvec")
+    EIG_SOLVER = {0: None, 1: "tridiagonal", 2: "jacobi"}
+    EIG_FORM = {0: None, 1: "persistent", 2: "chain"}
+    EIG_BACK = {0: None, 1: "wy", 2: "seq8", 3: "seq4"}
+
+    def eig_info(self):
+        """What the most recent small EVD of this context did (isle_hip_eig_info): dict(solver "tridiagonal" | "jacobi" | None, td_tried,
+        td_form "persistent" | "chain" | None, td_bailed, td_back "wy" | "seq8" | "seq4" | None, td_rejected, td_defect, jacobi_sweeps, n, nvec)."""
+        w = (C.c_int * len(self.EIG_INFO))()
+        d = C.c_float()
+        self._chk(self._lib.isle_hip_eig_info(self._h, w, C.byref(d)))
+        r = dict(zip(self.EIG_INFO, (int(x) for x in w)))
+        r.update(solver=self.EIG_SOLVER[r["solver"]], td_form=self.EIG_FORM[r["td_form"]], td_back=self.EIG_BACK[r["td_back"]],
+                 td_tried=bool(r["td_tried"]), td_bailed=bool(r["td_bailed"]), td_rejected=bool(r["td_rejected"]), td_defect=float(d.value))
+        return r
 
     # ---- k-means --------------------------------------------------------------------------
     def kmeans_init_on_projected_space(self, k, inject_seeds=None, rng_seed=1):

@@ -504,9 +504,11 @@ def test_the_three_grid_barriers_of_the_persistent_tridiagonalisation_give_the_s
     eigenvectors must agree bit for bit — a form that let a workgroup through early would read a stale column and differ."""
     S = ritz_like(n, n + 1)
     e0, v0 = hp.eig_sym(S)
+    assert hp.eig_info()["solver"] == "tridiagonal"
     for form in ("hier", "flat"):
         monkeypatch.setenv("ISLE_TD_BAR", form)
         e, v = hp.eig_sym(S)
+        assert hp.eig_info()["solver"] == "tridiagonal", form  # three Jacobi answers would agree bit for bit as well
         monkeypatch.delenv("ISLE_TD_BAR")
         assert np.array_equal(e.view(np.uint32), e0.view(np.uint32)), form
         assert np.array_equal(v.view(np.uint32), v0.view(np.uint32)), form
@@ -521,9 +523,13 @@ def test_back_transformation_by_blocks_of_four_reflectors_equals_the_sequential_
     n = 2010 with all vectors: 503 workgroups, two rounds; n = 1212: rows per thread that do not fill the unrolled eight."""
     S = ritz_like(n, n + 7)
     e1, v1 = hp.eig_sym(S)
+    i1 = hp.eig_info()
     monkeypatch.setenv("ISLE_TD_BACK", "seq")
     e0, v0 = hp.eig_sym(S)
+    i0 = hp.eig_info()
     monkeypatch.delenv("ISLE_TD_BACK")
+    # the two back-transformations are compared only if the tridiagonal solver answered with each (two Jacobi answers would agree as well)
+    assert i1["solver"] == i0["solver"] == "tridiagonal" and i1["td_back"] == "wy" and i0["td_back"] in ("seq8", "seq4")
     assert np.array_equal(e1.view(np.uint32), e0.view(np.uint32))
     assert np.abs(v1.astype(np.float64) - v0).max() <= 2e-6
     S64 = S.astype(np.float64)
