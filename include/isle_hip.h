@@ -792,6 +792,42 @@ int isle_hip_avg_doc_sz(isle_ctx* ctx, float* out);
 int isle_hip_counts_shape(isle_ctx* ctx, uint64_t* vocab_size, uint64_t* num_docs, uint64_t* nnz, uint64_t* doc_offset,
                           uint64_t* docs_global);
 
+/* ---- the vocabulary pruned by document frequency, on the resident count matrix (isle_amd/csrc/vocab.hip) ----------------------------------
+ * What filter_extremes / min_df / max_df do elsewhere, where A lies.  The rule is stated once, in isle_amd/csrc/vocab_host.h:
+ *   df[w]     the documents of the whole corpus (all ranks) whose column of A holds word w (a column holds a word at most once: its entries)
+ *   max_df'   max_df, or the corpus's document count (docs_global of isle_hip_counts_shape) where max_df == 0
+ *   passes    min_df <= df[w] <= max_df'
+ *   keep_n    > 0 and more than keep_n words pass: only the keep_n passers with the largest key (uint64)df[w] << 32 | (uint32)~w stay: the
+ *             larger df wins, the smaller word id among equal df
+ *   new ids   the kept words are numbered 0 .. new_vocab - 1 in ascending old id, kept_words[new] = old: every column stays sorted
+ *   new A     every document keeps its entries of kept words in their order, counts bit for bit, rows renumbered; the documents, the document
+ *             offset and docs_global stay; a document may become empty (empty documents are legal everywhere)
+ *   emptied   the documents of the corpus that had entries and have none afterwards
+ * isle_hip_word_doc_freq: df (vocab_size u32, nullable) and nothing else; it changes nothing resident.
+ * isle_hip_prune_vocab: df (the OLD vocab_size, nullable), kept_words (room for the old vocab_size, new_vocab written, nullable), new_vocab,
+ * nnz (this rank's entries afterwards), docs_emptied (the corpus's); each nullable.  One histogram over the entries (32-bit integer sums:
+ * order-independent), the rule on the fetched table on the host (4 bytes per word), one ordered compaction (flags, a 64-bit scan, a pack into
+ * twin buffers that are swapped in).  For everything resident the call is an ingest of the pruned matrix: what a fresh count matrix voids
+ * (the corpus average, the catchwords, the models, the resident inference result) is void, what it leaves (B, U, the partition) stays; a
+ * prune is followed by isle_hip_threshold like any ingest.
+ * ISLE_E_ARG, decided before anything is rewritten (A and everything resident stay exactly as they were): no count matrix,
+ * min_df > max_df', keep_n >= 2^32, no word kept.
+ * Document shards (world > 1): both calls are COLLECTIVE.  ALL RANKS CALL TOGETHER, a rank without documents included, with the same
+ * vocab_size, min_df, max_df and keep_n (checked: ISLE_E_COMM otherwise).  df is all-reduced (u32 sum over vocab_size), the rule runs
+ * replicated, docs_emptied is all-reduced: df, kept_words, new_vocab, docs_emptied and the refusals that depend on df are bit-identical on
+ * every rank; the new A and nnz are the shard's own, and equal the single-rank result cut at the same document bounds.
+ * The histogram has two forms that give the same integers: counters private to a workgroup in LDS over vocabulary parts, flushed with one
+ * atomic per (workgroup, word) (the default), and one global atomic per entry.  isle_hip_vocab_hist_form sets which one the context asks
+ * for (the rule: route_host.h route_vocab_hist); the switch is the context's and not an environment variable.  Device memory of a prune:
+ * 12 bytes per entry (flags, positions) and the twin buffers; device time is booked under ISLE_T_INGEST. */
+#define ISLE_VOCAB_HIST_AUTO 0   /* the rule's own choice */
+#define ISLE_VOCAB_HIST_LDS 1    /* workgroup-private counters in LDS, one atomic per (workgroup, word) */
+#define ISLE_VOCAB_HIST_GLOBAL 2 /* one global atomic per entry */
+int isle_hip_vocab_hist_form(isle_ctx* ctx, int form);
+int isle_hip_word_doc_freq(isle_ctx* ctx, uint32_t* df);
+int isle_hip_prune_vocab(isle_ctx* ctx, uint64_t min_df, uint64_t max_df, uint64_t keep_n, uint64_t* new_vocab, uint32_t* kept_words, uint32_t* df,
+                         uint64_t* nnz, uint64_t* docs_emptied);
+
 /* ---- measurement ----------------------------------------------------------------------- */
 /* Per-kernel-family device time accumulated with HIP events on the context's stream since the
  * last reset (only while enabled; enabling adds event records around each launch).

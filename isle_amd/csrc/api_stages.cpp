@@ -11,6 +11,7 @@
 #include "api_internal.h"
 #include "stage_host.h"
 #include "topdocs_host.h"
+#include "vocab_host.h"
 
 // ------------------------------------------------------------------------------------------
 // upstream stage: A -> B on the device
@@ -357,6 +358,107 @@ extern "C" int isle_hip_get_A(isle_ctx* c, float* counts, uint32_t* rows, int64_
   if (rows && c->a_nnz) HIPCHK(c, hipMemcpy(rows, c->a_rows.p, c->a_nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
   if (offs) HIPCHK(c, hipMemcpy(offs, c->a_offs.p, (c->a_D + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
   return 0;
+}
+
+// ---- the vocabulary pruned by document frequency (vocab.hip; the rule: vocab_host.h)
+// Several ranks hold the same n <= 4 control values, or all return ISLE_E_COMM: max over (v, ~v) gives the largest and the complement of
+// the smallest (in the transport's order of the words, signed or not: equal on all ranks exactly where the two agree)
+static int vocab_agree(isle_ctx* c, const char* who, const uint64_t* v, int n) {
+  if (!c->multi()) return 0;
+  DevBuf<uint64_t> word;
+  StreamDrain drain(c);
+  HIPCHK(c, word.reserve(8));
+  uint64_t tag[8];
+  for (int i = 0; i < n; ++i) tag[2 * i] = v[i], tag[2 * i + 1] = ~v[i];
+  ISLECHK(allreduce_host<uint64_t>(c, tag, 2 * (size_t)n, word.p, true));
+  static const char* const kName[4] = {"vocab_size", "min_df", "max_df", "keep_n"};
+  for (int i = 0; i < n; ++i)
+    if (tag[2 * i] != ~tag[2 * i + 1])
+      return isle_fail(c, ISLE_E_COMM, "%s: ranks disagree on %s (%llu and %llu)", who, kName[i], (unsigned long long)~tag[2 * i + 1], (unsigned long long)tag[2 * i]);
+  return 0;
+}
+
+// what both calls check of the resident A before any collective: a rank's own refusals
+static int vocab_A_ok(isle_ctx* c, const char* who) {
+  if (!c->res.a_ready) return isle_fail(c, ISLE_E_ARG, "%s: no count matrix", who);
+  if (c->a_D_global > 0xfffffff0ull)
+    return isle_fail(c, ISLE_E_ARG, "%s: %llu documents in the corpus, more than 4294967280: the counters are 32 bits wide", who, (unsigned long long)c->a_D_global);
+  return 0;
+}
+
+// df of the corpus: this rank's histogram, summed over the ranks, on the device (df_dev, a_V words) and on the host
+static int vocab_df_corpus(isle_ctx* c, DevBuf<uint32_t>& df_dev, std::vector<uint32_t>& df) {
+  HIPCHK(c, df_dev.reserve((size_t)c->a_V));
+  ISLECHK(k_vocab_df(c, route_vocab_hist(c->vocab_hist_form), df_dev.p));
+  ISLECHK(allreduce_sum<uint32_t>(c, df_dev.p, (size_t)c->a_V));
+  df.resize((size_t)c->a_V);
+  HIPCHK(c, hipMemcpyAsync(df.data(), df_dev.p, (size_t)c->a_V * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+extern "C" int isle_hip_vocab_hist_form(isle_ctx* c, int form) {
+  if (!c) return ISLE_E_ARG;
+  if (form != ISLE_VOCAB_HIST_AUTO && form != ISLE_VOCAB_HIST_LDS && form != ISLE_VOCAB_HIST_GLOBAL)
+    return isle_fail(c, ISLE_E_ARG, "vocab_hist_form: unknown form %d", form);
+  c->vocab_hist_form = form;
+  return 0;
+}
+
+extern "C" int isle_hip_word_doc_freq(isle_ctx* c, uint32_t* df_out) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(vocab_A_ok(c, "word_doc_freq"));
+  DevBuf<uint32_t> df_dev;
+  StreamDrain drain(c);
+  ISLECHK(vocab_agree(c, "word_doc_freq", &c->a_V, 1));  // (every local refusal lies before this line)
+  std::vector<uint32_t> df;
+  ISLECHK(vocab_df_corpus(c, df_dev, df));
+  if (df_out) std::copy(df.begin(), df.end(), df_out);
+  return 0;
+}
+
+// For the ledger an ingest of the pruned matrix: A_rewrite_begins is raised once the rule has accepted and the pruned matrix lies complete
+// in the twin buffers, right before they are swapped in; install_A ends it.  Every refusal leaves A and everything resident as it was.
+extern "C" int isle_hip_prune_vocab(isle_ctx* c, uint64_t min_df, uint64_t max_df, uint64_t keep_n, uint64_t* new_vocab, uint32_t* kept_words, uint32_t* df_out,
+                                    uint64_t* nnz_out, uint64_t* docs_emptied) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(vocab_A_ok(c, "prune_vocab"));
+  DevBuf<uint32_t> df_dev, remap_dev, new_rows;
+  DevBuf<float> new_cnt;
+  DevBuf<int64_t> new_offs;
+  DevBuf<uint64_t> word;
+  StreamDrain drain(c);
+  const uint64_t agreed[4] = {c->a_V, min_df, max_df, keep_n};
+  ISLECHK(vocab_agree(c, "prune_vocab", agreed, 4));  // (every local refusal lies before this line; the ones below are the same on every rank)
+  const std::string why = vocab_check_args(true, min_df, max_df, keep_n, c->a_D_global);
+  if (!why.empty()) return isle_fail(c, ISLE_E_ARG, "%s", why.c_str());
+  std::vector<uint32_t> df, remap, kept;
+  ISLECHK(vocab_df_corpus(c, df_dev, df));
+  const std::string none = vocab_rule(df.data(), c->a_V, min_df, max_df, keep_n, c->a_D_global, remap, kept);
+  if (!none.empty()) return isle_fail(c, ISLE_E_ARG, "%s", none.c_str());
+  // the pruned matrix out of place
+  HIPCHK(c, remap_dev.reserve((size_t)c->a_V));
+  HIPCHK(c, hipMemcpyAsync(remap_dev.p, remap.data(), (size_t)c->a_V * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  uint64_t total = 0, emptied = 0;
+  ISLECHK(k_vocab_compact(c, remap_dev.p, new_cnt, new_rows, new_offs, &total, &emptied));
+  if (c->multi()) {
+    HIPCHK(c, word.reserve(1));
+    ISLECHK(allreduce_host<uint64_t>(c, &emptied, 1, word.p));
+  }
+  // ... and swapped in: the old buffers go with this call
+  c->res.A_rewrite_begins();
+  std::swap(c->a_cnt.p, new_cnt.p), std::swap(c->a_cnt.cap, new_cnt.cap);
+  std::swap(c->a_rows.p, new_rows.p), std::swap(c->a_rows.cap, new_rows.cap);
+  std::swap(c->a_offs.p, new_offs.p), std::swap(c->a_offs.cap, new_offs.cap);
+  c->a_V = kept.size();
+  c->a_nnz = total;
+  if (new_vocab) *new_vocab = kept.size();
+  if (kept_words) std::copy(kept.begin(), kept.end(), kept_words);
+  if (df_out) std::copy(df.begin(), df.end(), df_out);
+  if (docs_emptied) *docs_emptied = emptied;
+  return install_A(c, c->a_doc_offset, c->a_D_global, total, nullptr, nnz_out);
 }
 
 // isle_hip_threshold, A -> B: the scalars its steps hand on.  What the host decides between them is stage_host.h.

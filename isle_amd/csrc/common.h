@@ -253,6 +253,7 @@ struct isle_ctx {
   DevBuf<float> zetas;             // V
   DevBuf<uint64_t> original_cols;  // D (B column -> global document id of A)
   float a_avg = 0.f;               // avg_doc_sz of the whole corpus (src/sparseMatrix.cpp:98)
+  int vocab_hist_form = 0;         // isle_hip_vocab_hist_form: what route_vocab_hist is asked with (0: the rule's own choice)
 
   // --- downstream stage (post.hip): catchwords, topic model, edge topics
   DevBuf<float> a_nv;              // normalised values of A
@@ -716,6 +717,13 @@ int k_td_hist(isle_ctx* c, const TdView& v, const uint32_t* doc, const uint64_t*
 int k_td_step(isle_ctx* c, const TdView& v, const uint32_t* bins, const uint64_t* cnt, int shift, uint64_t* prefix, uint32_t* rem);
 int k_td_collect(isle_ctx* c, const TdView& v, const uint32_t* doc, const uint64_t* tau, uint32_t* fill, uint64_t* table);
 int k_td_sort(isle_ctx* c, const TdView& v, const uint64_t* tables, uint32_t world, const uint64_t* cnt, uint32_t* docs, float* values, uint32_t* counts);
+
+// vocab.hip: the device steps of isle_hip_word_doc_freq / isle_hip_prune_vocab on the resident A (the rule: vocab_host.h).  k_vocab_df: df_dev
+// (a_V words, zeroed there) = this rank's entries per word.  k_vocab_compact: A under remap_dev (a_V words: the new id, or 0xffffffff) out of
+// place into the caller's twin buffers, sized there; *emptied: this rank's documents that lost all of their entries.  Device time: ISLE_T_INGEST.
+int k_vocab_df(isle_ctx* c, VocabHist form, uint32_t* df_dev);
+int k_vocab_compact(isle_ctx* c, const uint32_t* remap_dev, DevBuf<float>& new_cnt, DevBuf<uint32_t>& new_rows, DevBuf<int64_t>& new_offs, uint64_t* total,
+                    uint64_t* emptied);
 
 // model_load.hip: the text of a model file (n bytes on the device, ISLE_TEXT_SPARSE / ISLE_TEXT_DENSE) parsed into model_dev (V x ncols
 // column-major).  *err_key: ~0 = none, else (byte position << 3) | kind of the first offending byte (isle_hip_load_model_text names them);

@@ -409,3 +409,12 @@ inline TdBack route_td_back(int nvec, int num_cus, int kc, const RouteEnv& e) {
   if (!e.td_back) return TD_BACK_WY;
   return (nvec + 7) / 8 > num_cus / 2 && !kc ? TD_BACK_SEQ8 : TD_BACK_SEQ4;
 }
+
+// ---- the vocabulary pruned by document frequency (api_stages.cpp, vocab.hip) ------------------------------------------------------------
+// The document frequencies of A (vocab.hip, isle_hip_word_doc_freq / isle_hip_prune_vocab): 32-bit counters private to a workgroup in LDS
+// over vocabulary parts, flushed with one global atomic per (workgroup, word), or one global atomic per entry.  Integer sums: the form
+// cannot reach the result.  asked: the context's setting (isle_hip_vocab_hist_form: 0 this rule's choice, 1 LDS, 2 global atomics).  The LDS
+// form is the choice: 0.54 ms against 4.9 ms of device time on the 108 M entries of config 2 (V = 50 k: four parts; medians of 5, the two
+// forms alternating; tools/vocab_prune_probe.py, profiles/vocab_prune_c2.jsonl).  Not measured: a vocabulary of many more parts.
+enum VocabHist { VOCAB_FORM_LDS = 0, VOCAB_FORM_GLOBAL = 1 };
+inline VocabHist route_vocab_hist(int asked) { return asked == 2 ? VOCAB_FORM_GLOBAL : VOCAB_FORM_LDS; }

@@ -508,6 +508,30 @@ class FPSparseMatrixHip {
     check(isle_hip_get_A(ctx_, counts.data(), rows.data(), nullptr), "get_A");
     if (avg_doc_sz) check(isle_hip_avg_doc_sz(ctx_, avg_doc_sz), "avg_doc_sz");
   }
+  // The vocabulary of the count matrix A pruned by document frequency on the device (isle_hip_prune_vocab; the rule:
+  // isle_amd/csrc/vocab_host.h): words in fewer than min_df or more than max_df (0: no upper bound) documents go, of the rest the keep_n
+  // (0: no cap) most frequent stay; kept_words[new id] = old id.  For everything resident an ingest of the pruned A: B is the old A's until
+  // threshold_again.  A refusal throws and leaves A as it was.  df (the old vocabulary), entries (A's afterwards), emptied: nullable.
+  void prune_vocabulary(const uint64_t min_df, const uint64_t max_df, const uint64_t keep_n, std::vector<uint32_t>& kept_words,
+                        std::vector<uint32_t>* df = nullptr, uint64_t* entries = nullptr, uint64_t* emptied = nullptr) {
+    uint64_t new_vocab = 0;
+    kept_words.assign((size_t)vocab_size_, 0);
+    if (df) df->assign((size_t)vocab_size_, 0);
+    check(isle_hip_prune_vocab(ctx_, min_df, max_df, keep_n, &new_vocab, kept_words.data(), df ? df->data() : nullptr, entries, emptied), "prune_vocab");
+    kept_words.resize((size_t)new_vocab);
+    vocab_size_ = (word_id_t)new_vocab;
+    top5_ready_ = false;
+  }
+  std::vector<uint32_t> word_doc_freq() {
+    std::vector<uint32_t> df((size_t)vocab_size_, 0);
+    check(isle_hip_word_doc_freq(ctx_, df.data()), "word_doc_freq");
+    return df;
+  }
+  // B again from the resident A, with from_counts' outputs: what follows a prune_vocabulary
+  void threshold_again(doc_id_t num_topics, double sample_rate, std::vector<doc_id_t>& original_cols, uint64_t* entries_above_threshold = nullptr,
+                       float* avg_doc_sz = nullptr) {
+    threshold_on_device(num_topics, sample_rate, original_cols, nullptr, entries_above_threshold, avg_doc_sz);
+  }
   void get_doc_topic_sums(std::vector<int64_t>& offs, std::vector<uint32_t>& topic, std::vector<FPTYPE>& val) {
     offs.assign((size_t)a_docs_ + 1, 0);
     check(isle_hip_get_doc_topic_sums(ctx_, offs.data(), nullptr, nullptr), "get_doc_topic_sums");

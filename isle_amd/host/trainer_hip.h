@@ -371,7 +371,7 @@ class ISLETrainer {
   enum data_ingest { FILE_DATA_LOAD, PREPROCESSED_DATA_LOAD, ITERATIVE_DATA_LOAD };  // include/trainer.h:91-94
 
  private:
-  const word_id_t vocab_size;
+  word_id_t vocab_size;  // the constructor's, until prune_vocabulary() (the only writer)
   const doc_id_t num_docs;
   const offset_t max_entries;
   const doc_id_t num_topics;
@@ -433,6 +433,8 @@ class ISLETrainer {
   std::vector<FPTYPE> EdgeModel;  // fetched by get_edge_model()
   bool edge_model_fetched = false;
   std::vector<std::string> vocab_words;
+  word_id_t vocab_file_words = 0;     // prune_vocabulary(): the vocabulary the file's lines name (the constructor's vocab_size) ...
+  std::vector<uint32_t> kept_words;   // ... and the line of every word of the current vocabulary; empty: never pruned
   std::vector<std::vector<std::pair<word_id_t, FPTYPE>>> topwords;
   std::vector<std::vector<std::pair<word_id_t, FPTYPE>>> avg_topwords;  // output_avg_topic_coherence()
   std::vector<FPTYPE> AvgModel;  // vocab_size x num_topics, column-major, output_avg_topic_coherence()
@@ -638,11 +640,50 @@ class ISLETrainer {
     if (!vocab_words.empty()) return;
     std::ifstream in(vocab_file);
     std::string word;
-    while (in.good() && !in.eof() && vocab_words.size() < vocab_size) {
+    const word_id_t lines = kept_words.empty() ? vocab_size : vocab_file_words;
+    while (in.good() && !in.eof() && vocab_words.size() < lines) {
       in >> word;
       vocab_words.push_back(word);
     }
-    vocab_words.resize(vocab_size);
+    vocab_words.resize(lines);
+    if (!kept_words.empty()) {  // after prune_vocabulary(): word w of the model is line kept_words[w] of the file
+      std::vector<std::string> kept(vocab_size);
+      for (word_id_t w = 0; w < vocab_size; ++w) kept[w] = vocab_words[kept_words[w]];
+      vocab_words.swap(kept);
+    }
+  }
+
+  // The vocabulary pruned by document frequency, on the device (FPSparseMatrixHip::prune_vocabulary -> isle_hip_prune_vocab; the rule:
+  // isle_amd/csrc/vocab_host.h): words in fewer than min_df or more than max_df (0: no upper bound) documents go, of the rest the keep_n
+  // (0: no cap) most frequent stay.  After the data is loaded and before train(): A is compacted, B is thresholded again from it, vocab_size
+  // becomes the kept words' number and load_vocab() maps the vocabulary file's lines through the kept words, so that every file that prints
+  // words names the right ones.  VocabKept.tsv: new id, old id, df, the ids 1-based like the other writers.  Nothing in the CLI calls it.
+  void prune_vocabulary(const uint64_t min_df, const uint64_t max_df = 0, const uint64_t keep_n = 0) {
+    if (!is_data_loaded) throw std::runtime_error("prune_vocabulary() before the data is loaded");
+    if (is_training_complete) throw std::runtime_error("prune_vocabulary() after train()");
+    const word_id_t old_vocab = vocab_size;
+    const uint64_t old_entries = entries_in_A;
+    std::vector<uint32_t> kept, df;
+    uint64_t entries = 0, emptied = 0;
+    B_fl_CSC->prune_vocabulary(min_df, max_df, keep_n, kept, &df, &entries, &emptied);
+    std::vector<uint32_t> lines(kept);  // the old id as the vocabulary file numbers it: a second prune goes through the first one's lines
+    if (kept_words.empty()) vocab_file_words = old_vocab;
+    else
+      for (uint32_t& w : lines) w = kept_words[w];
+    {
+      FILE* f = std::fopen((log_dir + "/VocabKept.tsv").c_str(), "wb");
+      if (!f) throw std::runtime_error("cannot write " + log_dir + "/VocabKept.tsv");
+      for (size_t w = 0; w < kept.size(); ++w) std::fprintf(f, "%llu\t%llu\t%u\n", (unsigned long long)w + 1, (unsigned long long)lines[w] + 1, df[kept[w]]);
+      std::fclose(f);
+    }
+    kept_words.swap(lines);
+    vocab_size = (word_id_t)kept_words.size();
+    entries_in_A = entries;
+    vocab_words.clear();
+    B_fl_CSC->threshold_again(num_topics, flag_sample_docs ? (double)sample_rate : 0.0, original_cols, &entries_above_threshold, &avg_doc_sz);
+    log->print("Vocabulary pruned: words kept " + std::to_string(vocab_size) + " dropped " + std::to_string(old_vocab - vocab_size) + ", entries kept " +
+               std::to_string(entries) + " dropped " + std::to_string(old_entries - entries) + ", documents emptied " + std::to_string(emptied) + "\n");
+    log->next_time_secs("Pruning the vocabulary");
   }
 
   // src/trainer.cpp:776-826

@@ -482,6 +482,56 @@ class HotPath:
         self._chk(self._lib.isle_hip_get_A(self._h, _p(cnt), _p(rows), _p(offs)))
         return cnt, rows, offs
 
+    # ---- the vocabulary pruned by document frequency, on the resident A (include/isle_hip.h, isle_hip_prune_vocab) -----------------
+    def _counts_shape(self):
+        v = [C.c_uint64() for _ in range(5)]
+        self._chk(self._lib.isle_hip_counts_shape(self._h, *(C.byref(x) for x in v)))
+        return tuple(int(x.value) for x in v)
+
+    def vocab_hist_form(self, form="auto"):
+        """Which form of the document-frequency kernel this context asks for: "auto" (the library's rule), "lds" (workgroup-private
+        counters in LDS, one atomic per (workgroup, word)) or "global" (one global atomic per entry).  Same integers either way."""
+        self._chk(self._lib.isle_hip_vocab_hist_form(self._h, {"auto": 0, "lds": 1, "global": 2}[form]))
+
+    def word_doc_freq(self):
+        """df uint32 (vocab,): the documents of the whole corpus that hold each word of the resident count matrix.  Nothing resident
+        changes.  Under comm_init / comm_init_host COLLECTIVE: every rank calls, a rank without documents included, and gets the
+        corpus's table."""
+        df = np.empty(self._counts_shape()[0], np.uint32)
+        self._chk(self._lib.isle_hip_word_doc_freq(self._h, _p(df)))
+        return df
+
+    def prune_vocab(self, min_df=1, max_df=None, keep_n=None):
+        """Drops the words of the resident count matrix A that occur in fewer than min_df or more than max_df documents of the corpus,
+        and all but the keep_n most frequent of the rest (the larger df first, the smaller word id among equal df); the kept words are
+        renumbered in ascending old id and A is compacted on the device (isle_hip_prune_vocab states the rule).  max_df: None = no upper
+        bound; an int = that many documents; a float in (0, 1] = floor(max_df * docs_global) documents, docs_global the corpus's
+        document count (a float of 1.0 is the whole corpus, the int 1 one document).  keep_n: None = no cap.
+        For everything resident this is an ingest of the pruned matrix: run threshold() next.  A refusal (IsleHipError: min_df above
+        max_df, no word kept, ...) leaves A as it was.  Under comm_init / comm_init_host COLLECTIVE, with the same arguments on every rank.
+        -> dict(vocab, kept_words uint32 (vocab,): new id -> old id, df uint32 (old vocab,), nnz (this rank's), docs_emptied (the corpus's))."""
+        V, _, _, _, docs_global = self._counts_shape()
+        if max_df is None:
+            top = 0
+        elif isinstance(max_df, (float, np.floating)):
+            if not 0.0 < max_df <= 1.0:
+                raise ValueError("max_df: a float is a share of the corpus in (0, 1]")
+            top = int(np.floor(float(max_df) * docs_global))
+            if top == 0:
+                raise ValueError("max_df = %r of %d documents is no document" % (max_df, docs_global))
+        else:
+            top = int(max_df)
+            if top < 1:
+                raise ValueError("max_df: at least 1 document (None: no upper bound)")
+        keep = 0 if keep_n is None else int(keep_n)
+        if int(min_df) < 0 or (keep_n is not None and keep < 1):
+            raise ValueError("min_df >= 0 and keep_n >= 1 (None: no cap)")
+        nv, nz, gone = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        kept, df = np.empty(V, np.uint32), np.empty(V, np.uint32)
+        self._chk(self._lib.isle_hip_prune_vocab(self._h, int(min_df), top, keep, C.byref(nv), _p(kept), _p(df), C.byref(nz), C.byref(gone)))
+        self._a_shape = self._counts_shape()[:3]
+        return dict(vocab=int(nv.value), kept_words=kept[:int(nv.value)].copy(), df=df, nnz=int(nz.value), docs_emptied=int(gone.value))
+
     def threshold(self, num_topics, sample_rate=0.0, sample_seed=0):
         """normalize_docs + compute_thresholds + (sampled_)threshold_and_copy on the device
         (src/trainer.cpp:430-485); B becomes this context's matrix.  Returns a dict of scalars."""
