@@ -828,6 +828,52 @@ int isle_hip_word_doc_freq(isle_ctx* ctx, uint32_t* df);
 int isle_hip_prune_vocab(isle_ctx* ctx, uint64_t min_df, uint64_t max_df, uint64_t keep_n, uint64_t* new_vocab, uint32_t* kept_words, uint32_t* df,
                          uint64_t* nnz, uint64_t* docs_emptied);
 
+/* ---- documents pruned by length and as exact duplicates, on the resident count matrix (isle_amd/csrc/docs.hip) ----------------------------
+ * The other half of the hygiene a front end does before training: documents of too few or too many words or tokens go, and of documents
+ * with identical columns only the first stays.  The rule is stated once, in isle_amd/csrc/docs_host.h.  For a local document d:
+ *   words[d]    its entries (distinct words; u32)          tokens[d]   the sum of (uint64)count over them (exact; u64)
+ *   max_words'  max_words, or no bound where max_words == 0 (likewise max_tokens')
+ *   passes      min_words <= words[d] <= max_words'  and  min_tokens <= tokens[d] <= max_tokens'
+ *   equal       the same number of entries, the same rows and the same count BITS, entry by entry; all empty documents are equal
+ *   first_of[d] with drop_duplicates: the smallest local document equal to d; without it: d
+ *   kept        passes  and  first_of[d] == d
+ *   new ids     the kept documents numbered 0 .. new_docs - 1 in ascending old id; kept_docs[new] = the old number in the corpus
+ *               (doc_offset + d)
+ *   new A       the kept documents' columns, entries in order, rows unchanged, counts bit for bit; the vocabulary stays
+ * isle_hip_doc_lengths: words and tokens of this rank's documents (each nullable); changes nothing resident; never collective.
+ * isle_hip_doc_duplicates: first_of over ALL local documents (nullable) and the number of documents that are not the first of their kind;
+ * changes nothing resident.
+ * isle_hip_prune_docs: new_docs and nnz are this rank's afterwards, kept_docs has room for the old document count (new_docs written),
+ * first_of (the old document count, nullable) reports 0xffffffff for a document dropped by length and the representative's old local
+ * number for one dropped as a duplicate; docs_global is the corpus's document count afterwards; dropped[3] the corpus's documents below
+ * the bounds, above them, and duplicates among the passers (the first failing test decides, in the order words-min, tokens-min,
+ * words-max, tokens-max).  Each output is nullable.  For everything resident the call is an ingest of the pruned matrix (as
+ * isle_hip_prune_vocab): B is the old A's until isle_hip_threshold runs again.
+ * ISLE_E_ARG, decided before anything is rewritten (A and everything resident stay exactly as they were): no count matrix,
+ * min_words > max_words', min_tokens > max_tokens', drop_duplicates outside {0, 1}, no document kept in the corpus, and duplicates with
+ * several ranks (below).
+ * On the device: one pass over the entries gives words, tokens and a 64-bit hash per document (a commutative sum of a mix of
+ * (row, count bits): order-independent); the documents are sorted by hash (stable: ascending within a hash), and inside every run of equal
+ * hashes contents are compared with the run's current head, round by round, until every document has found the first of its kind: the hash
+ * is mechanism, equality of content is the rule.  isle_hip_doc_hash_form cuts the hash to its 2 low bits (ISLE_DOC_HASH_NARROW) so that
+ * every run holds many unequal documents: the same result by many more rounds, for the tests and the probe; a setting of the context, not
+ * an environment variable.  Then a scan of the kept flags, a 64-bit scan of the kept lengths, a copy into twin buffers that are swapped in.
+ * Device time is booked under ISLE_T_INGEST.
+ * Document shards (world > 1): isle_hip_prune_docs with drop_duplicates == 0 is COLLECTIVE.  ALL RANKS CALL TOGETHER, a rank without
+ * documents included, with the same vocab_size and the same five arguments (checked: ISLE_E_COMM otherwise).  dropped is all-reduced, the
+ * ranks' kept counts are exchanged: each rank's new doc_offset is the sum over the lower ranks, docs_global the sum over all; "no document
+ * kept" is the same refusal on every rank; a rank may end with no documents; every rank's new A is its slice of the single-rank result.
+ * drop_duplicates != 0 and isle_hip_doc_duplicates are refused with ISLE_E_ARG where world > 1, before any collective: equality across
+ * ranks needs the contents exchanged, which is out of scope. */
+#define ISLE_DOC_HASH_AUTO 0
+#define ISLE_DOC_HASH_FULL 1   /* 64-bit document hash */
+#define ISLE_DOC_HASH_NARROW 2 /* the same hash cut to its 2 low bits: every run holds many unequal documents; for the tests and the probe */
+int isle_hip_doc_hash_form(isle_ctx* ctx, int form);
+int isle_hip_doc_lengths(isle_ctx* ctx, uint32_t* words, uint64_t* tokens);
+int isle_hip_doc_duplicates(isle_ctx* ctx, uint32_t* first_of, uint64_t* n_duplicates);
+int isle_hip_prune_docs(isle_ctx* ctx, uint64_t min_words, uint64_t max_words, uint64_t min_tokens, uint64_t max_tokens, int drop_duplicates,
+                        uint64_t* new_docs, uint32_t* kept_docs, uint32_t* first_of, uint64_t* nnz, uint64_t* docs_global, uint64_t dropped[3]);
+
 /* ---- measurement ----------------------------------------------------------------------- */
 /* Per-kernel-family device time accumulated with HIP events on the context's stream since the
  * last reset (only while enabled; enabling adds event records around each launch).

@@ -71,6 +71,10 @@ SYMBOLS = {
     "isle_hip_vocab_hist_form": (_I, [_P, _I]),
     "isle_hip_word_doc_freq": (_I, [_P, _P]),
     "isle_hip_prune_vocab": (_I, [_P, _U64, _U64, _U64, _P, _P, _P, _P, _P]),
+    "isle_hip_doc_hash_form": (_I, [_P, _I]),
+    "isle_hip_doc_lengths": (_I, [_P, _P, _P]),
+    "isle_hip_doc_duplicates": (_I, [_P, _P, _P]),
+    "isle_hip_prune_docs": (_I, [_P, _U64, _U64, _U64, _U64, _I, _P, _P, _P, _P, _P, _P]),
     "isle_hip_block_ks": (_I, [_P, _I, _I, _I, _I, _F, _U64, _P, _P, _P, _P]),
     "isle_hip_block_ks_dense": (_I, [_P, _P, _U64, _I, _I, _I, _I, _F, _U64, _P, _P, _P, _P, _P, _P, _P]),
     "isle_hip_get_U": (_I, [_P, _P]),

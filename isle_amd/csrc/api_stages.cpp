@@ -12,6 +12,7 @@
 #include "stage_host.h"
 #include "topdocs_host.h"
 #include "vocab_host.h"
+#include "docs_host.h"
 
 // ------------------------------------------------------------------------------------------
 // upstream stage: A -> B on the device
@@ -361,20 +362,20 @@ extern "C" int isle_hip_get_A(isle_ctx* c, float* counts, uint32_t* rows, int64_
 }
 
 // ---- the vocabulary pruned by document frequency (vocab.hip; the rule: vocab_host.h)
-// Several ranks hold the same n <= 4 control values, or all return ISLE_E_COMM: max over (v, ~v) gives the largest and the complement of
+// Several ranks hold the same n <= 6 control values, or all return ISLE_E_COMM: max over (v, ~v) gives the largest and the complement of
 // the smallest (in the transport's order of the words, signed or not: equal on all ranks exactly where the two agree)
-static int vocab_agree(isle_ctx* c, const char* who, const uint64_t* v, int n) {
+static const char* const kVocabCtl[4] = {"vocab_size", "min_df", "max_df", "keep_n"};
+static int vocab_agree(isle_ctx* c, const char* who, const uint64_t* v, int n, const char* const* name = kVocabCtl) {
   if (!c->multi()) return 0;
   DevBuf<uint64_t> word;
   StreamDrain drain(c);
-  HIPCHK(c, word.reserve(8));
-  uint64_t tag[8];
+  HIPCHK(c, word.reserve(12));
+  uint64_t tag[12];
   for (int i = 0; i < n; ++i) tag[2 * i] = v[i], tag[2 * i + 1] = ~v[i];
   ISLECHK(allreduce_host<uint64_t>(c, tag, 2 * (size_t)n, word.p, true));
-  static const char* const kName[4] = {"vocab_size", "min_df", "max_df", "keep_n"};
   for (int i = 0; i < n; ++i)
     if (tag[2 * i] != ~tag[2 * i + 1])
-      return isle_fail(c, ISLE_E_COMM, "%s: ranks disagree on %s (%llu and %llu)", who, kName[i], (unsigned long long)~tag[2 * i + 1], (unsigned long long)tag[2 * i]);
+      return isle_fail(c, ISLE_E_COMM, "%s: ranks disagree on %s (%llu and %llu)", who, name[i], (unsigned long long)~tag[2 * i + 1], (unsigned long long)tag[2 * i]);
   return 0;
 }
 
@@ -459,6 +460,129 @@ extern "C" int isle_hip_prune_vocab(isle_ctx* c, uint64_t min_df, uint64_t max_d
   if (df_out) std::copy(df.begin(), df.end(), df_out);
   if (docs_emptied) *docs_emptied = emptied;
   return install_A(c, c->a_doc_offset, c->a_D_global, total, nullptr, nnz_out);
+}
+
+// ---- documents pruned by length and as exact duplicates (docs.hip; the rule: docs_host.h)
+// what the three calls check before any collective: a rank's own refusals (the bounds are checked behind the ranks' agreement on them)
+static int docs_A_ok(isle_ctx* c, const char* who, int drop_duplicates) {
+  const std::string why = docs_check_args(who, c->res.a_ready, DocsBounds{0, 0, 0, 0}, drop_duplicates, c->world);
+  if (!why.empty()) return isle_fail(c, ISLE_E_ARG, "%s", why.c_str());
+  return 0;
+}
+
+extern "C" int isle_hip_doc_hash_form(isle_ctx* c, int form) {
+  if (!c) return ISLE_E_ARG;
+  if (form != ISLE_DOC_HASH_AUTO && form != ISLE_DOC_HASH_FULL && form != ISLE_DOC_HASH_NARROW)
+    return isle_fail(c, ISLE_E_ARG, "doc_hash_form: unknown form %d", form);
+  c->doc_hash_form = form;
+  return 0;
+}
+
+extern "C" int isle_hip_doc_lengths(isle_ctx* c, uint32_t* words_out, uint64_t* tokens_out) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(docs_A_ok(c, "doc_lengths", 0));
+  const uint64_t D = c->a_D;
+  DevBuf<uint32_t> words;
+  DevBuf<uint64_t> tokens;
+  StreamDrain drain(c);
+  HIPCHK(c, words.reserve(D ? D : 1));
+  HIPCHK(c, tokens.reserve(D ? D : 1));
+  ISLECHK(k_docs_len_hash(c, words.p, tokens.p, nullptr));
+  if (words_out && D) HIPCHK(c, hipMemcpyAsync(words_out, words.p, D * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (tokens_out && D) HIPCHK(c, hipMemcpyAsync(tokens_out, tokens.p, D * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+extern "C" int isle_hip_doc_duplicates(isle_ctx* c, uint32_t* first_of_out, uint64_t* n_duplicates) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(docs_A_ok(c, "doc_duplicates", 1));
+  const uint64_t D = c->a_D;
+  DevBuf<uint32_t> words, first_of;
+  DevBuf<uint64_t> tokens, hash;
+  StreamDrain drain(c);
+  HIPCHK(c, words.reserve(D ? D : 1));
+  HIPCHK(c, tokens.reserve(D ? D : 1));
+  HIPCHK(c, hash.reserve(D ? D : 1));
+  HIPCHK(c, first_of.reserve(D ? D : 1));
+  ISLECHK(k_docs_len_hash(c, words.p, tokens.p, hash.p));
+  uint64_t dups = 0, rounds = 0;
+  ISLECHK(k_docs_first_of(c, route_doc_hash(c->doc_hash_form), words.p, hash.p, first_of.p, &dups, &rounds));
+  if (first_of_out && D) HIPCHK(c, hipMemcpyAsync(first_of_out, first_of.p, D * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (n_duplicates) *n_duplicates = dups;
+  return 0;
+}
+
+// For the ledger an ingest of the pruned matrix, as isle_hip_prune_vocab: A_rewrite_begins is raised once every refusal is behind and the
+// pruned matrix lies complete in the twin buffers, right before they are swapped in; install_A ends it.
+extern "C" int isle_hip_prune_docs(isle_ctx* c, uint64_t min_words, uint64_t max_words, uint64_t min_tokens, uint64_t max_tokens, int drop_duplicates,
+                                   uint64_t* new_docs_out, uint32_t* kept_docs_out, uint32_t* first_of_out, uint64_t* nnz_out, uint64_t* docs_global_out,
+                                   uint64_t dropped_out[3]) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(docs_A_ok(c, "prune_docs", drop_duplicates));
+  const uint64_t D = c->a_D;
+  const DocsBounds b = {min_words, max_words, min_tokens, max_tokens};
+  DevBuf<uint32_t> words, first_of, keep, kept_docs, new_rows;
+  DevBuf<uint64_t> tokens, hash, word;
+  DevBuf<float> new_cnt;
+  DevBuf<int64_t> new_offs;
+  StreamDrain drain(c);
+  static const char* const kDocsCtl[6] = {"vocab_size", "min_words", "max_words", "min_tokens", "max_tokens", "drop_duplicates"};
+  const uint64_t agreed[6] = {c->a_V, min_words, max_words, min_tokens, max_tokens, (uint64_t)drop_duplicates};
+  ISLECHK(vocab_agree(c, "prune_docs", agreed, 6, kDocsCtl));  // (every local refusal lies before this line; the ones below are the same on every rank)
+  const std::string why = docs_check_args("prune_docs", true, b, drop_duplicates, c->world);
+  if (!why.empty()) return isle_fail(c, ISLE_E_ARG, "%s", why.c_str());
+  // ---- the rule's flags
+  HIPCHK(c, words.reserve(D ? D : 1));
+  HIPCHK(c, tokens.reserve(D ? D : 1));
+  HIPCHK(c, first_of.reserve(D ? D : 1));
+  HIPCHK(c, keep.reserve(D ? D : 1));
+  HIPCHK(c, kept_docs.reserve(D ? D : 1));
+  if (drop_duplicates) HIPCHK(c, hash.reserve(D ? D : 1));
+  ISLECHK(k_docs_len_hash(c, words.p, tokens.p, drop_duplicates ? hash.p : nullptr));
+  if (drop_duplicates) {
+    uint64_t dups = 0, rounds = 0;
+    ISLECHK(k_docs_first_of(c, route_doc_hash(c->doc_hash_form), words.p, hash.p, first_of.p, &dups, &rounds));
+  }
+  const uint64_t bounds[4] = {min_words, max_words, min_tokens, max_tokens};
+  uint64_t dropped[3] = {0, 0, 0}, kept = 0;
+  ISLECHK(k_docs_keep(c, words.p, tokens.p, bounds, drop_duplicates != 0, first_of.p, keep.p, dropped, &kept));
+  // ---- the corpus's numbers: the ranks' kept counts (the own slot set, summed), then dropped
+  const size_t world = (size_t)std::max(1, c->world);
+  std::vector<uint64_t> sums(world + 3, 0);
+  sums[c->multi() ? (size_t)c->rank : 0] = kept;
+  std::copy(dropped, dropped + 3, sums.begin() + world);
+  if (c->multi()) {
+    HIPCHK(c, word.reserve(world + 3));
+    ISLECHK(allreduce_host<uint64_t>(c, sums.data(), world + 3, word.p));
+  }
+  uint64_t docs_global = 0, doc_offset = 0;
+  for (size_t q = 0; q < world; ++q) {
+    if (c->multi() && q < (size_t)c->rank) doc_offset += sums[q];
+    docs_global += sums[q];
+  }
+  if (!docs_global) return isle_fail(c, ISLE_E_ARG, "%s", docs_none_kept(b, drop_duplicates).c_str());
+  // ---- the pruned matrix out of place
+  uint64_t total = 0;
+  ISLECHK(k_docs_compact(c, keep.p, words.p, kept, new_cnt, new_rows, new_offs, kept_docs.p, &total));
+  if (kept_docs_out && kept) HIPCHK(c, hipMemcpyAsync(kept_docs_out, kept_docs.p, kept * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (first_of_out && D) HIPCHK(c, hipMemcpyAsync(first_of_out, first_of.p, D * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  // ... and swapped in: the old buffers go with this call
+  c->res.A_rewrite_begins();
+  std::swap(c->a_cnt.p, new_cnt.p), std::swap(c->a_cnt.cap, new_cnt.cap);
+  std::swap(c->a_rows.p, new_rows.p), std::swap(c->a_rows.cap, new_rows.cap);
+  std::swap(c->a_offs.p, new_offs.p), std::swap(c->a_offs.cap, new_offs.cap);
+  c->a_D = kept;
+  c->a_nnz = total;
+  if (new_docs_out) *new_docs_out = kept;
+  if (docs_global_out) *docs_global_out = docs_global;
+  if (dropped_out) std::copy(sums.begin() + world, sums.end(), dropped_out);
+  return install_A(c, doc_offset, docs_global, total, nullptr, nnz_out);
 }
 
 // isle_hip_threshold, A -> B: the scalars its steps hand on.  What the host decides between them is stage_host.h.

@@ -254,6 +254,7 @@ struct isle_ctx {
   DevBuf<uint64_t> original_cols;  // D (B column -> global document id of A)
   float a_avg = 0.f;               // avg_doc_sz of the whole corpus (src/sparseMatrix.cpp:98)
   int vocab_hist_form = 0;         // isle_hip_vocab_hist_form: what route_vocab_hist is asked with (0: the rule's own choice)
+  int doc_hash_form = 0;           // isle_hip_doc_hash_form: what route_doc_hash is asked with (0: the rule's own choice)
 
   // --- downstream stage (post.hip): catchwords, topic model, edge topics
   DevBuf<float> a_nv;              // normalised values of A
@@ -724,6 +725,22 @@ int k_td_sort(isle_ctx* c, const TdView& v, const uint64_t* tables, uint32_t wor
 int k_vocab_df(isle_ctx* c, VocabHist form, uint32_t* df_dev);
 int k_vocab_compact(isle_ctx* c, const uint32_t* remap_dev, DevBuf<float>& new_cnt, DevBuf<uint32_t>& new_rows, DevBuf<int64_t>& new_offs, uint64_t* total,
                     uint64_t* emptied);
+
+// docs.hip: the device steps of isle_hip_doc_lengths / isle_hip_doc_duplicates / isle_hip_prune_docs on the resident A (the rule:
+// docs_host.h).  Every array is the caller's, a_D elements (at least one).  Nothing resident is written.  Device time: ISLE_T_INGEST.
+// k_docs_len_hash: words, tokens and the 64-bit hash of every document (hash nullable).
+// k_docs_first_of: first_of[d] = the smallest document with d's content; hash is consumed (it becomes the sort's keys, cut as the form
+//   says); *dups: the documents that are not the first of their kind; *rounds: the rounds of the resolution.
+// k_docs_keep: the rule's flags.  first_of is read where dups (and rewritten as reported), written otherwise; keep[d] = 1 where d stays;
+//   dropped[3] and *kept are this rank's.
+// k_docs_compact: the kept columns out of place into the caller's twin buffers, sized there, and kept_docs (new_docs elements) =
+//   a_doc_offset + the old number; new_docs as k_docs_keep counted them.
+int k_docs_len_hash(isle_ctx* c, uint32_t* words, uint64_t* tokens, uint64_t* hash);
+int k_docs_first_of(isle_ctx* c, DocHash form, const uint32_t* words, uint64_t* hash, uint32_t* first_of, uint64_t* dups, uint64_t* rounds);
+int k_docs_keep(isle_ctx* c, const uint32_t* words, const uint64_t* tokens, const uint64_t bounds[4], bool dups, uint32_t* first_of, uint32_t* keep,
+                uint64_t dropped[3], uint64_t* kept);
+int k_docs_compact(isle_ctx* c, const uint32_t* keep, const uint32_t* words, uint64_t new_docs, DevBuf<float>& new_cnt, DevBuf<uint32_t>& new_rows,
+                   DevBuf<int64_t>& new_offs, uint32_t* kept_docs, uint64_t* total);
 
 // model_load.hip: the text of a model file (n bytes on the device, ISLE_TEXT_SPARSE / ISLE_TEXT_DENSE) parsed into model_dev (V x ncols
 // column-major).  *err_key: ~0 = none, else (byte position << 3) | kind of the first offending byte (isle_hip_load_model_text names them);

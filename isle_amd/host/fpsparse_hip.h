@@ -522,6 +522,31 @@ class FPSparseMatrixHip {
     vocab_size_ = (word_id_t)new_vocab;
     top5_ready_ = false;
   }
+  // The documents of the count matrix A pruned by length and as exact duplicates on the device (isle_hip_prune_docs; the rule:
+  // isle_amd/csrc/docs_host.h): documents of fewer than min_words or more than max_words entries, of fewer than min_tokens or more than
+  // max_tokens tokens go (a maximum of 0: no bound), and with drop_duplicates every document whose column equals an earlier one's bit for
+  // bit; kept_docs[new id] = old id.  For everything resident an ingest of the pruned A: B is the old A's until threshold_again.  A
+  // refusal throws and leaves A as it was.  first_of (the old documents), entries (A's afterwards), dropped[3]: nullable.
+  void prune_documents(const uint64_t min_words, const uint64_t max_words, const uint64_t min_tokens, const uint64_t max_tokens, const bool drop_duplicates,
+                       std::vector<uint32_t>& kept_docs, std::vector<uint32_t>* first_of = nullptr, uint64_t* entries = nullptr, uint64_t* dropped = nullptr) {
+    uint64_t new_docs = 0;
+    kept_docs.assign(std::max<size_t>((size_t)a_docs_, 1), 0);
+    if (first_of) first_of->assign(std::max<size_t>((size_t)a_docs_, 1), 0);
+    check(isle_hip_prune_docs(ctx_, min_words, max_words, min_tokens, max_tokens, drop_duplicates ? 1 : 0, &new_docs, kept_docs.data(),
+                              first_of ? first_of->data() : nullptr, entries, nullptr, dropped),
+          "prune_docs");
+    kept_docs.resize((size_t)new_docs);
+    if (first_of) first_of->resize((size_t)a_docs_);
+    a_docs_ = (doc_id_t)new_docs;
+    top5_ready_ = false;
+  }
+  void doc_lengths(std::vector<uint32_t>& words, std::vector<uint64_t>& tokens) {
+    words.assign(std::max<size_t>((size_t)a_docs_, 1), 0);
+    tokens.assign(std::max<size_t>((size_t)a_docs_, 1), 0);
+    check(isle_hip_doc_lengths(ctx_, words.data(), tokens.data()), "doc_lengths");
+    words.resize((size_t)a_docs_);
+    tokens.resize((size_t)a_docs_);
+  }
   std::vector<uint32_t> word_doc_freq() {
     std::vector<uint32_t> df((size_t)vocab_size_, 0);
     check(isle_hip_word_doc_freq(ctx_, df.data()), "word_doc_freq");

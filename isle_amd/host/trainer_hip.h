@@ -372,7 +372,7 @@ class ISLETrainer {
 
  private:
   word_id_t vocab_size;  // the constructor's, until prune_vocabulary() (the only writer)
-  const doc_id_t num_docs;
+  doc_id_t num_docs;  // the constructor's, until prune_documents() (the only other writer)
   const offset_t max_entries;
   const doc_id_t num_topics;
   const bool flag_tf_idf;  // a no-op in the reference too; only the directory name differs
@@ -435,6 +435,7 @@ class ISLETrainer {
   std::vector<std::string> vocab_words;
   word_id_t vocab_file_words = 0;     // prune_vocabulary(): the vocabulary the file's lines name (the constructor's vocab_size) ...
   std::vector<uint32_t> kept_words;   // ... and the line of every word of the current vocabulary; empty: never pruned
+  std::vector<uint32_t> kept_docs;    // prune_documents(): the number every current document had when the data was loaded; empty: never pruned
   std::vector<std::vector<std::pair<word_id_t, FPTYPE>>> topwords;
   std::vector<std::vector<std::pair<word_id_t, FPTYPE>>> avg_topwords;  // output_avg_topic_coherence()
   std::vector<FPTYPE> AvgModel;  // vocab_size x num_topics, column-major, output_avg_topic_coherence()
@@ -684,6 +685,43 @@ class ISLETrainer {
     log->print("Vocabulary pruned: words kept " + std::to_string(vocab_size) + " dropped " + std::to_string(old_vocab - vocab_size) + ", entries kept " +
                std::to_string(entries) + " dropped " + std::to_string(old_entries - entries) + ", documents emptied " + std::to_string(emptied) + "\n");
     log->next_time_secs("Pruning the vocabulary");
+  }
+
+  // The documents pruned by length and as exact duplicates, on the device (FPSparseMatrixHip::prune_documents -> isle_hip_prune_docs; the
+  // rule: isle_amd/csrc/docs_host.h): documents of fewer than min_words or more than max_words distinct words, of fewer than min_tokens
+  // or more than max_tokens tokens go (a maximum of 0: no upper bound), and with drop_duplicates every document whose column equals an
+  // earlier one's bit for bit.  After the data is loaded and before train(): A is compacted, B is thresholded again from it and num_docs
+  // becomes the kept documents' number.  DocsKept.tsv: new id, old id (the document's number when the data was loaded), words, tokens,
+  // the ids 1-based like the other writers.  FROM THEN ON EVERY PER-DOCUMENT REPORT PRINTS THE NEW NUMBERS: DocsKept.tsv is the way
+  // back.  Nothing in the CLI calls it.
+  void prune_documents(const uint64_t min_words, const uint64_t max_words = 0, const uint64_t min_tokens = 0, const uint64_t max_tokens = 0,
+                       const bool drop_duplicates = false) {
+    if (!is_data_loaded) throw std::runtime_error("prune_documents() before the data is loaded");
+    if (is_training_complete) throw std::runtime_error("prune_documents() after train()");
+    const doc_id_t old_docs = num_docs;
+    const uint64_t old_entries = entries_in_A;
+    std::vector<uint32_t> kept, words;
+    std::vector<uint64_t> tokens;
+    uint64_t entries = 0, dropped[3] = {0, 0, 0};
+    B_fl_CSC->prune_documents(min_words, max_words, min_tokens, max_tokens, drop_duplicates, kept, nullptr, &entries, dropped);
+    B_fl_CSC->doc_lengths(words, tokens);  // of the kept documents, in the new numbering
+    if (!kept_docs.empty())                // a second prune goes through the first one's numbers
+      for (uint32_t& d : kept) d = kept_docs[d];
+    {
+      FILE* f = std::fopen((log_dir + "/DocsKept.tsv").c_str(), "wb");
+      if (!f) throw std::runtime_error("cannot write " + log_dir + "/DocsKept.tsv");
+      for (size_t d = 0; d < kept.size(); ++d)
+        std::fprintf(f, "%llu\t%llu\t%u\t%llu\n", (unsigned long long)d + 1, (unsigned long long)kept[d] + 1, words[d], (unsigned long long)tokens[d]);
+      std::fclose(f);
+    }
+    kept_docs.swap(kept);
+    num_docs = (doc_id_t)kept_docs.size();
+    entries_in_A = entries;
+    B_fl_CSC->threshold_again(num_topics, flag_sample_docs ? (double)sample_rate : 0.0, original_cols, &entries_above_threshold, &avg_doc_sz);
+    log->print("Documents pruned: kept " + std::to_string(num_docs) + " of " + std::to_string(old_docs) + ", too short " + std::to_string(dropped[0]) +
+               ", too long " + std::to_string(dropped[1]) + ", duplicates " + std::to_string(dropped[2]) + ", entries kept " + std::to_string(entries) +
+               " dropped " + std::to_string(old_entries - entries) + "\n");
+    log->next_time_secs("Pruning the documents");
   }
 
   // src/trainer.cpp:776-826

@@ -532,6 +532,52 @@ class HotPath:
         self._a_shape = self._counts_shape()[:3]
         return dict(vocab=int(nv.value), kept_words=kept[:int(nv.value)].copy(), df=df, nnz=int(nz.value), docs_emptied=int(gone.value))
 
+    # ---- documents pruned by length and as exact duplicates, on the resident A (include/isle_hip.h, isle_hip_prune_docs) -----------
+    def doc_hash_form(self, form="auto"):
+        """Which key this context sorts documents by before it compares their contents: "auto" (the library's rule), "full" (the 64-bit
+        document hash) or "narrow" (the same hash cut to 2 bits: every run holds many unequal documents).  Same result either way."""
+        self._chk(self._lib.isle_hip_doc_hash_form(self._h, {"auto": 0, "full": 1, "narrow": 2}[form]))
+
+    def doc_lengths(self):
+        """(words uint32 (D,), tokens uint64 (D,)) of this rank's documents of the resident count matrix: the entries of each column and
+        the sum of their counts, each truncated to an integer.  Nothing resident changes; never collective."""
+        D = self._counts_shape()[1]
+        words, tokens = np.empty(D, np.uint32), np.empty(D, np.uint64)
+        self._chk(self._lib.isle_hip_doc_lengths(self._h, _p(words), _p(tokens)))
+        return words, tokens
+
+    def doc_duplicates(self):
+        """dict(first_of uint32 (D,): the smallest document with the same column (rows and count bits) as each document, itself where it
+        is the first of its kind; n_duplicates: the documents that are not).  Nothing resident changes.  One rank only: refused under a
+        communicator of several ranks."""
+        D = self._counts_shape()[1]
+        first, n = np.empty(D, np.uint32), C.c_uint64()
+        self._chk(self._lib.isle_hip_doc_duplicates(self._h, _p(first), C.byref(n)))
+        return dict(first_of=first, n_duplicates=int(n.value))
+
+    def prune_docs(self, min_words=1, max_words=None, min_tokens=0, max_tokens=None, drop_duplicates=False):
+        """Drops the documents of the resident count matrix A with fewer than min_words or more than max_words entries, or with fewer
+        than min_tokens or more than max_tokens tokens (None: no upper bound), and with drop_duplicates every document whose column
+        equals an earlier one's bit for bit; the kept documents are renumbered in ascending old id and A is compacted on the device
+        (isle_hip_prune_docs states the rule).  For everything resident this is an ingest of the pruned matrix: run threshold() next.
+        A refusal (IsleHipError: a minimum above its maximum, no document kept, duplicates under several ranks, ...) leaves A as it
+        was.  Under comm_init / comm_init_host COLLECTIVE without drop_duplicates, with the same arguments on every rank.
+        -> dict(docs (this rank's), kept_docs uint32 (docs,): new id -> old number in the corpus, first_of uint32 (old docs,):
+        0xffffffff where dropped by length, the representative where dropped as a duplicate, nnz (this rank's), docs_global,
+        dropped_short, dropped_long, dropped_duplicate (the corpus's))."""
+        top_w = 0 if max_words is None else int(max_words)
+        top_t = 0 if max_tokens is None else int(max_tokens)
+        if int(min_words) < 0 or int(min_tokens) < 0 or (max_words is not None and top_w < 1) or (max_tokens is not None and top_t < 1):
+            raise ValueError("min_words >= 0, min_tokens >= 0, max_words >= 1 and max_tokens >= 1 (None: no upper bound)")
+        D = self._counts_shape()[1]
+        nd, nz, dg = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        kept, first, dropped = np.empty(max(D, 1), np.uint32), np.empty(max(D, 1), np.uint32), np.zeros(3, np.uint64)
+        self._chk(self._lib.isle_hip_prune_docs(self._h, int(min_words), top_w, int(min_tokens), top_t, int(bool(drop_duplicates)), C.byref(nd), _p(kept),
+                                                _p(first), C.byref(nz), C.byref(dg), _p(dropped)))
+        self._a_shape = self._counts_shape()[:3]
+        return dict(docs=int(nd.value), kept_docs=kept[:int(nd.value)].copy(), first_of=first[:D].copy(), nnz=int(nz.value), docs_global=int(dg.value),
+                    dropped_short=int(dropped[0]), dropped_long=int(dropped[1]), dropped_duplicate=int(dropped[2]))
+
     def threshold(self, num_topics, sample_rate=0.0, sample_seed=0):
         """normalize_docs + compute_thresholds + (sampled_)threshold_and_copy on the device
         (src/trainer.cpp:430-485); B becomes this context's matrix.  Returns a dict of scalars."""
