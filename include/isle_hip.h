@@ -874,6 +874,35 @@ int isle_hip_doc_duplicates(isle_ctx* ctx, uint32_t* first_of, uint64_t* n_dupli
 int isle_hip_prune_docs(isle_ctx* ctx, uint64_t min_words, uint64_t max_words, uint64_t min_tokens, uint64_t max_tokens, int drop_duplicates,
                         uint64_t* new_docs, uint32_t* kept_docs, uint32_t* first_of, uint64_t* nnz, uint64_t* docs_global, uint64_t dropped[3]);
 
+/* ---- two topic models compared: L1 distances and topic matching (isle_amd/csrc/model_compare.hip) ---------------------------------------
+ * "Is this model the same as that one": this run against a file loaded back, the catch model against the average model, a run after a
+ * prune against the run before, a recovered model against planted topics.  The rule is stated once, in isle_amd/csrc/match_host.h.
+ *   dist[i][j]  sum over the words w of |(double)a[w, i] - (double)b[w, j]|, a (vocab x cols_a) and b (vocab x cols_b) column-major fp32;
+ *               row-major cols_a x cols_b doubles.  Terms formed and summed in double, in an order that is a function of (vocab, cols_a,
+ *               cols_b, slices) alone (no floating-point atomics: two calls give the same bits); |dist - exact| <= vocab 2^-53 exact.  A
+ *               column with any non-finite entry (the average model's empty clusters) makes its row or column of dist NaN.
+ *   matching    greedy: an edge (i, j) exists where dist[i][j] is finite; the edges are walked in the order (dist, i, j) (< on doubles:
+ *               -0 equals +0) and (i, j) is matched when both are free.  match_a[i] = j or -1, match_b[j] = i or -1, match_dist[i] = the
+ *               matched distance or NaN, mean_dist = the matched distances summed in ascending i over n_matched (NaN where nothing
+ *               matched).  The optimal (Hungarian) assignment is out of scope; the greedy mean is an upper bound of the optimal one.
+ *               On the device: rounds of mutually best pairs, one counter read back per round; rounds = the rounds that matched a pair.
+ * isle_hip_compare_models: each side is named as in isle_hip_model_top_words (which / model_host / cols; ISLE_MODEL_HOST uploads the
+ * caller's model for the call); both may be host models, both may name the same resident model (an exactly-0 diagonal).  The matcher runs
+ * on the device matrix where match_a, match_b, match_dist, n_matched or mean_dist is asked for; every output is nullable and only what is
+ * asked for is fetched.  Nothing resident changes.  Device time: ISLE_T_POST.  With several ranks every rank answers for itself, no
+ * collective; ISLE_MODEL_AVG is refused there like in every reader of a model.
+ * isle_hip_match_topics: the same matcher on the caller's na x nb row-major matrix (ties, +-0, +-inf and NaN patterns real distances never show).
+ * isle_hip_model_dist_slices: how many word slices the distance kernel cuts the vocabulary into (0: the rule route_model_dist_slices of
+ * isle_amd/csrc/route_host.h; >= 1: that many, capped at ceil(vocab / MC_CHUNK)); a setting of the context, not an environment variable.
+ * ISLE_E_ARG, decided before any launch (texts: match_host.h): an unknown model, a resident model that does not exist, vocab or cols
+ * other than a resident side's, vocab == 0 or > 0xfffffff0, cols_a or cols_b outside 1 .. 8192 (the matrix is cols_a cols_b 8 bytes,
+ * 512 MB at the limit), a null host model with ISLE_MODEL_HOST, na or nb outside 1 .. 8192, a null dist_host, slices < 0. */
+int isle_hip_model_dist_slices(isle_ctx* ctx, int slices);
+int isle_hip_compare_models(isle_ctx* ctx, int which_a, const float* a_host, int cols_a, int which_b, const float* b_host, int cols_b, uint64_t vocab,
+                            double* dist, int32_t* match_a, int32_t* match_b, double* match_dist, uint64_t* n_matched, double* mean_dist, uint32_t* rounds);
+int isle_hip_match_topics(isle_ctx* ctx, const double* dist_host, int na, int nb, int32_t* match_a, int32_t* match_b, double* match_dist,
+                          uint64_t* n_matched, double* mean_dist, uint32_t* rounds);
+
 /* ---- measurement ----------------------------------------------------------------------- */
 /* Per-kernel-family device time accumulated with HIP events on the context's stream since the
  * last reset (only while enabled; enabling adds event records around each launch).

@@ -75,6 +75,9 @@ SYMBOLS = {
     "isle_hip_doc_lengths": (_I, [_P, _P, _P]),
     "isle_hip_doc_duplicates": (_I, [_P, _P, _P]),
     "isle_hip_prune_docs": (_I, [_P, _U64, _U64, _U64, _U64, _I, _P, _P, _P, _P, _P, _P]),
+    "isle_hip_model_dist_slices": (_I, [_P, _I]),
+    "isle_hip_compare_models": (_I, [_P, _I, _P, _I, _I, _P, _I, _U64, _P, _P, _P, _P, _P, _P, _P]),
+    "isle_hip_match_topics": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "isle_hip_block_ks": (_I, [_P, _I, _I, _I, _I, _F, _U64, _P, _P, _P, _P]),
     "isle_hip_block_ks_dense": (_I, [_P, _P, _U64, _I, _I, _I, _I, _F, _U64, _P, _P, _P, _P, _P, _P, _P]),
     "isle_hip_get_U": (_I, [_P, _P]),

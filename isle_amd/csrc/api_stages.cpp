@@ -13,6 +13,7 @@
 #include "topdocs_host.h"
 #include "vocab_host.h"
 #include "docs_host.h"
+#include "match_host.h"
 
 // ------------------------------------------------------------------------------------------
 // upstream stage: A -> B on the device
@@ -1124,6 +1125,97 @@ extern "C" int isle_hip_model_top_words(isle_ctx* c, int which, const float* mod
   if (weights) HIPCHK(c, hipMemcpyAsync(weights, w_d.p, m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
+}
+
+// ---- two models compared: L1 distances and the greedy matching (model_compare.hip; the rule: match_host.h)
+extern "C" int isle_hip_model_dist_slices(isle_ctx* c, int slices) {
+  if (!c) return ISLE_E_ARG;
+  const std::string why = mc_check_slices(slices);
+  if (!why.empty()) return isle_fail(c, ISLE_E_ARG, "%s", why.c_str());
+  c->model_dist_slices = slices;
+  return 0;
+}
+
+// what match_host.h's checks ask about a side, from the ledger alone
+static McSide mc_side(const isle_ctx* c, int which, const float* host, int cols) {
+  McSide m = {which, host != nullptr, cols, false, c->a_V, c->res.p_k};
+  if (which == ISLE_MODEL_CATCH) m.resident = c->res.p_model_ready;
+  else if (which == ISLE_MODEL_AVG) m.resident = c->res.p_avg_ready;
+  else if (which == ISLE_MODEL_LOADED) m.resident = c->res.ml_ready, m.res_vocab = c->ml_V, m.res_cols = c->ml_cols;
+  return m;
+}
+
+// the matcher on a device matrix and the fetches of what was asked for (mean_dist: the fetched distances summed in ascending i on the host)
+static int mc_match_and_fetch(isle_ctx* c, const double* dist_dev, int na, int nb, int32_t* match_a, int32_t* match_b, double* match_dist, uint64_t* n_matched,
+                              double* mean_dist, uint32_t* rounds) {
+  DevBuf<int32_t> m_d;
+  DevBuf<double> md_d;
+  StreamDrain drain(c);
+  HIPCHK(c, m_d.reserve((size_t)na + nb));
+  HIPCHK(c, md_d.reserve((size_t)na));
+  uint64_t n = 0;
+  uint32_t r = 0;
+  ISLECHK(k_mc_match(c, dist_dev, na, nb, m_d.p, m_d.p + na, md_d.p, &n, &r));
+  std::vector<int32_t> ma;
+  std::vector<double> md;
+  if (mean_dist) {
+    ma.resize((size_t)na);
+    md.resize((size_t)na);
+    HIPCHK(c, hipMemcpyAsync(ma.data(), m_d.p, (size_t)na * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(md.data(), md_d.p, (size_t)na * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (match_a) HIPCHK(c, hipMemcpyAsync(match_a, m_d.p, (size_t)na * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (match_b) HIPCHK(c, hipMemcpyAsync(match_b, m_d.p + na, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (match_dist) HIPCHK(c, hipMemcpyAsync(match_dist, md_d.p, (size_t)na * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (mean_dist) {
+    uint64_t counted = 0;
+    *mean_dist = mc_mean(ma, md, &counted);
+    if (counted != n) return isle_fail(c, ISLE_E_HIP, "match_topics: %llu rows are matched where the rounds counted %llu", (unsigned long long)counted, (unsigned long long)n);
+  }
+  if (n_matched) *n_matched = n;
+  if (rounds) *rounds = r;
+  return 0;
+}
+
+extern "C" int isle_hip_compare_models(isle_ctx* c, int which_a, const float* a_host, int cols_a, int which_b, const float* b_host, int cols_b, uint64_t vocab,
+                                       double* dist, int32_t* match_a, int32_t* match_b, double* match_dist, uint64_t* n_matched, double* mean_dist,
+                                       uint32_t* rounds) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(model_reader_ok(c, which_a, "compare_models"));
+  ISLECHK(model_reader_ok(c, which_b, "compare_models"));
+  const std::string why = mc_check_compare(mc_side(c, which_a, a_host, cols_a), mc_side(c, which_b, b_host, cols_b), vocab);
+  if (!why.empty()) return isle_fail(c, ISLE_E_ARG, "%s", why.c_str());
+  const float *a_dev = nullptr, *b_dev = nullptr;
+  DevBuf<float> up_a, up_b;
+  DevBuf<double> dist_d;
+  StreamDrain drain(c);  // both uploads live until the stream is drained
+  ISLECHK(model_source(c, which_a, a_host, vocab, cols_a, "compare_models", &up_a, &a_dev));
+  ISLECHK(model_source(c, which_b, b_host, vocab, cols_b, "compare_models", &up_b, &b_dev));
+  HIPCHK(c, dist_d.reserve((size_t)cols_a * cols_b));
+  ISLECHK(k_mc_dist(c, a_dev, cols_a, b_dev, cols_b, vocab, route_model_dist_slices(vocab, cols_a, cols_b, c->num_cus, c->model_dist_slices), dist_d.p));
+  if (dist) HIPCHK(c, hipMemcpyAsync(dist, dist_d.p, (size_t)cols_a * cols_b * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (match_a || match_b || match_dist || n_matched || mean_dist) {
+    ISLECHK(mc_match_and_fetch(c, dist_d.p, cols_a, cols_b, match_a, match_b, match_dist, n_matched, mean_dist, rounds));
+  } else if (rounds) {
+    *rounds = 0;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+extern "C" int isle_hip_match_topics(isle_ctx* c, const double* dist_host, int na, int nb, int32_t* match_a, int32_t* match_b, double* match_dist,
+                                     uint64_t* n_matched, double* mean_dist, uint32_t* rounds) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  const std::string why = mc_check_match(dist_host != nullptr, na, nb);
+  if (!why.empty()) return isle_fail(c, ISLE_E_ARG, "%s", why.c_str());
+  DevBuf<double> dist_d;
+  StreamDrain drain(c);
+  HIPCHK(c, dist_d.reserve((size_t)na * nb));
+  HIPCHK(c, hipMemcpyAsync(dist_d.p, dist_host, (size_t)na * nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  return mc_match_and_fetch(c, dist_d.p, na, nb, match_a, match_b, match_dist, n_matched, mean_dist, rounds);
 }
 
 // ... of the edge topics a * M[:, p] + b * M[:, s] of a model, formed from its two columns while they are read (tw_select_k's edge source)

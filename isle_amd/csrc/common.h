@@ -255,6 +255,7 @@ struct isle_ctx {
   float a_avg = 0.f;               // avg_doc_sz of the whole corpus (src/sparseMatrix.cpp:98)
   int vocab_hist_form = 0;         // isle_hip_vocab_hist_form: what route_vocab_hist is asked with (0: the rule's own choice)
   int doc_hash_form = 0;           // isle_hip_doc_hash_form: what route_doc_hash is asked with (0: the rule's own choice)
+  int model_dist_slices = 0;       // isle_hip_model_dist_slices: what route_model_dist_slices is asked with (0: the rule's own choice)
 
   // --- downstream stage (post.hip): catchwords, topic model, edge topics
   DevBuf<float> a_nv;              // normalised values of A
@@ -741,6 +742,15 @@ int k_docs_keep(isle_ctx* c, const uint32_t* words, const uint64_t* tokens, cons
                 uint64_t dropped[3], uint64_t* kept);
 int k_docs_compact(isle_ctx* c, const uint32_t* keep, const uint32_t* words, uint64_t new_docs, DevBuf<float>& new_cnt, DevBuf<uint32_t>& new_rows,
                    DevBuf<int64_t>& new_offs, uint32_t* kept_docs, uint64_t* total);
+
+// model_compare.hip: the device steps of isle_hip_compare_models / isle_hip_match_topics (the rule: match_host.h).  Every array is the
+// caller's, on the device.  Nothing resident is written.  Device time: ISLE_T_POST.
+// k_mc_dist: dist (ka x kb row-major doubles) = the L1 distances of the columns of a (V x ka) and b (V x kb), column-major fp32, the words
+//   cut into `slices` slices (route_model_dist_slices); a and b may be one buffer.  Its scratch goes with the call: the stream is drained when it returns.
+// k_mc_match: the greedy matching of dist (na x nb) by rounds of mutually best pairs; match_a (na), match_b (nb), match_dist (na);
+//   *n_matched and *rounds (the rounds that matched a pair) are on the host when it returns.
+int k_mc_dist(isle_ctx* c, const float* a, int ka, const float* b, int kb, uint64_t V, uint32_t slices, double* dist);
+int k_mc_match(isle_ctx* c, const double* dist, int na, int nb, int32_t* match_a, int32_t* match_b, double* match_dist, uint64_t* n_matched, uint32_t* rounds);
 
 // model_load.hip: the text of a model file (n bytes on the device, ISLE_TEXT_SPARSE / ISLE_TEXT_DENSE) parsed into model_dev (V x ncols
 // column-major).  *err_key: ~0 = none, else (byte position << 3) | kind of the first offending byte (isle_hip_load_model_text names them);

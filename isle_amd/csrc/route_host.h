@@ -427,3 +427,13 @@ inline VocabHist route_vocab_hist(int asked) { return asked == 2 ? VOCAB_FORM_GL
 // against 754 ms of wall time (medians of 5; tools/docs_prune_probe.py, profiles/docs_prune_c2.jsonl); the narrow form exists for the tests.
 enum DocHash { DOC_FORM_FULL = 0, DOC_FORM_NARROW = 1 };
 inline DocHash route_doc_hash(int asked) { return asked == 2 ? DOC_FORM_NARROW : DOC_FORM_FULL; }
+
+// ---- two topic models compared (api_stages.cpp, model_compare.hip) --------------------------------------------------------------------------
+#include "match_host.h"  // MC_TILE, MC_CHUNK, mc_slices (included here: tests cite lines above by number)
+// The word slices of mc_dist_k (match_host.h states the arithmetic, mc_slices): ceil(ka / MC_TILE) ceil(kb / MC_TILE) pair tiles are 256
+// workgroups at k = 1000 and 16 at k = 200, so the words are cut into enough slices, each a multiple of MC_CHUNK words, that every compute
+// unit gets MC_SLICE_WAVES workgroups; the slices' partial matrices are added in ascending slice order by mc_reduce_k, and with one slice
+// none is written.  asked: the context's setting (isle_hip_model_dist_slices: 0 this rule's choice, >= 1 forced).  The slices fix the order
+// of summation and nothing else: where every sum is exactly representable the bits are the same for every count.  README for what was
+// measured.
+inline uint32_t route_model_dist_slices(uint64_t V, int ka, int kb, int num_cus, int asked = 0) { return mc_slices(V, ka, kb, num_cus, asked); }

@@ -577,6 +577,51 @@ class FPSparseMatrixHip {
     check(isle_hip_topic_top_docs(ctx_, source, (int)num_topics, n, doc_base, 0, nullptr, nullptr, nullptr, docs.data(), values.data(), counts.data(),
                                   entries ? entries->data() : nullptr), "topic_top_docs");
   }
+  // Two models compared on the device (isle_hip_compare_models; the rule: isle_amd/csrc/match_host.h): dist (cols_a x cols_b row-major) =
+  // the L1 distances of their topics in double, and the greedy matching of the topics by it: match_a[i] = the matched topic of b or -1,
+  // match_b the inverse, match_dist[i] = the matched distance or NaN, mean_dist over the n_matched pairs.  A side is a resident model
+  // (ISLE_MODEL_CATCH / ISLE_MODEL_AVG / ISLE_MODEL_LOADED; host null, cols ignored) or, with ISLE_MODEL_HOST, host (vocab x cols
+  // column-major); vocab is read from a resident side.  dist is nullable.  -> the rounds of the matcher.
+  struct TopicMatch {
+    std::vector<int32_t> match_a, match_b;
+    std::vector<double> match_dist;
+    uint64_t n_matched = 0;
+    double mean_dist = 0.0;
+    uint32_t rounds = 0;
+  };
+  TopicMatch compare_models(const int which_a, const int which_b, std::vector<double>* dist = nullptr, const FPTYPE* a_host = nullptr, const doc_id_t cols_a = 0,
+                            const FPTYPE* b_host = nullptr, const doc_id_t cols_b = 0, const word_id_t vocab = 0) {
+    const doc_id_t ka = which_a == ISLE_MODEL_HOST ? cols_a : model_cols(which_a), kb = which_b == ISLE_MODEL_HOST ? cols_b : model_cols(which_b);
+    const word_id_t V = which_a != ISLE_MODEL_HOST ? model_vocab(which_a) : which_b != ISLE_MODEL_HOST ? model_vocab(which_b) : vocab;
+    TopicMatch m;
+    m.match_a.assign(std::max<size_t>((size_t)ka, 1), -1);
+    m.match_b.assign(std::max<size_t>((size_t)kb, 1), -1);
+    m.match_dist.assign(std::max<size_t>((size_t)ka, 1), 0.0);
+    if (dist) dist->assign(std::max<size_t>((size_t)ka * kb, 1), 0.0);
+    check(isle_hip_compare_models(ctx_, which_a, a_host, (int)ka, which_b, b_host, (int)kb, V, dist ? dist->data() : nullptr, m.match_a.data(), m.match_b.data(),
+                                  m.match_dist.data(), &m.n_matched, &m.mean_dist, &m.rounds),
+          "compare_models");
+    m.match_a.resize((size_t)ka);
+    m.match_b.resize((size_t)kb);
+    m.match_dist.resize((size_t)ka);
+    if (dist) dist->resize((size_t)ka * kb);
+    return m;
+  }
+  // The same matcher on the caller's na x nb row-major matrix (isle_hip_match_topics)
+  TopicMatch match_topics(const std::vector<double>& dist, const int na, const int nb) {
+    TopicMatch m;
+    m.match_a.assign((size_t)std::max(na, 1), -1);
+    m.match_b.assign((size_t)std::max(nb, 1), -1);
+    m.match_dist.assign((size_t)std::max(na, 1), 0.0);
+    check(isle_hip_match_topics(ctx_, dist.empty() ? nullptr : dist.data(), na, nb, m.match_a.data(), m.match_b.data(), m.match_dist.data(), &m.n_matched, &m.mean_dist,
+                                &m.rounds),
+          "match_topics");
+    m.match_a.resize((size_t)std::max(na, 0));
+    m.match_b.resize((size_t)std::max(nb, 0));
+    m.match_dist.resize((size_t)std::max(na, 0));
+    return m;
+  }
+  void model_dist_slices(const int slices) { check(isle_hip_model_dist_slices(ctx_, slices), "model_dist_slices"); }
   doc_id_t count_docs() const { return a_docs_; }  // documents of the count matrix A (B may hold fewer after sampling)
   // DenseMatrix::write_to_file_as_sparse (format = ISLE_TEXT_SPARSE) / write_to_file (ISLE_TEXT_DENSE), src/denseMatrix.cpp:124-186, of a
   // resident model (ISLE_MODEL_CATCH / ISLE_MODEL_AVG), or with ISLE_MODEL_HOST of model_host (vocab x ncols column-major): the text is

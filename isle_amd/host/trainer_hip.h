@@ -39,6 +39,10 @@
 // doc_catchword_text / doc_topic_sums_text / top_two_text state their bytes.  With print_doctopic set, write_model_to_file() calls
 // output_doc_topic() (the call the reference left commented out at :664-667); the flag defaults to false.  Deviation: equal (topic, value)
 // pairs of DocTopicCatchwordSums.tsv go by document ascending (the reference's sort is unstable).
+// Model comparison: output_model_comparison(model_file) reads a model file into the resident loaded model and compares this run's catch
+// model with it on the device: L1 distances of all topic pairs in double, greedy matching (isle_amd/csrc/match_host.h states the rule; the
+// optimal assignment is out of scope).  TopicMatch.tsv (trainer_detail::topic_match_text states its bytes) and the log line "Avg L1
+// distance of matched topics:".  The reference has no such output; nothing in this class or the CLI calls it.
 // Not mirrored (dead under the shipped hyper-parameters or outside the path): load_preprocessed_data_from_file,
 // compute_input_svd, construct_edge_topics_v1.
 #pragma once
@@ -363,6 +367,18 @@ inline std::string edge_top_words_text(const std::vector<std::tuple<int, int, ui
     o << "\n\n";
   }
   return o.str();
+}
+// TopicMatch.tsv (ISLETrainer::output_model_comparison): "<topic>\t<matched topic or -1>\t<distance>\n" per topic of this run, topics 1-based
+// like the model files, the distance as %.17g and "nan" where the topic stayed unmatched.
+inline std::string topic_match_text(const std::vector<int32_t>& match_a, const std::vector<double>& match_dist) {
+  std::string out;
+  char line[96];
+  for (size_t t = 0; t < match_a.size(); ++t) {
+    if (match_a[t] < 0) std::snprintf(line, sizeof line, "%llu\t-1\tnan\n", (unsigned long long)t + 1);
+    else std::snprintf(line, sizeof line, "%llu\t%d\t%.17g\n", (unsigned long long)t + 1, match_a[t] + 1, match_dist[t]);
+    out += line;
+  }
+  return out;
 }
 }  // namespace trainer_detail
 
@@ -969,6 +985,26 @@ class ISLETrainer {
         std::fwrite(text, 1, trainer_detail::doc_line_text((uint64_t)docs[(size_t)t * n + i] + 1, (uint64_t)t + 1, values[(size_t)t * n + i], text), f);
     std::fclose(f);
     log->next_time_secs("Writing the heaviest documents of every topic");
+  }
+  // "Is this model the same as that one": the model file model_file (format ISLE_TEXT_SPARSE / ISLE_TEXT_DENSE, vocab_size x num_topics, as
+  // write_model_to_file writes it) is read on the device into the resident loaded model (FPSparseMatrixHip::load_model_file) and this
+  // run's catch model (side a) is compared with it (side b): the L1 distances of all topic pairs in double and the greedy matching by
+  // them, on the device (FPSparseMatrixHip::compare_models -> isle_hip_compare_models; the rule: isle_amd/csrc/match_host.h).
+  // TopicMatch.tsv: trainer_detail::topic_match_text states its bytes.  The log gets the mean distance of the matched topics.  The
+  // reference has no such output; not part of what ISLETrain writes by default.
+  void output_model_comparison(const std::string& model_file, const int format = ISLE_TEXT_SPARSE) {
+    if (!is_training_complete) throw std::runtime_error("output_model_comparison() before train()");
+    B_fl_CSC->load_model_file(model_file, vocab_size, num_topics, format);
+    const FPSparseMatrixHip::TopicMatch m = B_fl_CSC->compare_models(ISLE_MODEL_CATCH, ISLE_MODEL_LOADED);
+    const std::string text = trainer_detail::topic_match_text(m.match_a, m.match_dist);
+    FILE* f = std::fopen((log_dir + "/TopicMatch.tsv").c_str(), "wb");
+    if (!f) throw std::runtime_error("cannot write " + log_dir + "/TopicMatch.tsv");
+    std::fwrite(text.data(), 1, text.size(), f);
+    std::fclose(f);
+    char mean[40];
+    std::snprintf(mean, sizeof mean, "%.17g", m.mean_dist);
+    log->print(std::string("Avg L1 distance of matched topics: ") + mean + " (" + std::to_string(m.n_matched) + " of " + std::to_string(num_topics) + " matched)\n");
+    log->next_time_secs("Comparing the model with a model file");
   }
   void finish_log() { log->total("TVSD"); }  // the "Total time for TVSD" line the reference's train() ends with (:652)
 

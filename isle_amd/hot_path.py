@@ -794,6 +794,63 @@ class HotPath:
         self._chk(self._lib.isle_hip_model_top_words(self._h, which, _p(host), int(V), int(cols), int(n), _p(ids), _p(w)))
         return (ids, w) if with_weights else ids
 
+    # ---- two models compared: L1 distances and topic matching (include/isle_hip.h, isle_hip_compare_models) ------------------------
+    def _model_side(self, model):
+        """-> (which, host array or None, V, cols) of a model named as in model_top_words"""
+        if isinstance(model, str):
+            V, cols = self._resident_shape(model)
+            return self._MODELS[model], None, V, cols
+        host = np.asfortranarray(model, np.float32)
+        if host.ndim != 2:
+            raise ValueError("model must be (V, cols)")
+        return 2, host, host.shape[0], host.shape[1]
+
+    @staticmethod
+    def _match_outputs(na, nb):
+        ok = 1 <= na <= 8192 and 1 <= nb <= 8192       # beyond: the library refuses before it writes
+        return (np.empty(na if ok else 1, np.int32), np.empty(nb if ok else 1, np.int32), np.empty(na if ok else 1, np.float64), C.c_uint64(), C.c_double(),
+                C.c_uint32())
+
+    def model_dist_slices(self, n=0):
+        """How many word slices this context's distance kernel cuts the vocabulary into: 0 (the library's rule) or n >= 1 (capped at
+        ceil(V / 64)).  With exactly representable sums the same bits either way; otherwise the order of summation follows it."""
+        self._chk(self._lib.isle_hip_model_dist_slices(self._h, int(n)))
+
+    def compare_models(self, a="catch", b="loaded", fetch_dist=True, match=True):
+        """The L1 distance of every topic of model a to every topic of model b, in double on the device, and the greedy matching of the
+        topics by it (isle_hip_compare_models states the rule).  Each side: "catch", "avg", "loaded" or a (V, cols) array; both may be
+        arrays, both may name the same model.  A column with a non-finite entry (an empty cluster's in "avg") gives NaN distances and
+        stays unmatched.  Nothing resident changes; under comm_init / comm_init_host each rank answers for itself ("avg" is refused).
+        -> dict(dist float64 (cols_a, cols_b) or None, match_a int32 (cols_a,): the matched topic of b or -1, match_b int32 (cols_b,),
+        match_dist float64 (cols_a,): NaN where unmatched, n_matched, mean_dist, rounds); the match entries are None without match."""
+        wa, ha, Va, ka = self._model_side(a)
+        wb, hb, Vb, kb = self._model_side(b)
+        if ha is not None and hb is not None and Va != Vb:
+            raise ValueError("the two models have %d and %d words" % (Va, Vb))
+        V = Vb if ha is None and hb is not None else Va
+        ok = 1 <= ka <= 8192 and 1 <= kb <= 8192
+        dist = np.empty((ka, kb) if ok else (1, 1), np.float64) if fetch_dist else None
+        ma, mb, md, n, mean, rounds = self._match_outputs(ka, kb)
+        if not match:
+            ma = mb = md = None
+        self._chk(self._lib.isle_hip_compare_models(self._h, wa, _p(ha), int(ka), wb, _p(hb), int(kb), int(V), _p(dist), _p(ma), _p(mb), _p(md),
+                                                    C.byref(n) if match else None, C.byref(mean) if match else None, C.byref(rounds)))
+        return dict(dist=dist, match_a=ma, match_b=mb, match_dist=md, n_matched=int(n.value) if match else None,
+                    mean_dist=float(mean.value) if match else None, rounds=int(rounds.value))
+
+    def match_topics(self, dist):
+        """The greedy matching of the rows and columns of a (na, nb) float64 matrix on the device, by the rule of compare_models: an
+        edge where the entry is finite, edges in the order (value, row, column).  -> dict(match_a, match_b, match_dist, n_matched,
+        mean_dist, rounds)."""
+        d = np.ascontiguousarray(dist, np.float64)
+        if d.ndim != 2:
+            raise ValueError("dist must be (na, nb)")
+        na, nb = d.shape
+        ma, mb, md, n, mean, rounds = self._match_outputs(na, nb)
+        self._chk(self._lib.isle_hip_match_topics(self._h, _p(d) if d.size else None, int(na), int(nb), _p(ma), _p(mb), _p(md), C.byref(n), C.byref(mean),
+                                                  C.byref(rounds)))
+        return dict(match_a=ma, match_b=mb, match_dist=md, n_matched=int(n.value), mean_dist=float(mean.value), rounds=int(rounds.value))
+
     def topic_diversity(self, num_topics, model="catch"):
         """Topic diversity (ISLETrainer::output_topic_diversity, src/trainer.cpp:750-774) of a resident model, in double:
         dist[t] = |m_t - mean topic|^2 over the finite topics (NaN for the others) and their mean.  -> dict(dist float64 (k,), avg)."""
