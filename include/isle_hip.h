@@ -784,6 +784,63 @@ int isle_hip_top_two_line_text(uint64_t doc_number, uint64_t t1_number, uint64_t
 #define ISLE_TOPDOCS_MAX_N 256
 int isle_hip_topic_top_docs(isle_ctx* ctx, int source, int num_topics, int n, uint64_t doc_base, uint64_t num_rows, const int64_t* doc_offsets,
                             const uint32_t* topic, const float* value, uint32_t* docs, float* values, uint32_t* counts, uint64_t* topic_entries);
+/* The n documents most similar to each of num_queries query documents, scored and selected on the device (isle_amd/csrc/similar_docs.hip and
+ * the selection of topic_docs.hip) from sparse topic weights that are stored by document.  The rule is stated once, in
+ * isle_amd/csrc/simdocs_host.h:
+ *   a row is a document's entries (topic, weight), topics ascending strictly; its document is doc = doc_base + row.  A query is the same kind
+ *   of list.  Every weight is finite, >= 0 and < 2^31 (-0.0 counts as 0); the first entry outside that domain is named in the refusal.
+ *   candidates  row r is a candidate of query q when some topic is STORED in both, whatever the weights (a shared topic of weight 0 makes a
+ *               candidate of score 0), unless doc_base + r == exclude[q] (0xffffffff: nothing is excluded).  candidates[q] counts them (all ranks).
+ *   score       a the row's, b the query's weight at a common topic, common topics ascending:
+ *     ISLE_SIM_DOT            s = sum (double)a (double)b                             score = (float)s
+ *     ISLE_SIM_COSINE         s likewise; nr = sum over ALL entries of the row (double)a (double)a, nq likewise over the query;
+ *                             den = sqrtf((float)nr) * sqrtf((float)nq) in fp32       score = den == 0 ? 0 : (float)s / den (fp32 division)
+ *     ISLE_SIM_BHATTACHARYYA  s = sum (double)sqrtf(a * b), product and root in fp32  score = (float)s   (distributions: 1 - Hellinger^2)
+ *   result      isle_hip_topic_top_docs' with the query in the place of the topic: key = ord(bits(score)) << 32 | ~doc, the larger key wins
+ *               (the higher score, the smaller document among bit-equal scores).  docs[q n + i] / scores[q n + i] for
+ *               i < counts[q] = min(n, candidates[q]), the unused slots 0xffffffff / 0.0f; candidates is nullable.
+ * Device and host agree bit for bit: a product of two fp32 values is exact in double (s + a b rounds once with or without an fma), the rest
+ * is single IEEE operations.  NOT CERTIFIED: fp32 products a * b that are subnormal (BHATTACHARYYA, weights below 2^-60).
+ * source, doc_base, num_rows, doc_offsets / topic / value are isle_hip_topic_top_docs'.  num_topics is the column count of the last
+ * isle_hip_infer_resident (INFER), the topic model's (SUMS); another value is refused.
+ * The queries: query_rows non-null: rows query_rows[q] of the source, gathered on the device (q_* are ignored); where exclude is null,
+ * exclude[q] defaults to doc_base + query_rows[q]: a document is not its own neighbour.  Otherwise the caller's CSR q_offsets
+ * (num_queries + 1) / q_topic / q_weight, uploaded for the call and checked on the host in this order, each condition over all queries
+ * before the next: the offsets ascend from 0, every topic < num_topics, the topics of a query ascend strictly, the weight domain.
+ * ISLE_E_ARG, decided before any launch or collective: an unknown source or measure, num_queries outside 1 .. ISLE_SIMDOCS_MAX_QUERIES, n
+ * outside 1 .. ISLE_TOPDOCS_MAX_N, world x n > 8192, doc_base + rows > 0xfffffff1, a query_rows[q] that is not below the rows, null docs /
+ * scores / counts, a bad query, the sources' own conditions.  Found on the device: a row entry with a weight outside the domain (the text names
+ * the entry, its row and its value), a topic >= num_topics or topics that do not ascend (HOST); 2^32 candidate pairs or more on a rank ("ask
+ * with fewer queries").  After any refusal the context is usable and nothing resident has changed.
+ * The queries are densified into a num_topics x Qp fp32 table (Qp = num_queries rounded up to a power of two) that lives in LDS, copied once
+ * per workgroup, while it fits in 64 KiB, else in global memory (route_host.h route_simdocs_table).  isle_hip_simdocs_table_form sets which
+ * home the context asks for: a setting of the context, not an environment variable; LDS where the table does not fit is global all the same.
+ * Both homes give the same bits.
+ * Document shards (world > 1): COLLECTIVE, as isle_hip_topic_top_docs.  ALL RANKS CALL TOGETHER with the same source, measure, num_topics, n,
+ * num_queries (agreed: ISLE_E_COMM otherwise), the same queries and exclude (one agreed 64-bit hash: ISLE_E_COMM otherwise) and their own
+ * doc_base.  A bad row entry or too many pairs on one rank travels as one all-reduced word ahead of the selection: every rank returns
+ * ISLE_E_ARG, the rank that holds the entry names it.  Every rank returns the corpus's lists, bit-identical, the lists one rank holding all
+ * rows returns.  query_rows WITH world > 1 IS REFUSED: the row lives on one rank, and exchanging it is out of scope.
+ * The call changes nothing resident and keeps nothing: a second call returns the same arrays, and isle_hip_get_infer_entries,
+ * isle_hip_infer_text, isle_hip_topic_top_docs and isle_hip_doc_report_text return what they returned before.  Device memory of a call
+ * (derived, not measured): 12 bytes per candidate pair (query, score, document), 8 (rows + 1) bytes of offsets, 4 bytes per row of counts,
+ * the table; every row a candidate of every query is 64 M pairs = 0.77 GB at 1 M rows x 64 queries.  Device time is booked under
+ * ISLE_T_INFER for ISLE_TOPDOCS_INFER and under ISLE_T_POST otherwise.  Measured on one rank at configuration 2 only
+ * (tools/similar_docs_probe.py, profiles/similar_docs_c2.jsonl; the README row); at the one shape where the table's two homes were timed
+ * against each other (64 queries, 200 topics) the global home was the faster one.  NO TIME IS MEASURED on several ranks. */
+#define ISLE_SIM_DOT 0
+#define ISLE_SIM_COSINE 1
+#define ISLE_SIM_BHATTACHARYYA 2
+#define ISLE_SIMDOCS_MAX_QUERIES 64
+#define ISLE_SIMDOCS_TABLE_AUTO 0   /* the rule's own choice */
+#define ISLE_SIMDOCS_TABLE_LDS 1    /* LDS, copied once per workgroup, while the table fits in 64 KiB */
+#define ISLE_SIMDOCS_TABLE_GLOBAL 2 /* global memory */
+int isle_hip_similar_docs(isle_ctx* ctx, int source /* ISLE_TOPDOCS_INFER | _SUMS | _HOST */, int measure, int num_topics, int n, uint64_t doc_base,
+                          uint64_t num_rows, const int64_t* doc_offsets, const uint32_t* topic, const float* value, int num_queries,
+                          const uint64_t* query_rows /* nullable */, const int64_t* q_offsets, const uint32_t* q_topic, const float* q_weight,
+                          const uint32_t* exclude /* nullable: num_queries documents, 0xffffffff = none */, uint32_t* docs, float* scores,
+                          uint32_t* counts, uint64_t* candidates /* nullable */);
+int isle_hip_simdocs_table_form(isle_ctx* ctx, int form);
 /* The avg_doc_sz of the resident count matrix as the context holds it (see above; computed on first use).  world > 1: the corpus value
  * over all ranks' documents, collective where it has to be computed (see isle_hip_infer_resident).  ISLE_E_ARG: no count matrix, out null. */
 int isle_hip_avg_doc_sz(isle_ctx* ctx, float* out);

@@ -11,6 +11,7 @@
 #include "api_internal.h"
 #include "stage_host.h"
 #include "topdocs_host.h"
+#include "simdocs_host.h"
 #include "vocab_host.h"
 #include "docs_host.h"
 #include "match_host.h"
@@ -1524,10 +1525,94 @@ extern "C" int isle_hip_doc_report_text(isle_ctx* c, int what, uint64_t doc_begi
   return k_doc_report_text(c, what, doc_begin, doc_end, sink, user, nbytes, nlines);
 }
 
+// The selection of topic_docs.hip on a CSR of (topic, value) by row, with the collectives between its steps: the counts' all-reduce with the
+// word that says whether any rank found a bad entry, the eight rounds with the bins' all-reduce, the collect, the all-gather, the replicated
+// sort and the lists on the host.  name: the call's, for the messages.  isle_hip_topic_top_docs runs it on its source, isle_hip_similar_docs
+// on the (query, score) pairs of similar_docs.hip, the query in the place of the topic.
+static int td_select(isle_ctx* c, const TdView& v, const char* name, uint32_t* docs, float* values, uint32_t* counts, uint64_t* topic_entries) {
+  const size_t T = (size_t)v.num_topics, W = (size_t)c->world, n = (size_t)v.n;
+  const uint64_t rows = v.rows, nnz = v.nnz;
+  DevBuf<uint32_t> doc, rem, fill, bins, out_docs, out_counts;
+  DevBuf<float> out_values;
+  DevBuf<uint64_t> cnt, prefix, tables, err;
+  StreamDrain drain(c);
+  HIPCHK(c, doc.reserve(nnz ? nnz : 1));
+  HIPCHK(c, cnt.reserve(T + 1));
+  HIPCHK(c, err.reserve(1));
+  HIPCHK(c, prefix.reserve(T));
+  HIPCHK(c, rem.reserve(T));
+  HIPCHK(c, fill.reserve(T));
+  HIPCHK(c, bins.reserve(T * 256));
+  HIPCHK(c, tables.reserve((W + 1) * T * n));
+  HIPCHK(c, out_docs.reserve(T * n));
+  HIPCHK(c, out_values.reserve(T * n));
+  HIPCHK(c, out_counts.reserve(T));
+  // the documents, this rank's counts, the form of the rows; the counts of the corpus travel with the number of ranks that refuse
+  uint64_t bad = ~0ull;
+  ISLECHK(k_td_docs(c, v, doc.p, cnt.p, err.p, &bad));
+  const uint64_t refuses = bad != ~0ull;
+  HIPCHK(c, hipMemcpy(cnt.p + T, &refuses, sizeof(uint64_t), hipMemcpyHostToDevice));
+  ISLECHK(allreduce_sum<uint64_t>(c, cnt.p, T + 1));
+  std::vector<uint64_t> cnt_host(T + 1);
+  HIPCHK(c, hipMemcpyAsync(cnt_host.data(), cnt.p, (T + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (refuses) {
+    const uint64_t e = bad >> 2;
+    std::vector<int64_t> off(rows + 1);
+    uint32_t tp = 0;
+    HIPCHK(c, hipMemcpy(off.data(), v.off, (rows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&tp, v.topic + e, sizeof(tp), hipMemcpyDeviceToHost));
+    const uint64_t row = (uint64_t)(std::upper_bound(off.begin(), off.end(), (int64_t)e) - off.begin()) - 1;
+    return isle_fail(c, ISLE_E_ARG, "%s", topdocs_fault_text((unsigned)(bad & 3), e, row, tp, v.num_topics).c_str());
+  }
+  if (cnt_host[T]) return isle_fail(c, ISLE_E_ARG, "%s: another rank refused its entries (a topic >= num_topics, or topics that do not ascend in a row)", name);
+  const uint64_t cnt_end = c->multi() ? (1ull << 31) : (1ull << 32);  // the bins are u32; the host-staged transport sums signed words
+  for (size_t t = 0; t < T; ++t)
+    if (cnt_host[t] >= cnt_end)
+      return isle_fail(c, ISLE_E_ARG, "%s: topic %zu has %llu entries, 2^%d or more", name, t, (unsigned long long)cnt_host[t], c->multi() ? 31 : 32);
+  // eight rounds, most significant byte first: every rank steps to the same smallest selected key from the same integers
+  ISLECHK(k_td_init(c, v, cnt.p, prefix.p, rem.p));
+  for (int shift = 56; shift >= 0; shift -= 8) {
+    ISLECHK(k_td_hist(c, v, doc.p, prefix.p, shift, bins.p));
+    ISLECHK(allreduce_sum<uint32_t>(c, bins.p, T * 256));
+    ISLECHK(k_td_step(c, v, bins.p, cnt.p, shift, prefix.p, rem.p));
+  }
+  // each rank's winners, the tables side by side, the sort replicated
+  uint64_t* const mine = c->multi() ? tables.p + W * T * n : tables.p;
+  ISLECHK(k_td_collect(c, v, doc.p, prefix.p, fill.p, mine));
+  if (c->multi()) {
+    TimeScope ts(c, ISLE_T_COMM);
+    ISLECHK(isle_allgather(c, mine, tables.p, T * n, ISLE_DT_U64));
+  }
+  ISLECHK(k_td_sort(c, v, tables.p, c->multi() ? (uint32_t)W : 1u, cnt.p, out_docs.p, out_values.p, out_counts.p));
+  HIPCHK(c, hipMemcpyAsync(docs, out_docs.p, T * n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(values, out_values.p, T * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(counts, out_counts.p, T * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (topic_entries) std::copy(cnt_host.begin(), cnt_host.begin() + T, topic_entries);
+  return 0;
+}
+
+// the caller's CSR on the device for the call (rows may be 0: one offset)
+static int td_upload(isle_ctx* c, uint64_t rows, uint64_t nnz, const int64_t* doc_offsets, const uint32_t* topic, const float* value, DevBuf<int64_t>& up_off,
+                     DevBuf<uint32_t>& up_topic, DevBuf<float>& up_value, TdView* v) {
+  const int64_t zero = 0;
+  HIPCHK(c, up_off.reserve(rows + 1));
+  HIPCHK(c, up_topic.reserve(nnz ? nnz : 1));
+  HIPCHK(c, up_value.reserve(nnz ? nnz : 1));
+  HIPCHK(c, hipMemcpy(up_off.p, rows ? doc_offsets : &zero, (rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  if (nnz) HIPCHK(c, hipMemcpy(up_topic.p, topic, nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (nnz) HIPCHK(c, hipMemcpy(up_value.p, value, nnz * sizeof(float), hipMemcpyHostToDevice));
+  v->off = up_off.p;
+  v->topic = up_topic.p;
+  v->value = up_value.p;
+  return 0;
+}
+
 // The n heaviest documents of every topic (topic_docs.hip; the rule: topdocs_host.h), selected on entries that lie by document.  Several
 // ranks: collective — the control values are agreed, the counts (with a word that says whether any rank found a bad entry) and the bins of
-// every round are all-reduced, the ranks' tables of winners all-gathered and sorted replicated.  Every rank takes every step, a rank
-// without rows or without entries included.  Nothing resident is written.
+// every round are all-reduced, the ranks' tables of winners all-gathered and sorted replicated (td_select).  Every rank takes every step, a
+// rank without rows or without entries included.  Nothing resident is written.
 extern "C" int isle_hip_topic_top_docs(isle_ctx* c, int source, int num_topics, int n, uint64_t doc_base, uint64_t num_rows, const int64_t* doc_offsets,
                                        const uint32_t* topic, const float* value, uint32_t* docs, float* values, uint32_t* counts, uint64_t* topic_entries) {
   if (!c) return ISLE_E_ARG;
@@ -1550,11 +1635,9 @@ extern "C" int isle_hip_topic_top_docs(isle_ctx* c, int source, int num_topics, 
     nnz = (uint64_t)doc_offsets[rows];
     if (nnz && (!topic || !value)) return isle_fail(c, ISLE_E_ARG, "topic_top_docs: null topic / value with %llu entries", (unsigned long long)nnz);
   }
-  const size_t T = (size_t)num_topics, W = (size_t)c->world;
   DevBuf<int64_t> up_off;
-  DevBuf<uint32_t> up_topic, doc, rem, fill, bins, out_docs, out_counts;
-  DevBuf<float> up_value, out_values;
-  DevBuf<uint64_t> cnt, prefix, tables, err;
+  DevBuf<uint32_t> up_topic;
+  DevBuf<float> up_value;
   StreamDrain drain(c);
   if (c->multi()) {  // (every local refusal lies before this line)
     ISLECHK(agree_i32(c, source, "topic_top_docs: source"));
@@ -1563,73 +1646,147 @@ extern "C" int isle_hip_topic_top_docs(isle_ctx* c, int source, int num_topics, 
   }
   TdView v = {infer ? c->inf_off.p : c->p_dts_off.p, infer ? c->inf_topic.p : c->p_dts_topic.p, infer ? c->inf_weight.p : c->p_dts_val.p,
               rows,  nnz, doc_base, (uint32_t)num_topics, (uint32_t)n, infer ? ISLE_T_INFER : ISLE_T_POST};
-  if (source == ISLE_TOPDOCS_HOST) {
-    const int64_t zero = 0;
-    HIPCHK(c, up_off.reserve(rows + 1));
-    HIPCHK(c, up_topic.reserve(nnz ? nnz : 1));
-    HIPCHK(c, up_value.reserve(nnz ? nnz : 1));
-    HIPCHK(c, hipMemcpy(up_off.p, rows ? doc_offsets : &zero, (rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (nnz) HIPCHK(c, hipMemcpy(up_topic.p, topic, nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (nnz) HIPCHK(c, hipMemcpy(up_value.p, value, nnz * sizeof(float), hipMemcpyHostToDevice));
-    v.off = up_off.p;
-    v.topic = up_topic.p;
-    v.value = up_value.p;
+  if (source == ISLE_TOPDOCS_HOST) ISLECHK(td_upload(c, rows, nnz, doc_offsets, topic, value, up_off, up_topic, up_value, &v));
+  return td_select(c, v, "topic_top_docs", docs, values, counts, topic_entries);
+}
+
+// The context's home of the query table of isle_hip_similar_docs (route_host.h, route_simdocs_table): a setting, not an environment switch.
+extern "C" int isle_hip_simdocs_table_form(isle_ctx* c, int form) {
+  if (!c) return ISLE_E_ARG;
+  const std::string why = simdocs_check_form(form);
+  if (!why.empty()) return isle_fail(c, ISLE_E_ARG, "%s", why.c_str());
+  c->simdocs_table_form = form;
+  return 0;
+}
+
+// The n documents most similar to each query (similar_docs.hip; the rule: simdocs_host.h): the queries densified into a table, every row
+// scored against every query it shares a stored topic with, the (query, score) pairs written as a CSR by row, and td_select on that CSR with
+// the query in the place of the topic.  Several ranks: collective — the control values and a hash of the queries are agreed, one word says
+// whether any rank refuses its rows, then td_select's collectives.  Nothing resident is written.
+extern "C" int isle_hip_similar_docs(isle_ctx* c, int source, int measure, int num_topics, int n, uint64_t doc_base, uint64_t num_rows,
+                                     const int64_t* doc_offsets, const uint32_t* topic, const float* value, int num_queries, const uint64_t* query_rows,
+                                     const int64_t* q_offsets, const uint32_t* q_topic, const float* q_weight, const uint32_t* exclude, uint32_t* docs,
+                                     float* scores, uint32_t* counts, uint64_t* candidates) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  const bool infer = source == ISLE_TOPDOCS_INFER, sums = source == ISLE_TOPDOCS_SUMS;
+  if (infer && !c->res.inf_valid)
+    return isle_fail(c, ISLE_E_ARG, "similar_docs: no resident result (run isle_hip_infer_resident; a new count matrix voids it)");
+  if (sums && !c->res.p_model_ready) return isle_fail(c, ISLE_E_ARG, "similar_docs: run isle_hip_topic_model first (a new count matrix voids its result)");
+  const uint64_t rows = infer ? c->inf_docs : (sums ? c->a_D : num_rows);
+  const std::string why = simdocs_check_args(source, measure, num_topics, n, num_queries, c->world, doc_base, rows);
+  if (!why.empty()) return isle_fail(c, ISLE_E_ARG, "%s", why.c_str());
+  if (sums && num_topics != c->res.p_k)
+    return isle_fail(c, ISLE_E_ARG, "similar_docs: num_topics = %d, the resident topic model has %d topics", num_topics, c->res.p_k);
+  if (infer && num_topics != c->inf_cols)
+    return isle_fail(c, ISLE_E_ARG, "similar_docs: num_topics = %d, the resident inference result has %d topics", num_topics, c->inf_cols);
+  if (!docs || !scores || !counts) return isle_fail(c, ISLE_E_ARG, "similar_docs: null docs / scores / counts");
+  uint64_t nnz = infer ? c->inf_n : (sums ? c->p_dts_n : 0);
+  if (source == ISLE_TOPDOCS_HOST && rows) {
+    if (!doc_offsets) return isle_fail(c, ISLE_E_ARG, "similar_docs: null doc_offsets with %llu rows", (unsigned long long)rows);
+    const std::string bad_off = topdocs_check_offsets(doc_offsets, rows);
+    if (!bad_off.empty()) return isle_fail(c, ISLE_E_ARG, "similar_docs: %s", bad_off.c_str() + sizeof("topic_top_docs: ") - 1);
+    nnz = (uint64_t)doc_offsets[rows];
+    if (nnz && (!topic || !value)) return isle_fail(c, ISLE_E_ARG, "similar_docs: null topic / value with %llu entries", (unsigned long long)nnz);
   }
-  HIPCHK(c, doc.reserve(nnz ? nnz : 1));
-  HIPCHK(c, cnt.reserve(T + 1));
+  const uint32_t Q = (uint32_t)num_queries, Qp = simdocs_qp(Q);
+  uint64_t qnnz = 0;
+  if (query_rows) {
+    if (c->world > 1) return isle_fail(c, ISLE_E_ARG, "similar_docs: query_rows with %d ranks: a row lives on one rank, pass the queries as a CSR", c->world);
+    const std::string bad_rows = simdocs_check_query_rows(query_rows, num_queries, rows);
+    if (!bad_rows.empty()) return isle_fail(c, ISLE_E_ARG, "%s", bad_rows.c_str());
+  } else {
+    if (!q_offsets) return isle_fail(c, ISLE_E_ARG, "similar_docs: null q_offsets and no query_rows");
+    if (q_offsets[0] == 0 && q_offsets[num_queries] > 0 && (!q_topic || !q_weight)) return isle_fail(c, ISLE_E_ARG, "similar_docs: null q_topic / q_weight");
+    const std::string bad_q = simdocs_check_queries(num_queries, (uint32_t)num_topics, q_offsets, q_topic, q_weight);
+    if (!bad_q.empty()) return isle_fail(c, ISLE_E_ARG, "%s", bad_q.c_str());
+    qnnz = (uint64_t)q_offsets[num_queries];
+  }
+  std::vector<uint32_t> ex(Qp, SIMDOCS_NO_DOC);
+  for (uint32_t q = 0; q < Q; ++q) ex[q] = exclude ? exclude[q] : (query_rows ? (uint32_t)(doc_base + query_rows[q]) : SIMDOCS_NO_DOC);
+  DevBuf<int64_t> up_off, dq_off, pair_off, blk;
+  DevBuf<uint32_t> up_topic, dq_topic, d_ex, cnt, qid;
+  DevBuf<float> up_value, dq_weight, table, score;
+  DevBuf<double> nq;
+  DevBuf<uint64_t> d_qrows, err, word;
+  StreamDrain drain(c);
+  if (c->multi()) {  // (every local refusal lies before this line)
+    ISLECHK(agree_i32(c, source, "similar_docs: source"));
+    ISLECHK(agree_i32(c, measure, "similar_docs: measure"));
+    ISLECHK(agree_i32(c, num_topics, "similar_docs: num_topics"));
+    ISLECHK(agree_i32(c, n, "similar_docs: n"));
+    ISLECHK(agree_i32(c, num_queries, "similar_docs: num_queries"));
+    // (query_rows reach this line with a communicator of one rank only: the rows' numbers stand for their entries)
+    const uint64_t h = query_rows ? simdocs_hash_bytes(simdocs_hash_bytes(0xcbf29ce484222325ull, query_rows, (size_t)Q * sizeof(uint64_t)), ex.data(), (size_t)Q * sizeof(uint32_t))
+                                  : simdocs_query_hash(num_queries, q_offsets, q_topic, q_weight, exclude);
+    uint64_t tag[2] = {h, ~h};  // max over (v, ~v): the largest and the complement of the smallest
+    HIPCHK(c, word.reserve(2));
+    ISLECHK(allreduce_host<uint64_t>(c, tag, 2, word.p, true));
+    if (tag[0] != ~tag[1]) return isle_fail(c, ISLE_E_COMM, "similar_docs: ranks disagree on the queries or the excluded documents (a hash of them differs)");
+  }
+  const int fam = infer ? ISLE_T_INFER : ISLE_T_POST;
+  TdView v = {infer ? c->inf_off.p : c->p_dts_off.p, infer ? c->inf_topic.p : c->p_dts_topic.p, infer ? c->inf_weight.p : c->p_dts_val.p,
+              rows,  nnz, doc_base, (uint32_t)num_topics, (uint32_t)n, fam};
+  if (source == ISLE_TOPDOCS_HOST) ISLECHK(td_upload(c, rows, nnz, doc_offsets, topic, value, up_off, up_topic, up_value, &v));
+  // the query CSR on the device: uploaded, or gathered from the source's rows
+  HIPCHK(c, dq_off.reserve((size_t)Q + 1));
+  if (query_rows) {
+    std::vector<int64_t> q_off_host((size_t)Q + 1);
+    HIPCHK(c, d_qrows.reserve(Q));
+    HIPCHK(c, hipMemcpy(d_qrows.p, query_rows, (size_t)Q * sizeof(uint64_t), hipMemcpyHostToDevice));
+    ISLECHK(k_sd_gather_offsets(c, v, d_qrows.p, Q, dq_off.p, q_off_host.data()));
+    qnnz = (uint64_t)q_off_host[Q];
+    HIPCHK(c, dq_topic.reserve(qnnz ? qnnz : 1));
+    HIPCHK(c, dq_weight.reserve(qnnz ? qnnz : 1));
+    ISLECHK(k_sd_gather(c, v, d_qrows.p, Q, dq_off.p, dq_topic.p, dq_weight.p));
+  } else {
+    HIPCHK(c, dq_topic.reserve(qnnz ? qnnz : 1));
+    HIPCHK(c, dq_weight.reserve(qnnz ? qnnz : 1));
+    HIPCHK(c, hipMemcpy(dq_off.p, q_offsets, ((size_t)Q + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (qnnz) HIPCHK(c, hipMemcpy(dq_topic.p, q_topic, qnnz * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (qnnz) HIPCHK(c, hipMemcpy(dq_weight.p, q_weight, qnnz * sizeof(float), hipMemcpyHostToDevice));
+  }
+  HIPCHK(c, table.reserve((size_t)num_topics * Qp));
+  HIPCHK(c, nq.reserve(Qp));
+  HIPCHK(c, d_ex.reserve(Qp));
+  HIPCHK(c, hipMemcpy(d_ex.p, ex.data(), (size_t)Qp * sizeof(uint32_t), hipMemcpyHostToDevice));
+  ISLECHK(k_sd_table(c, fam, Q, (uint32_t)num_topics, dq_off.p, dq_topic.p, dq_weight.p, table.p, nq.p));
+  // the rows' candidate counts and their form; one word through the ranks says whether any of them refuses
+  const bool lds = route_simdocs_table(num_queries, (uint64_t)num_topics, c->simdocs_table_form) == SIMDOCS_HOME_LDS;
+  HIPCHK(c, cnt.reserve(rows ? rows : 1));
+  HIPCHK(c, pair_off.reserve(rows + 1));
+  HIPCHK(c, blk.reserve(isle_scan_scratch(rows)));
   HIPCHK(c, err.reserve(1));
-  HIPCHK(c, prefix.reserve(T));
-  HIPCHK(c, rem.reserve(T));
-  HIPCHK(c, fill.reserve(T));
-  HIPCHK(c, bins.reserve(T * 256));
-  HIPCHK(c, tables.reserve((W + 1) * T * (size_t)n));
-  HIPCHK(c, out_docs.reserve(T * (size_t)n));
-  HIPCHK(c, out_values.reserve(T * (size_t)n));
-  HIPCHK(c, out_counts.reserve(T));
-  // the documents, this rank's counts, the form of the rows; the counts of the corpus travel with the number of ranks that refuse
-  uint64_t bad = ~0ull;
-  ISLECHK(k_td_docs(c, v, doc.p, cnt.p, err.p, &bad));
-  const uint64_t refuses = bad != ~0ull;
-  HIPCHK(c, hipMemcpy(cnt.p + T, &refuses, sizeof(uint64_t), hipMemcpyHostToDevice));
-  ISLECHK(allreduce_sum<uint64_t>(c, cnt.p, T + 1));
-  std::vector<uint64_t> cnt_host(T + 1);
-  HIPCHK(c, hipMemcpyAsync(cnt_host.data(), cnt.p, (T + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (refuses) {
+  uint64_t bad = ~0ull, pairs = 0;
+  ISLECHK(k_sd_count(c, v, lds, Q, table.p, d_ex.p, cnt.p, pair_off.p, blk.p, err.p, &bad, &pairs));
+  const bool too_many = pairs >= (1ull << 32);
+  uint64_t refusing = (bad != ~0ull || too_many) ? 1 : 0;
+  if (c->multi()) {
+    HIPCHK(c, word.reserve(2));
+    ISLECHK(allreduce_host<uint64_t>(c, &refusing, 1, word.p));
+  }
+  if (bad != ~0ull) {
     const uint64_t e = bad >> 2;
+    const unsigned what = (unsigned)(bad & 3);
     std::vector<int64_t> off(rows + 1);
     uint32_t tp = 0;
+    float w = 0.f;
     HIPCHK(c, hipMemcpy(off.data(), v.off, (rows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(&tp, v.topic + e, sizeof(tp), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&w, v.value + e, sizeof(w), hipMemcpyDeviceToHost));
     const uint64_t row = (uint64_t)(std::upper_bound(off.begin(), off.end(), (int64_t)e) - off.begin()) - 1;
-    return isle_fail(c, ISLE_E_ARG, "%s", topdocs_fault_text((unsigned)(bad & 3), e, row, tp, (uint32_t)num_topics).c_str());
+    if (what == SIMDOCS_BAD_WEIGHT) return isle_fail(c, ISLE_E_ARG, "%s", simdocs_weight_text("row", e, row, w).c_str());
+    return isle_fail(c, ISLE_E_ARG, "similar_docs: %s", topdocs_fault_text(what, e, row, tp, (uint32_t)num_topics).c_str() + sizeof("topic_top_docs: ") - 1);
   }
-  if (cnt_host[T]) return isle_fail(c, ISLE_E_ARG, "topic_top_docs: another rank refused its entries (a topic >= num_topics, or topics that do not ascend in a row)");
-  const uint64_t cnt_end = c->multi() ? (1ull << 31) : (1ull << 32);  // the bins are u32; the host-staged transport sums signed words
-  for (size_t t = 0; t < T; ++t)
-    if (cnt_host[t] >= cnt_end)
-      return isle_fail(c, ISLE_E_ARG, "topic_top_docs: topic %zu has %llu entries, 2^%d or more", t, (unsigned long long)cnt_host[t], c->multi() ? 31 : 32);
-  // eight rounds, most significant byte first: every rank steps to the same smallest selected key from the same integers
-  ISLECHK(k_td_init(c, v, cnt.p, prefix.p, rem.p));
-  for (int shift = 56; shift >= 0; shift -= 8) {
-    ISLECHK(k_td_hist(c, v, doc.p, prefix.p, shift, bins.p));
-    ISLECHK(allreduce_sum<uint32_t>(c, bins.p, T * 256));
-    ISLECHK(k_td_step(c, v, bins.p, cnt.p, shift, prefix.p, rem.p));
-  }
-  // each rank's winners, the tables side by side, the sort replicated
-  uint64_t* const mine = c->multi() ? tables.p + W * T * (size_t)n : tables.p;
-  ISLECHK(k_td_collect(c, v, doc.p, prefix.p, fill.p, mine));
-  if (c->multi()) {
-    TimeScope ts(c, ISLE_T_COMM);
-    ISLECHK(isle_allgather(c, mine, tables.p, T * (size_t)n, ISLE_DT_U64));
-  }
-  ISLECHK(k_td_sort(c, v, tables.p, c->multi() ? (uint32_t)W : 1u, cnt.p, out_docs.p, out_values.p, out_counts.p));
-  HIPCHK(c, hipMemcpyAsync(docs, out_docs.p, T * (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(values, out_values.p, T * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(counts, out_counts.p, T * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (topic_entries) std::copy(cnt_host.begin(), cnt_host.begin() + T, topic_entries);
-  return 0;
+  if (too_many)
+    return isle_fail(c, ISLE_E_ARG, "similar_docs: %llu candidate pairs on this rank, 2^32 or more: ask with fewer queries", (unsigned long long)pairs);
+  if (refusing) return isle_fail(c, ISLE_E_ARG, "similar_docs: another rank refused its rows (a bad weight or topic, or 2^32 candidate pairs or more)");
+  // the pairs' (query, score) by row, and the selection with the query in the place of the topic
+  HIPCHK(c, qid.reserve(pairs ? pairs : 1));
+  HIPCHK(c, score.reserve(pairs ? pairs : 1));
+  ISLECHK(k_sd_score(c, v, measure, lds, Q, table.p, d_ex.p, nq.p, pair_off.p, qid.p, score.p));
+  const TdView sel = {pair_off.p, qid.p, score.p, rows, pairs, doc_base, Q, (uint32_t)n, fam};
+  return td_select(c, sel, "similar_docs", docs, scores, counts, candidates);
 }
 
 extern "C" int isle_hip_avg_doc_sz(isle_ctx* c, float* out) {

@@ -256,6 +256,7 @@ struct isle_ctx {
   int vocab_hist_form = 0;         // isle_hip_vocab_hist_form: what route_vocab_hist is asked with (0: the rule's own choice)
   int doc_hash_form = 0;           // isle_hip_doc_hash_form: what route_doc_hash is asked with (0: the rule's own choice)
   int model_dist_slices = 0;       // isle_hip_model_dist_slices: what route_model_dist_slices is asked with (0: the rule's own choice)
+  int simdocs_table_form = 0;      // isle_hip_simdocs_table_form: what route_simdocs_table is asked with (0: the rule's own choice)
 
   // --- downstream stage (post.hip): catchwords, topic model, edge topics
   DevBuf<float> a_nv;              // normalised values of A
@@ -294,6 +295,7 @@ struct isle_ctx {
   DevBuf<int32_t> inf_top_topic;   // docs x 5, < 0 = no further topic: what isle_hip_infer_text(ISLE_DOCTEXT_TOP) prints
   DevBuf<float> inf_top_weight;
   uint64_t inf_docs = 0, inf_n = 0;
+  int inf_cols = 0;                // the columns of that call's model: the topics of inf_topic
   // the model of the last successful isle_hip_load_model_text (model_load.hip): independent of A, B, the partition and the catchwords
   DevBuf<float> ml_model;          // ml_V x ml_cols col-major
   uint64_t ml_V = 0;
@@ -719,6 +721,21 @@ int k_td_hist(isle_ctx* c, const TdView& v, const uint32_t* doc, const uint64_t*
 int k_td_step(isle_ctx* c, const TdView& v, const uint32_t* bins, const uint64_t* cnt, int shift, uint64_t* prefix, uint32_t* rem);
 int k_td_collect(isle_ctx* c, const TdView& v, const uint32_t* doc, const uint64_t* tau, uint32_t* fill, uint64_t* table);
 int k_td_sort(isle_ctx* c, const TdView& v, const uint64_t* tables, uint32_t world, const uint64_t* cnt, uint32_t* docs, float* values, uint32_t* counts);
+
+// similar_docs.hip: the device steps of isle_hip_similar_docs (the rule: simdocs_host.h) ahead of that selection.  v: the source's rows, its
+// num_topics the table's; lds: the table's home (route_simdocs_table); Qp = simdocs_qp(Q).  Every buffer is the call's, on the device unless
+// named host.  k_sd_gather_offsets / k_sd_gather: the queries are rows qrows_dev of the source -> the query CSR.  k_sd_table: table
+// (num_topics x Qp) and nq (Qp) from the query CSR.  k_sd_count: cnt (rows), pair_off (rows + 1; blk: scan scratch of `rows`), *bad: ~0, or
+// (entry << 2) | what of the first bad entry of a row (1, 2: topdocs_entry_fault; SIMDOCS_BAD_WEIGHT), *pairs: this rank's candidate
+// pairs.  k_sd_score: (query, score) of every pair at pair_off: with pair_off a TdView whose topic is the query.  exclude: Qp documents.
+int k_sd_gather_offsets(isle_ctx* c, const TdView& v, const uint64_t* qrows_dev, uint32_t Q, int64_t* q_off_dev, int64_t* q_off_host);
+int k_sd_gather(isle_ctx* c, const TdView& v, const uint64_t* qrows_dev, uint32_t Q, const int64_t* q_off_dev, uint32_t* q_topic, float* q_weight);
+int k_sd_table(isle_ctx* c, int fam, uint32_t Q, uint32_t num_topics, const int64_t* q_off, const uint32_t* q_topic, const float* q_weight, float* table,
+               double* nq);
+int k_sd_count(isle_ctx* c, const TdView& v, bool lds, uint32_t Q, const float* table, const uint32_t* exclude, uint32_t* cnt, int64_t* pair_off, int64_t* blk,
+               uint64_t* err_dev, uint64_t* bad, uint64_t* pairs);
+int k_sd_score(isle_ctx* c, const TdView& v, int measure, bool lds, uint32_t Q, const float* table, const uint32_t* exclude, const double* nq,
+               const int64_t* pair_off, uint32_t* qid, float* score);
 
 // vocab.hip: the device steps of isle_hip_word_doc_freq / isle_hip_prune_vocab on the resident A (the rule: vocab_host.h).  k_vocab_df: df_dev
 // (a_V words, zeroed there) = this rank's entries per word.  k_vocab_compact: A under remap_dev (a_V words: the new id, or 0xffffffff) out of

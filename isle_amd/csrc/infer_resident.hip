@@ -235,6 +235,7 @@ int k_infer_resident(isle_ctx* c, const float* model_cm_dev, int k, uint64_t doc
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->inf_docs = R;
   c->inf_n = (uint64_t)running;
+  c->inf_cols = k;
   c->res.inference_done();
   if (nconverged) *nconverged = nc;
   if (nentries) *nentries = (uint64_t)running;

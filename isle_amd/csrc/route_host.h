@@ -437,3 +437,23 @@ inline DocHash route_doc_hash(int asked) { return asked == 2 ? DOC_FORM_NARROW :
 // of summation and nothing else: where every sum is exactly representable the bits are the same for every count.  README for what was
 // measured.
 inline uint32_t route_model_dist_slices(uint64_t V, int ka, int kb, int num_cus, int asked = 0) { return mc_slices(V, ka, kb, num_cus, asked); }
+
+// ---- the documents most similar to a query document (api_stages.cpp, similar_docs.hip) -----------------------------------------------------
+// The home of the query table of isle_hip_similar_docs (num_topics x Qp fp32, Qp = Q rounded up to a power of two; simdocs_host.h): LDS,
+// copied once per workgroup, while the table fits in SIMDOCS_LDS_TABLE_BYTES, else global memory (256 KiB at num_topics = 1024, Q = 64: it
+// stays in L2).  64 KiB is TOPDOCS_LDS_BINS_BYTES's budget and reasoning: two workgroups in the 160 KiB of a CU.  Both homes hold the same
+// words and give the same bits.  asked: the context's setting (isle_hip_simdocs_table_form: 0 this rule's choice, 1 LDS, 2 global); LDS
+// where the table does not fit the budget is global all the same.  THE THRESHOLD IS A CHOICE THAT THE ONE MEASUREMENT DOES NOT SUPPORT: at
+// Q = 64, num_topics = 200 (a 51 KiB table, config 2, 1 M rows, cosine, the two homes alternating, medians of 5; tools/similar_docs_probe.py,
+// profiles/similar_docs_c2.jsonl) the GLOBAL home was the faster one, 6.65 ms against 8.68 ms of device time on the 27.3 M catchword sums
+// and 1.04 ms against 1.84 ms on the 1.31 M inference entries.  A 51 KiB table leaves three workgroups of four waves on a compute unit and
+// the LDS launch is capped at two workgroups per unit, where the global form runs eight; whether a smaller table (fewer queries, fewer
+// topics) turns the order round, and whether the LDS form with larger workgroups catches up, IS NOT MEASURED.  The rule stays as stated.
+enum SimdocsTable { SIMDOCS_HOME_LDS = 0, SIMDOCS_HOME_GLOBAL = 1 };
+constexpr uint64_t SIMDOCS_LDS_TABLE_BYTES = 64 * 1024;
+inline SimdocsTable route_simdocs_table(int Q, uint64_t num_topics, int asked) {
+  uint64_t qp = 1;
+  while (qp < (uint64_t)Q) qp <<= 1;
+  if (asked == 2) return SIMDOCS_HOME_GLOBAL;
+  return num_topics * qp * 4 <= SIMDOCS_LDS_TABLE_BYTES ? SIMDOCS_HOME_LDS : SIMDOCS_HOME_GLOBAL;
+}

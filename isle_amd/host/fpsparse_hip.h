@@ -577,6 +577,21 @@ class FPSparseMatrixHip {
     check(isle_hip_topic_top_docs(ctx_, source, (int)num_topics, n, doc_base, 0, nullptr, nullptr, nullptr, docs.data(), values.data(), counts.data(),
                                   entries ? entries->data() : nullptr), "topic_top_docs");
   }
+  // The n documents most similar to each query row of a resident source, scored and selected on the device (isle_hip_similar_docs; the
+  // rule: isle_amd/csrc/simdocs_host.h): source ISLE_TOPDOCS_SUMS or ISLE_TOPDOCS_INFER as topic_top_docs, measure ISLE_SIM_*, the queries
+  // rows query_rows of the source (a query's own document is not its neighbour).  docs / scores query_rows.size() x n query-major, the
+  // unused slots 0xffffffff / 0.0f; counts[q] = min(n, the query's candidates); candidates (nullable): the candidate counts.
+  void similar_documents(const int source, const int measure, const doc_id_t num_topics, const int n, const uint64_t doc_base,
+                         const std::vector<uint64_t>& query_rows, std::vector<uint32_t>& docs, std::vector<FPTYPE>& scores, std::vector<uint32_t>& counts,
+                         std::vector<uint64_t>* candidates = nullptr) {
+    const size_t Q = query_rows.size();
+    docs.assign(Q * (size_t)n, 0);
+    scores.assign(Q * (size_t)n, 0.0f);
+    counts.assign(Q, 0);
+    if (candidates) candidates->assign(Q, 0);
+    check(isle_hip_similar_docs(ctx_, source, measure, (int)num_topics, n, doc_base, 0, nullptr, nullptr, nullptr, (int)Q, query_rows.data(), nullptr, nullptr,
+                                nullptr, nullptr, docs.data(), scores.data(), counts.data(), candidates ? candidates->data() : nullptr), "similar_docs");
+  }
   // Two models compared on the device (isle_hip_compare_models; the rule: isle_amd/csrc/match_host.h): dist (cols_a x cols_b row-major) =
   // the L1 distances of their topics in double, and the greedy matching of the topics by it: match_a[i] = the matched topic of b or -1,
   // match_b the inverse, match_dist[i] = the matched distance or NaN, mean_dist over the n_matched pairs.  A side is a resident model

@@ -986,6 +986,33 @@ class ISLETrainer {
     std::fclose(f);
     log->next_time_secs("Writing the heaviest documents of every topic");
   }
+  // "Which documents are like this one": for every document of query_docs (at most ISLE_SIMDOCS_MAX_QUERIES) its n most similar documents
+  // by the resident catchword sums, scored (measure: ISLE_SIM_*) and selected on the device (FPSparseMatrixHip::similar_documents ->
+  // isle_hip_similar_docs); a document is not its own neighbour.  Call it when the topic model exists (after train()).  SimilarDocs.tsv: for
+  // each query in the order given and each neighbour in list order (the higher score first, the smaller document among bit-equal scores)
+  // one line "<query doc + 1>\t<doc + 1>\t<score>\n" as isle_hip_doc_line_text prints it.  The reference has no such file; not part of
+  // what ISLETrain writes by default.
+  void output_similar_docs(const std::vector<doc_id_t>& query_docs, const int n = 10, const int measure = ISLE_SIM_COSINE) {
+    if (!is_training_complete) throw std::runtime_error("output_similar_docs() before train()");
+    std::vector<uint32_t> docs, counts;
+    std::vector<FPTYPE> scores;
+    const std::vector<uint64_t> rows(query_docs.begin(), query_docs.end());
+    B_fl_CSC->similar_documents(ISLE_TOPDOCS_SUMS, measure, num_topics, n, 0, rows, docs, scores, counts);
+    FILE* f = std::fopen((log_dir + "/SimilarDocs.tsv").c_str(), "wb");
+    if (!f) throw std::runtime_error("cannot write " + log_dir + "/SimilarDocs.tsv");
+    char text[40];
+    for (size_t q = 0; q < rows.size(); ++q)
+      for (uint32_t i = 0; i < counts[q]; ++i) {
+        const int len = isle_hip_doc_line_text(rows[q] + 1, (uint64_t)docs[q * (size_t)n + i] + 1, scores[q * (size_t)n + i], text);
+        if (len < 0) {
+          std::fclose(f);
+          throw std::runtime_error("output_similar_docs: a score outside the domain of the line text");
+        }
+        std::fwrite(text, 1, (size_t)len, f);
+      }
+    std::fclose(f);
+    log->next_time_secs("Writing the most similar documents of the query documents");
+  }
   // "Is this model the same as that one": the model file model_file (format ISLE_TEXT_SPARSE / ISLE_TEXT_DENSE, vocab_size x num_topics, as
   // write_model_to_file writes it) is read on the device into the resident loaded model (FPSparseMatrixHip::load_model_file) and this
   // run's catch model (side a) is compared with it (side b): the L1 distances of all topic pairs in double and the greedy matching by

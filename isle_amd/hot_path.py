@@ -1303,6 +1303,70 @@ class HotPath:
                                                     _p(entries)))
         return dict(docs=docs, values=values, counts=counts, topic_entries=entries)
 
+    # ---- the documents most similar to a query document, scored and selected on the device (include/isle_hip.h, isle_hip_similar_docs) ----
+    _SIM = {"dot": 0, "cosine": 1, "bhattacharyya": 2}
+
+    def simdocs_table_form(self, form="auto"):
+        """The home of similar_docs' query table: "auto" (LDS while the table fits in 64 KiB, else global memory), "lds", "global".  A
+        setting of the context; both homes give the same bits ("lds" where the table does not fit is global all the same)."""
+        self._chk(self._lib.isle_hip_simdocs_table_form(self._h, {"auto": 0, "lds": 1, "global": 2}.get(form, form)))
+
+    def similar_docs(self, queries, n, source="infer", measure="cosine", num_topics=None, doc_base=0, exclude=None):
+        """The n (1 .. 256) documents most similar to each of 1 .. 64 queries, over sparse topic weights stored by document: source as
+        topic_top_docs ("infer", "sums" or a CSR (doc_offsets, topic, weight)); the document of a row is doc_base + row.  queries: an
+        integer array of rows of the source (gathered on the device; a query's own document is excluded unless exclude is given), or a
+        CSR (q_offsets (Q + 1,), q_topic, q_weight), topics ascending strictly within a query.  measure "dot", "cosine" or
+        "bhattacharyya" (include/isle_hip.h states the arithmetic; device and host agree bit for bit).  A row is a candidate of a query
+        when they STORE a common topic, whatever the weights; exclude: per query a document that is no candidate (0xffffffff: none).
+        The higher score comes first, the smaller document among bit-equal scores.  Weights are finite, >= 0 and < 2^31.
+        Under comm_init / comm_init_host the call is COLLECTIVE as topic_top_docs: the same queries (a CSR: rows are refused) on every
+        rank, each rank its own doc_base; every rank gets the corpus's lists.
+        -> dict(docs uint32 (Q, n), scores float32 (Q, n), counts uint32 (Q,) = min(n, candidates), candidates uint64 (Q,)); the unused
+        slots hold 0xffffffff / 0.0."""
+        off = tp = va = None
+        rows = 0
+        if isinstance(source, str):
+            kind = self._TOPDOCS[source]
+            if num_topics is None:
+                num_topics = getattr(self, "_post_k", 0) if source == "sums" else getattr(self, "_inf_cols", 0)
+        else:
+            kind = 2
+            off = np.ascontiguousarray(source[0], np.int64)
+            tp = _as_u32(source[1], "topic")
+            va = np.ascontiguousarray(source[2], np.float32)
+            if off.ndim != 1 or off.size < 1 or va.ndim != 1 or tp.size != va.size or (off.size > 1 and int(off[-1]) != tp.size):
+                raise ValueError("source: (doc_offsets (rows + 1,), topic, weight) with doc_offsets[-1] entries")
+            rows = off.size - 1
+        qrows = qo = qt = qw = None
+        if isinstance(queries, (tuple, list)) and len(queries) == 3 and np.ndim(queries[0]) >= 1:
+            qo = np.ascontiguousarray(queries[0], np.int64)
+            qt = _as_u32(queries[1], "q_topic")
+            qw = np.ascontiguousarray(queries[2], np.float32)
+            if qo.ndim != 1 or qo.size < 1 or qw.ndim != 1 or qt.size != qw.size:
+                raise ValueError("queries: rows, or (q_offsets (Q + 1,), q_topic, q_weight)")
+            Q = qo.size - 1
+            if num_topics is None:
+                num_topics = max(int(tp.max()) + 1 if tp is not None and tp.size else 1, int(qt.max()) + 1 if qt.size else 1)
+        else:
+            qrows = np.ascontiguousarray(queries, np.uint64).reshape(-1)
+            Q = qrows.size
+            if num_topics is None:
+                num_topics = int(tp.max()) + 1 if tp is not None and tp.size else 1
+        ex = None
+        if exclude is not None:
+            ex = np.ascontiguousarray(exclude, np.uint32).reshape(-1)
+            if ex.size != Q:
+                raise ValueError("exclude: one document per query")
+        n = int(n)
+        shape = (max(Q, 0), max(n, 0))
+        docs = np.empty(shape, np.uint32)
+        scores = np.empty(shape, np.float32)
+        counts = np.empty(shape[0], np.uint32)
+        cand = np.empty(shape[0], np.uint64)
+        self._chk(self._lib.isle_hip_similar_docs(self._h, kind, self._SIM.get(measure, measure), int(num_topics), n, int(doc_base), rows, _p(off), _p(tp),
+                                                  _p(va), Q, _p(qrows), _p(qo), _p(qt), _p(qw), _p(ex), _p(docs), _p(scores), _p(counts), _p(cand)))
+        return dict(docs=docs, scores=scores, counts=counts, candidates=cand)
+
     def timing_enable(self, on=True):
         """0 / False: off; 1 / True: events around every launch; 2: around the Gram-apply launches only."""
         self._chk(self._lib.isle_hip_timing_enable(self._h, int(on)))
