@@ -993,6 +993,55 @@ int isle_hip_timing_reset(isle_ctx* ctx);
 int isle_hip_timing_get(isle_ctx* ctx, double* ms, uint64_t* launches);
 int isle_hip_synchronize(isle_ctx* ctx);
 
+/* ---- near-duplicate documents found and pruned by MinHash, on the resident count matrix (isle_amd/csrc/near_dups.hip) ----------------------
+ * Documents that differ only in a date, a signature or a boilerplate sentence do to the trainer what exact copies do; exact equality
+ * (isle_hip_prune_docs) does not see them.  The standard answer, on the device: MinHash signatures over a document's word set, banding
+ * to find candidate pairs, an exact Jaccard test on the candidates.  The rule is stated once, in isle_amd/csrc/neardup_host.h; every
+ * quantity is an integer.  For a local document d:
+ *   S_d          the rows of its entries (counts are ignored), n_d their number
+ *   similar      inter den >= num uni in 64-bit integers, inter = |S_a & S_b|, uni = n_a + n_b - inter; the threshold is the rational
+ *                num/den, 1 <= num <= den <= 65535.  Two empty documents are similar, an empty and a non-empty one never.
+ *   sig[d][i]    the minimum over w in S_d of mix(((i + 1) << 32) | w), i < H = bands rows_per_band (mix: docs_host.h docs_mix); all ones
+ *                for an empty document.  1 <= bands <= 64, 1 <= rows_per_band <= 8, H <= 128.
+ *   key[b][d]    k = 0; k = mix(k ^ sig[d][b rows_per_band + j]) for j = 0 .. rows_per_band - 1
+ *   resolution   parent[d] = d.  Band by band, in order: the live documents (parent[d] == d) are grouped by key[b]; inside a group, in
+ *                ascending document order, the first document is a leader, every later one is tested against the group's leaders in the
+ *                order they became leaders and takes the first similar one as its parent, or becomes a leader itself.
+ *   parent[d]    the verified neighbour: parent[d] < d and similar(d, parent[d]) where d was attached, d itself otherwise
+ *   first_of[d]  the root of the parent chain; kept <=> first_of[d] == d; n_dropped: the documents not kept
+ *   pairs_tested the (document, leader) tests made; rounds: the largest number of leaders in a group, summed over the bands
+ *   new A        the kept documents' columns in ascending old id, entries in order, counts bit for bit; kept_docs[new] = doc_offset + old
+ * Documents with the same word set always share first_of; with num == den the partition is exactly "equal word sets".
+ * isle_hip_neardup_key_form: ISLE_NEARDUP_KEY_NARROW cuts the band keys to their 2 low bits, so that every group holds many dissimilar
+ * documents (for the tests); it decides which pairs become candidates, so first_of may differ between the forms where num < den: each
+ * form answers as the rule states for that form.  A setting of the context, not an environment variable.
+ * isle_hip_doc_signatures: sig (docs x H row-major, nullable) and the band keys, not cut (bands x docs band-major, nullable).
+ * isle_hip_doc_jaccard: inter and uni (each nullable) of the caller's n_pairs pairs (a[i], b[i]) of local documents; a[i] == b[i] is
+ * allowed; a document >= the local document count is refused, the first such pair named.
+ * isle_hip_doc_near_duplicates: parent, first_of (the local document count each) and the three counters; each output nullable.
+ * None of the three changes anything resident.
+ * isle_hip_prune_near_docs: the documents not kept leave A.  new_docs and nnz are this rank's afterwards, kept_docs has room for the old
+ * document count (new_docs written), parent and first_of are the old documents'; docs_global the corpus's document count afterwards.
+ * Each output is nullable.  For everything resident the call is an ingest of the pruned matrix, as isle_hip_prune_docs is: B is the old
+ * A's until isle_hip_threshold runs again.  Roots stay, so some document is always kept.
+ * ISLE_E_ARG, decided before anything is launched or rewritten (A and everything resident stay exactly as they were; the texts:
+ * neardup_host.h): no count matrix; num, den, bands or rows_per_band out of range; world > 1, before any collective (similarity across
+ * ranks needs the contents exchanged: out of scope).
+ * On the device: a wave per document, lane i owns hash function i; the band keys are folded inside the wave and stored band-major; per
+ * band the live documents are sorted by key (stable) and resolved in rounds against their run's current leader: the length filter, then
+ * the shorter document's rows searched in the longer one's; pointer jumping gives the roots; isle_hip_prune_docs's compaction builds the
+ * new A.  Beyond A the call holds 8 bands docs bytes of keys and the sort's twin buffers.  Device time is booked under ISLE_T_INGEST. */
+#define ISLE_NEARDUP_KEY_AUTO 0
+#define ISLE_NEARDUP_KEY_FULL 1   /* the band's 64-bit key */
+#define ISLE_NEARDUP_KEY_NARROW 2 /* the same key cut to its 2 low bits: every group holds many dissimilar documents; for the tests */
+int isle_hip_neardup_key_form(isle_ctx* ctx, int form);
+int isle_hip_doc_signatures(isle_ctx* ctx, int bands, int rows_per_band, uint64_t* sig, uint64_t* keys);
+int isle_hip_doc_jaccard(isle_ctx* ctx, uint64_t n_pairs, const uint32_t* a, const uint32_t* b, uint32_t* inter, uint32_t* uni);
+int isle_hip_doc_near_duplicates(isle_ctx* ctx, uint64_t num, uint64_t den, int bands, int rows_per_band, uint32_t* parent, uint32_t* first_of,
+                                 uint64_t* n_dropped, uint64_t* pairs_tested, uint64_t* rounds);
+int isle_hip_prune_near_docs(isle_ctx* ctx, uint64_t num, uint64_t den, int bands, int rows_per_band, uint64_t* new_docs, uint32_t* kept_docs,
+                             uint32_t* parent, uint32_t* first_of, uint64_t* nnz, uint64_t* docs_global, uint64_t* n_dropped);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,6 +77,11 @@ SYMBOLS = {
     "isle_hip_doc_lengths": (_I, [_P, _P, _P]),
     "isle_hip_doc_duplicates": (_I, [_P, _P, _P]),
     "isle_hip_prune_docs": (_I, [_P, _U64, _U64, _U64, _U64, _I, _P, _P, _P, _P, _P, _P]),
+    "isle_hip_neardup_key_form": (_I, [_P, _I]),
+    "isle_hip_doc_signatures": (_I, [_P, _I, _I, _P, _P]),
+    "isle_hip_doc_jaccard": (_I, [_P, _U64, _P, _P, _P, _P]),
+    "isle_hip_doc_near_duplicates": (_I, [_P, _U64, _U64, _I, _I, _P, _P, _P, _P, _P]),
+    "isle_hip_prune_near_docs": (_I, [_P, _U64, _U64, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "isle_hip_model_dist_slices": (_I, [_P, _I]),
     "isle_hip_compare_models": (_I, [_P, _I, _P, _I, _I, _P, _I, _U64, _P, _P, _P, _P, _P, _P, _P]),
     "isle_hip_match_topics": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),

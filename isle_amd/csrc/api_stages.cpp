@@ -1798,3 +1798,132 @@ extern "C" int isle_hip_avg_doc_sz(isle_ctx* c, float* out) {
   *out = c->a_avg;
   return 0;
 }
+
+// ---- near-duplicate documents by MinHash (near_dups.hip; the rule: neardup_host.h)
+#include "neardup_host.h"  // (included here, above its only users)
+// what the four calls check before anything is launched: every refusal is a rank's own and comes before any collective (there is none)
+static int nd_args_ok(isle_ctx* c, const char* who, uint64_t num, uint64_t den, int bands, int rows_per_band) {
+  const std::string why = nd_check_args(who, c->res.a_ready, num, den, bands, rows_per_band, c->world);
+  if (!why.empty()) return isle_fail(c, ISLE_E_ARG, "%s", why.c_str());
+  return 0;
+}
+
+extern "C" int isle_hip_neardup_key_form(isle_ctx* c, int form) {
+  if (!c) return ISLE_E_ARG;
+  if (form != ISLE_NEARDUP_KEY_AUTO && form != ISLE_NEARDUP_KEY_FULL && form != ISLE_NEARDUP_KEY_NARROW)
+    return isle_fail(c, ISLE_E_ARG, "neardup_key_form: unknown form %d", form);
+  c->neardup_key_form = form;
+  return 0;
+}
+
+extern "C" int isle_hip_doc_signatures(isle_ctx* c, int bands, int rows_per_band, uint64_t* sig_out, uint64_t* keys_out) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(nd_args_ok(c, "doc_signatures", 1, 1, bands, rows_per_band));
+  const uint64_t D = c->a_D, H = (uint64_t)bands * rows_per_band;
+  DevBuf<uint64_t> sig, keys;
+  StreamDrain drain(c);
+  if (sig_out) HIPCHK(c, sig.reserve(D ? D * H : 1));
+  if (keys_out) HIPCHK(c, keys.reserve(D ? D * bands : 1));
+  ISLECHK(k_nd_signatures(c, bands, rows_per_band, sig_out ? sig.p : nullptr, keys_out ? keys.p : nullptr));
+  if (sig_out && D) HIPCHK(c, hipMemcpyAsync(sig_out, sig.p, D * H * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  if (keys_out && D) HIPCHK(c, hipMemcpyAsync(keys_out, keys.p, D * bands * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+extern "C" int isle_hip_doc_jaccard(isle_ctx* c, uint64_t n_pairs, const uint32_t* a, const uint32_t* b, uint32_t* inter_out, uint32_t* uni_out) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(nd_args_ok(c, "doc_jaccard", 1, 1, 1, 1));
+  if (n_pairs && (!a || !b)) return isle_fail(c, ISLE_E_ARG, "doc_jaccard: null pairs");
+  const uint64_t bad = nd_first_bad_pair(n_pairs, a, b, c->a_D);
+  if (bad < n_pairs) return isle_fail(c, ISLE_E_ARG, "%s", nd_bad_pair(bad, a[bad], b[bad], c->a_D).c_str());
+  if (!n_pairs) return 0;
+  DevBuf<uint32_t> a_dev, b_dev, inter, uni;
+  StreamDrain drain(c);
+  HIPCHK(c, a_dev.reserve(n_pairs));
+  HIPCHK(c, b_dev.reserve(n_pairs));
+  HIPCHK(c, inter.reserve(n_pairs));
+  HIPCHK(c, uni.reserve(n_pairs));
+  HIPCHK(c, hipMemcpyAsync(a_dev.p, a, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b_dev.p, b, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  ISLECHK(k_nd_jaccard(c, n_pairs, a_dev.p, b_dev.p, inter.p, uni.p));
+  if (inter_out) HIPCHK(c, hipMemcpyAsync(inter_out, inter.p, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (uni_out) HIPCHK(c, hipMemcpyAsync(uni_out, uni.p, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// what isle_hip_doc_near_duplicates and isle_hip_prune_near_docs share: the keys, the resolution, the roots and the kept flags
+struct NdFound {
+  DevBuf<uint64_t> keys;
+  DevBuf<uint32_t> parent, first_of, keep;
+  uint64_t kept = 0, pairs_tested = 0, rounds = 0;
+};
+static int nd_find(isle_ctx* c, uint64_t num, uint64_t den, int bands, int rows_per_band, NdFound& f) {
+  const uint64_t D = c->a_D;
+  HIPCHK(c, f.keys.reserve(D ? D * bands : 1));
+  HIPCHK(c, f.parent.reserve(D ? D : 1));
+  HIPCHK(c, f.first_of.reserve(D ? D : 1));
+  HIPCHK(c, f.keep.reserve(D ? D : 1));
+  ISLECHK(k_nd_signatures(c, bands, rows_per_band, nullptr, f.keys.p));
+  return k_nd_resolve(c, route_neardup_key(c->neardup_key_form), num, den, bands, f.keys.p, f.parent.p, f.first_of.p, f.keep.p, &f.kept, &f.pairs_tested, &f.rounds);
+}
+
+extern "C" int isle_hip_doc_near_duplicates(isle_ctx* c, uint64_t num, uint64_t den, int bands, int rows_per_band, uint32_t* parent_out, uint32_t* first_of_out,
+                                            uint64_t* n_dropped, uint64_t* pairs_tested, uint64_t* rounds) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(nd_args_ok(c, "doc_near_duplicates", num, den, bands, rows_per_band));
+  const uint64_t D = c->a_D;
+  NdFound f;
+  StreamDrain drain(c);
+  ISLECHK(nd_find(c, num, den, bands, rows_per_band, f));
+  if (parent_out && D) HIPCHK(c, hipMemcpyAsync(parent_out, f.parent.p, D * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (first_of_out && D) HIPCHK(c, hipMemcpyAsync(first_of_out, f.first_of.p, D * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (n_dropped) *n_dropped = D - f.kept;
+  if (pairs_tested) *pairs_tested = f.pairs_tested;
+  if (rounds) *rounds = f.rounds;
+  return 0;
+}
+
+// For the ledger an ingest of the pruned matrix, as isle_hip_prune_docs: A_rewrite_begins is raised once every refusal is behind and the
+// pruned matrix lies complete in the twin buffers, right before they are swapped in; install_A ends it.
+extern "C" int isle_hip_prune_near_docs(isle_ctx* c, uint64_t num, uint64_t den, int bands, int rows_per_band, uint64_t* new_docs_out, uint32_t* kept_docs_out,
+                                        uint32_t* parent_out, uint32_t* first_of_out, uint64_t* nnz_out, uint64_t* docs_global_out, uint64_t* n_dropped) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(nd_args_ok(c, "prune_near_docs", num, den, bands, rows_per_band));
+  const uint64_t D = c->a_D;
+  NdFound f;
+  DevBuf<uint32_t> words, kept_docs, new_rows;
+  DevBuf<uint64_t> tokens;
+  DevBuf<float> new_cnt;
+  DevBuf<int64_t> new_offs;
+  StreamDrain drain(c);
+  ISLECHK(nd_find(c, num, den, bands, rows_per_band, f));
+  // ---- the pruned matrix out of place: the exact duplicates' compaction with these flags
+  HIPCHK(c, words.reserve(D ? D : 1));
+  HIPCHK(c, tokens.reserve(D ? D : 1));
+  HIPCHK(c, kept_docs.reserve(D ? D : 1));
+  ISLECHK(k_docs_len_hash(c, words.p, tokens.p, nullptr));
+  uint64_t total = 0;
+  ISLECHK(k_docs_compact(c, f.keep.p, words.p, f.kept, new_cnt, new_rows, new_offs, kept_docs.p, &total));
+  if (kept_docs_out && f.kept) HIPCHK(c, hipMemcpyAsync(kept_docs_out, kept_docs.p, f.kept * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (parent_out && D) HIPCHK(c, hipMemcpyAsync(parent_out, f.parent.p, D * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (first_of_out && D) HIPCHK(c, hipMemcpyAsync(first_of_out, f.first_of.p, D * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  // ... and swapped in: the old buffers go with this call
+  c->res.A_rewrite_begins();
+  std::swap(c->a_cnt.p, new_cnt.p), std::swap(c->a_cnt.cap, new_cnt.cap);
+  std::swap(c->a_rows.p, new_rows.p), std::swap(c->a_rows.cap, new_rows.cap);
+  std::swap(c->a_offs.p, new_offs.p), std::swap(c->a_offs.cap, new_offs.cap);
+  c->a_D = f.kept;
+  c->a_nnz = total;
+  if (new_docs_out) *new_docs_out = f.kept;
+  if (docs_global_out) *docs_global_out = f.kept;
+  if (n_dropped) *n_dropped = D - f.kept;
+  return install_A(c, 0, f.kept, total, nullptr, nnz_out);
+}

@@ -255,6 +255,7 @@ struct isle_ctx {
   float a_avg = 0.f;               // avg_doc_sz of the whole corpus (src/sparseMatrix.cpp:98)
   int vocab_hist_form = 0;         // isle_hip_vocab_hist_form: what route_vocab_hist is asked with (0: the rule's own choice)
   int doc_hash_form = 0;           // isle_hip_doc_hash_form: what route_doc_hash is asked with (0: the rule's own choice)
+  int neardup_key_form = 0;        // isle_hip_neardup_key_form: what route_neardup_key is asked with (0: the rule's own choice)
   int model_dist_slices = 0;       // isle_hip_model_dist_slices: what route_model_dist_slices is asked with (0: the rule's own choice)
   int simdocs_table_form = 0;      // isle_hip_simdocs_table_form: what route_simdocs_table is asked with (0: the rule's own choice)
 
@@ -759,6 +760,18 @@ int k_docs_keep(isle_ctx* c, const uint32_t* words, const uint64_t* tokens, cons
                 uint64_t dropped[3], uint64_t* kept);
 int k_docs_compact(isle_ctx* c, const uint32_t* keep, const uint32_t* words, uint64_t new_docs, DevBuf<float>& new_cnt, DevBuf<uint32_t>& new_rows,
                    DevBuf<int64_t>& new_offs, uint32_t* kept_docs, uint64_t* total);
+
+// near_dups.hip: the device steps of isle_hip_doc_signatures / isle_hip_doc_jaccard / isle_hip_doc_near_duplicates /
+// isle_hip_prune_near_docs on the resident A (the rule: neardup_host.h).  Every array is the caller's, on the device.  Nothing resident is
+// written.  Device time: ISLE_T_INGEST.
+// k_nd_signatures: sig (a_D x H row-major, nullable) and the band keys, not cut (bands x a_D band-major, nullable); queued, not drained.
+// k_nd_jaccard: inter and uni of the n_pairs pairs (a[i], b[i]), every id < a_D (the caller has checked); queued, not drained.
+// k_nd_resolve: the resolution across the bands from the keys: parent, first_of and keep (a_D each); *kept, *pairs_tested and *rounds are
+//   on the host when it returns.
+int k_nd_signatures(isle_ctx* c, int bands, int rows_per_band, uint64_t* sig, uint64_t* keys);
+int k_nd_jaccard(isle_ctx* c, uint64_t n_pairs, const uint32_t* a, const uint32_t* b, uint32_t* inter, uint32_t* uni);
+int k_nd_resolve(isle_ctx* c, NdKey form, uint64_t num, uint64_t den, int bands, const uint64_t* keys, uint32_t* parent, uint32_t* first_of, uint32_t* keep,
+                 uint64_t* kept, uint64_t* pairs_tested, uint64_t* rounds);
 
 // model_compare.hip: the device steps of isle_hip_compare_models / isle_hip_match_topics (the rule: match_host.h).  Every array is the
 // caller's, on the device.  Nothing resident is written.  Device time: ISLE_T_POST.

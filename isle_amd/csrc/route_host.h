@@ -457,3 +457,13 @@ inline SimdocsTable route_simdocs_table(int Q, uint64_t num_topics, int asked) {
   if (asked == 2) return SIMDOCS_HOME_GLOBAL;
   return num_topics * qp * 4 <= SIMDOCS_LDS_TABLE_BYTES ? SIMDOCS_HOME_LDS : SIMDOCS_HOME_GLOBAL;
 }
+
+// ---- near-duplicate documents by MinHash (api_stages.cpp, near_dups.hip) ---------------------------------------------------------------------
+// The key the live documents of a band are sorted by before the exact Jaccard test runs inside every run of equal keys (neardup_host.h):
+// the band's 64-bit key, or the same key cut to DOCS_NARROW_BITS bits so that every run holds many dissimilar documents.  Unlike the exact
+// duplicates' hash the form CAN reach the result where num < den: it decides which pairs become candidates, and each form is held to the
+// rule's statement of that form; with num == den both give "equal word sets".  asked: the context's setting (isle_hip_neardup_key_form: 0
+// this rule's choice, 1 full, 2 narrow).  The full key is the choice: it is what banding means, and a run then holds candidates alone;
+// the narrow form exists for the tests.  Not measured: the narrow form at size.
+enum NdKey { ND_FORM_FULL = 0, ND_FORM_NARROW = 1 };
+inline NdKey route_neardup_key(int asked) { return asked == 2 ? ND_FORM_NARROW : ND_FORM_FULL; }

@@ -540,6 +540,66 @@ class FPSparseMatrixHip {
     a_docs_ = (doc_id_t)new_docs;
     top5_ready_ = false;
   }
+  // which key the near-duplicate calls sort a band's documents by: ISLE_NEARDUP_KEY_AUTO / _FULL / _NARROW (isle_hip_neardup_key_form)
+  void neardup_key_form(const int form) { check(isle_hip_neardup_key_form(ctx_, form), "neardup_key_form"); }
+  // MinHash signatures (docs x bands rows_per_band, row-major) and band keys (bands x docs, band-major) of A's documents; each nullable
+  void doc_signatures(const int bands, const int rows_per_band, std::vector<uint64_t>* sig, std::vector<uint64_t>* keys) {
+    if (sig) sig->assign(std::max<size_t>((size_t)a_docs_ * bands * rows_per_band, 1), 0);
+    if (keys) keys->assign(std::max<size_t>((size_t)a_docs_ * bands, 1), 0);
+    check(isle_hip_doc_signatures(ctx_, bands, rows_per_band, sig ? sig->data() : nullptr, keys ? keys->data() : nullptr), "doc_signatures");
+    if (sig) sig->resize((size_t)a_docs_ * bands * rows_per_band);
+    if (keys) keys->resize((size_t)a_docs_ * bands);
+  }
+  // the exact sizes of the intersection and the union of the word sets of A's documents a[i] and b[i]
+  void doc_jaccard(const std::vector<uint32_t>& a, const std::vector<uint32_t>& b, std::vector<uint32_t>& inter, std::vector<uint32_t>& uni) {
+    if (a.size() != b.size()) throw std::runtime_error("doc_jaccard: the two lists differ in length");
+    inter.assign(std::max<size_t>(a.size(), 1), 0);
+    uni.assign(std::max<size_t>(a.size(), 1), 0);
+    check(isle_hip_doc_jaccard(ctx_, a.size(), a.data(), b.data(), inter.data(), uni.data()), "doc_jaccard");
+    inter.resize(a.size());
+    uni.resize(a.size());
+  }
+  // The near duplicates among the documents of the count matrix A, by MinHash banding and an exact Jaccard test on the device
+  // (isle_hip_doc_near_duplicates; the rule: isle_amd/csrc/neardup_host.h): parent[d] the verified earlier neighbour (d where it has
+  // none), first_of[d] the root of the parent chain.  Nothing resident changes.  -> the documents that are not their own root.
+  uint64_t near_duplicates(const uint64_t num, const uint64_t den, const int bands, const int rows_per_band, std::vector<uint32_t>& parent,
+                           std::vector<uint32_t>& first_of, uint64_t* pairs_tested = nullptr, uint64_t* rounds = nullptr) {
+    uint64_t dropped = 0;
+    parent.assign(std::max<size_t>((size_t)a_docs_, 1), 0);
+    first_of.assign(std::max<size_t>((size_t)a_docs_, 1), 0);
+    check(isle_hip_doc_near_duplicates(ctx_, num, den, bands, rows_per_band, parent.data(), first_of.data(), &dropped, pairs_tested, rounds), "doc_near_duplicates");
+    parent.resize((size_t)a_docs_);
+    first_of.resize((size_t)a_docs_);
+    return dropped;
+  }
+  // ... and pruned (isle_hip_prune_near_docs): every document that is not its own root goes; kept_docs[new id] = old id.  For everything
+  // resident an ingest of the pruned A: B is the old A's until threshold_again.  A refusal throws and leaves A as it was.  parent and
+  // first_of are the old documents'; inter and uni (nullable) the exact sizes of every old document with its parent, taken before the prune.
+  void prune_near_duplicates(const uint64_t num, const uint64_t den, const int bands, const int rows_per_band, std::vector<uint32_t>& kept_docs,
+                             std::vector<uint32_t>& parent, std::vector<uint32_t>& first_of, std::vector<uint32_t>* inter = nullptr,
+                             std::vector<uint32_t>* uni = nullptr, uint64_t* entries = nullptr) {
+    const size_t old_docs = (size_t)a_docs_;
+    if (inter || uni) {
+      near_duplicates(num, den, bands, rows_per_band, parent, first_of);
+      std::vector<uint32_t> self(old_docs), in(std::max<size_t>(old_docs, 1)), un(std::max<size_t>(old_docs, 1));
+      for (size_t d = 0; d < old_docs; ++d) self[d] = (uint32_t)d;
+      check(isle_hip_doc_jaccard(ctx_, old_docs, self.data(), parent.data(), in.data(), un.data()), "doc_jaccard");
+      in.resize(old_docs), un.resize(old_docs);
+      if (inter) inter->swap(in);
+      if (uni) uni->swap(un);
+    }
+    uint64_t new_docs = 0;
+    kept_docs.assign(std::max<size_t>(old_docs, 1), 0);
+    parent.assign(std::max<size_t>(old_docs, 1), 0);
+    first_of.assign(std::max<size_t>(old_docs, 1), 0);
+    check(isle_hip_prune_near_docs(ctx_, num, den, bands, rows_per_band, &new_docs, kept_docs.data(), parent.data(), first_of.data(), entries, nullptr, nullptr),
+          "prune_near_docs");
+    kept_docs.resize((size_t)new_docs);
+    parent.resize(old_docs);
+    first_of.resize(old_docs);
+    a_docs_ = (doc_id_t)new_docs;
+    top5_ready_ = false;
+  }
   void doc_lengths(std::vector<uint32_t>& words, std::vector<uint64_t>& tokens) {
     words.assign(std::max<size_t>((size_t)a_docs_, 1), 0);
     tokens.assign(std::max<size_t>((size_t)a_docs_, 1), 0);

@@ -740,6 +740,50 @@ class ISLETrainer {
     log->next_time_secs("Pruning the documents");
   }
 
+  // The near duplicates pruned, on the device (FPSparseMatrixHip::prune_near_duplicates -> isle_hip_prune_near_docs; the rule:
+  // isle_amd/csrc/neardup_host.h): every document whose word set has Jaccard similarity >= num/den with an earlier document that MinHash
+  // banding (bands x rows_per_band) made its candidate goes.  After the data is loaded and before train(), like prune_documents: A is
+  // compacted, B is thresholded again from it, num_docs becomes the kept documents' number and kept_docs stays up to date, so the
+  // per-document reports print the new numbers.  DocsKept.tsv as prune_documents writes it.  NearDuplicates.tsv: one line per dropped
+  // document, doc, parent, first_of, inter, uni: the ids 1-based and the numbers the documents had when the data was loaded, inter and uni
+  // those of (doc, parent), taken before the prune.  Nothing in the CLI calls it.
+  void prune_near_duplicates(const uint64_t num = 4, const uint64_t den = 5, const int bands = 16, const int rows_per_band = 4) {
+    if (!is_data_loaded) throw std::runtime_error("prune_near_duplicates() before the data is loaded");
+    if (is_training_complete) throw std::runtime_error("prune_near_duplicates() after train()");
+    const doc_id_t old_docs = num_docs;
+    const uint64_t old_entries = entries_in_A;
+    std::vector<uint32_t> kept, parent, first_of, inter, uni, words;
+    std::vector<uint64_t> tokens;
+    uint64_t entries = 0;
+    B_fl_CSC->prune_near_duplicates(num, den, bands, rows_per_band, kept, parent, first_of, &inter, &uni, &entries);
+    B_fl_CSC->doc_lengths(words, tokens);  // of the kept documents, in the new numbering
+    const auto loaded = [&](uint32_t d) { return (unsigned long long)(kept_docs.empty() ? d : kept_docs[d]) + 1; };  // a second prune goes through the first one's numbers
+    {
+      FILE* f = std::fopen((log_dir + "/NearDuplicates.tsv").c_str(), "wb");
+      if (!f) throw std::runtime_error("cannot write " + log_dir + "/NearDuplicates.tsv");
+      for (size_t d = 0; d < first_of.size(); ++d)
+        if (first_of[d] != d) std::fprintf(f, "%llu\t%llu\t%llu\t%u\t%u\n", loaded((uint32_t)d), loaded(parent[d]), loaded(first_of[d]), inter[d], uni[d]);
+      std::fclose(f);
+    }
+    if (!kept_docs.empty())
+      for (uint32_t& d : kept) d = kept_docs[d];
+    {
+      FILE* f = std::fopen((log_dir + "/DocsKept.tsv").c_str(), "wb");
+      if (!f) throw std::runtime_error("cannot write " + log_dir + "/DocsKept.tsv");
+      for (size_t d = 0; d < kept.size(); ++d)
+        std::fprintf(f, "%llu\t%llu\t%u\t%llu\n", (unsigned long long)d + 1, (unsigned long long)kept[d] + 1, words[d], (unsigned long long)tokens[d]);
+      std::fclose(f);
+    }
+    kept_docs.swap(kept);
+    num_docs = (doc_id_t)kept_docs.size();
+    entries_in_A = entries;
+    B_fl_CSC->threshold_again(num_topics, flag_sample_docs ? (double)sample_rate : 0.0, original_cols, &entries_above_threshold, &avg_doc_sz);
+    log->print("Near duplicates pruned: kept " + std::to_string(num_docs) + " of " + std::to_string(old_docs) + " at " + std::to_string(num) + "/" + std::to_string(den) +
+               ", " + std::to_string(bands) + " bands of " + std::to_string(rows_per_band) + ", entries kept " + std::to_string(entries) + " dropped " +
+               std::to_string(old_entries - entries) + "\n");
+    log->next_time_secs("Pruning the near duplicates");
+  }
+
   // src/trainer.cpp:776-826
   void output_cluster_summary() {
     if (!is_training_complete) throw std::runtime_error("output_cluster_summary() before train()");

@@ -578,6 +578,79 @@ class HotPath:
         return dict(docs=int(nd.value), kept_docs=kept[:int(nd.value)].copy(), first_of=first[:D].copy(), nnz=int(nz.value), docs_global=int(dg.value),
                     dropped_short=int(dropped[0]), dropped_long=int(dropped[1]), dropped_duplicate=int(dropped[2]))
 
+    # ---- near-duplicate documents by MinHash, on the resident A (include/isle_hip.h, isle_hip_prune_near_docs) -----------------------
+    def neardup_key_form(self, form="auto"):
+        """Which key this context sorts a band's live documents by before the exact Jaccard test: "auto" (the library's rule), "full"
+        (the band's 64-bit key) or "narrow" (the same key cut to 2 bits: every group holds many dissimilar documents; for the tests).
+        The form decides which pairs become candidates: with a threshold below 1 the two may answer differently."""
+        self._chk(self._lib.isle_hip_neardup_key_form(self._h, {"auto": 0, "full": 1, "narrow": 2}[form]))
+
+    @staticmethod
+    def _neardup_threshold(threshold):
+        """a float becomes Fraction(threshold).limit_denominator(1000), a (num, den) tuple is taken as it is -> (num, den)"""
+        if isinstance(threshold, tuple):
+            num, den = threshold
+            return int(num), int(den)
+        from fractions import Fraction
+        f = Fraction(float(threshold)).limit_denominator(1000)
+        return f.numerator, f.denominator
+
+    def doc_signatures(self, bands=16, rows_per_band=4, sig=True, keys=True):
+        """MinHash signatures and band keys of this rank's documents of the resident count matrix: dict(sig uint64 (D, bands *
+        rows_per_band), keys uint64 (bands, D), not cut), each only where asked for.  Nothing resident changes."""
+        D = self._counts_shape()[1]
+        H = int(bands) * int(rows_per_band)
+        ok = 1 <= int(bands) <= 64 and 1 <= int(rows_per_band) <= 8 and H <= 128     # (the library refuses by name; no buffer is sized from a refused shape)
+        s = np.empty((D, H), np.uint64) if sig and ok else None
+        k = np.empty((int(bands), D), np.uint64) if keys and ok else None
+        self._chk(self._lib.isle_hip_doc_signatures(self._h, int(bands), int(rows_per_band), None if s is None else _p(s), None if k is None else _p(k)))
+        out = {}
+        if s is not None:
+            out["sig"] = s
+        if k is not None:
+            out["keys"] = k
+        return out
+
+    def doc_jaccard(self, a, b):
+        """(inter uint32 (n,), uni uint32 (n,)): the exact sizes of the intersection and the union of the word sets of the documents
+        a[i] and b[i] of this rank (a[i] == b[i] allowed).  Nothing resident changes."""
+        a, b = np.ascontiguousarray(a, np.uint32).reshape(-1), np.ascontiguousarray(b, np.uint32).reshape(-1)
+        if a.size != b.size:
+            raise ValueError("doc_jaccard: %d and %d documents" % (a.size, b.size))
+        inter, uni = np.empty(a.size, np.uint32), np.empty(a.size, np.uint32)
+        self._chk(self._lib.isle_hip_doc_jaccard(self._h, a.size, _p(a), _p(b), _p(inter), _p(uni)))
+        return inter, uni
+
+    def near_duplicates(self, threshold=0.8, bands=16, rows_per_band=4):
+        """The documents of the resident count matrix whose word set has Jaccard similarity >= threshold with an earlier document's,
+        found by MinHash banding and verified exactly (isle_hip_doc_near_duplicates states the rule).  threshold: a float (it becomes
+        Fraction(threshold).limit_denominator(1000)) or a (num, den) tuple.  Nothing resident changes.  One rank only.
+        -> dict(parent uint32 (D,): the verified neighbour, the document itself where it has none; first_of uint32 (D,): the root of
+        the parent chain; n_dropped, pairs_tested, rounds, num, den)."""
+        num, den = self._neardup_threshold(threshold)
+        D = self._counts_shape()[1]
+        parent, first = np.empty(D, np.uint32), np.empty(D, np.uint32)
+        nd, pt, rd = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._chk(self._lib.isle_hip_doc_near_duplicates(self._h, num, den, int(bands), int(rows_per_band), _p(parent), _p(first), C.byref(nd), C.byref(pt),
+                                                         C.byref(rd)))
+        return dict(parent=parent, first_of=first, n_dropped=int(nd.value), pairs_tested=int(pt.value), rounds=int(rd.value), num=num, den=den)
+
+    def prune_near_docs(self, threshold=0.8, bands=16, rows_per_band=4):
+        """Drops every document of the resident count matrix A that near_duplicates attaches to an earlier one; the kept documents are
+        renumbered in ascending old id and A is compacted on the device.  For everything resident this is an ingest of the pruned
+        matrix: run threshold() next.  A refusal leaves A as it was.  One rank only.
+        -> dict(docs, kept_docs uint32 (docs,): new id -> old number in the corpus, parent and first_of uint32 (old docs,), nnz,
+        docs_global, n_dropped, num, den)."""
+        num, den = self._neardup_threshold(threshold)
+        D = self._counts_shape()[1]
+        kept, parent, first = np.empty(max(D, 1), np.uint32), np.empty(max(D, 1), np.uint32), np.empty(max(D, 1), np.uint32)
+        nd, nz, dg, gone = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._chk(self._lib.isle_hip_prune_near_docs(self._h, num, den, int(bands), int(rows_per_band), C.byref(nd), _p(kept), _p(parent), _p(first), C.byref(nz),
+                                                     C.byref(dg), C.byref(gone)))
+        self._a_shape = self._counts_shape()[:3]
+        return dict(docs=int(nd.value), kept_docs=kept[:int(nd.value)].copy(), parent=parent[:D].copy(), first_of=first[:D].copy(), nnz=int(nz.value),
+                    docs_global=int(dg.value), n_dropped=int(gone.value), num=num, den=den)
+
     def threshold(self, num_topics, sample_rate=0.0, sample_seed=0):
         """normalize_docs + compute_thresholds + (sampled_)threshold_and_copy on the device
         (src/trainer.cpp:430-485); B becomes this context's matrix.  Returns a dict of scalars."""
