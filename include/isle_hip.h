@@ -841,6 +841,53 @@ int isle_hip_similar_docs(isle_ctx* ctx, int source /* ISLE_TOPDOCS_INFER | _SUM
                           const uint32_t* exclude /* nullable: num_queries documents, 0xffffffff = none */, uint32_t* docs, float* scores,
                           uint32_t* counts, uint64_t* candidates /* nullable */);
 int isle_hip_simdocs_table_form(isle_ctx* ctx, int form);
+/* Topic prevalence by group of documents, summed on the device (isle_amd/csrc/topic_prevalence.hip and api_stages.cpp): how much of the
+ * corpus each topic is, and how that differs between parts of it.  The sources and the row form are isle_hip_topic_top_docs': the resident
+ * inference entries (ISLE_TOPDOCS_INFER), the resident catchword sums (ISLE_TOPDOCS_SUMS), or a CSR doc_offsets / topic / value uploaded
+ * for the call (ISLE_TOPDOCS_HOST), topics ascending strictly within a row; for INFER and SUMS num_rows and the three arrays are ignored.
+ * The rule, stated once as plain C++ in isle_amd/csrc/prevalence_host.h:
+ *   weights  every weight is finite, >= 0 and < 2^31; -0.0 counts as 0 (its term is +0.0)
+ *   labels   groups: one uint32 per row, the caller's, uploaded for the call; NULL: every row has label 0 and num_groups must be 1.
+ *            ISLE_GROUP_NONE: the row belongs to no group; it is counted in *unlabelled and nowhere else.  Any other label >= num_groups
+ *            is refused.
+ *   per row  rs_r = 0.0, then rs_r = rs_r + (double)w over the row's entries in stored order.  The term x_r(t) of a stored topic is
+ *            (double)w, with normalise (double)w / rs_r (one IEEE division; +0.0 where rs_r == 0); +0.0 for a topic the row does not store.
+ *            The dominant topic of a row with entries is the entry with the largest weight, the smaller topic among equal weights
+ *            (-0 = +0); a row without entries has none.
+ *   outputs  for every group g < num_groups and topic t < num_topics, the tables num_groups x num_topics group-major:
+ *            docs[g]        the rows labelled g, rows without entries included
+ *            count[g,t]     the rows of g that store t, whatever the weight
+ *            dominant[g,t]  the rows of g whose dominant topic is t
+ *            sum[g,t]       r_0 < r_1 < .. < r_{n-1} the rows of g: v0_i = x_{r_i}(t), v(j+1)_i = (((0.0 + vj_{64i}) + vj_{64i+1}) + ..
+ *                           + vj_{64i+63}) over the indices that exist, every + one IEEE double addition, until one value is left
+ *                           (at least once); n = 0 gives 0.0.
+ * The radix-64 tree is part of the rule: every level is parallel, and the device and the header's host loop agree bit for bit, on every
+ * call.  Against the exact rational sum, without normalise, the relative error is at most c u / (1 - c u), c = count[g,t], u = 2^-53
+ * (Higham's bound for any order of summation).  The caller forms mean[g,t] = sum[g,t] / (double)docs[g], NaN where docs[g] == 0.
+ * Limits: 1 <= num_topics <= 8192, 1 <= num_groups, num_groups x num_topics <= ISLE_PREVALENCE_MAX_CELLS, fewer than 2^32 rows.
+ * ISLE_E_ARG, decided before any launch: an unknown source, normalise outside {0, 1}, the limits, NULL outputs (unlabelled may be NULL),
+ * groups == NULL with num_groups != 1, the sources' own conditions as isle_hip_topic_top_docs states them, and world > 1, before any
+ * collective: a bit-equal sum across ranks needs the list order exchanged, which is not built.  Found on the device, each naming the first
+ * offender through one 64-bit atomicMin: a bad label (the first such row; reported before a bad entry), and the first entry with a topic
+ * >= num_topics, topics that do not ascend, or a weight outside the domain.  After any refusal the context is usable.  The call changes
+ * nothing resident and keeps nothing.  Device time: ISLE_T_INFER for INFER, ISLE_T_POST otherwise.
+ * The private table of a block's owner holds one tile of topics: 1024 (8 KiB of doubles), or 64 where isle_hip_prevalence_tile_form asks
+ * for the narrow form, which exists so that small tests cross tile edges; topics beyond a tile are taken tile after tile, and both forms
+ * give the same bits.  The form is a setting of the context, not an environment switch.
+ * Device memory of a call, derived, not measured (R rows, E entries, G groups, k topics, w = min(k, tile)): the tables 8 G (1 + 3 k)
+ * bytes; 8 R bytes of row sums with normalise; with labels 28 R bytes of labels and sort pairs and 1.5 R of the sort's histogram (the
+ * context's sort scratch, which stays with the context); the level bases 8 (L + 1) (G + 1), L <= 6; the level-0 partials
+ * (R / 64 + G) w 8 bytes and their parents, a 64th of that, reused per tile; a HOST source adds its upload, 8 (R + 1) + 8 E. */
+#define ISLE_GROUP_NONE 0xffffffffu
+#define ISLE_PREVALENCE_MAX_CELLS (1u << 24)
+#define ISLE_PREVALENCE_TILE_AUTO 0
+#define ISLE_PREVALENCE_TILE_WIDE 1    /* 1024 topics per table */
+#define ISLE_PREVALENCE_TILE_NARROW 2  /* 64 topics per table: for the tests */
+int isle_hip_topic_prevalence(isle_ctx* ctx, int source /* ISLE_TOPDOCS_INFER | _SUMS | _HOST */, int num_topics, uint64_t num_rows,
+                              const int64_t* doc_offsets, const uint32_t* topic, const float* value, const uint32_t* groups /* nullable */,
+                              uint32_t num_groups, int normalise, uint64_t* docs, uint64_t* unlabelled /* nullable */, uint64_t* count,
+                              uint64_t* dominant, double* sum);
+int isle_hip_prevalence_tile_form(isle_ctx* ctx, int form);
 /* The avg_doc_sz of the resident count matrix as the context holds it (see above; computed on first use).  world > 1: the corpus value
  * over all ranks' documents, collective where it has to be computed (see isle_hip_infer_resident).  ISLE_E_ARG: no count matrix, out null. */
 int isle_hip_avg_doc_sz(isle_ctx* ctx, float* out);

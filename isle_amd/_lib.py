@@ -68,6 +68,8 @@ SYMBOLS = {
     "isle_hip_topic_top_docs": (_I, [_P, _I, _I, _I, _U64, _U64, _P, _P, _P, _P, _P, _P, _P]),
     "isle_hip_similar_docs": (_I, [_P, _I, _I, _I, _I, _U64, _U64, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "isle_hip_simdocs_table_form": (_I, [_P, _I]),
+    "isle_hip_topic_prevalence": (_I, [_P, _I, _I, _U64, _P, _P, _P, _P, C.c_uint32, _I, _P, _P, _P, _P, _P]),
+    "isle_hip_prevalence_tile_form": (_I, [_P, _I]),
     "isle_hip_avg_doc_sz": (_I, [_P, _P]),
     "isle_hip_counts_shape": (_I, [_P, _P, _P, _P, _P, _P]),
     "isle_hip_vocab_hist_form": (_I, [_P, _I]),

@@ -12,6 +12,7 @@
 #include "stage_host.h"
 #include "topdocs_host.h"
 #include "simdocs_host.h"
+#include "prevalence_host.h"
 #include "vocab_host.h"
 #include "docs_host.h"
 #include "match_host.h"
@@ -1787,6 +1788,130 @@ extern "C" int isle_hip_similar_docs(isle_ctx* c, int source, int measure, int n
   ISLECHK(k_sd_score(c, v, measure, lds, Q, table.p, d_ex.p, nq.p, pair_off.p, qid.p, score.p));
   const TdView sel = {pair_off.p, qid.p, score.p, rows, pairs, doc_base, Q, (uint32_t)n, fam};
   return td_select(c, sel, "similar_docs", docs, scores, counts, candidates);
+}
+
+// The context's topic tile of isle_hip_topic_prevalence (prevalence_host.h, prev_tile): a setting, not an environment switch.
+extern "C" int isle_hip_prevalence_tile_form(isle_ctx* c, int form) {
+  if (!c) return ISLE_E_ARG;
+  const std::string why = prevalence_check_form(form);
+  if (!why.empty()) return isle_fail(c, ISLE_E_ARG, "%s", why.c_str());
+  c->prevalence_tile_form = form;
+  return 0;
+}
+
+// Topic prevalence by document group (topic_prevalence.hip; the rule: prevalence_host.h): the row pass with its checks and integer tables,
+// the rows listed by group (a stable sort by label; the identity without labels), the bases of every level, and per topic tile the level-0
+// partials and the folds, the last of which writes sum.  One rank only: refused with several, before any collective.  Nothing resident is
+// written and nothing is kept.
+extern "C" int isle_hip_topic_prevalence(isle_ctx* c, int source, int num_topics, uint64_t num_rows, const int64_t* doc_offsets, const uint32_t* topic,
+                                         const float* value, const uint32_t* groups, uint32_t num_groups, int normalise, uint64_t* docs, uint64_t* unlabelled,
+                                         uint64_t* count, uint64_t* dominant, double* sum) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  const bool infer = source == ISLE_TOPDOCS_INFER, sums = source == ISLE_TOPDOCS_SUMS;
+  if (infer && !c->res.inf_valid)
+    return isle_fail(c, ISLE_E_ARG, "topic_prevalence: no resident result (run isle_hip_infer_resident; a new count matrix voids it)");
+  if (sums && !c->res.p_model_ready) return isle_fail(c, ISLE_E_ARG, "topic_prevalence: run isle_hip_topic_model first (a new count matrix voids its result)");
+  const uint64_t rows = infer ? c->inf_docs : (sums ? c->a_D : num_rows);
+  const std::string why = prevalence_check_args(source, num_topics, num_groups, normalise, groups != nullptr, c->world, rows);
+  if (!why.empty()) return isle_fail(c, ISLE_E_ARG, "%s", why.c_str());
+  if (sums && num_topics != c->res.p_k)
+    return isle_fail(c, ISLE_E_ARG, "topic_prevalence: num_topics = %d, the resident topic model has %d topics", num_topics, c->res.p_k);
+  if (infer && num_topics != c->inf_cols)
+    return isle_fail(c, ISLE_E_ARG, "topic_prevalence: num_topics = %d, the resident inference result has %d topics", num_topics, c->inf_cols);
+  if (!docs || !count || !dominant || !sum) return isle_fail(c, ISLE_E_ARG, "topic_prevalence: null docs / count / dominant / sum");
+  uint64_t nnz = infer ? c->inf_n : (sums ? c->p_dts_n : 0);
+  if (source == ISLE_TOPDOCS_HOST && rows) {
+    if (!doc_offsets) return isle_fail(c, ISLE_E_ARG, "topic_prevalence: null doc_offsets with %llu rows", (unsigned long long)rows);
+    const std::string bad_off = topdocs_check_offsets(doc_offsets, rows);
+    if (!bad_off.empty()) return isle_fail(c, ISLE_E_ARG, "topic_prevalence: %s", bad_off.c_str() + sizeof("topic_top_docs: ") - 1);
+    nnz = (uint64_t)doc_offsets[rows];
+    if (nnz && (!topic || !value)) return isle_fail(c, ISLE_E_ARG, "topic_prevalence: null topic / value with %llu entries", (unsigned long long)nnz);
+  }
+  const uint32_t G = num_groups;
+  const size_t k = (size_t)num_topics, cells = (size_t)G * k;
+  DevBuf<int64_t> up_off;
+  DevBuf<uint32_t> up_topic, d_groups, row_a, row_b;
+  DevBuf<float> up_value;
+  DevBuf<uint64_t> d_docs, d_count, d_dom, err, key_a, key_b, bases, cnt, blk;
+  DevBuf<double> d_sum, rs, part_a, part_b;
+  StreamDrain drain(c);
+  TdView v = {infer ? c->inf_off.p : c->p_dts_off.p, infer ? c->inf_topic.p : c->p_dts_topic.p, infer ? c->inf_weight.p : c->p_dts_val.p,
+              rows,  nnz, 0, (uint32_t)num_topics, 0, infer ? ISLE_T_INFER : ISLE_T_POST};
+  if (source == ISLE_TOPDOCS_HOST) ISLECHK(td_upload(c, rows, nnz, doc_offsets, topic, value, up_off, up_topic, up_value, &v));
+  const bool labelled = groups != nullptr && rows > 0;
+  if (labelled) {
+    HIPCHK(c, d_groups.reserve(rows));
+    HIPCHK(c, hipMemcpy(d_groups.p, groups, rows * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(c, key_a.reserve(rows));
+    HIPCHK(c, key_b.reserve(rows));
+    HIPCHK(c, row_a.reserve(rows));
+    HIPCHK(c, row_b.reserve(rows));
+  }
+  HIPCHK(c, d_docs.reserve((size_t)G + 1));
+  HIPCHK(c, d_count.reserve(cells));
+  HIPCHK(c, d_dom.reserve(cells));
+  HIPCHK(c, d_sum.reserve(cells));
+  HIPCHK(c, err.reserve(2));
+  if (normalise) HIPCHK(c, rs.reserve(rows ? rows : 1));
+  // the row pass: the checks, the integer tables, the row sums, the sort's pairs
+  uint64_t bad_row = ~0ull, bad_entry = ~0ull;
+  ISLECHK(k_tp_rows(c, v, labelled ? d_groups.p : nullptr, G, d_docs.p, d_count.p, d_dom.p, normalise ? rs.p : nullptr, labelled ? key_a.p : nullptr,
+                    labelled ? row_a.p : nullptr, err.p, &bad_row, &bad_entry));
+  if (bad_row != ~0ull) return isle_fail(c, ISLE_E_ARG, "%s", prevalence_label_text(bad_row, groups[bad_row], G).c_str());
+  if (bad_entry != ~0ull) {
+    const uint64_t e = bad_entry >> 2;
+    std::vector<int64_t> off(rows + 1);
+    uint32_t tp = 0;
+    float w = 0.f;
+    HIPCHK(c, hipMemcpy(off.data(), v.off, (rows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&tp, v.topic + e, sizeof(tp), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&w, v.value + e, sizeof(w), hipMemcpyDeviceToHost));
+    const uint64_t row = (uint64_t)(std::upper_bound(off.begin(), off.end(), (int64_t)e) - off.begin()) - 1;
+    return isle_fail(c, ISLE_E_ARG, "%s", prevalence_entry_text((unsigned)(bad_entry & 3), e, row, tp, w, (uint32_t)num_topics).c_str());
+  }
+  std::vector<uint64_t> docs_host((size_t)G + 1);
+  HIPCHK(c, hipMemcpy(docs_host.data(), d_docs.p, ((size_t)G + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  // the levels of the tree: as many as the largest group needs; the values of every level over all groups
+  const int levels = prev_levels(*std::max_element(docs_host.begin(), docs_host.begin() + G));
+  std::vector<uint64_t> totals((size_t)levels + 2, 0), lvl(docs_host.begin(), docs_host.begin() + G);
+  for (int j = 0; j <= levels; ++j)
+    for (size_t g = 0; g < G; ++g) {
+      totals[j] += lvl[g];
+      lvl[g] = (lvl[g] + PREV_FAN - 1) / PREV_FAN;
+    }
+  HIPCHK(c, hipMemsetAsync(d_sum.p, 0, cells * sizeof(double), c->stream));
+  if (levels) {
+    // the rows by group: a stable sort by label keeps the rows of a group ascending; the rows of no group sort behind every group
+    const uint32_t* list = nullptr;
+    if (labelled) {
+      int bits = 1;
+      while (bits < 32 && (G >> bits)) ++bits;
+      bool in_a = true;
+      {
+        TimeScope ts(c, v.fam);
+        ISLECHK(k_sort_pairs_u64(c, key_a.p, row_a.p, key_b.p, row_b.p, rows, bits, &in_a));
+      }
+      list = in_a ? row_a.p : row_b.p;
+    }
+    HIPCHK(c, bases.reserve(((size_t)levels + 1) * ((size_t)G + 1)));
+    HIPCHK(c, cnt.reserve(G));
+    HIPCHK(c, blk.reserve(isle_scan_scratch(G)));
+    ISLECHK(k_tp_bases(c, v.fam, d_docs.p, G, levels, bases.p, cnt.p, blk.p));
+    const uint32_t tile = prev_tile((uint32_t)num_topics, c->prevalence_tile_form);
+    HIPCHK(c, part_a.reserve(levels > 1 ? (size_t)totals[1] * tile : 1));
+    HIPCHK(c, part_b.reserve(levels > 2 ? (size_t)totals[2] * tile : 1));
+    for (uint32_t t0 = 0; t0 < (uint32_t)num_topics; t0 += tile)
+      ISLECHK(k_tp_tile(c, v, list, normalise ? rs.p : nullptr, G, bases.p, levels, totals.data(), t0, std::min(tile, (uint32_t)num_topics - t0), part_a.p,
+                        part_b.p, d_sum.p));
+  }
+  HIPCHK(c, hipMemcpyAsync(count, d_count.p, cells * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dominant, d_dom.p, cells * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(sum, d_sum.p, cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::copy(docs_host.begin(), docs_host.begin() + G, docs);
+  if (unlabelled) *unlabelled = docs_host[G];
+  return 0;
 }
 
 extern "C" int isle_hip_avg_doc_sz(isle_ctx* c, float* out) {

@@ -258,6 +258,7 @@ struct isle_ctx {
   int neardup_key_form = 0;        // isle_hip_neardup_key_form: what route_neardup_key is asked with (0: the rule's own choice)
   int model_dist_slices = 0;       // isle_hip_model_dist_slices: what route_model_dist_slices is asked with (0: the rule's own choice)
   int simdocs_table_form = 0;      // isle_hip_simdocs_table_form: what route_simdocs_table is asked with (0: the rule's own choice)
+  int prevalence_tile_form = 0;    // isle_hip_prevalence_tile_form: what prev_tile (prevalence_host.h) is asked with (0: the rule's own choice)
 
   // --- downstream stage (post.hip): catchwords, topic model, edge topics
   DevBuf<float> a_nv;              // normalised values of A
@@ -737,6 +738,21 @@ int k_sd_count(isle_ctx* c, const TdView& v, bool lds, uint32_t Q, const float* 
                uint64_t* err_dev, uint64_t* bad, uint64_t* pairs);
 int k_sd_score(isle_ctx* c, const TdView& v, int measure, bool lds, uint32_t Q, const float* table, const uint32_t* exclude, const double* nq,
                const int64_t* pair_off, uint32_t* qid, float* score);
+
+// topic_prevalence.hip: the device steps of isle_hip_topic_prevalence (the rule: prevalence_host.h).  v: the source's rows, its num_topics k;
+// G groups.  Every buffer is the call's, on the device unless named host; device time goes to v.fam.
+// k_tp_rows: docs (G + 1: the last counts the rows of no group), count and dominant (G x k), zeroed there; rs (rows, nullable): the row
+//   sums; label / rowid (rows each, nullable): the pairs of the sort by label; *bad_row: ~0, or the first row with a bad label;
+//   *bad_entry: ~0, or (entry << 2) | what of the first bad entry (1, 2: topdocs_entry_fault; PREV_BAD_WEIGHT).  Drained when it returns.
+// k_tp_bases: bases ((levels + 1) x (G + 1)): per level the exclusive scan of every group's values, level 0 the rows; cnt: G words,
+//   blk: scan scratch of G.
+// k_tp_tile: topics [t0, t0 + tw) of sum (G x k, zeroed by the caller) through every level; list: the rows by group (null: the identity);
+//   totals (host, levels + 1): the values of each level over all groups; part_a / part_b: totals[1] x tw and totals[2] x tw doubles.
+int k_tp_rows(isle_ctx* c, const TdView& v, const uint32_t* groups_dev, uint32_t G, uint64_t* docs, uint64_t* count, uint64_t* dominant, double* rs,
+              uint64_t* label, uint32_t* rowid, uint64_t* err_dev, uint64_t* bad_row, uint64_t* bad_entry);
+int k_tp_bases(isle_ctx* c, int fam, const uint64_t* docs, uint32_t G, int levels, uint64_t* bases, uint64_t* cnt, uint64_t* blk);
+int k_tp_tile(isle_ctx* c, const TdView& v, const uint32_t* list, const double* rs, uint32_t G, const uint64_t* bases, int levels, const uint64_t* totals,
+              uint32_t t0, uint32_t tw, double* part_a, double* part_b, double* sum);
 
 // vocab.hip: the device steps of isle_hip_word_doc_freq / isle_hip_prune_vocab on the resident A (the rule: vocab_host.h).  k_vocab_df: df_dev
 // (a_V words, zeroed there) = this rank's entries per word.  k_vocab_compact: A under remap_dev (a_V words: the new id, or 0xffffffff) out of

@@ -652,6 +652,29 @@ class FPSparseMatrixHip {
     check(isle_hip_similar_docs(ctx_, source, measure, (int)num_topics, n, doc_base, 0, nullptr, nullptr, nullptr, (int)Q, query_rows.data(), nullptr, nullptr,
                                 nullptr, nullptr, docs.data(), scores.data(), counts.data(), candidates ? candidates->data() : nullptr), "similar_docs");
   }
+  // Topic prevalence by group of documents, summed on the device (isle_hip_topic_prevalence; the rule: isle_amd/csrc/prevalence_host.h)
+  // from a resident source, ISLE_TOPDOCS_SUMS or ISLE_TOPDOCS_INFER as topic_top_docs.  groups: one label per row of the source
+  // (ISLE_GROUP_NONE: no group), or empty: every row has label 0 and num_groups is 1.  docs (num_groups); count, dominant, sum (num_groups x
+  // num_topics group-major); the sums are added in the rule's order: the same bits on every call.  -> the rows of no group.
+  struct TopicPrevalence {
+    std::vector<uint64_t> docs, count, dominant;
+    std::vector<double> sum;
+    uint64_t unlabelled = 0;
+  };
+  TopicPrevalence topic_prevalence(const int source, const doc_id_t num_topics, const std::vector<uint32_t>& groups, const uint32_t num_groups,
+                                   const bool normalise) {
+    TopicPrevalence p;
+    if (source == ISLE_TOPDOCS_SUMS && !groups.empty() && groups.size() != (size_t)a_docs_)  // (the library reads one label per row)
+      throw std::runtime_error("topic_prevalence: " + std::to_string(groups.size()) + " labels for " + std::to_string((size_t)a_docs_) + " documents");
+    const size_t cells = (size_t)num_groups * (size_t)num_topics;
+    p.docs.assign(num_groups, 0);
+    p.count.assign(cells, 0);
+    p.dominant.assign(cells, 0);
+    p.sum.assign(cells, 0.0);
+    check(isle_hip_topic_prevalence(ctx_, source, (int)num_topics, 0, nullptr, nullptr, nullptr, groups.empty() ? nullptr : groups.data(), num_groups,
+                                    normalise ? 1 : 0, p.docs.data(), &p.unlabelled, p.count.data(), p.dominant.data(), p.sum.data()), "topic_prevalence");
+    return p;
+  }
   // Two models compared on the device (isle_hip_compare_models; the rule: isle_amd/csrc/match_host.h): dist (cols_a x cols_b row-major) =
   // the L1 distances of their topics in double, and the greedy matching of the topics by it: match_a[i] = the matched topic of b or -1,
   // match_b the inverse, match_dist[i] = the matched distance or NaN, mean_dist over the n_matched pairs.  A side is a resident model

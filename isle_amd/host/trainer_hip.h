@@ -1057,6 +1057,29 @@ class ISLETrainer {
     std::fclose(f);
     log->next_time_secs("Writing the most similar documents of the query documents");
   }
+  // "How much of the corpus is each topic, and how does that differ between its parts": the resident catchword sums added up by group of
+  // documents on the device (FPSparseMatrixHip::topic_prevalence -> isle_hip_topic_prevalence; the rule: isle_amd/csrc/prevalence_host.h).
+  // groups: one label per document (ISLE_GROUP_NONE: no group), or empty with num_groups = 1: the whole corpus.  Call it when the topic
+  // model exists (after train()).  TopicPrevalence.tsv: one line per cell with count > 0, group ascending, then topic ascending,
+  // "<group>\t<topic + 1>\t<docs>\t<with_topic>\t<dominant>\t<sum>\t<mean>\n": the group is the caller's label, the topic 1-based as in every
+  // file of the trainer, docs the documents of the group, with_topic those that store the topic, dominant those whose heaviest topic it
+  // is, sum and mean = sum / docs as %.17g.  Formatted on the host: at most 2^24 cells.  The reference has no such file; not part of
+  // what ISLETrain writes by default.
+  void output_topic_prevalence(const std::vector<uint32_t>& groups, const uint32_t num_groups = 1, const bool normalise = false) {
+    if (!is_training_complete) throw std::runtime_error("output_topic_prevalence() before train()");
+    const FPSparseMatrixHip::TopicPrevalence p = B_fl_CSC->topic_prevalence(ISLE_TOPDOCS_SUMS, num_topics, groups, num_groups, normalise);
+    FILE* f = std::fopen((log_dir + "/TopicPrevalence.tsv").c_str(), "wb");
+    if (!f) throw std::runtime_error("cannot write " + log_dir + "/TopicPrevalence.tsv");
+    for (uint32_t g = 0; g < num_groups; ++g)
+      for (doc_id_t t = 0; t < num_topics; ++t) {
+        const size_t at = (size_t)g * num_topics + t;
+        if (!p.count[at]) continue;
+        std::fprintf(f, "%u\t%llu\t%llu\t%llu\t%llu\t%.17g\t%.17g\n", g, (unsigned long long)(t + 1), (unsigned long long)p.docs[g],
+                     (unsigned long long)p.count[at], (unsigned long long)p.dominant[at], p.sum[at], p.sum[at] / (double)p.docs[g]);
+      }
+    std::fclose(f);
+    log->next_time_secs("Writing the topic prevalence by document group");
+  }
   // "Is this model the same as that one": the model file model_file (format ISLE_TEXT_SPARSE / ISLE_TEXT_DENSE, vocab_size x num_topics, as
   // write_model_to_file writes it) is read on the device into the resident loaded model (FPSparseMatrixHip::load_model_file) and this
   // run's catch model (side a) is compared with it (side b): the L1 distances of all topic pairs in double and the greedy matching by

@@ -1440,6 +1440,66 @@ class HotPath:
                                                   _p(va), Q, _p(qrows), _p(qo), _p(qt), _p(qw), _p(ex), _p(docs), _p(scores), _p(counts), _p(cand)))
         return dict(docs=docs, scores=scores, counts=counts, candidates=cand)
 
+    # ---- topic prevalence by group of documents, summed on the device (include/isle_hip.h, isle_hip_topic_prevalence) ----------------
+    GROUP_NONE = 0xFFFFFFFF
+
+    def prevalence_tile_form(self, form="auto"):
+        """The topics of one private table of topic_prevalence: "auto" / "wide" (1024) or "narrow" (64, so that small tests cross tile
+        edges).  A setting of the context; both forms give the same bits."""
+        self._chk(self._lib.isle_hip_prevalence_tile_form(self._h, {"auto": 0, "wide": 1, "narrow": 2}.get(form, form)))
+
+    def topic_prevalence(self, source="infer", groups=None, num_groups=None, normalise=False, num_topics=None):
+        """How much of the corpus each topic is, by group of documents, over sparse topic weights stored by document: source as
+        topic_top_docs ("infer", "sums" or a CSR (doc_offsets, topic, weight)).  groups: one uint32 label per row (GROUP_NONE = 0xffffffff:
+        the row belongs to no group and is counted in `unlabelled` alone), or None: every row has label 0.  num_groups: None = the largest
+        label that is not GROUP_NONE + 1, or 1 without labels.  normalise: every row's weights divided by the row's sum first.  Weights
+        are finite, >= 0 and < 2^31.  The sums are added in a stated order (include/isle_hip.h: rows ascending, 64 at a time, level by
+        level), so they are the same bits on every call and equal isle_amd/csrc/prevalence_host.h's host loop bit for bit.
+        One rank only: under comm_init / comm_init_host with several ranks the call is refused.  Nothing resident changes.
+        -> dict(docs uint64 (G,), unlabelled int, count uint64 (G, k) = rows of the group that store the topic, dominant uint64 (G, k) =
+        rows whose heaviest topic it is, sum float64 (G, k), mean float64 (G, k) = sum / docs, NaN for a group without rows)."""
+        off = tp = va = None
+        rows = 0
+        if isinstance(source, str):
+            kind = self._TOPDOCS[source]
+            if num_topics is None:
+                num_topics = getattr(self, "_post_k", 0) if source == "sums" else getattr(self, "_inf_cols", 0)
+        else:
+            kind = 2
+            off = np.ascontiguousarray(source[0], np.int64)
+            tp = _as_u32(source[1], "topic")
+            va = np.ascontiguousarray(source[2], np.float32)
+            if off.ndim != 1 or off.size < 1 or va.ndim != 1 or tp.size != va.size or (off.size > 1 and int(off[-1]) != tp.size):
+                raise ValueError("source: (doc_offsets (rows + 1,), topic, weight) with doc_offsets[-1] entries")
+            rows = off.size - 1
+            if num_topics is None:
+                num_topics = int(tp.max()) + 1 if tp.size else 1
+        lab = None
+        if groups is not None:
+            lab = _as_u32(groups, "groups").reshape(-1)
+            have = rows if kind == 2 else (getattr(self, "_a_shape", (0, 0, 0))[1] if kind == 1 else getattr(self, "_inf_rows", 0))
+            if lab.size != have:  # (the library reads one label per row of the source)
+                raise ValueError("groups: %d labels for the %d rows of the source" % (lab.size, have))
+            if num_groups is None:
+                real = lab[lab != self.GROUP_NONE]
+                num_groups = int(real.max()) + 1 if real.size else 1
+        elif num_groups is None:
+            num_groups = 1
+        k, G = int(num_topics), int(num_groups)
+        if not 0 <= G <= 0xFFFFFFFF:
+            raise ValueError("num_groups: a 32-bit number")
+        shape = (G, max(k, 0))
+        docs = np.zeros(G, np.uint64)
+        count = np.zeros(shape, np.uint64)
+        dominant = np.zeros(shape, np.uint64)
+        total = np.zeros(shape, np.float64)
+        none = C.c_uint64(0)
+        self._chk(self._lib.isle_hip_topic_prevalence(self._h, kind, k, rows, _p(off), _p(tp), _p(va), _p(lab), G, int(normalise), _p(docs), C.byref(none),
+                                                      _p(count), _p(dominant), _p(total)))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mean = total / docs.astype(np.float64)[:, None]
+        return dict(docs=docs, unlabelled=int(none.value), count=count, dominant=dominant, sum=total, mean=mean)
+
     def timing_enable(self, on=True):
         """0 / False: off; 1 / True: events around every launch; 2: around the Gram-apply launches only."""
         self._chk(self._lib.isle_hip_timing_enable(self._h, int(on)))
