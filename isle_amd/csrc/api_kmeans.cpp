@@ -160,7 +160,9 @@ static int kmpp_draw_by_ranks(isle_ctx* c, HostRng& rng, int ndraw, bool injecte
   for (int i = 0; i < ndraw; ++i) {
     dice[i] = *grand * rng.fraction();  // :2184
     const double x = dice[i] - my_off;
-    const bool mine = (x >= 0.0 && x < st.my[0]) || (c->world == 1);
+    // a die that no interval holds (the total is zero, or the fraction rounded to 1) is the last document's, as the search's clamp
+    // makes it on one rank: the rank that holds that document answers
+    const bool mine = (x >= 0.0 && x < st.my[0]) || (c->world == 1) || (holds_last && dice[i] >= *grand);
     st.local[i] = mine ? std::min(std::max(x, 0.0), st.my[0]) : -1.0;
   }
   if (ndraw <= 16) {

@@ -311,7 +311,9 @@ int k_kmpp_update(isle_ctx* c, const float* P, const float* pn, uint64_t D, int 
   // measured rates: a pass of the pass-1 stream costs ~2.8 ps per nonzero (= 15.4 bytes of streaming at 5.5 TB/s), the materialised
   // projection streams at 5.5 TB/s for <= 16 new seeds (kmpp_min_pt_k) and 2.3x slower through the matrix-core tile beyond.
   {
-    if (route_kmpp_sparse(c->res.thin_product_possible(k), c->nnz, D, ldk, nc, k_gl_panel_width(c), c->route)) {
+    const bool thin = route_kmpp_sparse(c->res.thin_product_possible(k), c->nnz, D, ldk, nc, k_gl_panel_width(c), c->route);
+    if (c->knob_on(KN_DEBUG_HAMERLY)) fprintf(stderr, "[k-means++] %d new seeds %s\n", nc, thin ? "through thin products of B" : "on the projection");
+    if (thin) {
       // (Round 3 also built the pruned round of accelerated k-means++ seeding — only the documents a new seed can reach by the
       // triangle inequality, from the materialised projection.  On this corpus the documents of topics without a seed stay within
       // reach: 98 % at 20 seeds, 50 % at 570, 28 % at 906 of 1000, and a visited document costs a 4 kB row plus 2 k flops per new seed
