@@ -888,6 +888,50 @@ int isle_hip_topic_prevalence(isle_ctx* ctx, int source /* ISLE_TOPDOCS_INFER | 
                               uint32_t num_groups, int normalise, uint64_t* docs, uint64_t* unlabelled /* nullable */, uint64_t* count,
                               uint64_t* dominant, double* sum);
 int isle_hip_prevalence_tile_form(isle_ctx* ctx, int form);
+/* Held-out scores per document on the device (isle_amd/csrc/score_docs.hip and api_stages.cpp): how well given topic weights predict the
+ * entries of a sparse matrix of counts; with weights fitted on one part of every document and the other part scored, document completion.
+ * The model is isle_hip_infer_resident's (`which`, model_host, vocab x ncols column-major).  The weights are the rows of the last
+ * isle_hip_infer_resident (ISLE_TOPDOCS_INFER: num_rows must be its row count) or a CSR w_offsets / w_topic / w_weight uploaded for the call
+ * (ISLE_TOPDOCS_HOST), topics ascending strictly within a row.  The entries are documents [doc_begin, doc_begin + num_rows) of the resident
+ * A (ISLE_SCORE_RESIDENT; with ISLE_TOPDOCS_INFER doc_begin must be that call's doc_begin) or a CSC counts / rows / offsets uploaded for
+ * the call (ISLE_SCORE_HOST: offsets num_rows + 1 ascending from 0, doc_begin ignored).  Row r of the weights scores document r of the entries.
+ * The rule, stated once as plain C++ in isle_amd/csrc/score_host.h, for a document with weights (t_0 < t_1 < .., th_j) and an entry (w, c):
+ *   weights  th'_j = (double)th_j; with normalise (double)th_j / s_d (one IEEE division), s_d the row's sum of (double)th_j in stored order
+ *            from 0.0; a row whose sum is 0 then has no weights.  Every weight is finite, >= 0 and < 2^31.
+ *   z        z = fma((double)M[w,t_j], th'_j, z) over j ascending from z = 0.0: fused, one rounding per stored topic.  Without normalise
+ *            every product is exact in double, so an unfused loop gives the same bits.
+ *   classes  z NaN, infinite or negative: unscored.  Else z < floor (floor > 0; z == 0 included): scored at floor and counted in floored.
+ *            Else z == 0: unscored.  Else scored at z.  An unscored entry adds nothing to score and tokens and is counted in
+ *            unscored_entries and, with (double)c, in unscored_tokens: a NaN column of a catch model never poisons a document.
+ *   term     ISLE_SCORE_LOG: (double)c * log(z); ISLE_SCORE_PROB: (double)c * z; the product rounded once, never fused into the sum
+ *   sums     per document of n entries: lane i < 64 adds the terms of the entries i, i + 64, .. ascending from 0.0, then
+ *            p[i] = p[i] + p[i + s] for s = 32, 16, .., 1; the sum is p[0].  score, tokens (the (double)c of scored entries) and
+ *            unscored_tokens are summed so.  z_out (nullable, ISLE_SCORE_HOST only): z of every entry, in entry order.
+ * ISLE_SCORE_PROB without normalise equals the header's host loop bit for bit, as do z_out, tokens and the counters in every mode; two
+ * calls give the same bits in every mode; for ISLE_SCORE_LOG |score - exact| <= g / (1 - g) sum c |ln z|, g = (2 K + 1 + ceil(n / 64) + 6)
+ * 2^-53, K the device logarithm's error in ulps (profiles/score_certificate.md).  Corpus totals are not formed on the device:
+ * isle_hip_score_total is the ascending sequential sum on the host (no context, no device), so that every caller gets the same bits and
+ * the arrays of document shards side by side give the single-rank total; perplexity = exp(-total score / total tokens) for ISLE_SCORE_LOG.
+ * ISLE_E_ARG, decided before any launch: an unknown source or measure, normalise outside {0, 1}, floor not finite or < 0, ncols outside
+ * [1, 1024], the model's conditions as isle_hip_infer_resident states them (vocab must be A's with ISLE_SCORE_RESIDENT), no resident
+ * result, num_rows or doc_begin that differ from the resident result's, a document range outside A, offsets that do not ascend from 0,
+ * NULL arrays, z_out with ISLE_SCORE_RESIDENT.  Found on the device, each naming the first offender through one 64-bit atomicMin: a
+ * weight entry with a topic >= ncols, topics that do not ascend, or a weight outside the domain (before any entry is read); then an entry
+ * with a word >= vocab or a count that is not finite or < 0.  After any refusal the context is usable.  The call changes nothing resident
+ * and keeps nothing.  Device time: ISLE_T_INFER.  world > 1: no collective; every rank scores its own rows, ISLE_MODEL_AVG is refused as
+ * isle_hip_infer_resident refuses it, and the ranks' arrays side by side are the single-rank arrays bit for bit.
+ * Device memory of a call, derived, not measured: the packed model 4 vocab round4(ncols) bytes, 8 num_rows of row sums, 32 num_rows of
+ * outputs, 8 bytes per entry of z_out, and the uploads of the HOST forms. */
+#define ISLE_SCORE_RESIDENT 0
+#define ISLE_SCORE_HOST 1
+#define ISLE_SCORE_LOG 0
+#define ISLE_SCORE_PROB 1
+int isle_hip_score_docs(isle_ctx* ctx, int which, const float* model_host, uint64_t vocab, int ncols, int weights_source, uint64_t num_rows,
+                        const int64_t* w_offsets, const uint32_t* w_topic, const float* w_weight, int entries_source, uint64_t doc_begin,
+                        const float* counts, const uint32_t* rows, const int64_t* offsets, int measure, int normalise, double floor,
+                        double* score, double* tokens, uint32_t* unscored_entries, double* unscored_tokens, uint32_t* floored,
+                        double* z_out /* nullable */);
+int isle_hip_score_total(const double* v, uint64_t n, double* out);
 /* The avg_doc_sz of the resident count matrix as the context holds it (see above; computed on first use).  world > 1: the corpus value
  * over all ranks' documents, collective where it has to be computed (see isle_hip_infer_resident).  ISLE_E_ARG: no count matrix, out null. */
 int isle_hip_avg_doc_sz(isle_ctx* ctx, float* out);

@@ -70,6 +70,8 @@ SYMBOLS = {
     "isle_hip_simdocs_table_form": (_I, [_P, _I]),
     "isle_hip_topic_prevalence": (_I, [_P, _I, _I, _U64, _P, _P, _P, _P, C.c_uint32, _I, _P, _P, _P, _P, _P]),
     "isle_hip_prevalence_tile_form": (_I, [_P, _I]),
+    "isle_hip_score_docs": (_I, [_P, _I, _P, _U64, _I, _I, _U64, _P, _P, _P, _I, _U64, _P, _P, _P, _I, _I, C.c_double, _P, _P, _P, _P, _P, _P]),
+    "isle_hip_score_total": (_I, [_P, _U64, _P]),
     "isle_hip_avg_doc_sz": (_I, [_P, _P]),
     "isle_hip_counts_shape": (_I, [_P, _P, _P, _P, _P, _P]),
     "isle_hip_vocab_hist_form": (_I, [_P, _I]),

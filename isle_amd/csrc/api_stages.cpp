@@ -1914,6 +1914,136 @@ extern "C" int isle_hip_topic_prevalence(isle_ctx* c, int source, int num_topics
   return 0;
 }
 
+// ---- held-out scores per document (score_docs.hip; the rule: score_host.h)
+#include "score_host.h"  // (included here, above its only users)
+extern "C" int isle_hip_score_total(const double* v, uint64_t n, double* out) {
+  if (!out || (n && !v)) return ISLE_E_ARG;
+  *out = score_total(v, n);
+  return 0;
+}
+
+// the row of entry e (a position in the arrays the offsets point into) under offsets that lie on the device (rows + 1 of them)
+static int sc_row_of(isle_ctx* c, const int64_t* off_dev, uint64_t rows, uint64_t e, uint64_t* row) {
+  std::vector<int64_t> off(rows + 1);
+  HIPCHK(c, hipMemcpy(off.data(), off_dev, (rows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+  *row = (uint64_t)(std::upper_bound(off.begin(), off.end(), (int64_t)e) - off.begin()) - 1;
+  return 0;
+}
+
+// Every refusal that needs no entry comes before the first launch and before any upload; the weight rows are checked on the device before
+// the walk reads them.  No collective: with several ranks every rank scores its own rows.  Nothing resident is written, nothing is kept.
+extern "C" int isle_hip_score_docs(isle_ctx* c, int which, const float* model_host, uint64_t vocab, int ncols, int weights_source, uint64_t num_rows,
+                                   const int64_t* w_offsets, const uint32_t* w_topic, const float* w_weight, int entries_source, uint64_t doc_begin,
+                                   const float* counts, const uint32_t* rows_in, const int64_t* offsets, int measure, int normalise, double floor,
+                                   double* score, double* tokens, uint32_t* unscored_entries, double* unscored_tokens, uint32_t* floored, double* z_out) {
+  if (!c) return ISLE_E_ARG;
+  ISLECHK(isle_enter(c));
+  ISLECHK(model_reader_ok(c, which, "score_docs"));
+  const std::string why = score_check_args(weights_source, entries_source, measure, normalise, floor, ncols);
+  if (!why.empty()) return isle_fail(c, ISLE_E_ARG, "%s", why.c_str());
+  const bool infer = weights_source == ISLE_TOPDOCS_INFER, resident = entries_source == ISLE_SCORE_RESIDENT;
+  if (infer && !c->res.inf_valid)
+    return isle_fail(c, ISLE_E_ARG, "score_docs: no resident result (run isle_hip_infer_resident; a new count matrix voids it)");
+  if (resident) ISLECHK(post_prepare_sharded(c, "score_docs"));
+  if (vocab == 0 || vocab > 0xfffffff0ull) return isle_fail(c, ISLE_E_ARG, "score_docs: vocab out of range");
+  if (infer && num_rows != c->inf_docs) return isle_fail(c, ISLE_E_ARG, "%s", score_rows_text(num_rows, c->inf_docs, "the resident inference result").c_str());
+  if (infer && ncols != c->inf_cols)
+    return isle_fail(c, ISLE_E_ARG, "score_docs: ncols = %d, the resident inference result has %d topics", ncols, c->inf_cols);
+  if (resident) {
+    if (doc_begin > c->a_D || num_rows > c->a_D - doc_begin) return isle_fail(c, ISLE_E_ARG, "%s", score_range_text(doc_begin, num_rows, c->a_D).c_str());
+    if (vocab != c->a_V) return isle_fail(c, ISLE_E_ARG, "%s", score_vocab_text(vocab, c->a_V).c_str());
+    if (infer && doc_begin != c->inf_doc_begin) return isle_fail(c, ISLE_E_ARG, "%s", score_begin_text(doc_begin, c->inf_doc_begin).c_str());
+    if (z_out) return isle_fail(c, ISLE_E_ARG, "score_docs: z_out with ISLE_SCORE_RESIDENT (fetch the entries and pass them as ISLE_SCORE_HOST)");
+  }
+  if (num_rows && (!score || !tokens || !unscored_entries || !unscored_tokens || !floored))
+    return isle_fail(c, ISLE_E_ARG, "score_docs: null score / tokens / unscored_entries / unscored_tokens / floored");
+  uint64_t w_nnz = infer ? c->inf_n : 0, e_nnz = 0;
+  if (!infer && num_rows) {
+    if (!w_offsets) return isle_fail(c, ISLE_E_ARG, "score_docs: null w_offsets with %llu rows", (unsigned long long)num_rows);
+    const std::string bad_off = score_check_offsets("w_offsets", w_offsets, num_rows);
+    if (!bad_off.empty()) return isle_fail(c, ISLE_E_ARG, "%s", bad_off.c_str());
+    w_nnz = (uint64_t)w_offsets[num_rows];
+    if (w_nnz && (!w_topic || !w_weight)) return isle_fail(c, ISLE_E_ARG, "score_docs: null w_topic / w_weight with %llu entries", (unsigned long long)w_nnz);
+  }
+  if (!resident && num_rows) {
+    if (!offsets) return isle_fail(c, ISLE_E_ARG, "score_docs: null offsets with %llu rows", (unsigned long long)num_rows);
+    const std::string bad_off = score_check_offsets("offsets", offsets, num_rows);
+    if (!bad_off.empty()) return isle_fail(c, ISLE_E_ARG, "%s", bad_off.c_str());
+    e_nnz = (uint64_t)offsets[num_rows];
+    if (e_nnz && (!counts || !rows_in)) return isle_fail(c, ISLE_E_ARG, "score_docs: null counts / rows with %llu entries", (unsigned long long)e_nnz);
+  }
+  const float* dev = nullptr;
+  DevBuf<float> up, packed, up_value, e_cnt;
+  DevBuf<int64_t> up_off, e_off;
+  DevBuf<uint32_t> up_topic, e_rows, d_ue, d_fl;
+  DevBuf<uint64_t> err;
+  DevBuf<double> rs, d_score, d_tok, d_ut, d_z;
+  StreamDrain drain(c);
+  ISLECHK(model_source(c, which, model_host, vocab, ncols, "score_docs", &up, &dev));
+  if (!num_rows) return 0;
+  const int ld = (ncols + 3) & ~3;
+  TdView w = {c->inf_off.p, c->inf_topic.p, c->inf_weight.p, num_rows, w_nnz, 0, (uint32_t)ncols, 0, ISLE_T_INFER};
+  if (!infer) ISLECHK(td_upload(c, num_rows, w_nnz, w_offsets, w_topic, w_weight, up_off, up_topic, up_value, &w));
+  HIPCHK(c, err.reserve(1));
+  HIPCHK(c, rs.reserve(num_rows));
+  uint64_t bad = ~0ull;
+  ISLECHK(k_sc_rows(c, w, rs.p, err.p, &bad));
+  if (bad != ~0ull) {
+    const uint64_t e = bad >> 2;
+    uint64_t row = 0;
+    uint32_t tp = 0;
+    float wt = 0.f;
+    ISLECHK(sc_row_of(c, w.off, num_rows, e, &row));
+    HIPCHK(c, hipMemcpy(&tp, w.topic + e, sizeof(tp), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&wt, w.value + e, sizeof(wt), hipMemcpyDeviceToHost));
+    return isle_fail(c, ISLE_E_ARG, "%s", score_weight_text((unsigned)(bad & 3), e, row, tp, wt, (uint32_t)ncols).c_str());
+  }
+  // the entries: documents [doc_begin, doc_begin + num_rows) of A where they lie, or the caller's, uploaded
+  const float* cnt_dev = c->a_cnt.p;
+  const uint32_t* word_dev = c->a_rows.p;
+  const int64_t* off_dev = resident ? c->a_offs.p + doc_begin : nullptr;
+  if (!resident) {
+    HIPCHK(c, e_off.reserve(num_rows + 1));
+    HIPCHK(c, e_cnt.reserve(e_nnz ? e_nnz : 1));
+    HIPCHK(c, e_rows.reserve(e_nnz ? e_nnz : 1));
+    HIPCHK(c, hipMemcpy(e_off.p, offsets, (num_rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (e_nnz) HIPCHK(c, hipMemcpy(e_cnt.p, counts, e_nnz * sizeof(float), hipMemcpyHostToDevice));
+    if (e_nnz) HIPCHK(c, hipMemcpy(e_rows.p, rows_in, e_nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
+    cnt_dev = e_cnt.p;
+    word_dev = e_rows.p;
+    off_dev = e_off.p;
+  }
+  HIPCHK(c, packed.reserve((size_t)vocab * ld));
+  ISLECHK(k_inf_pack(c, dev, vocab, ncols, packed.p));
+  HIPCHK(c, d_score.reserve(num_rows));
+  HIPCHK(c, d_tok.reserve(num_rows));
+  HIPCHK(c, d_ut.reserve(num_rows));
+  HIPCHK(c, d_ue.reserve(num_rows));
+  HIPCHK(c, d_fl.reserve(num_rows));
+  const bool with_z = z_out && e_nnz;
+  if (with_z) HIPCHK(c, d_z.reserve(e_nnz));
+  ISLECHK(k_sc_walk(c, w, packed.p, ld, vocab, cnt_dev, word_dev, off_dev, normalise ? rs.p : nullptr, measure, floor, d_score.p, d_tok.p, d_ue.p, d_ut.p,
+                    d_fl.p, with_z ? d_z.p : nullptr, err.p, &bad));
+  if (bad != ~0ull) {
+    const uint64_t e = bad >> 1;
+    uint64_t row = 0;
+    uint32_t wd = 0;
+    float ct = 0.f;
+    ISLECHK(sc_row_of(c, off_dev, num_rows, e, &row));
+    HIPCHK(c, hipMemcpy(&wd, word_dev + e, sizeof(wd), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&ct, cnt_dev + e, sizeof(ct), hipMemcpyDeviceToHost));
+    return isle_fail(c, ISLE_E_ARG, "%s", score_entry_text((unsigned)(bad & 1), e, row, wd, ct, vocab).c_str());
+  }
+  HIPCHK(c, hipMemcpyAsync(score, d_score.p, num_rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(tokens, d_tok.p, num_rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(unscored_tokens, d_ut.p, num_rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(unscored_entries, d_ue.p, num_rows * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(floored, d_fl.p, num_rows * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (with_z) HIPCHK(c, hipMemcpyAsync(z_out, d_z.p, e_nnz * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 extern "C" int isle_hip_avg_doc_sz(isle_ctx* c, float* out) {
   if (!c) return ISLE_E_ARG;
   ISLECHK(isle_enter(c));

@@ -296,8 +296,8 @@ struct isle_ctx {
   DevBuf<float> inf_weight;
   DevBuf<int32_t> inf_top_topic;   // docs x 5, < 0 = no further topic: what isle_hip_infer_text(ISLE_DOCTEXT_TOP) prints
   DevBuf<float> inf_top_weight;
-  uint64_t inf_docs = 0, inf_n = 0;
-  int inf_cols = 0;                // the columns of that call's model: the topics of inf_topic
+  uint64_t inf_docs = 0, inf_n = 0, inf_doc_begin = 0;  // inf_doc_begin: that call's first document of A
+  int inf_cols = 0;               // the columns of that call's model: the topics of inf_topic
   // the model of the last successful isle_hip_load_model_text (model_load.hip): independent of A, B, the partition and the catchwords
   DevBuf<float> ml_model;          // ml_V x ml_cols col-major
   uint64_t ml_V = 0;
@@ -753,6 +753,20 @@ int k_tp_rows(isle_ctx* c, const TdView& v, const uint32_t* groups_dev, uint32_t
 int k_tp_bases(isle_ctx* c, int fam, const uint64_t* docs, uint32_t G, int levels, uint64_t* bases, uint64_t* cnt, uint64_t* blk);
 int k_tp_tile(isle_ctx* c, const TdView& v, const uint32_t* list, const double* rs, uint32_t G, const uint64_t* bases, int levels, const uint64_t* totals,
               uint32_t t0, uint32_t tw, double* part_a, double* part_b, double* sum);
+
+// infer_resident.hip: a V x k column-major device model into `out`, V x round4(k) row-major with zero padding (inf_pack_k)
+int k_inf_pack(isle_ctx* c, const float* model_cm_dev, uint64_t V, int k, float* out);
+// score_docs.hip: the device steps of isle_hip_score_docs (the rule: score_host.h).  w: the weight rows, its num_topics the model's columns.
+// Every buffer is the call's; device time goes to ISLE_T_INFER.
+// k_sc_rows: every weight row checked, rs (rows) = the row sums s_d; *bad: ~0, or (entry << 2) | what of the first bad weight entry (1, 2:
+//   topdocs_entry_fault; SCORE_BAD_WEIGHT).  Drained when it returns.
+// k_sc_walk: M: the packed model, vocab x ld; document r has the entries [off[r], off[r + 1]) of cnt / word (off need not begin at 0);
+//   rs: the row sums, or null without normalise; the five per-document outputs (rows each); z_out: null, or z of entry e at z_out[e];
+//   *bad: ~0, or (entry << 1) | what of the first bad entry (SCORE_BAD_WORD, SCORE_BAD_COUNT).  Drained when it returns.
+int k_sc_rows(isle_ctx* c, const TdView& w, double* rs, uint64_t* err_dev, uint64_t* bad);
+int k_sc_walk(isle_ctx* c, const TdView& w, const float* M, int ld, uint64_t vocab, const float* cnt, const uint32_t* word, const int64_t* off,
+              const double* rs, int measure, double floor, double* score, double* tokens, uint32_t* unscored_entries, double* unscored_tokens,
+              uint32_t* floored, double* z_out, uint64_t* err_dev, uint64_t* bad);
 
 // vocab.hip: the device steps of isle_hip_word_doc_freq / isle_hip_prune_vocab on the resident A (the rule: vocab_host.h).  k_vocab_df: df_dev
 // (a_V words, zeroed there) = this rank's entries per word.  k_vocab_compact: A under remap_dev (a_V words: the new id, or 0xffffffff) out of

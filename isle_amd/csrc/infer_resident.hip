@@ -147,6 +147,14 @@ T* shifted(T* p, int64_t elems) {  // p - elems as an address: the kernels add p
 
 }  // namespace
 
+int k_inf_pack(isle_ctx* c, const float* model_cm_dev, uint64_t V, int k, float* out) {
+  const int ld = (k + 3) & ~3;
+  TimeScope ts(c, ISLE_T_INFER);
+  hipLaunchKernelGGL(inf_pack_k, dim3((unsigned)((V + PK - 1) / PK), (unsigned)((ld + PK - 1) / PK)), dim3(256), 0, c->stream, model_cm_dev, V, k, ld, out);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
 int k_infer_resident(isle_ctx* c, const float* model_cm_dev, int k, uint64_t doc_begin, uint64_t doc_end, int iters, float Lfguess,
                      float avg_doc_sz, float min_weight, uint64_t chunk_docs, int32_t* top_topic, float* top_weight, float* llh,
                      uint64_t* nconverged, uint64_t* nentries) {
@@ -234,6 +242,7 @@ int k_infer_resident(isle_ctx* c, const float* model_cm_dev, int k, uint64_t doc
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->inf_docs = R;
+  c->inf_doc_begin = doc_begin;
   c->inf_n = (uint64_t)running;
   c->inf_cols = k;
   c->res.inference_done();

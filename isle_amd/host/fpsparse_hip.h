@@ -675,6 +675,38 @@ class FPSparseMatrixHip {
                                     normalise ? 1 : 0, p.docs.data(), &p.unlabelled, p.count.data(), p.dominant.data(), p.sum.data()), "topic_prevalence");
     return p;
   }
+  // Held-out scores per document on the device (isle_hip_score_docs; the rule: isle_amd/csrc/score_host.h) with the weights of the last
+  // infer_documents_resident (ISLE_TOPDOCS_INFER; doc_begin = its doc_begin, num_rows = its documents) under the model `which` (model_host
+  // and ncols with ISLE_MODEL_HOST only).  held == nullptr: the entries are those documents of the resident count matrix; else the caller's
+  // CSC (counts, rows, offsets of num_rows documents), e.g. the held-out part of every document.  measure ISLE_SCORE_LOG / _PROB; floor > 0:
+  // an entry with z < floor is scored at floor.  Per document score, tokens, unscored_entries, unscored_tokens, floored; the totals are
+  // isle_hip_score_total's ascending sums, perplexity = exp(-total_score / total_tokens) (ISLE_SCORE_LOG).  Nothing resident changes.
+  struct HeldEntries {
+    const FPTYPE* counts;
+    const uint32_t* rows;
+    const int64_t* offsets;
+  };
+  struct DocScores {
+    std::vector<double> score, tokens, unscored_tokens;
+    std::vector<uint32_t> unscored_entries, floored;
+    double total_score = 0.0, total_tokens = 0.0, perplexity = 0.0;
+  };
+  DocScores score_documents(const int which, const doc_id_t doc_begin, const doc_id_t num_rows, const int measure, const bool normalise, const double floor,
+                            const HeldEntries* held = nullptr, const FPTYPE* model_host = nullptr, const doc_id_t ncols = 0) {
+    DocScores s;
+    const size_t n = (size_t)num_rows;
+    s.score.assign(n, 0.0), s.tokens.assign(n, 0.0), s.unscored_tokens.assign(n, 0.0);
+    s.unscored_entries.assign(n, 0), s.floored.assign(n, 0);
+    const bool host = which == ISLE_MODEL_HOST;
+    check(isle_hip_score_docs(ctx_, which, model_host, model_vocab(which), (int)(host ? ncols : model_cols(which)), ISLE_TOPDOCS_INFER, num_rows, nullptr,
+                              nullptr, nullptr, held ? ISLE_SCORE_HOST : ISLE_SCORE_RESIDENT, doc_begin, held ? held->counts : nullptr,
+                              held ? held->rows : nullptr, held ? held->offsets : nullptr, measure, normalise ? 1 : 0, floor, s.score.data(), s.tokens.data(),
+                              s.unscored_entries.data(), s.unscored_tokens.data(), s.floored.data(), nullptr), "score_docs");
+    isle_hip_score_total(s.score.data(), n, &s.total_score);
+    isle_hip_score_total(s.tokens.data(), n, &s.total_tokens);
+    s.perplexity = std::exp(-s.total_score / s.total_tokens);
+    return s;
+  }
   // Two models compared on the device (isle_hip_compare_models; the rule: isle_amd/csrc/match_host.h): dist (cols_a x cols_b row-major) =
   // the L1 distances of their topics in double, and the greedy matching of the topics by it: match_a[i] = the matched topic of b or -1,
   // match_b the inverse, match_dist[i] = the matched distance or NaN, mean_dist over the n_matched pairs.  A side is a resident model

@@ -380,6 +380,18 @@ inline std::string topic_match_text(const std::vector<int32_t>& match_a, const s
   }
   return out;
 }
+// DocScores.tsv (ISLETrainer::output_doc_scores): "<document>\t<tokens>\t<score>\t<unscored entries>\n" per document, documents 1-based from
+// first_number, tokens and score as %.17g (a double read back is the same bits).
+inline std::string doc_scores_text(const uint64_t first_number, const std::vector<double>& tokens, const std::vector<double>& score,
+                                   const std::vector<uint32_t>& unscored_entries) {
+  std::string out;
+  char line[128];
+  for (size_t d = 0; d < score.size(); ++d) {
+    std::snprintf(line, sizeof line, "%llu\t%.17g\t%.17g\t%u\n", (unsigned long long)(first_number + d), tokens[d], score[d], unscored_entries[d]);
+    out += line;
+  }
+  return out;
+}
 }  // namespace trainer_detail
 
 class ISLETrainer {
@@ -1079,6 +1091,30 @@ class ISLETrainer {
       }
     std::fclose(f);
     log->next_time_secs("Writing the topic prevalence by document group");
+  }
+  // "How well does the model predict these words": every document's held-out score on the device under this run's catch model, with the
+  // weights output_doc_topic_weights() left resident (call it first), normalised per document (FPSparseMatrixHip::score_documents ->
+  // isle_hip_score_docs; the rule: isle_amd/csrc/score_host.h).  held: the CSC of the words to score, one column per document of the count
+  // matrix (for document completion: the part of every document the weights were not fitted to); nullptr: the resident count matrix
+  // itself, which is then an in-sample figure under the same two headings.  floor > 0: a word the model gives less than floor is scored at
+  // floor; with 0 such an entry is left out and counted.  DocScores.tsv: trainer_detail::doc_scores_text states its bytes.  The log gets
+  // the log-likelihood per token and the perplexity, totals summed ascending on the host.  The reference has no such output; not part of
+  // what ISLETrain writes by default.
+  void output_doc_scores(const FPSparseMatrixHip::HeldEntries* held = nullptr, const double floor = 0.0) {
+    if (!is_training_complete) throw std::runtime_error("output_doc_scores() before train()");
+    const doc_id_t docs = B_fl_CSC->count_docs();
+    const FPSparseMatrixHip::DocScores s = B_fl_CSC->score_documents(ISLE_MODEL_CATCH, 0, docs, ISLE_SCORE_LOG, true, floor, held);
+    const std::string text = trainer_detail::doc_scores_text(1, s.tokens, s.score, s.unscored_entries);
+    FILE* f = std::fopen((log_dir + "/DocScores.tsv").c_str(), "wb");
+    if (!f) throw std::runtime_error("cannot write " + log_dir + "/DocScores.tsv");
+    std::fwrite(text.data(), 1, text.size(), f);
+    std::fclose(f);
+    char num[40];
+    std::snprintf(num, sizeof num, "%.17g", s.total_score / s.total_tokens);
+    log->print(std::string("Held-out log-likelihood per token: ") + num + "\n");
+    std::snprintf(num, sizeof num, "%.17g", s.perplexity);
+    log->print(std::string("Perplexity: ") + num + "\n");
+    log->next_time_secs("Scoring held-out words per document");
   }
   // "Is this model the same as that one": the model file model_file (format ISLE_TEXT_SPARSE / ISLE_TEXT_DENSE, vocab_size x num_topics, as
   // write_model_to_file writes it) is read on the device into the resident loaded model (FPSparseMatrixHip::load_model_file) and this

@@ -138,6 +138,53 @@ def parse_weight(token, format="sparse"):
     return None if rc else np.float32(out.value)
 
 
+def score_total(v):
+    """The corpus total of per-document values: the ascending sequential sum in double (isle_amd/csrc/score_host.h score_total), on the
+    host through the library, so that Python and C++ get the same bits and shards side by side give the single-rank total."""
+    v = np.ascontiguousarray(v, np.float64).reshape(-1)
+    out = C.c_double(0.0)
+    if load_library().isle_hip_score_total(_p(v) if v.size else None, int(v.size), C.byref(out)) != 0:
+        raise IsleHipError("score_total: bad arguments")
+    return float(out.value)
+
+
+def _docs_mix(x):
+    """docs_mix of isle_amd/csrc/docs_host.h (the finaliser of splitmix64) on a uint64 array."""
+    with np.errstate(over="ignore"):
+        x = x + np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return x ^ (x >> np.uint64(31))
+
+
+def held_out_mask(docs, words, seed, num, den, doc_offset=0):
+    """score_held_out of isle_amd/csrc/score_host.h for every (doc_offset + doc, word) -> bool array."""
+    if not (int(den) >= 1 and 0 <= int(num) <= int(den)):
+        raise ValueError("held-out share num / den: 0 <= num <= den, den >= 1")
+    key = ((np.asarray(docs, np.uint64) + np.uint64(doc_offset)) << np.uint64(32)) | np.asarray(words, np.uint64)
+    return _docs_mix(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) ^ key) % np.uint64(den) < np.uint64(num)
+
+
+def split_held_out(counts, rows, offs, seed, num, den, doc_offset=0):
+    """Splits a count matrix in CSC by entry for document completion: the entry (doc, word) is held out when
+    docs_mix(seed ^ (((doc_offset + doc) << 32) | word)) % den < num (score_held_out, isle_amd/csrc/score_host.h).  The split is
+    deterministic and does not depend on how the documents are sharded: doc_offset is the shard's first document in the corpus.
+    -> ((counts, rows, offs) observed, (counts, rows, offs) held), both in the input's order."""
+    counts = np.ascontiguousarray(counts, np.float32)
+    rows = _as_u32(rows, "rows")
+    offs = np.ascontiguousarray(offs, np.int64)
+    D = offs.size - 1
+    doc = np.repeat(np.arange(D, dtype=np.uint64), np.diff(offs))
+    held = held_out_mask(doc, rows, seed, num, den, doc_offset)
+
+    def part(m):
+        o = np.zeros(D + 1, np.int64)
+        np.cumsum(np.bincount(doc[m].astype(np.int64), minlength=D), out=o[1:])
+        return counts[m], rows[m], o
+
+    return part(~held), part(held)
+
+
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -1254,6 +1301,7 @@ class HotPath:
                                                     -1.0 if min_weight is None else float(min_weight), int(chunk_docs), _p(tt), _p(tw),
                                                     _p(llh), C.byref(nc), C.byref(ne)))
         self._inf_rows = n
+        self._inf_begin = b
         self._inf_cols = int(cols)
         out = dict(top_topic=tt, top_weight=tw, llh=llh, nconverged=int(nc.value), nentries=int(ne.value), avg_doc_sz=self.avg_doc_sz())
         if fetch_entries:
@@ -1499,6 +1547,100 @@ class HotPath:
         with np.errstate(divide="ignore", invalid="ignore"):
             mean = total / docs.astype(np.float64)[:, None]
         return dict(docs=docs, unlabelled=int(none.value), count=count, dominant=dominant, sum=total, mean=mean)
+
+    # ---- held-out scores per document (include/isle_hip.h, isle_hip_score_docs) ------------------------------------------------------
+    _SCORE_MEASURES = {"log": 0, "prob": 1}
+
+    def score_docs(self, model="catch", weights="infer", entries="resident", docs=None, measure="log", normalise=False, floor=0.0, with_z=False):
+        """How well topic weights predict the entries of a count matrix, per document: z = M[w, :] . theta[:, d] at every entry (w, c), the
+        term c log z ("log") or c z ("prob"), summed per document in a stated order (include/isle_hip.h; the rule:
+        isle_amd/csrc/score_host.h).  model: as infer_resident.  weights: "infer" (the rows of the last infer_resident) or a CSR
+        (offs, topic, weight), topics ascending strictly within a row.  entries: "resident" (documents docs = (begin, end) of A; None: the
+        documents of the last infer_resident with weights="infer", else the first rows of A) or a CSC (counts, rows, offs) uploaded for
+        the call.  normalise: every row's weights divided by the row's sum first.  floor > 0: an entry with z < floor is scored at floor
+        and counted in `floored`; otherwise an entry with z == 0, and always one with z NaN, infinite or negative, is unscored: it adds
+        nothing and is counted.  with_z (a caller's CSC only): z of every entry.  Nothing resident changes.
+        Under comm_init / comm_init_host: no collective; every rank scores its own rows, and the ranks' arrays side by side are the
+        single-rank arrays bit for bit.  model="avg" is refused there.
+        -> dict(score, tokens, unscored_tokens float64 (n,), unscored_entries, floored uint32 (n,), total_score, total_tokens (through
+        score_total), perplexity = exp(-total_score / total_tokens) for "log" (NaN without tokens; None for "prob")[, z float64])."""
+        if isinstance(model, str):
+            which, host = self._MODELS[model], None
+            V, cols = self._resident_shape(model)
+        else:
+            host = np.asfortranarray(model, np.float32)
+            if host.ndim != 2:
+                raise ValueError("model must be (V, cols)")
+            which, (V, cols) = 2, host.shape
+        woff = wtp = wva = None
+        if isinstance(weights, str):
+            if weights != "infer":
+                raise ValueError("weights: \"infer\" or (offs, topic, weight)")
+            wkind, n = 0, None  # (the rows are the entries' documents; the library holds them to the resident result's)
+        else:
+            wkind = 2
+            woff = np.ascontiguousarray(weights[0], np.int64)
+            wtp = _as_u32(weights[1], "topic")
+            wva = np.ascontiguousarray(weights[2], np.float32)
+            if woff.ndim != 1 or woff.size < 1 or wva.ndim != 1 or wtp.size != wva.size or (woff.size > 1 and int(woff[-1]) != wtp.size):
+                raise ValueError("weights: (offs (rows + 1,), topic, weight) with offs[-1] entries")
+            n = woff.size - 1
+        cnt = rws = off = None
+        begin = 0
+        if isinstance(entries, str):
+            if entries != "resident":
+                raise ValueError("entries: \"resident\" or (counts, rows, offs)")
+            ekind = 0
+            if docs is not None:
+                begin, have = int(docs[0]), max(int(docs[1]) - int(docs[0]), 0)
+            else:
+                begin, have = (getattr(self, "_inf_begin", 0), getattr(self, "_inf_rows", 0)) if wkind == 0 else (0, n)
+            if n is not None and have != n:
+                raise ValueError("docs: %d documents for %d weight rows" % (have, n))
+            n = have
+        else:
+            ekind = 1
+            cnt = np.ascontiguousarray(entries[0], np.float32)
+            rws = _as_u32(entries[1], "rows")
+            off = np.ascontiguousarray(entries[2], np.int64)
+            if off.ndim != 1 or off.size < 1 or cnt.ndim != 1 or rws.size != cnt.size or (off.size > 1 and int(off[-1]) != cnt.size):
+                raise ValueError("entries: (counts, rows, offs (docs + 1,)) with offs[-1] entries")
+            if n is not None and off.size - 1 != n:
+                raise ValueError("entries: %d documents for %d weight rows" % (off.size - 1, n))
+            n = off.size - 1
+        if with_z and ekind != 1:
+            raise ValueError("with_z needs a caller's CSC (fetch A with get_A and pass it)")
+        score = np.zeros(n, np.float64)
+        tokens = np.zeros(n, np.float64)
+        ut = np.zeros(n, np.float64)
+        ue = np.zeros(n, np.uint32)
+        fl = np.zeros(n, np.uint32)
+        z = np.zeros(cnt.size, np.float64) if with_z else None
+        m = self._SCORE_MEASURES[measure] if isinstance(measure, str) else int(measure)
+        self._chk(self._lib.isle_hip_score_docs(self._h, which, _p(host), int(V), int(cols), wkind, n, _p(woff), _p(wtp), _p(wva), ekind, begin, _p(cnt),
+                                                _p(rws), _p(off), m, int(normalise), float(floor), _p(score), _p(tokens), _p(ue), _p(ut), _p(fl),
+                                                _p(z)))
+        out = dict(score=score, tokens=tokens, unscored_entries=ue, unscored_tokens=ut, floored=fl, total_score=score_total(score),
+                   total_tokens=score_total(tokens), perplexity=None)
+        if m == 0:
+            with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+                out["perplexity"] = float(np.exp(-np.float64(out["total_score"]) / np.float64(out["total_tokens"])))
+        if with_z:
+            out["z"] = z
+        return out
+
+    def completion_score(self, V, counts, rows, offs, model, seed=0, num=1, den=2, iters=15, Lf=10.0, floor=0.0, doc_offset=0):
+        """Document completion, the held-out measure of a topic model: split_held_out(counts, rows, offs, seed, num, den, doc_offset);
+        upload_counts of the observed part, which REPLACES THE RESIDENT COUNT MATRIX A (and voids what was derived from it);
+        infer_resident(model, min_weight=0.0) on it; score_docs of the held part as a caller's CSC with weights="infer", measure "log",
+        normalise=True.  model: a (V, cols) array, or "loaded" (a resident catch or average model goes with the A it came from).
+        -> score_docs' dict, and observed / held (the two CSC parts), nconverged."""
+        obs, held = split_held_out(counts, rows, offs, seed, num, den, doc_offset)
+        self.upload_counts(V, *obs)
+        inf = self.infer_resident(model, iters=iters, Lf=Lf, min_weight=0.0, fetch_entries=False)
+        out = self.score_docs(model, weights="infer", entries=held, measure="log", normalise=True, floor=floor)
+        out.update(observed=obs, held=held, nconverged=inf["nconverged"])
+        return out
 
     def timing_enable(self, on=True):
         """0 / False: off; 1 / True: events around every launch; 2: around the Gram-apply launches only."""
